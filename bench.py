@@ -13,6 +13,17 @@ all-reduce of the run summary per timed region.
 
 Rank 0 prints ONE JSON line.  `value` = LM iterations (successful + unsuccessful trust-region
 steps, as slam.cpp:949-950 counts them) of all ranks / max-over-ranks wall time of the K steps.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.
+Everything else - the cross-rank result check, the profiled steps (per-kernel times, roofline), the
+two-stream run, the CPU baselines, the streamed legs, the 500-line / latency / pose-graph / mixed
+precision configurations - runs only with --full (the --no-* options then pick among them):
+
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (rank 0's
+windows): every window's solved camera poses and LM summary, and the full solved parameter vectors of
+a fixed, seeded sample of windows (all of them when they fit in 48 MB).
 """
 import argparse
 import json
@@ -286,6 +297,45 @@ def cross_rank_result_check(batches, where, lo, B, rank, world, dev, local_rank,
                    "1-window batches with the same chunk count and compares bytes" % k}
 
 
+def make_windows(lo, hi, lines, workers):
+    """Windows [lo, hi), window i = synth.make_window(i): a window is a function of its id alone, so the inputs do not depend on the
+    number of worker processes.  Called before the process opens the GPU (the workers are forked)."""
+    if workers <= 1 or hi - lo < 2 * workers:
+        return [synth.make_window(i, num_lines=lines) for i in range(lo, hi)]
+    import functools
+    import multiprocessing as mp
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(max_workers=workers, mp_context=mp.get_context("fork")) as ex:
+        return list(ex.map(functools.partial(synth.make_window, num_lines=lines), range(lo, hi),
+                           chunksize=max(1, (hi - lo) // (4 * workers))))
+
+
+DUMP_PARAMETER_BYTES = 48 << 20      # full parameter vectors in the dump: all windows up to this size, else a seeded sample
+
+
+def last_step_outputs(batches, where, lo, B):
+    """What a caller of the timed path receives from its last step, for --dump-outputs (float64): the solved camera poses and the LM
+    summary of every window of the rank, and the whole solved parameter vector of a fixed, seeded sample of its windows."""
+    sizes = [batches[where[i][0]].sizes[where[i][1]] for i in range(B)]
+    k = max(1, min(B, DUMP_PARAMETER_BYTES // max(8 * (6 * c + 4 * l) for c, l in sizes)))
+    sample = set(range(B)) if k == B else set(np.random.default_rng(20240611).choice(B, size=k, replace=False).tolist())
+    cams, summ, params, ids = [], [], [], []
+    for i in range(B):
+        bt, li = batches[where[i][0]], where[i][1]
+        x = bt.parameters(li)
+        s = bt.summary(li)
+        cams.append(x[:6 * sizes[i][0]])
+        summ.append([s["initial_cost"], s["final_cost"], s["num_successful_steps"], s["num_unsuccessful_steps"], s["termination_type"]])
+        if i in sample:
+            params.append(x)
+            ids.append(lo + i)
+    return {"camera_parameters": np.stack(cams).astype(np.float64),
+            "summary_initial_final_cost_successful_unsuccessful_termination": np.asarray(summ, dtype=np.float64),
+            "window_ids": np.arange(lo, lo + B, dtype=np.float64),
+            "parameters": np.concatenate(params).astype(np.float64),
+            "parameters_window_ids": np.asarray(ids, dtype=np.float64)}
+
+
 def time_batch(windows, device, steps, warmup, **opt):
     """Resident batch of `windows`, `steps` timed solves (hipGraph replay): (LM iterations / s, ms per solve)."""
     bt = capi.LBABatch(device=device)
@@ -524,6 +574,11 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="the rank's windows are split into this many batches on separate HIP streams, so that the "
                          "latency-bound kernels of one batch (reduced solve, LM update) overlap the sweeps of the other")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the cross-rank result check, the profiled steps (per-kernel times, roofline), "
+                         "the two-stream run, the CPU baselines, the streamed legs and the extra configurations (the --no-* options pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float64, rank 0's windows)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -531,6 +586,12 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d (launch with torch.distributed.run for N > 1)" % (args.gpus, world))
+    # ---- synthetic inputs of the named shape, distinct per rank, generated before the GPU is opened
+    # BASELINE configs[3]: a stream of world x B independent windows, window i = synth.make_window(i), split contiguously
+    # over the ranks (dist.shard_range): every rank holds B windows (weak scaling), no data-path collective
+    B = args.windows
+    lo, hi = shard_range(B * world, rank, world)
+    windows = make_windows(lo, hi, args.lines, max(1, min(16, host_cpu_info()["usable_threads"] // world)))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device; the product has no CPU path")
     # one process per GPU; SLSLAM_BENCH_SHARE_GPU=1 lets several ranks share a device (dry runs of the
@@ -559,12 +620,7 @@ def main():
     else:
         seen, ranks_seen = [me], 1
 
-    # ---- synthetic inputs of the named shape, distinct per rank, resident in HBM before timing
-    # BASELINE configs[3]: a stream of world x B independent windows, window i = synth.make_window(i), split contiguously
-    # over the ranks (dist.shard_range): every rank holds B windows (weak scaling), no data-path collective
-    B = args.windows
-    lo, hi = shard_range(B * world, rank, world)
-    windows = [synth.make_window(i, num_lines=args.lines) for i in range(lo, hi)]
+    # ---- the windows, resident in HBM before timing
     use_graph = not args.eager          # the production launch mode: one hipGraph replay per solve (one host call, insensitive to a busy host)
     ns = max(1, min(args.streams, B))
     bstreams = [torch.cuda.current_stream()] + [torch.cuda.Stream() for _ in range(ns - 1)]
@@ -621,13 +677,20 @@ def main():
         per_rank = tt.tolist()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
-    check = cross_rank_result_check(batches, where, lo, B, rank, world, dev, local_rank, args.lines, args.elim, keep=args.keep_jacobian) if not args.no_result_check else None
+    if args.dump_outputs and rank == 0:          # the last timed step's results, before anything else runs on the batches
+        for bt, st in zip(batches, bstreams):
+            bt.download(st.cuda_stream)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in last_step_outputs(batches, where, lo, B).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    check = cross_rank_result_check(batches, where, lo, B, rank, world, dev, local_rank, args.lines, args.elim, keep=args.keep_jacobian) \
+        if args.full and not args.no_result_check else None
 
     # ---- per-kernel times (roofline): outside the timed region, same process, same resident batches - a profiled pass of eager
     # launches with hipEvents around every kernel (events recorded by graph nodes cannot be read back on this runtime).  The sum
     # of the kernel times per step must agree with the graph-replay step measured above.
     profile_steps = 0
-    if use_graph and args.profile_steps > 0:
+    if args.full and use_graph and args.profile_steps > 0:
         for bt in batches:
             bt.set_profiling(True)
         profile_steps = args.profile_steps
@@ -640,7 +703,7 @@ def main():
     # solve, LM update) overlap the observation sweeps of the other.  Per-kernel durations are not comparable in
     # this mode (kernels of the two halves share the GPU), so the roofline numbers come from the region above.
     overlap = None
-    if ns == 1 and not args.no_overlap_run and B >= 2:
+    if args.full and ns == 1 and not args.no_overlap_run and B >= 2:
         ostreams = [torch.cuda.current_stream(), torch.cuda.Stream()]
         obatches = []
         for si in range(2):
@@ -710,7 +773,7 @@ def main():
         kts = [bt.kernel_times() for bt in batches]
         kt = {k: (sum(x[k][0] for x in kts), sum(x[k][1] for x in kts)) for k in kts[0]}
         ms, n = kt["linearise_schur"]
-        if n > 0:
+        if args.full and n > 0:
             # one launch covers the windows of ONE stream's batch
             bytes_launch = algorithmic_bytes_linearise(counts) / ns
             achieved = bytes_launch / (ms / n * 1e-3) / 1e9
@@ -776,7 +839,7 @@ def main():
                 out["reduced_solve_mfma"] = {"instruction": "v_mfma_f64_16x16x4_f64", "mfma_per_launch": nm, "avg_launch_ms": sms / sn,
                                              "achieved_tflops": tf, "peak_tflops": FP64_VECTOR_PEAK_TFLOPS, "utilisation": tf / FP64_VECTOR_PEAK_TFLOPS,
                                              "note": "60x60 systems: latency-bound (one workgroup per window), 3 % of the step"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             v, sample, outs = cpu_baseline(windows)
             hinfo = host_cpu_info()
             out["cpu_baseline"] = {"value": v, "unit": "LM iterations/s", "cores": 1, "kind": "port", "sample": sample,
@@ -806,7 +869,7 @@ def main():
             err = np.concatenate(err)
             out["traj_error_vs_oracle"] = {"rms_m": float(np.sqrt((err ** 2).mean())), "mean_m": float(err.mean()),
                                            "keyframes": int(err.size)}
-        if world == 1 and not args.no_streamed and ns == 1:
+        if args.full and world == 1 and not args.no_streamed and ns == 1:
             resident_params = {i: batches[where[i][0]].parameters(where[i][1]).copy() for i in range(B)} if B <= 4096 else {}
             # the resident batches are done: their HBM, graphs and queues go back before the stream of windows starts (an idle batch kept open beside
             # the stream's slots makes the process's HIP streams share hardware queues, and uploads then wait behind solves: tools/streamed_dbg.py)
@@ -833,7 +896,7 @@ def main():
                                                                  host_threads=args.host_threads, mode="host", **sopt)
                 except capi.SlslamError as e:
                     out["streamed_pageable"] = {"error": str(e)}
-        if world == 1 and not args.no_extra_configs:
+        if args.full and world == 1 and not args.no_extra_configs:
             for bt in batches:           # release HBM before the extra measurements
                 bt.close()
             batches = []
@@ -871,7 +934,7 @@ def main():
         # ---- BASELINE config 4 as it reads - a STREAM of windows sharded over the GPUs: every rank streams its shard of every set through a
         # stream object of its own (page-locked arrays, the build stage on the device, results in place), host threads = the quota's share
         sb = None
-        if not args.no_streamed and ns == 1:
+        if args.full and not args.no_streamed and ns == 1:
             resident_params = {}
             for bt in batches:
                 bt.close()

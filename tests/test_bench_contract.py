@@ -32,7 +32,7 @@ def test_algorithmic_figures_follow_the_survey_formulas():
 @pytest.mark.gpu
 def test_bench_line_contract():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--windows", "8",
-           "--lines", "200", "--no-cpu-baseline", "--no-extra-configs"]
+           "--lines", "200", "--full", "--no-cpu-baseline", "--no-extra-configs"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -61,3 +61,37 @@ def test_bench_line_contract():
     assert chk["window_ids"] == [0, 1, 2, 3] and len(chk["crc32_of_gathered_parameters"]) == 4
     assert chk["bitwise_equal_to_rank0_resolve"] is True and chk["max_abs_diff"] == 0.0
     assert "traffic_source" in d["roofline"]
+
+
+@pytest.mark.gpu
+def test_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times only the headline: the contract keys are there, the extra measurements are not.
+    --dump-outputs writes the last timed step's results as float64 .npy files, the same bytes from run to run, and they are the
+    results a caller of the timed path gets (the summary's final costs add up to the line's own sum)."""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--windows", "8",
+               "--lines", "200", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["unit"] == "LM iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert d["value"] == pytest.approx(d["lm_iterations"] / (d["ms_per_step"] * d["steps"] * 1e-3), rel=1e-6)
+        for key in ("roofline", "kernel_ms_per_step", "cpu_baseline", "streamed", "two_streams_overlapped", "mixed_precision"):
+            assert key not in d, key
+        files = sorted(out.glob("*.npy"))
+        assert files and sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        s = arrays["summary_initial_final_cost_successful_unsuccessful_termination"]
+        assert s.shape == (8, 5) and s[:, 1].sum() == pytest.approx(d["sum_final_cost_rank0"], rel=1e-12)
+        assert arrays["camera_parameters"].shape[0] == 8 and np.isfinite(arrays["parameters"]).all()
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name

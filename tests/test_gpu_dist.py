@@ -114,7 +114,7 @@ def test_bench_two_ranks_shared_gpu(hip):
     windows, lines = 24, 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--windows", str(windows), "--lines", str(lines), "--no-cpu-baseline", "--no-overlap-run", "--no-extra-configs", "--stream-batches", "6"]
+           "--windows", str(windows), "--lines", str(lines), "--full", "--no-cpu-baseline", "--no-overlap-run", "--no-extra-configs", "--stream-batches", "6"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -300,13 +300,12 @@ def test_trajectory_writer_reproduces_the_reference_files():
 
 
 def test_trajectory_writer_reproduces_every_shipped_trajectory_file():
-    """Build-container check: ALL lines of the six trajectory files the reference ships (matlab_script/traj_slslam_*.txt, 1354
-    keyframes of the it3f / myungdong / olympic4f runs) go text -> pose -> slslam_format_trajectory_line -> the same text.
-    Reads the reference tree at test time (nothing of it is committed beyond the 25-line excerpt above); skipped where absent."""
+    """ALL lines of the six trajectory files the reference ships (matlab_script/traj_slslam_*.txt, 1354 keyframes of the it3f /
+    myungdong / olympic4f runs; stored as data under tests/golden/traj_slslam/) go text -> pose -> slslam_format_trajectory_line ->
+    the same text."""
     import glob
-    files = sorted(glob.glob("/root/reference/matlab_script/traj_slslam_*.txt"))
-    if not files:
-        pytest.skip("reference tree not present")
+    files = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "traj_slslam", "traj_slslam_*.txt")))
+    assert len(files) == 6, files
     C, lib = _host_lib()
 
     class Pose(C.Structure):

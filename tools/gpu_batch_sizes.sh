@@ -1,12 +1,12 @@
 #!/bin/bash
 # throughput by batch size and elimination sweep (does the automatic choice pick the faster one?): LM it/s of the short bench
-cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; mkdir -p results; export TMPDIR=/tmp
 TAG=${1:-bs}
-: > gpurun_out/${TAG}.txt
+: > results/${TAG}.txt
 for W in ${SIZES:-16 64 128 256 512 1024}; do
   for E in 0 1 4; do
-    timeout 300 python bench.py --steps 10 --warmup 2 --windows $W --elim $E --no-cpu-baseline --no-overlap-run --no-extra-configs --no-result-check > gpurun_out/${TAG}_b.json 2> gpurun_out/${TAG}_b.err
-    python - $W $E gpurun_out/${TAG}_b.json >> gpurun_out/${TAG}.txt <<'PY'
+    timeout 300 python bench.py --full --steps 10 --warmup 2 --windows $W --elim $E --no-cpu-baseline --no-overlap-run --no-extra-configs --no-result-check > results/${TAG}_b.json 2> results/${TAG}_b.err
+    python - $W $E results/${TAG}_b.json >> results/${TAG}.txt <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[3]))
@@ -16,4 +16,4 @@ except Exception as e:
 PY
   done
 done
-cat gpurun_out/${TAG}.txt
+cat results/${TAG}.txt

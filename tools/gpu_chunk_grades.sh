@@ -1,13 +1,13 @@
 #!/bin/bash
 # graded chunk sizes: throughput of the short bench by the weights of a window's chunks (comma-separated lists; "equal" = equal chunks; "default" = the library's)
-cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; mkdir -p results; export TMPDIR=/tmp
 TAG=${1:-cg}; shift
-: > gpurun_out/${TAG}.txt
+: > results/${TAG}.txt
 for LT in "$@"; do
   unset SLSLAM_EQUAL_CHUNKS SLSLAM_CHUNK_WEIGHTS
   if [ "$LT" = "equal" ]; then export SLSLAM_EQUAL_CHUNKS=1; elif [ "$LT" != "default" ]; then export SLSLAM_CHUNK_WEIGHTS=$LT; fi
-  timeout 300 python bench.py --steps 10 --warmup 2 ${BENCH_ARGS} --no-cpu-baseline --no-overlap-run --no-extra-configs --no-result-check > gpurun_out/${TAG}_b.json 2> gpurun_out/${TAG}_b.err
-  python - $LT gpurun_out/${TAG}_b.json >> gpurun_out/${TAG}.txt <<'PY'
+  timeout 300 python bench.py --full --steps 10 --warmup 2 ${BENCH_ARGS} --no-cpu-baseline --no-overlap-run --no-extra-configs --no-result-check > results/${TAG}_b.json 2> results/${TAG}_b.err
+  python - $LT results/${TAG}_b.json >> results/${TAG}.txt <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[2]))
@@ -16,4 +16,4 @@ except Exception as e:
     print("weights %s FAILED %r" % (sys.argv[1], e))
 PY
 done
-cat gpurun_out/${TAG}.txt
+cat results/${TAG}.txt

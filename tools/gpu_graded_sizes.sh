@@ -1,13 +1,13 @@
 #!/bin/bash
 # graded against equal chunk sizes by batch size (automatic sweep): LM it/s of the short bench
-cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; mkdir -p results; export TMPDIR=/tmp
 TAG=${1:-gs}
-: > gpurun_out/${TAG}.txt
+: > results/${TAG}.txt
 for W in ${SIZES:-256 512 768 1024 1536 2048}; do
   for EQ in 0 1; do
     if [ $EQ = 1 ]; then export SLSLAM_EQUAL_CHUNKS=1; else unset SLSLAM_EQUAL_CHUNKS; fi
-    timeout 400 python bench.py --steps 10 --warmup 2 --windows $W --no-cpu-baseline --no-overlap-run --no-extra-configs > gpurun_out/${TAG}_b.json 2> gpurun_out/${TAG}_b.err
-    python - $W $EQ gpurun_out/${TAG}_b.json >> gpurun_out/${TAG}.txt <<'PY'
+    timeout 400 python bench.py --full --steps 10 --warmup 2 --windows $W --no-cpu-baseline --no-overlap-run --no-extra-configs > results/${TAG}_b.json 2> results/${TAG}_b.err
+    python - $W $EQ results/${TAG}_b.json >> results/${TAG}.txt <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[3]))
@@ -17,4 +17,4 @@ except Exception as e:
 PY
   done
 done
-cat gpurun_out/${TAG}.txt
+cat results/${TAG}.txt

@@ -1,13 +1,13 @@
 #!/bin/bash
 # kept-Jacobian sweep: parity tests of the grouped sweep, then the short bench with lba_keep_jacobian = 1 / 0 on the same box.
-cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; mkdir -p results; export TMPDIR=/tmp
 TAG=${1:-keep}
-timeout 1500 python -m pytest tests/test_gpu_lba.py -x -q -k "kept_jacobian or matrix_core or grouped" > gpurun_out/${TAG}_tests.log 2>&1
-tail -5 gpurun_out/${TAG}_tests.log
-: > gpurun_out/${TAG}_ab.txt
+timeout 1500 python -m pytest tests/test_gpu_lba.py -x -q -k "kept_jacobian or matrix_core or grouped" > results/${TAG}_tests.log 2>&1
+tail -5 results/${TAG}_tests.log
+: > results/${TAG}_ab.txt
 for KEEP in ${KEEPS:-0 1 0}; do
-  timeout 600 python bench.py --steps ${BENCH_STEPS:-10} --warmup 2 --keep-jacobian $KEEP ${BENCH_ARGS} --no-cpu-baseline --no-overlap-run --no-extra-configs > gpurun_out/${TAG}_b${KEEP}.json 2> gpurun_out/${TAG}_b${KEEP}.err
-  python - $KEEP gpurun_out/${TAG}_b${KEEP}.json >> gpurun_out/${TAG}_ab.txt <<'PY'
+  timeout 600 python bench.py --full --steps ${BENCH_STEPS:-10} --warmup 2 --keep-jacobian $KEEP ${BENCH_ARGS} --no-cpu-baseline --no-overlap-run --no-extra-configs > results/${TAG}_b${KEEP}.json 2> results/${TAG}_b${KEEP}.err
+  python - $KEEP results/${TAG}_b${KEEP}.json >> results/${TAG}_ab.txt <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[2]))
@@ -17,4 +17,4 @@ except Exception as e:
     print("keep %s FAILED %r" % (sys.argv[1], e))
 PY
 done
-cat gpurun_out/${TAG}_ab.txt
+cat results/${TAG}_ab.txt

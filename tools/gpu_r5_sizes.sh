@@ -1,11 +1,11 @@
 #!/bin/bash
 # resident and streamed throughput by windows per batch (final code of round 5): the short bench with its streamed leg
-cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; mkdir -p results; export TMPDIR=/tmp
 TAG=${1:-r5_sizes}
-: > gpurun_out/${TAG}.txt
+: > results/${TAG}.txt
 for W in ${SIZES:-128 256 512 768 1024 1536 2048}; do
-  timeout 600 python bench.py --steps 10 --warmup 2 --windows $W --stream-batches 24 --no-cpu-baseline --no-overlap-run --no-extra-configs --no-result-check > gpurun_out/${TAG}_b.json 2> gpurun_out/${TAG}_b.err
-  python - $W gpurun_out/${TAG}_b.json >> gpurun_out/${TAG}.txt <<'PY'
+  timeout 600 python bench.py --full --steps 10 --warmup 2 --windows $W --stream-batches 24 --no-cpu-baseline --no-overlap-run --no-extra-configs --no-result-check > results/${TAG}_b.json 2> results/${TAG}_b.err
+  python - $W results/${TAG}_b.json >> results/${TAG}.txt <<'PY'
 import json,sys
 try:
     d=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1]); s=d.get("streamed") or {}
@@ -16,4 +16,4 @@ except Exception as e:
     print("windows %s FAILED %r" % (sys.argv[1], e))
 PY
 done
-cat gpurun_out/${TAG}.txt
+cat results/${TAG}.txt

@@ -2,16 +2,16 @@
 # builds the library with extra compile flags ON the GPU box (hipcc is in the image) and runs the short bench: one line per variant.
 # (BENCH_ARGS: extra bench.py arguments, e.g. "--elim 4"; BENCH_STEPS: timed steps, default 10)
 # usage: gpu_variant_bench.sh TAG "flags variant 1" "flags variant 2" ...
-cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; mkdir -p results; export TMPDIR=/tmp
 TAG=$1; shift
-: > gpurun_out/${TAG}_variants.txt
+: > results/${TAG}_variants.txt
 for FLAGS in "$@"; do
-  SLSLAM_EXTRA_FLAGS="$FLAGS" python -c "from slslam_amd import build; build.build_lib(force=True)" > gpurun_out/${TAG}_build.log 2>&1 || { echo "BUILD FAILED: $FLAGS" >> gpurun_out/${TAG}_variants.txt; continue; }
+  SLSLAM_EXTRA_FLAGS="$FLAGS" python -c "from slslam_amd import build; build.build_lib(force=True)" > results/${TAG}_build.log 2>&1 || { echo "BUILD FAILED: $FLAGS" >> results/${TAG}_variants.txt; continue; }
   CLK0=$(rocm-smi --showclocks 2>/dev/null | grep -m1 sclk | sed 's/.*(\([0-9]*Mhz\)).*/\1/')
-  timeout 600 python bench.py --steps ${BENCH_STEPS:-10} --warmup 2 ${BENCH_ARGS} --no-cpu-baseline --no-overlap-run --no-extra-configs > gpurun_out/${TAG}_b.json 2> gpurun_out/${TAG}_b.err
+  timeout 600 python bench.py --full --steps ${BENCH_STEPS:-10} --warmup 2 ${BENCH_ARGS} --no-cpu-baseline --no-overlap-run --no-extra-configs > results/${TAG}_b.json 2> results/${TAG}_b.err
   CLK1=$(rocm-smi --showclocks 2>/dev/null | grep -m1 sclk | sed 's/.*(\([0-9]*Mhz\)).*/\1/')
-  echo -n "[sclk $CLK0 -> $CLK1] " >> gpurun_out/${TAG}_variants.txt
-  python - "$FLAGS" gpurun_out/${TAG}_b.json >> gpurun_out/${TAG}_variants.txt <<'PY'
+  echo -n "[sclk $CLK0 -> $CLK1] " >> results/${TAG}_variants.txt
+  python - "$FLAGS" results/${TAG}_b.json >> results/${TAG}_variants.txt <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[2]))
@@ -22,4 +22,4 @@ except Exception as e:
 PY
 done
 python -c "from slslam_amd import build; build.build_lib(force=True)" > /dev/null 2>&1
-cat gpurun_out/${TAG}_variants.txt
+cat results/${TAG}_variants.txt

@@ -1,14 +1,14 @@
 #!/bin/bash
 # the short bench through variant builds of the library (tools/variant_lib.sh), interleaved with the product build on the same box
 #   tools/gpu_variant_compare.sh <tag> <variant> [variant ...]
-cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; mkdir -p results; export TMPDIR=/tmp
 TAG=$1; shift
-: > gpurun_out/${TAG}.txt
+: > results/${TAG}.txt
 for rep in 1 2; do
 for V in product "$@"; do
-  if [ $V = product ]; then unset SLSLAM_HIP_LIBRARY; else export SLSLAM_HIP_LIBRARY=/root/repo/slslam_amd/_lib/variants/$V.so; fi
-  timeout 400 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-overlap-run --no-extra-configs --no-streamed > gpurun_out/${TAG}_b.json 2> gpurun_out/${TAG}_b.err
-  python - $V gpurun_out/${TAG}_b.json >> gpurun_out/${TAG}.txt <<'PY'
+  if [ $V = product ]; then unset SLSLAM_HIP_LIBRARY; else export SLSLAM_HIP_LIBRARY=$PWD/slslam_amd/_lib/variants/$V.so; fi
+  timeout 400 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-overlap-run --no-extra-configs --no-streamed > results/${TAG}_b.json 2> results/${TAG}_b.err
+  python - $V results/${TAG}_b.json >> results/${TAG}.txt <<'PY'
 import json,sys
 try:
     d=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
@@ -19,4 +19,4 @@ except Exception as e:
 PY
 done
 done
-cat gpurun_out/${TAG}.txt
+cat results/${TAG}.txt
