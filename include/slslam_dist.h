@@ -53,7 +53,9 @@ int  slslam_dist_debug_fail_next_shard(slslam_dist* d);
  * the whole set (sums[0] LM iterations, sums[1] initial cost, sums[2] final cost).  Replaces, per set and rank, the loop over
  * LBAProblem::build + ceres::Solve (src/slam.cpp:924-944) of the shard.  submit() is local (no collective); collect() is collective:
  * every rank calls it once per set, in the order of the submits, with the ticket its submit returned (-1 if its submit failed: the rank
- * still enters the all-reduce, and every rank returns an error for that set). */
+ * still enters the all-reduce, and every rank returns an error for that set).  A rank whose shard of a set is empty (n_mine = 0) gets
+ * SLSLAM_DIST_EMPTY_TICKET: its collect contributes zeros to the sums and uses no slot of the stream. */
+#define SLSLAM_DIST_EMPTY_TICKET (-2)
 typedef struct slslam_dist_stream slslam_dist_stream;
 int  slslam_dist_stream_create(slslam_dist* d, const slslam_solver_options* opt, int depth, slslam_dist_stream** out);
 void slslam_dist_stream_destroy(slslam_dist_stream* s);

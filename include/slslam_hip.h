@@ -230,7 +230,7 @@ int  slslam_lba_batch_wait(slslam_lba_batch* b);
  * room the arrays have, or need another path / sweep - build a new batch then.
  * Host arrays are read before the call returns - EXCEPT arrays in page-locked memory (slslam_pinned_alloc / _register) when the device
  * builds (options.device_build = 0): those are read by the GPU after the call returns and must stay valid until the results have been
- * waited for.  When the device builds, what only the build can find out arrives with the results: a window with bad input, of a shape
+ * waited for.  For arrays in ordinary (pageable) memory the results depend only on what the arrays held when this call was made.  When the device builds, what only the build can find out arrives with the results: a window with bad input, of a shape
  * for the host path, or a refill that does not fit the room is flagged - slslam_lba_batch_get_parameters / _get_summary of such a window
  * return SLSLAM_ERR_INVALID_ARGUMENT / SLSLAM_ERR_UNSUPPORTED (the other windows are solved); sizes that cannot fit are still refused here.
  * `stream` must be the stream the batch is solved on. */
@@ -300,7 +300,9 @@ int  slslam_pack_indices(int n, const int* camera_index, const int* line_index, 
  * flight on HIP streams of their own, so that packing (host threads), upload (copy engine), solve and download of consecutive
  * batches overlap.  submit() = LBAProblem::build + ceres::Solve for `n` windows, asynchronous: it returns when the windows' arrays
  * have been read or handed to the GPU (`parameters` of each window must stay valid - it is written by collect -, and so must arrays in
- * page-locked memory, which the GPU reads in place: slslam_pinned_alloc); collect() waits for that submit's
+ * page-locked memory, which the GPU reads in place: slslam_pinned_alloc).  For arrays in ordinary (pageable) memory the results depend
+ * only on what the arrays held when submit() was called: the caller may reuse or free them once it returns - all but `parameters`,
+ * which must stay allocated but whose content is not read again.  collect() waits for that submit's
  * results and writes every window's solved parameters in place (the in/out contract of reference src/slam.cpp:957-972) and, when
  * `summaries` is not NULL, summaries[0 .. n).  Tickets must be collected before their slot comes round again (every `depth` submits:
  * SLSLAM_ERR_STATE otherwise).  options: as for a batch; host_threads (0 = up to 16) pack and copy; refill_headroom_percent 0 = 10. */

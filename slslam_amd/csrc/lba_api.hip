@@ -299,7 +299,7 @@ struct slslam_lba_batch {
   bool device_built = false;                 // the batch's present windows were built on the device
   bool inplace_export = false;               // ... and their `parameters` arrays are pinned: results can be written straight into them
   bool results_inplace = false;              // the last download wrote them there
-  std::vector<slslam_lba_window> src_windows;   // the callers' descriptors of a device-built refill (fallback of flagged windows, in-place export)
+  std::vector<slslam_lba_window> src_windows;   // the callers' descriptors of a device-built refill (the in-place export's parameter arrays)
   std::vector<int> build_status;             // per window, after wait(): 0 or the SLSLAM_ERR_* a flagged window is reported with
   long long n_device_builds = 0, n_zero_copy = 0;
   // windows beyond the tiled sweeps (lba_big.h)
@@ -1631,8 +1631,8 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
   // ---- where the device reads the windows: where they are when all their arrays are page-locked (slslam_pinned_alloc /
   // slslam_pinned_register), else a pinned staging copy made here by the host threads (indices narrowed on the way)
   bool all_pinned = true, params_pinned = true;
+  const std::vector<PinnedRegistry::Range> rs = PinnedRegistry::get().snapshot();
   {
-    const std::vector<PinnedRegistry::Range> rs = PinnedRegistry::get().snapshot();
     for (int i = 0; i < B && (all_pinned || params_pinned); ++i) {
       const slslam_lba_window& w = windows[i];
       const size_t M = (size_t)w.num_observations, np = (size_t)6 * w.num_cameras + (size_t)4 * w.num_lines;
@@ -1689,7 +1689,7 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
       }
     }
     // the ranges the copy engine is to move: the callers' arrays and - a run of its own, never merged with a neighbour - the narrowed block
-    struct Rg { uintptr_t lo, hi; bool idx; };
+    using Rg = CopyRange;
     std::vector<Rg> rg;
     rg.reserve((size_t)5 * B + 1);
     size_t payload = 0;
@@ -1706,12 +1706,11 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
       payload += (pk ? 68 : narrow ? 64 : 80) * M + 8 * np;
     }
     std::sort(rg.begin(), rg.end(), [](const Rg& x, const Rg& y) { return x.lo < y.lo; });
-    bool barrier = true;                                  // the next range starts a run whatever lies before it
-    for (const Rg& g : rg) {
-      if (g.idx) { idx_run = (int)runs.size(); runs.push_back(Run{ g.lo, g.hi, 0 }); barrier = true; continue; }
-      if (!barrier && g.lo <= runs.back().hi + 4096) runs.back().hi = std::max(runs.back().hi, g.hi);
-      else runs.push_back(Run{ g.lo, g.hi, 0 });
-      barrier = false;
+    {
+      // (lba_pack.cpp: neighbours within a page of each other, inside one registration, go up as one copy)
+      std::vector<AddrRange> regs(rs.size());
+      for (size_t k = 0; k < rs.size(); ++k) regs[k] = AddrRange{ rs[k].lo, rs[k].hi };
+      for (const AddrRange& a : plan_copy_runs(rg.data(), rg.size(), regs.data(), regs.size(), &idx_run)) runs.push_back(Run{ a.lo, a.hi, 0 });
     }
     for (Run& r : runs) { r.dev_off = dev_need + (r.lo & 255); dev_need += ((r.lo & 255) + (r.hi - r.lo) + 255) & ~(size_t)255; }     // (device address = host address modulo 256)
     if (runs.size() > (size_t)std::max(8, B / 16) || dev_need > payload + payload / 8 + (1u << 20)) { runs.clear(); dev_need = 0; idx_run = -1; }     // scattered: zero copy
@@ -2591,28 +2590,37 @@ extern "C" int slslam_lba_stream_collect(slslam_lba_stream* st, int ticket, slsl
   bool dev = bt->device_built && !bt->part[0];
   std::vector<int> flagged;
   if (dev) for (int i = 0; i < sl.n; ++i) if (bt->build_status[(size_t)i] != SLSLAM_OK) flagged.push_back(i);
+  // A window as submit() handed it over, from what the device read (bt->host_src: the staging copy of pageable arrays, or the caller's
+  // page-locked ones), its initial parameters put back into the caller's `parameters` first: results depend only on what the caller's arrays
+  // held at submit time - a pageable array may have been reused or freed since, and `parameters` is written here, never read.
+  std::vector<std::vector<int>> idx((size_t)sl.n);
+  auto as_submitted = [&](int i) -> slslam_lba_window {
+    const RawWin& r = bt->host_src[(size_t)i];
+    slslam_lba_window w{};
+    w.num_cameras = r.C; w.num_lines = r.L; w.num_observations = r.M; w.observations = r.obs; w.parameters = sl.out_params[(size_t)i];
+    const size_t np = (size_t)6 * r.C + (size_t)4 * r.L;
+    if (np && r.params_in != w.parameters) std::memcpy(w.parameters, r.params_in, np * sizeof(double));
+    if (r.packed) {
+      const size_t M = (size_t)r.M;
+      std::vector<int>& v = idx[(size_t)i];
+      v.resize(4 * M);
+      for (size_t q = 0; q < M; ++q) { const uint32_t x = r.packed[q]; v[q] = (int)((x >> 16) & 0xffu); v[M + q] = (int)(x & 0xffffu); v[2 * M + 2 * q] = (int)((x >> 24) & 1u); v[2 * M + 2 * q + 1] = (int)((x >> 25) & 1u); }
+      w.camera_index = v.data(); w.line_index = v.data() + M; w.fixed_index = v.data() + 2 * M;
+    } else { w.camera_index = r.cam; w.line_index = r.line; w.fixed_index = r.fixed; }
+    return w;
+  };
   // A refill that did not fit the room the slot's arrays have (only the device knows the tiles a set needs: k_build_layout flags the refill as
   // a whole) is what submit answers with a new batch when the HOST can see it: the same here, late - the set is packed by the host threads into
   // a batch of its own size (plus the stream's headroom), solved as ONE batch, and that batch takes the slot, so that the sets that follow fit.
-  // (Solving 1024 flagged windows one by one would take a second, and the next set of that shape would be flagged again.)
-  bool whole_nofit = dev && sl.n > 0 && (int)flagged.size() == sl.n && bt->h_buildwin && (int)bt->src_windows.size() == sl.n;
-  for (int i = 0; whole_nofit && i < sl.n; ++i) if (!(bt->h_buildwin[i].status & kBuildNoFit)) whole_nofit = false;
+  // (Solving 1024 flagged windows one by one would take a second, and the next set of that shape would be flagged again.)  The layout's fit flag
+  // decides, whatever else the windows were flagged for: the host packer takes a window for the host path (a camera that sees a line twice)
+  // in its stride - only a window with bad input, which the packer refuses, keeps the set on the per-window path below.
+  bool whole_nofit = dev && sl.n > 0 && bt->h_buildwin && bt->h_totals && bt->h_totals[3] == 0 && (int)bt->host_src.size() == sl.n;
+  for (int i = 0; whole_nofit && i < sl.n; ++i) if (bt->h_buildwin[i].status & kBuildInvalid) whole_nofit = false;
   if (whole_nofit) {
     const int n = sl.n;
-    std::vector<slslam_lba_window> ws(bt->src_windows);
-    std::vector<std::vector<int>> idx((size_t)n);
-    for (int i = 0; i < n; ++i) {
-      const RawWin& r = bt->host_src[(size_t)i];
-      ws[(size_t)i].parameters = sl.out_params[(size_t)i];
-      if (ws[(size_t)i].num_observations > 0 && (!ws[(size_t)i].camera_index || !ws[(size_t)i].line_index || !ws[(size_t)i].fixed_index)) {
-        if (!r.packed) return SLSLAM_ERR_STATE;
-        const size_t M = (size_t)r.M;
-        std::vector<int>& v = idx[(size_t)i];
-        v.resize(4 * M);
-        for (size_t q = 0; q < M; ++q) { const uint32_t x = r.packed[q]; v[q] = (int)((x >> 16) & 0xffu); v[M + q] = (int)(x & 0xffffu); v[2 * M + 2 * q] = (int)((x >> 24) & 1u); v[2 * M + 2 * q + 1] = (int)((x >> 25) & 1u); }
-        ws[(size_t)i].camera_index = v.data(); ws[(size_t)i].line_index = v.data() + M; ws[(size_t)i].fixed_index = v.data() + 2 * M;
-      }
-    }
+    std::vector<slslam_lba_window> ws((size_t)n);
+    for (int i = 0; i < n; ++i) ws[(size_t)i] = as_submitted(i);
     slslam_lba_batch* nb = nullptr;
     if ((rc = slslam_lba_batch_create(st->device, &nb)) != SLSLAM_OK) return rc;
     nb->ext_pool = st->pool.get();
@@ -2644,18 +2652,10 @@ extern "C" int slslam_lba_stream_collect(slslam_lba_stream* st, int ticket, slsl
   if (dev && bt->results_inplace) { for (int i = 0; i < sl.n; ++i) one(i); }      // (summaries only: not worth waking the pool)
   else st->pool->run(sl.n, one);
   // windows the device build flagged (a camera that sees a line twice, a line with more than 64 observations, more than 20 free cameras,
-  // no room in the slot's arrays, bad input): solved here through the host path, one by one, from what the device read (the caller's
-  // page-locked arrays, or the staging copy) - their status is whatever that path says
+  // no room in the slot's arrays, bad input): solved here through the host path, one by one, from what the device read - their status is
+  // whatever that path says
   for (int i : flagged) {
-    const RawWin& r = bt->host_src[(size_t)i];
-    std::vector<int> cam, line, fixed;
-    slslam_lba_window w{};
-    w.num_cameras = r.C; w.num_lines = r.L; w.num_observations = r.M; w.observations = r.obs; w.parameters = sl.out_params[(size_t)i];
-    if (r.packed) {
-      cam.resize((size_t)r.M); line.resize((size_t)r.M); fixed.resize(2 * (size_t)r.M);
-      for (int q = 0; q < r.M; ++q) { const uint32_t v = r.packed[q]; line[(size_t)q] = (int)(v & 0xffffu); cam[(size_t)q] = (int)((v >> 16) & 0xffu); fixed[2 * (size_t)q] = (v >> 24) & 1u; fixed[2 * (size_t)q + 1] = (v >> 25) & 1u; }
-      w.camera_index = cam.data(); w.line_index = line.data(); w.fixed_index = fixed.data();
-    } else { w.camera_index = r.cam; w.line_index = r.line; w.fixed_index = r.fixed; }
+    slslam_lba_window w = as_submitted(i);
     slslam_solver_options o = st->opt;
     o.refill_headroom_percent = 0; o.host_threads = 1; o.device_build = -1;
     slslam_summary sm;

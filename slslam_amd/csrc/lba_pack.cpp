@@ -558,4 +558,27 @@ std::vector<int> chunk_boundaries_graded(int ntiles, int nchunks, const int* wei
   return b;
 }
 
+std::vector<AddrRange> plan_copy_runs(const CopyRange* ranges, size_t n, const AddrRange* regs, size_t nregs, int* barrier_run) {
+  // the registration that holds [lo, hi) whole, or -1
+  auto reg_of = [&](uintptr_t lo, uintptr_t hi) -> long {
+    const AddrRange* it = std::upper_bound(regs, regs + nregs, lo, [](uintptr_t v, const AddrRange& r) { return v < r.lo; });
+    if (it == regs) return -1;
+    --it;
+    return lo >= it->lo && hi <= it->hi ? (long)(it - regs) : -1;
+  };
+  std::vector<AddrRange> runs;
+  int br = -1;
+  long open = -1;                                   // the registration of the run a range may still join; -1: none
+  for (size_t k = 0; k < n; ++k) {
+    const CopyRange& g = ranges[k];
+    if (g.barrier) { br = (int)runs.size(); runs.push_back(AddrRange{ g.lo, g.hi }); open = -1; continue; }
+    const long reg = reg_of(g.lo, g.hi);
+    if (open >= 0 && reg == open && g.lo <= runs.back().hi + 4096) runs.back().hi = std::max(runs.back().hi, g.hi);
+    else runs.push_back(AddrRange{ g.lo, g.hi });
+    open = reg;
+  }
+  if (barrier_run) *barrier_run = br;
+  return runs;
+}
+
 }  // namespace slslam

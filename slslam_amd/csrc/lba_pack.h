@@ -67,5 +67,14 @@ std::vector<int> chunk_boundaries(int ntiles, int tiles_per_chunk);
 // ends with everybody's LAST chunk - the shorter that one is, the less the slots wait for the slowest); every chunk gets at least one tile
 std::vector<int> chunk_boundaries_graded(int ntiles, int nchunks, const int* weights);
 
+// The copies the copy engine makes of a refill whose arrays are all page-locked (lba_api.hip::refill_device): arrays that lie next to each
+// other go up as one run.  ranges: sorted by lo; barrier = the narrowed index block, a run of its own that nothing merges across.  regs: the
+// page-locked registrations (slslam_pinned_alloc / _register), sorted by lo, disjoint.  A range joins the run before it when it starts at most
+// 4096 bytes past the run's end AND lies in the same registration as the run: a copy never spans two registrations, even abutting ones.
+// Returns the runs in address order; *barrier_run = the index of the barrier's run, or -1.
+struct AddrRange { uintptr_t lo, hi; };
+struct CopyRange { uintptr_t lo, hi; bool barrier; };
+std::vector<AddrRange> plan_copy_runs(const CopyRange* ranges, size_t n, const AddrRange* regs, size_t nregs, int* barrier_run);
+
 }  // namespace slslam
 #endif

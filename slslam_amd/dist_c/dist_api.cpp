@@ -221,6 +221,8 @@ extern "C" void slslam_dist_stream_destroy(slslam_dist_stream* s) {
 
 extern "C" int slslam_dist_stream_submit(slslam_dist_stream* s, const slslam_lba_window* my_windows, int n_mine, int* ticket) {
   if (!s || !ticket) return SLSLAM_ERR_INVALID_ARGUMENT;
+  // an empty shard (a set with fewer windows than ranks): nothing to solve, but the rank still takes part in the set's all-reduce
+  if (n_mine == 0) { *ticket = SLSLAM_DIST_EMPTY_TICKET; return SLSLAM_OK; }
   // no collective here: a rank whose submit fails reports it at collect time (ticket -1 is accepted there), so that the ranks stay in step
   int t = -1;
   const int rc = slslam_lba_stream_submit(s->st, my_windows, n_mine, &t);
@@ -234,8 +236,9 @@ extern "C" int slslam_dist_stream_collect(slslam_dist_stream* s, int ticket, dou
   slslam_dist* d = s->d;
   DIST_HIP(hipSetDevice(d->device));
   double local[4] = { 0.0, 0.0, 0.0, 0.0 };
-  int rc = ticket < 0 ? SLSLAM_ERR_STATE : SLSLAM_OK;      // (this rank's submit had failed: it still enters the all-reduce)
-  if (rc == SLSLAM_OK) {
+  // (ticket -1: this rank's submit had failed - it still enters the all-reduce; SLSLAM_DIST_EMPTY_TICKET: an empty shard contributes zeros)
+  int rc = ticket < 0 && ticket != SLSLAM_DIST_EMPTY_TICKET ? SLSLAM_ERR_STATE : SLSLAM_OK;
+  if (rc == SLSLAM_OK && ticket >= 0) {
     const int n = s->n_of_ticket[(size_t)(ticket % s->depth)];
     s->summaries.resize((size_t)std::max(1, n));
     rc = slslam_lba_stream_collect(s->st, ticket, s->summaries.data());

@@ -152,10 +152,38 @@ int main(int argc, char** argv) {
       }
     }
     slslam_dist_stream_destroy(ds);
-    (void)slslam_pinned_free(arena);
     (void)dev_builds; (void)zero_copy; (void)fallbacks;
-    if (!same) { std::fprintf(stderr, "rank %d: streamed sets differ from the batch call\n", rank); return 4; }
+    if (!same) { (void)slslam_pinned_free(arena); std::fprintf(stderr, "rank %d: streamed sets differ from the batch call\n", rank); return 4; }
     std::printf("rank %d: streamed fan-out ok (3 sets through slslam_dist_stream, sums and parameters equal to the batch call)\n", rank);
+    // an EMPTY shard between two real ones (a set with fewer windows than ranks): the submit succeeds with a ticket of its own, distinct from
+    // -1 (a failed submit), and its collect enters the all-reduce with zeros; the sets around it are solved as before
+    for (int k = 0; k < 2; ++k)
+      for (size_t i = 0; i < mine.size(); ++i) {
+        const std::vector<double>& x0 = keep[(i + (size_t)k) % mine.size()];
+        std::memcpy(sets[(size_t)k][i].parameters, x0.data(), x0.size() * sizeof(double));
+      }
+    slslam_dist_stream* es = nullptr;
+    int erc = slslam_dist_stream_create(d, &opt, 2, &es);
+    int et[3] = { -1, -1, -1 };
+    double esum[3][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
+    if (erc == SLSLAM_OK) erc = slslam_dist_stream_submit(es, sets[0].data(), (int)sets[0].size(), &et[0]);
+    if (erc == SLSLAM_OK) erc = slslam_dist_stream_submit(es, nullptr, 0, &et[1]);
+    if (erc == SLSLAM_OK) erc = slslam_dist_stream_submit(es, sets[1].data(), (int)sets[1].size(), &et[2]);
+    for (int k = 0; k < 3 && erc == SLSLAM_OK; ++k) erc = slslam_dist_stream_collect(es, et[k], esum[k]);
+    slslam_dist_stream_destroy(es);
+    if (erc != SLSLAM_OK) { (void)slslam_pinned_free(arena); std::fprintf(stderr, "rank %d: empty shard: %s (tickets %d %d %d)\n", rank, slslam_status_string(erc), et[0], et[1], et[2]); return 5; }
+    bool eq = et[1] != -1 && esum[1][0] == 0.0 && esum[1][1] == 0.0 && esum[1][2] == 0.0;
+    for (int k = 0; k < 2; ++k) {
+      const double* q = esum[k == 0 ? 0 : 2];
+      eq = eq && q[0] == sums[0] && std::fabs(q[1] - sums[1]) <= 1e-12 * sums[1] && std::fabs(q[2] - sums[2]) <= 1e-12 * sums[2];
+      for (size_t i = 0; i < mine.size(); ++i) {
+        const std::vector<double>& wnt = solved[(i + (size_t)k) % mine.size()];
+        eq = eq && std::memcmp(sets[(size_t)k][i].parameters, wnt.data(), wnt.size() * sizeof(double)) == 0;
+      }
+    }
+    (void)slslam_pinned_free(arena);
+    if (!eq) { std::fprintf(stderr, "rank %d: empty shard: sums or parameters wrong (ticket %d)\n", rank, et[1]); return 6; }
+    std::printf("rank %d: empty shard ok (ticket %d, zeros in the all-reduce, the sets around it equal to the batch call)\n", rank, et[1]);
   }
   slslam_dist_destroy(d);
   return rc;

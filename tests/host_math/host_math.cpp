@@ -190,3 +190,18 @@ int hm_chunk_boundaries_graded(int ntiles, int nchunks, const int* weights, int*
   return (int)b.size();
 }
 }
+
+// ---- the copy-engine runs of a refill from page-locked arrays (lba_pack.cpp): ranges sorted by lo, registrations sorted and disjoint
+extern "C" {
+int hm_plan_copy_runs(int n, const unsigned long long* lo, const unsigned long long* hi, const int* barrier, int nregs,
+                      const unsigned long long* reg_lo, const unsigned long long* reg_hi, unsigned long long* out_lo, unsigned long long* out_hi,
+                      int cap, int* barrier_run) {
+  std::vector<slslam::CopyRange> rg((size_t)n);
+  for (int i = 0; i < n; ++i) rg[(size_t)i] = slslam::CopyRange{ (uintptr_t)lo[i], (uintptr_t)hi[i], barrier[i] != 0 };
+  std::vector<slslam::AddrRange> regs((size_t)nregs);
+  for (int i = 0; i < nregs; ++i) regs[(size_t)i] = slslam::AddrRange{ (uintptr_t)reg_lo[i], (uintptr_t)reg_hi[i] };
+  const std::vector<slslam::AddrRange> runs = slslam::plan_copy_runs(rg.data(), rg.size(), regs.data(), regs.size(), barrier_run);
+  for (size_t i = 0; i < runs.size() && (int)i < cap; ++i) { out_lo[i] = runs[i].lo; out_hi[i] = runs[i].hi; }
+  return (int)runs.size();
+}
+}

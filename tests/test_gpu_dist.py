@@ -169,6 +169,8 @@ def test_c_level_fan_out_through_rccl(tmp_path):
     # the streamed form (slslam_dist_stream_*): the shard three times through a depth-2 stream from page-locked arrays - refills built on the
     # device - with the per-set all-reduce; sums and parameters equal to the batch call
     assert "streamed fan-out ok" in p.stdout, p.stdout + p.stderr
+    # an empty shard between two real ones (slslam_dist_stream_submit with n_mine = 0): a ticket of its own, zeros in the all-reduce
+    assert "empty shard ok" in p.stdout, p.stdout + p.stderr
     out = np.fromfile(tmp_path / "out.bin")
     sums, slot, count = out[:3], int(out[3]), int(out[4])
     gathered = out[5:5 + slot]

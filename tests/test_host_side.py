@@ -889,6 +889,92 @@ def test_graded_chunk_boundaries(host_math):
             assert b == equal(nt, (nt + m - 1) // m), (nt, nc, b)
 
 
+def _copy_runs(host_math, ranges, regs):
+    U = C.c_ulonglong
+    n, nr = len(ranges), len(regs)
+    lo = (U * max(n, 1))(*[r[0] for r in ranges]); hi = (U * max(n, 1))(*[r[1] for r in ranges])
+    bar = (C.c_int * max(n, 1))(*[int(r[2]) for r in ranges])
+    rlo = (U * max(nr, 1))(*[r[0] for r in regs]); rhi = (U * max(nr, 1))(*[r[1] for r in regs])
+    olo, ohi, br = (U * max(n, 1))(), (U * max(n, 1))(), C.c_int(-7)
+    k = host_math.hm_plan_copy_runs(n, lo, hi, bar, nr, rlo, rhi, olo, ohi, max(n, 1), C.byref(br))
+    return [(olo[i], ohi[i]) for i in range(k)], br.value
+
+
+def _copy_runs_rule(ranges, regs):
+    """The rule, stated plainly: a range joins the run before it when it starts at most 4096 bytes past that run's end and lies in the
+    same page-locked registration; the narrowed index block (barrier) is a run of its own that nothing joins."""
+    def reg(lo, hi):
+        return next((k for k, (a, b) in enumerate(regs) if a <= lo and hi <= b), -1)
+    runs, bar, open_reg = [], -1, -1
+    for lo, hi, barrier in ranges:
+        r = -1 if barrier else reg(lo, hi)
+        if r >= 0 and r == open_reg and lo <= runs[-1][1] + 4096:
+            runs[-1][1] = max(runs[-1][1], hi)
+        else:
+            bar = len(runs) if barrier else bar
+            runs.append([lo, hi])
+        open_reg = r
+    return [tuple(x) for x in runs], bar
+
+
+def test_copy_runs_never_span_two_registrations(host_math):
+    """plan_copy_runs (lba_pack.cpp): which of a refill's page-locked arrays go up the link as ONE copy of the copy engine.  Neighbours within
+    a page of each other merge - but only inside one registration (slslam_pinned_alloc / _register): a copy whose source spans two
+    registrations, abutting or a page apart, reads memory the runtime knows as two separate ranges.  The narrowed index block is a run of
+    its own.  Hand-made tables with their expected runs, then random ones against the rule stated in Python."""
+    A = 1 << 40
+    big = [(A, A + (1 << 20))]
+    cases = [
+        # abutting registrations: two copies, however close the arrays
+        ([(A + 4096, A + 8192, 0), (A + 8192, A + 9000, 0)], [(A, A + 8192), (A + 8192, A + 16384)],
+         [(A + 4096, A + 8192), (A + 8192, A + 9000)], -1),
+        # registrations one page apart: the gap is exactly 4096 bytes, still two copies
+        ([(A + 7000, A + 8192, 0), (A + 12288, A + 13000, 0)], [(A, A + 8192), (A + 12288, A + 20480)],
+         [(A + 7000, A + 8192), (A + 12288, A + 13000)], -1),
+        # inside one registration: a gap of exactly 4096 bytes merges, 4097 does not
+        ([(A, A + 100, 0), (A + 4196, A + 4300, 0), (A + 8397, A + 8400, 0)], big, [(A, A + 4300), (A + 8397, A + 8400)], -1),
+        # the narrowed block (outside the registry) between two arrays of one registration: three copies, nothing merges across it
+        ([(A, A + 100, 0), (A + 200, A + 300, 1), (A + 400, A + 500, 0)], [(A, A + 100), (A + 400, A + 8192)],
+         [(A, A + 100), (A + 200, A + 300), (A + 400, A + 500)], 1),
+        ([(A, A + 100, 0), (A + 200, A + 300, 1), (A + 400, A + 500, 0)], big, [(A, A + 100), (A + 200, A + 300), (A + 400, A + 500)], 1),
+        # overlapping ranges (two sets over the same arrays): one copy; the run's end is the furthest end, not the last range's
+        ([(A, A + 10000, 0), (A + 100, A + 200, 0), (A + 500, A + 800, 0), (A + 13000, A + 14000, 0), (A + 13500, A + 13600, 0)], big,
+         [(A, A + 14000)], -1),
+        # a range in no registration is a copy of its own
+        ([(A, A + 100, 0), (A + 200, A + 300, 0)], [(A, A + 150)], [(A, A + 100), (A + 200, A + 300)], -1),
+        ([], big, [], -1),
+    ]
+    for ranges, regs, want, want_bar in cases:
+        got = _copy_runs(host_math, ranges, regs)
+        assert got == (want, want_bar), (ranges, regs, got)
+        assert _copy_runs_rule(ranges, regs) == (want, want_bar)
+    rng = np.random.default_rng(11)
+    for trial in range(400):
+        regs, at = [], A
+        for _ in range(int(rng.integers(1, 6))):
+            at += int(rng.choice([0, 4096, 4097, 8192, int(rng.integers(1, 20000))]))     # abutting, one page apart, a little more, far
+            size = int(rng.integers(1, 40000))
+            regs.append((at, at + size)); at += size
+        ranges = []
+        for _ in range(int(rng.integers(0, 30))):
+            a, b = regs[int(rng.integers(len(regs)))]
+            lo = a + int(rng.integers(0, b - a)); hi = lo + 1 + int(rng.integers(0, b - lo))
+            ranges.append((lo, min(hi, b), 0))
+        if rng.random() < 0.5:
+            lo = (regs[-1][1] if rng.random() < 0.5 else A) + int(rng.integers(0, 5000))
+            ranges.append((lo, lo + int(rng.integers(1, 9000)), 1))
+        ranges.sort(key=lambda r: r[0])
+        got = _copy_runs(host_math, ranges, regs)
+        assert got == _copy_runs_rule(ranges, regs), (trial, ranges, regs)
+        runs, bar = got
+        # every run lies in one registration (the barrier's aside), and every range in a run
+        for k, (lo, hi) in enumerate(runs):
+            if k != bar:
+                assert any(a <= lo and hi <= b for a, b in regs), (trial, lo, hi)
+        for lo, hi, _ in ranges:
+            assert any(a <= lo and hi <= b for a, b in runs)
+
+
 def test_packer_layout_matches_the_golden_digest(host_math):
     """Everything pack_window emits for a fixed family of windows (bench shapes, wide tracks, 20 free cameras, motion-only, scrambled order
     with holes and constant lines), both packings, against tests/golden/packer_digest.json (made by tests/golden/make_packer_digest.py): a
