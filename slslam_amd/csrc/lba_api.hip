@@ -100,15 +100,24 @@ extern "C" const char* slslam_status_string(int s) {
 
 namespace {
 
+// The owners below free what they hold when they go; they are not copied (a copy would free it twice) and not moved (a DeviceArena
+// keeps the addresses of the DevBufs it fills in).
+struct NoCopy {
+  NoCopy() = default;
+  NoCopy(const NoCopy&) = delete;
+  NoCopy& operator=(const NoCopy&) = delete;
+};
+
 template <typename T>
-struct DevBuf {
+struct DevBuf : NoCopy {
   T* p = nullptr;
   size_t n = 0;
   bool in_arena = false;            // carved out of a DeviceArena: the arena frees it
+  ~DevBuf() { release(); }
   int alloc(size_t count) {
-    n = count; in_arena = false;
-    if (count == 0) { p = nullptr; return SLSLAM_OK; }
-    HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
+    release();
+    if (count > 0) HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
+    n = count;
     return SLSLAM_OK;
   }
   void release() { if (p && !in_arena) (void)hipFree(p); p = nullptr; n = 0; in_arena = false; }
@@ -116,16 +125,17 @@ struct DevBuf {
 
 // Results on the host: pageable, or pinned for a batch that is refilled (its downloads are asynchronous copies).
 template <typename T>
-struct HostArr {
+struct HostArr : NoCopy {
   T* p = nullptr;
   size_t n = 0;
   bool pinned = false;
   std::vector<T> v;
-  int alloc(size_t count, bool pin) {
+  ~HostArr() { release(); }
+  int alloc(size_t count, bool pin, bool zero = true) {        // (zero = false: a staging block, written before it is read)
     release();
-    n = count; pinned = pin && count > 0;
-    if (pinned) { HIP_TRY(hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault)); std::memset((void*)p, 0, count * sizeof(T)); }
+    if (pin && count > 0) { HIP_TRY(hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault)); pinned = true; if (zero) std::memset((void*)p, 0, count * sizeof(T)); }
     else { v.assign(count, T()); p = v.data(); }
+    n = count;
     return SLSLAM_OK;
   }
   void release() { if (pinned && p) (void)hipHostFree(p); p = nullptr; n = 0; pinned = false; std::vector<T>().swap(v); }
@@ -144,7 +154,7 @@ struct HostArr {
 // it (fill_window, one window per host thread) and the image goes up in one copy.  A batch that is to be refilled
 // (slslam_solver_options.refill_headroom_percent > 0) keeps the image, in pinned memory: slslam_lba_batch_refill packs the next set of
 // windows into it and uploads the arrays with asynchronous copies on the caller's stream.
-struct DeviceArena {
+struct DeviceArena : NoCopy {
   struct Item { void** pp; size_t bytes; const void* host; size_t host_bytes; int group; size_t off; };   // group 0 uploaded, 1 scratch, 2 zeroed
   std::vector<Item> items;
   char* base = nullptr;
@@ -152,10 +162,10 @@ struct DeviceArena {
   int device = 0;
   bool cached = false;              // one-shot solves: the block comes from / returns to the thread's DeviceBlockCache
   char* stage = nullptr;            // host image of the uploaded arrays (offsets as on the device)
-  size_t stage_bytes = 0;
   bool stage_pinned = false;        // hipHostMalloc'ed and kept for refills; otherwise a vector that lives until push()
   bool keep_stage = false;
   std::vector<char> stage_vec;
+  ~DeviceArena() { release(); }
   template <typename T>
   void add(DevBuf<T>& d, size_t count, const T* host, size_t host_count, int group) {
     d.n = count; d.in_arena = true; d.p = nullptr;
@@ -192,7 +202,6 @@ struct DeviceArena {
       stage_vec.assign(upload_end, 0);
       stage = stage_vec.data();
     }
-    stage_bytes = upload_end;
     for (const Item& it : items) {
       *it.pp = base + it.off;
       if (it.host && it.host_bytes) std::memcpy(stage + it.off, it.host, it.host_bytes);
@@ -285,16 +294,13 @@ struct slslam_lba_batch {
   DevBuf<RawWin> d_rawwin; DevBuf<BuildWin> d_buildwin; DevBuf<uint32_t> d_raw_idx, d_fmask; DevBuf<double> d_line_raw; DevBuf<uint8_t> d_lflags;
   DevBuf<int> d_item_base, d_totals, d_line_pos;
   DevBuf<uint32_t> d_mid_keys; DevBuf<BuildLine> d_mid_li; DevBuf<uint4> d_mid_rows; DevBuf<uint16_t> d_mid_next, d_mid_trows, d_mid_tptr; DevBuf<BuildMid> d_mid;
-  RawWin* h_rawwin = nullptr;                // pinned [B]: what the device reads of every window (uploaded per refill)
-  BuildWin* h_buildwin = nullptr;            // pinned [B]: what came of every window (downloaded with the results)
-  WinDesc* h_wins_dl = nullptr;              // pinned [B]: the descriptors the device made
-  int* h_totals = nullptr;                   // pinned [8]
-  char* h_raw_stage = nullptr;               // pinned, made on demand: pageable inputs are copied here (indices narrowed on the way)
-  size_t raw_stage_bytes = 0;
-  char* d_stage_in = nullptr;                // device, made on demand: where the copy engine puts a refill's arrays (k_ingest reads them from here)
-  size_t d_stage_bytes = 0;
+  HostArr<RawWin> h_rawwin;                  // pinned [B]: what the device reads of every window (uploaded per refill)
+  HostArr<BuildWin> h_buildwin;              // pinned [B]: what came of every window (downloaded with the results)
+  HostArr<WinDesc> h_wins_dl;                // pinned [B]: the descriptors the device made
+  HostArr<int> h_totals;                     // pinned [8]
+  HostArr<char> h_raw_stage;                 // pinned, made on demand: pageable inputs are copied here (indices narrowed on the way)
+  DevBuf<char> d_stage_in;                   // device, made on demand: where the copy engine puts a refill's arrays (k_ingest reads them from here)
   std::vector<RawWin> host_src;              // per window: host-readable pointers to what the device was given (the callers' page-locked arrays, or the staging copy)
-  int ingest_mode = 0;                       // of the last device-built refill: 0 zero-copy kernel reads of the callers' page-locked arrays, 1 copy engine
   bool ingest_pinned = false;                // ... its observations and parameters were read where the caller holds them (page-locked), no staging copy
   bool device_built = false;                 // the batch's present windows were built on the device
   bool inplace_export = false;               // ... and their `parameters` arrays are pinned: results can be written straight into them
@@ -320,6 +326,7 @@ struct slslam_lba_batch {
   long long nobs = 0;
   int num_cus = 256;
   bool fused_motion_only = false;
+  bool share_cam_tab = false;            // the sweeps read the camera tables of a window from d_cam_tab (BatchPtrs.cam_tab)
   size_t lds_motion_only = 0;
   size_t lds_lin = 0, lds_solve = 0, lds_bs = 0, lds_bs_stream = 0, lds_cost = 0;
   // graph
@@ -355,26 +362,12 @@ struct slslam_lba_batch {
     ev_used.clear(); ev_next = 0;
   }
 
+  // what the batch owns (the DevBufs of the arena only point into it; the parts of a mixed batch: drop_parts)
   void release() {
-    d_sys_map.release(); d_wins.release(); d_tiles.release(); d_chunks.release(); d_items.release(); d_lane_map.release(); d_lane_ctx.release(); d_line_desc.release(); d_dbg_cycles.release();
-    d_cam_x.release(); d_cam_x0.release(); d_cam_scale.release(); d_cam_tab.release(); d_cam_cf.release(); d_cam_win.release();
-    d_line_x.release(); d_line_x0.release(); d_line_scale.release(); d_line_ptr.release(); d_line_flags.release();
-    d_line_win.release(); d_line_orig.release(); d_ob.release(); d_ob_cam.release(); d_ob_orig.release(); d_ob_raw.release();
-    d_slab.release(); d_bs_part.release(); d_cost_part.release(); d_ysys.release(); d_params_out.release();
-    d_state.release(); d_trace.release(); d_param_off.release(); d_iter_counter.release(); d_active.release();
-    d_fstore.release(); d_line_elim.release(); d_line_h.release(); d_slab_sum.release();
-    d_rawwin.release(); d_buildwin.release(); d_raw_idx.release(); d_fmask.release(); d_line_raw.release(); d_lflags.release(); d_item_base.release(); d_totals.release(); d_line_pos.release();
-    d_mid_keys.release(); d_mid_li.release(); d_mid_rows.release(); d_mid_next.release(); d_mid_trows.release(); d_mid_tptr.release(); d_mid.release();
-    if (h_rawwin) (void)hipHostFree(h_rawwin); if (h_buildwin) (void)hipHostFree(h_buildwin); if (h_wins_dl) (void)hipHostFree(h_wins_dl);
-    if (h_totals) (void)hipHostFree(h_totals); if (h_raw_stage) (void)hipHostFree(h_raw_stage);
-    if (d_stage_in) (void)hipFree(d_stage_in);
-    d_stage_in = nullptr; d_stage_bytes = 0;
-    h_rawwin = nullptr; h_buildwin = nullptr; h_wins_dl = nullptr; h_totals = nullptr; h_raw_stage = nullptr; raw_stage_bytes = 0;
-    d_big_ob_line.release(); d_big_cam_ptr.release(); d_big_cam_obs.release(); d_big_pair_ptr.release(); d_big_pair_row.release();
-    d_big_pair_col.release(); d_big_pair_desc.release(); d_big_flags.release(); d_big_J.release(); d_big_F.release(); d_big_cost.release();
-    d_big_camtab.release(); d_big_line_acc.release(); d_big_sys.release(); d_big_scal.release(); d_big_linv.release(); d_big_sys_off.release();
     arena.release();
+    d_stage_in.release();
     h_state.release(); h_trace.release(); h_params.release();
+    h_rawwin.release(); h_buildwin.release(); h_wins_dl.release(); h_totals.release(); h_raw_stage.release();
     if (ev_stage_free) { (void)hipEventDestroy(ev_stage_free); ev_stage_free = nullptr; }
     if (ev_results) { (void)hipEventDestroy(ev_results); ev_results = nullptr; }
     if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
@@ -399,13 +392,23 @@ extern "C" int slslam_lba_batch_create(int device, slslam_lba_batch** out) {
   return SLSLAM_OK;
 }
 
+namespace {
+// The two parts of a mixed batch and what routes between them (see `part`): on destroy and after a failed finalize_mixed
+void drop_parts(slslam_lba_batch* b) {
+  for (int h = 0; h < 2; ++h) {
+    if (b->part[h]) { slslam_lba_batch_destroy(b->part[h]); b->part[h] = nullptr; }
+    b->d_part_out[h].release(); b->d_part_off[h].release(); b->part_param_off[h].clear();
+  }
+  if (b->part_stream) { (void)hipStreamSynchronize(b->part_stream); (void)hipStreamDestroy(b->part_stream); b->part_stream = nullptr; }
+  if (b->part_fork) { (void)hipEventDestroy(b->part_fork); b->part_fork = nullptr; }
+  if (b->part_join) { (void)hipEventDestroy(b->part_join); b->part_join = nullptr; }
+}
+}  // namespace
+
 extern "C" void slslam_lba_batch_destroy(slslam_lba_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  for (int h = 0; h < 2; ++h) if (b->part[h]) { slslam_lba_batch_destroy(b->part[h]); b->part[h] = nullptr; b->d_part_out[h].release(); }
-  if (b->part_stream) { (void)hipStreamSynchronize(b->part_stream); (void)hipStreamDestroy(b->part_stream); }
-  if (b->part_fork) (void)hipEventDestroy(b->part_fork);
-  if (b->part_join) (void)hipEventDestroy(b->part_join);
+  drop_parts(b);
   b->release();
   delete b;
 }
@@ -435,13 +438,7 @@ int finalize_mixed(slslam_lba_batch* b) {
     if (pb && (size_t)b->route[i].second < pb->wins.size()) back[i] = std::move(pb->wins[(size_t)b->route[i].second]);
   }
   if (b->wins.empty() && !b->route.empty()) b->wins = std::move(back);
-  for (int h = 0; h < 2; ++h) {
-    if (b->part[h]) { slslam_lba_batch_destroy(b->part[h]); b->part[h] = nullptr; }
-    b->d_part_out[h].release(); b->d_part_off[h].release(); b->part_param_off[h].clear();
-  }
-  if (b->part_stream) { (void)hipStreamDestroy(b->part_stream); b->part_stream = nullptr; }
-  if (b->part_fork) { (void)hipEventDestroy(b->part_fork); b->part_fork = nullptr; }
-  if (b->part_join) { (void)hipEventDestroy(b->part_join); b->part_join = nullptr; }
+  drop_parts(b);
   b->route.clear(); b->finalized = false;
   return rc;
 }
@@ -507,6 +504,7 @@ struct LayoutPlan {
   std::vector<Chunk> chunks;                    // dispatch order
   long long ncam = 0, nline = 0, nobs = 0, ntiles = 0, nitems = 0, sys = 0, slab = 0, params = 0;
   int maxC = 1, maxn = 0, max_chunks = 0, max_sys = 0;
+  std::vector<uint16_t> sys_map;                // (finalize) the reduced solve's LDS maps, one per system order
 };
 
 int plan_layout(slslam_lba_batch* b, const std::vector<PackedWindow>& wins, bool frozen, LayoutPlan* out) {
@@ -689,7 +687,9 @@ bool run_all(HostPool* pool, int n, const std::function<void(int)>& fn) {
   return ok;
 }
 
-HostPool* batch_pool(slslam_lba_batch* b, int threads) {
+// The host threads for n independent windows: slslam_solver_options.host_threads of them, else 8 from 64 windows on - never more than n
+HostPool* batch_pool(slslam_lba_batch* b, size_t n) {
+  int threads = (int)std::min<size_t>(n, b->opt.host_threads > 0 ? (size_t)b->opt.host_threads : (n >= 64 ? 8 : 1));
   if (threads <= 1) return nullptr;
   if (b->ext_pool) return b->ext_pool;
   const int hw = (int)std::thread::hardware_concurrency();
@@ -756,102 +756,107 @@ int device_init_after_upload(slslam_lba_batch* b, hipStream_t s) {
   return SLSLAM_OK;
 }
 
-}  // namespace
+// What the uploaded / scratch arrays of a batch get for `used` elements: that, or for a refillable batch room for refill_headroom_percent more
+size_t room(const slslam_lba_batch* b, long long used) {
+  const long long pct = b->refillable ? std::min(b->opt.refill_headroom_percent, 400) : 0;
+  return (size_t)(b->refillable ? used + (used * pct) / 100 + 64 : used);
+}
 
-extern "C" int slslam_lba_batch_finalize(slslam_lba_batch* b, const slslam_solver_options* opt) {
-  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (b->finalized) return SLSLAM_ERR_STATE;
-  if (opt) b->opt = *opt;
-  if (b->opt.max_num_iterations < 0 || b->opt.max_num_iterations > 100000) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (!(b->opt.initial_trust_region_radius > 0.0) || !(b->opt.baseline == b->opt.baseline)) return SLSLAM_ERR_INVALID_ARGUMENT;
-  b->pol = make_policy(b->opt);
-  HIP_TRY(hipSetDevice(b->device));
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) == hipSuccess && cus > 0) b->num_cus = cus;
+// The kernels' dynamic LDS limit, where a launch needs more than the default
+hipError_t allow_lds(std::initializer_list<const void*> kernels, size_t bytes) {
+  for (const void* k : kernels) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
   }
+  return hipSuccess;
+}
+
+// The slab-sum stride of windows whose sums go straight into the LDS image of the reduced solve (BatchPtrs.slab_sum_image)
+long long slab_sum_image_stride(const std::vector<WinDesc>& wins) {
+  long long ext = 0;
+  for (const WinDesc& wd : wins) { const int N = solve_pad(wd.n); ext = std::max<long long>(ext, (long long)N * solve_stride(wd.n) + 6LL * N); }
+  return ((ext + kSlabScalars + 1) / 2) * 2;
+}
+
+// ---- which elimination sweep: the matrix-core one (lba_eliminate_mfma.h) needs the reduced system in the registers of
+// one workgroup (<= 10 free cameras) and one observation per (line, free camera); everything else takes the LDS-atomic sweep.
+// *mixed: the batch was finalized as a mixed batch (finalize_mixed), with that result.
+int choose_sweep(slslam_lba_batch* b, bool* mixed) {
+  *mixed = false;
   const int B = (int)b->wins.size();
-
-  // ---- which elimination sweep: the matrix-core one (lba_eliminate_mfma.h) needs the reduced system in the registers of
-  // one workgroup (<= 10 free cameras) and one observation per (line, free camera); everything else takes the LDS-atomic sweep
-  {
-    bool mfma_ok = !b->opt.reuse_elimination && b->opt.max_num_iterations > 0 && B > 0;
-    for (const PackedWindow& P : b->wins) if (P.Cf > kMfmaMaxFree || P.dup_free_obs) mfma_ok = false;
-    int want = b->opt.lba_elimination;
-    if (want < 0 || want > 4 || b->opt.lba_precision < 0 || b->opt.lba_precision > 1) return SLSLAM_ERR_INVALID_ARGUMENT;
-    // mixed precision lives in the grouped matrix-core sweep: asked for, it is that sweep or nothing
-    b->elim_mixed = b->opt.lba_precision == 1;
-    if (b->elim_mixed) {
-      if (want == 0) want = 4;
-      if (want != 4 || b->opt.reuse_elimination || b->opt.max_num_iterations <= 0) return SLSLAM_ERR_UNSUPPORTED;
-    }
-    // automatic = the LDS-atomic sweep: the matrix-core sweep measures slower on MI355X - not because of the matrix pipe (a wave
-    // issues a v_mfma_f64_16x16x4_f64 every 64 cycles, tools/micro/mfma_f64_bench.hip) but because of its operand path through
-    // LDS and its front end
-    b->big_mode = false;
-    int nbig = 0;
-    for (const PackedWindow& P : b->wins) if (P.big) { b->big_mode = true; ++nbig; }
-    if (nbig > 0 && nbig < B && !b->opt.reuse_elimination) return finalize_mixed(b);       // oversize windows apart (see `part`)
-    if (b->big_mode) { mfma_ok = false; if (b->opt.reuse_elimination) return SLSLAM_ERR_UNSUPPORTED; }
-    if (b->elim_mixed && !mfma_ok) return SLSLAM_ERR_UNSUPPORTED;
-    // automatic (0): the grouped matrix-core sweep (lba_eliminate_grouped.h) for a batch that fills the chip with long chunks -
-    // there it measures faster than the LDS-atomic sweep (1.20 against 1.27 ms per launch on the 1024 x 2000-line batch, DESIGN.md
-    // section 7d); a small batch cuts its windows into chunks of a tile or two, for which the grouped sweep's per-chunk work
-    // (zeroing its 20 KB of accumulator tiles in memory, adding the group sums into them) is not worth it
-    long long tiles_in_batch = 0;
-    for (const PackedWindow& P : b->wins) tiles_in_batch += (long long)P.tiles.size();
-    // (reproducible: no choice by the batch - 0 means the LDS-atomic sweep, and a requested matrix-core sweep is run or refused)
-    if (b->opt.reproducible && want >= 2 && !mfma_ok) return SLSLAM_ERR_UNSUPPORTED;
-    const bool auto_grouped = want == 0 && !b->opt.reproducible && mfma_ok && b->opt.chunks_per_window == 0 && tiles_in_batch >= 16LL * 8 * b->num_cus;
-    b->elim_mode = ((want >= 2 || auto_grouped) && mfma_ok) ? 1 : 0;
-    b->elim_waves = b->elim_mode == 0 ? 1 : (want == 3 ? 2 : 1);
-    b->elim_grouped = b->elim_mode == 1 && (want == 4 || auto_grouped);
-    b->pol.keep_jacobian = (b->elim_grouped && !b->elim_mixed && b->opt.lba_keep_jacobian && b->opt.max_num_iterations > 1) ? 1 : 0;
-    {
-      // the grouped sweep wants the lines of a window in the order of their first free camera: pack again (the default packing
-      // deals rows to the tiles by pair-item count, which this sweep has no use for).  Both directions: a batch whose finalize failed
-      // after this point keeps its windows as they are now, and a second attempt with another sweep must not read line descriptors in
-      // the other layout
-      const int want_grouping = b->elim_grouped ? 1 : 0;
-      std::vector<int> todo;
-      for (int wi = 0; wi < B; ++wi) if (b->wins[(size_t)wi].grouping != want_grouping && !b->wins[(size_t)wi].big) todo.push_back(wi);
-      std::vector<int> st(todo.size(), SLSLAM_OK);
-      auto one = [&](int q) {
-        PackedWindow Q;
-        st[(size_t)q] = repack_window(b->wins[(size_t)todo[(size_t)q]], want_grouping, &Q);
-        if (st[(size_t)q] == SLSLAM_OK) b->wins[(size_t)todo[(size_t)q]] = std::move(Q);
-      };
-      HostPool* pool = batch_pool(b, (int)std::min<size_t>(todo.size(), b->opt.host_threads > 0 ? (size_t)b->opt.host_threads : (todo.size() >= 64 ? 8 : 1)));
-      if (!run_all(pool, (int)todo.size(), one)) return SLSLAM_ERR_NO_MEMORY;
-      for (int r : st) if (r != SLSLAM_OK) return r;
-    }
+  bool mfma_ok = !b->opt.reuse_elimination && b->opt.max_num_iterations > 0 && B > 0;
+  for (const PackedWindow& P : b->wins) if (P.Cf > kMfmaMaxFree || P.dup_free_obs) mfma_ok = false;
+  int want = b->opt.lba_elimination;
+  if (want < 0 || want > 4 || b->opt.lba_precision < 0 || b->opt.lba_precision > 1) return SLSLAM_ERR_INVALID_ARGUMENT;
+  // mixed precision lives in the grouped matrix-core sweep: asked for, it is that sweep or nothing
+  b->elim_mixed = b->opt.lba_precision == 1;
+  if (b->elim_mixed) {
+    if (want == 0) want = 4;
+    if (want != 4 || b->opt.reuse_elimination || b->opt.max_num_iterations <= 0) return SLSLAM_ERR_UNSUPPORTED;
   }
+  // automatic = the LDS-atomic sweep: the matrix-core sweep measures slower on MI355X - not because of the matrix pipe (a wave
+  // issues a v_mfma_f64_16x16x4_f64 every 64 cycles, tools/micro/mfma_f64_bench.hip) but because of its operand path through
+  // LDS and its front end
+  b->big_mode = false;
+  int nbig = 0;
+  for (const PackedWindow& P : b->wins) if (P.big) { b->big_mode = true; ++nbig; }
+  if (nbig > 0 && nbig < B && !b->opt.reuse_elimination) { *mixed = true; return finalize_mixed(b); }       // oversize windows apart (see `part`)
+  if (b->big_mode) { mfma_ok = false; if (b->opt.reuse_elimination) return SLSLAM_ERR_UNSUPPORTED; }
+  if (b->elim_mixed && !mfma_ok) return SLSLAM_ERR_UNSUPPORTED;
+  // automatic (0): the grouped matrix-core sweep (lba_eliminate_grouped.h) for a batch that fills the chip with long chunks -
+  // there it measures faster than the LDS-atomic sweep (1.20 against 1.27 ms per launch on the 1024 x 2000-line batch, DESIGN.md
+  // section 7d); a small batch cuts its windows into chunks of a tile or two, for which the grouped sweep's per-chunk work
+  // (zeroing its 20 KB of accumulator tiles in memory, adding the group sums into them) is not worth it
+  long long tiles_in_batch = 0;
+  for (const PackedWindow& P : b->wins) tiles_in_batch += (long long)P.tiles.size();
+  // (reproducible: no choice by the batch - 0 means the LDS-atomic sweep, and a requested matrix-core sweep is run or refused)
+  if (b->opt.reproducible && want >= 2 && !mfma_ok) return SLSLAM_ERR_UNSUPPORTED;
+  const bool auto_grouped = want == 0 && !b->opt.reproducible && mfma_ok && b->opt.chunks_per_window == 0 && tiles_in_batch >= 16LL * 8 * b->num_cus;
+  b->elim_mode = ((want >= 2 || auto_grouped) && mfma_ok) ? 1 : 0;
+  b->elim_waves = b->elim_mode == 0 ? 1 : (want == 3 ? 2 : 1);
+  b->elim_grouped = b->elim_mode == 1 && (want == 4 || auto_grouped);
+  b->pol.keep_jacobian = (b->elim_grouped && !b->elim_mixed && b->opt.lba_keep_jacobian && b->opt.max_num_iterations > 1) ? 1 : 0;
+  // the grouped sweep wants the lines of a window in the order of their first free camera: pack again (the default packing
+  // deals rows to the tiles by pair-item count, which this sweep has no use for).  Both directions: a batch whose finalize failed
+  // after this point keeps its windows as they are now, and a second attempt with another sweep must not read line descriptors in
+  // the other layout
+  const int want_grouping = b->elim_grouped ? 1 : 0;
+  std::vector<int> todo;
+  for (int wi = 0; wi < B; ++wi) if (b->wins[(size_t)wi].grouping != want_grouping && !b->wins[(size_t)wi].big) todo.push_back(wi);
+  std::vector<int> st(todo.size(), SLSLAM_OK);
+  auto one = [&](int q) {
+    PackedWindow Q;
+    st[(size_t)q] = repack_window(b->wins[(size_t)todo[(size_t)q]], want_grouping, &Q);
+    if (st[(size_t)q] == SLSLAM_OK) b->wins[(size_t)todo[(size_t)q]] = std::move(Q);
+  };
+  if (!run_all(batch_pool(b, todo.size()), (int)todo.size(), one)) return SLSLAM_ERR_NO_MEMORY;
+  for (int r : st) if (r != SLSLAM_OK) return r;
+  return SLSLAM_OK;
+}
 
-  // ---- global layout: where every window's slices go (serial: prefix sums and chunk cuts), then the slices themselves (fill_window)
-  LayoutPlan plan;
+// ---- global layout: where every window's slices go (serial: prefix sums and chunk cuts; the slices themselves: fill_and_push), the
+// capacities, the reduced solve's sys_map tables and the initial LM state
+int plan_capacities(slslam_lba_batch* b, LayoutPlan& plan) {
+  const int B = (int)b->wins.size();
   {
     const int prc = plan_layout(b, b->wins, /*frozen=*/false, &plan);
     if (prc != SLSLAM_OK) return prc;
   }
-  const long long ncam = plan.ncam, nline = plan.nline, nobs = plan.nobs, sys = plan.sys, slab = plan.slab, param_off = plan.params;
-  const int maxC = plan.maxC, maxn = plan.maxn;
   b->h_wins = plan.wins; b->h_param_off = plan.param_off; b->h_ob_orig_off = plan.ob_orig_off; b->h_win_graded = plan.win_graded;
   if (b->h_win_graded.empty()) b->h_win_graded.assign(1, 0);
-  b->nobs = nobs;
+  b->nobs = plan.nobs;
   // a batch that is going to be refilled (slslam_lba_batch_refill) gets room beyond what its first windows need: the next windows'
   // observation, line, tile and item counts differ a little
   b->refillable = b->opt.refill_headroom_percent > 0 && !b->big_mode;
-  const long long pct = b->refillable ? std::min(b->opt.refill_headroom_percent, 400) : 0;
-  auto room = [&](long long used) -> size_t { return (size_t)(b->refillable ? used + (used * pct) / 100 + 64 : used); };
-  const size_t cap_cam = std::max<size_t>(1, room(ncam)), cap_line = std::max<size_t>(1, room(nline)), cap_obs = std::max<size_t>(1, room(nobs));
-  const size_t cap_tiles = std::max<size_t>(1, room(plan.ntiles)), cap_items = std::max<size_t>(1, room(plan.nitems));
+  const size_t cap_cam = std::max<size_t>(1, room(b, plan.ncam)), cap_line = std::max<size_t>(1, room(b, plan.nline)), cap_obs = std::max<size_t>(1, room(b, plan.nobs));
   if (cap_obs > 0x7fffffffULL || cap_line > 0x7fffffffULL) return SLSLAM_ERR_UNSUPPORTED;
   // reduced solve: where each entry of a chunk partial goes in its LDS image, one table per distinct system order (a refillable batch:
   // one per free-camera count up to the largest of its first windows - the next windows may have any of them)
-  std::vector<uint16_t> sys_map(1, (uint16_t)0xFFFF);
-  b->sys_map_off_of_cf.assign((size_t)maxn / 6 + 1, -1);
+  std::vector<uint16_t>& sys_map = plan.sys_map;
+  sys_map.assign(1, (uint16_t)0xFFFF);
+  b->sys_map_off_of_cf.assign((size_t)plan.maxn / 6 + 1, -1);
   if (!b->big_mode) {
-    for (int cf = 0; cf <= maxn / 6; ++cf) {
+    for (int cf = 0; cf <= plan.maxn / 6; ++cf) {
       bool wanted = b->refillable;
       for (const WinDesc& wd : b->h_wins) if (wd.n == 6 * cf) wanted = true;
       if (!wanted) continue;
@@ -862,9 +867,9 @@ extern "C" int slslam_lba_batch_finalize(slslam_lba_batch* b, const slslam_solve
   }
   for (WinDesc& wd : b->h_wins) { const int off = b->sys_map_off_of_cf[(size_t)wd.n / 6]; wd.map_off = off < 0 ? 0 : off; }
   // (the chunk array too: a refill may cut its windows into a few more chunks; the launches cover the whole array, unused entries are marked)
-  b->total_params = param_off; b->nchunk = (int)room((long long)plan.chunks.size()); b->nline = (int)cap_line; b->ncam = (int)cap_cam;
-  b->used_ncam = ncam; b->used_nline = nline; b->used_nobs = nobs; b->used_tiles = plan.ntiles; b->used_items = plan.nitems;
-  b->cap_maxC = maxC; b->cap_maxn = maxn;
+  b->total_params = plan.params; b->nchunk = (int)room(b, (long long)plan.chunks.size()); b->nline = (int)cap_line; b->ncam = (int)cap_cam;
+  b->used_ncam = plan.ncam; b->used_nline = plan.nline; b->used_nobs = plan.nobs; b->used_tiles = plan.ntiles; b->used_items = plan.nitems;
+  b->cap_maxC = plan.maxC; b->cap_maxn = plan.maxn;
 
   // ---- initial LM state (Ceres: LevenbergMarquardtStrategy ctor)
   b->h_state0.assign(B, LMState());
@@ -873,14 +878,123 @@ extern "C" int slslam_lba_batch_finalize(slslam_lba_batch* b, const slslam_solve
     std::memset(&st, 0, sizeof(st));
     st.radius = b->pol.initial_radius; st.decrease_factor = 2.0; st.status = kRunning; st.fresh = 1;
   }
+  return SLSLAM_OK;
+}
 
-  // ---- one allocation, one upload
-  int rc;
+// The gather lists of the global-memory path (lba_big.h), uploaded from here: they live until the arena's layout()
+struct BigLists {
+  std::vector<int> big_ob_line, big_cam_ptr, big_cam_obs, big_pair_ptr, big_pair_row, big_pair_col, big_pair_desc;
+  int build(slslam_lba_batch* b, const LayoutPlan& plan);
+};
+
+int BigLists::build(slslam_lba_batch* b, const LayoutPlan& plan) {
+  const int B = (int)b->wins.size();
+  const long long ncam = plan.ncam, nline = plan.nline, nobs = plan.nobs;
+  DeviceArena& ar = b->arena;
+  // gather lists of the global-memory path (lba_big.h): per camera its observations, per (window, camera pair r >= c) the
+  // observation pairs of the lines both cameras see - every sum is walked in list order, so results are reproducible
+  if (B > 0xffff) return SLSLAM_ERR_UNSUPPORTED;
+  // a camera-pair descriptor packs (window, row camera, column camera) as wi | r << 16 | c << 24, decoded with & 0xff (lba_big.h):
+  // more than 127 free cameras would spill into the next field (and shift into the sign bit)
+  for (const PackedWindow& P : b->wins) if (P.Cf > 127) return SLSLAM_ERR_UNSUPPORTED;
+  long long sys_cursor = 0, linv_cursor = 0, oc = 0, lc = 0;
+  b->h_big_sys_off.resize(B); b->h_big_linv_off.resize(B);
+  big_ob_line.reserve((size_t)nobs);
+  big_cam_ptr.assign((size_t)ncam + 1, 0);
+  big_cam_obs.resize((size_t)std::max<long long>(1, nobs));
+  std::vector<int> pr_row, pr_col, pr_id;                  // unsorted items with their global pair id
+  {
+    size_t items = 0, pairs = 0;
+    for (const PackedWindow& P : b->wins) {
+      pairs += (size_t)(P.Cf * (P.Cf + 1)) / 2;
+      for (int s2 = 0; s2 < P.L; ++s2) {
+        if (P.line_flags[s2] & 1) continue;
+        const int o0 = P.line_ptr[s2], k = P.line_ptr[s2 + 1] - o0;
+        int kf = 0;
+        while (kf < k && P.cam_cf[P.ob_cam[o0 + kf]] >= 0) ++kf;
+        items += (size_t)(kf * (kf - 1)) / 2;
+      }
+    }
+    pr_row.reserve(items); pr_col.reserve(items); pr_id.reserve(items); big_pair_desc.reserve(pairs);
+  }
+  long long pair_base = 0;
+  for (int wi = 0; wi < B; ++wi) {
+    const PackedWindow& P = b->wins[wi];
+    const int cam_off = b->h_wins[wi].cam_off;
+    b->h_big_sys_off[wi] = sys_cursor; sys_cursor += big_sys_doubles(6 * P.Cf);
+    b->h_big_linv_off[wi] = linv_cursor; linv_cursor += (long long)((6 * P.Cf + kNB - 1) / kNB + 1) * kNB * kNB;
+    for (int o = 0; o < P.M; ++o) big_cam_ptr[(size_t)cam_off + P.ob_cam[o] + 1]++;
+    for (int r = 0; r < P.Cf; ++r)
+      for (int c = 0; c <= r; ++c) big_pair_desc.push_back(wi | (r << 16) | (c << 24));
+    for (int s2 = 0; s2 < P.L; ++s2) {
+      const int o0 = P.line_ptr[s2], k = P.line_ptr[s2 + 1] - o0;
+      for (int j = 0; j < k; ++j) big_ob_line.push_back((int)lc + s2);
+      if (P.line_flags[s2] & 1) continue;
+      int kf = 0;                                        // free-camera observations come first
+      while (kf < k && P.cam_cf[P.ob_cam[o0 + kf]] >= 0) ++kf;
+      for (int i = 0; i < kf; ++i)
+        for (int j = i + 1; j < kf; ++j) {
+          const int ci = P.cam_cf[P.ob_cam[o0 + i]], cj = P.cam_cf[P.ob_cam[o0 + j]];
+          const bool jr = cj >= ci;                      // row: the camera with the larger free index (lower triangle)
+          const int r = jr ? cj : ci, c = jr ? ci : cj;
+          pr_row.push_back((int)(oc + o0 + (jr ? j : i))); pr_col.push_back((int)(oc + o0 + (jr ? i : j)));
+          pr_id.push_back((int)(pair_base + (r * (r + 1)) / 2 + c));
+        }
+    }
+    pair_base += (long long)(P.Cf * (P.Cf + 1)) / 2;
+    oc += P.M; lc += P.L;
+  }
+  for (size_t c = 0; c < (size_t)ncam; ++c) big_cam_ptr[c + 1] += big_cam_ptr[c];
+  {
+    std::vector<int> fill(big_cam_ptr.begin(), big_cam_ptr.end() - 1);
+    long long og = 0;
+    for (int wi = 0; wi < B; ++wi) {
+      const PackedWindow& P = b->wins[wi];
+      for (int o = 0; o < P.M; ++o, ++og) big_cam_obs[(size_t)fill[(size_t)b->h_wins[wi].cam_off + P.ob_cam[o]]++] = (int)og;
+    }
+  }
+  const size_t npairs = big_pair_desc.size();
+  big_pair_ptr.assign(npairs + 1, 0);
+  for (int id : pr_id) big_pair_ptr[(size_t)id + 1]++;
+  for (size_t q = 0; q < npairs; ++q) big_pair_ptr[q + 1] += big_pair_ptr[q];
+  big_pair_row.resize(std::max<size_t>(1, pr_id.size())); big_pair_col.resize(std::max<size_t>(1, pr_id.size()));
+  {
+    std::vector<int> fill(big_pair_ptr.begin(), big_pair_ptr.end() - 1);          // counting sort: items of a pair stay in line order
+    for (size_t q = 0; q < pr_id.size(); ++q) { const int at = fill[(size_t)pr_id[q]]++; big_pair_row[(size_t)at] = pr_row[q]; big_pair_col[(size_t)at] = pr_col[q]; }
+  }
+  if (big_ob_line.empty()) big_ob_line.push_back(0);
+  b->big.npairs = (long long)npairs;
+  if (big_pair_desc.empty()) big_pair_desc.push_back(0);
+  ar.upload(b->d_big_ob_line, big_ob_line);
+  ar.upload(b->d_big_cam_ptr, big_cam_ptr);
+  ar.upload(b->d_big_cam_obs, big_cam_obs);
+  ar.upload(b->d_big_pair_ptr, big_pair_ptr);
+  ar.upload(b->d_big_pair_row, big_pair_row);
+  ar.upload(b->d_big_pair_col, big_pair_col);
+  ar.upload(b->d_big_pair_desc, big_pair_desc);
+  ar.upload(b->d_big_sys_off, b->h_big_sys_off);
+  ar.scratch(b->d_big_J, (size_t)std::max<long long>(1, nobs) * kBigObs);
+  ar.scratch(b->d_big_F, (size_t)std::max<long long>(1, nobs) * kBigF);
+  ar.scratch(b->d_big_cost, (size_t)std::max<long long>(1, nobs) * 2);
+  ar.scratch(b->d_big_camtab, (size_t)std::max<long long>(1, ncam) * 2 * kBigCam);
+  ar.zeroed(b->d_big_line_acc, (size_t)std::max<long long>(1, nline) * kBigLine);
+  ar.zeroed(b->d_big_sys, (size_t)std::max<long long>(1, sys_cursor));
+  ar.zeroed(b->d_big_scal, (size_t)std::max(1, B) * kBgScal);
+  ar.zeroed(b->d_big_flags, (size_t)std::max(1, B) * 2);
+  ar.scratch(b->d_big_linv, (size_t)std::max<long long>(1, linv_cursor));
+  return SLSLAM_OK;
+}
+
+// ---- one allocation, one upload: every device array of the batch reserved in the arena, then laid out
+int reserve_arena(slslam_lba_batch* b, const LayoutPlan& plan, BigLists* big_lists) {
+  const int B = (int)b->wins.size();
+  const size_t cap_cam = (size_t)b->ncam, cap_line = (size_t)b->nline, cap_obs = std::max<size_t>(1, room(b, plan.nobs));
+  const size_t cap_tiles = std::max<size_t>(1, room(b, plan.ntiles)), cap_items = std::max<size_t>(1, room(b, plan.nitems));
   DeviceArena& ar = b->arena;
   ar.device = b->device;
   ar.keep_stage = b->refillable;
   ar.staged(b->d_wins, (size_t)std::max(1, B));
-  ar.upload(b->d_sys_map, sys_map);
+  ar.upload(b->d_sys_map, plan.sys_map);
   ar.staged(b->d_tiles, cap_tiles);
   ar.staged(b->d_chunks, (size_t)std::max(1, b->nchunk));
   ar.staged(b->d_items, 2 * cap_items);
@@ -899,8 +1013,8 @@ extern "C" int slslam_lba_batch_finalize(slslam_lba_batch* b, const slslam_solve
   // the other paths (reuse_elimination, streamed F, matrix-core sweep) keep building their tables per sweep.  Small batches only:
   // there a chunk is a tile or two and the tables are a tenth of a sweep; in a batch that fills the chip a chunk is ~33 tiles, the
   // tables are nothing, and reading them would add 30 MB to a sweep's traffic
-  const bool share_cam_tab = B <= b->num_cus && !b->big_mode && !b->fused_motion_only && b->elim_mode == 0 && !b->opt.reuse_elimination && !b->pol.store_f && b->opt.max_num_iterations > 0 && !(b->pol.debug_flags & 16384);
-  ar.zeroed(b->d_cam_tab, share_cam_tab ? std::max<size_t>(1, (size_t)2 * kCamTab * cap_cam) : 1);
+  b->share_cam_tab = B <= b->num_cus && !b->big_mode && !b->fused_motion_only && b->elim_mode == 0 && !b->opt.reuse_elimination && !b->pol.store_f && b->opt.max_num_iterations > 0 && !(b->pol.debug_flags & 16384);
+  ar.zeroed(b->d_cam_tab, b->share_cam_tab ? std::max<size_t>(1, (size_t)2 * kCamTab * cap_cam) : 1);
   ar.staged(b->d_cam_cf, cap_cam);
   ar.staged(b->d_cam_win, cap_cam);
   // both parameter buffers, buffer-major [2][nline][kLineRec]: (a, b, g, t) | sin/cos table (filled on the device)
@@ -931,7 +1045,7 @@ extern "C" int slslam_lba_batch_finalize(slslam_lba_batch* b, const slslam_solve
   }
   ar.staged(b->d_ob_cam, cap_obs);
   ar.staged(b->d_ob_orig, cap_obs);
-  ar.scratch(b->d_slab, std::max<size_t>(1, room(slab)));
+  ar.scratch(b->d_slab, std::max<size_t>(1, room(b, plan.slab)));
   {
     // windows cut into many chunks (small batches): their partials are summed by a kernel of their own, spread over the chip
     const int max_chunks = plan.max_chunks, max_sys = plan.max_sys;
@@ -940,161 +1054,77 @@ extern "C" int slslam_lba_batch_finalize(slslam_lba_batch* b, const slslam_solve
     // once, here)
     b->slab_sum_image = b->slab_sum_stride && b->elim_mode == 0;
     if (b->slab_sum_image) {
-      long long ext = 0;
-      for (const WinDesc& wd : b->h_wins) { const int N = solve_pad(wd.n); ext = std::max<long long>(ext, (long long)N * solve_stride(wd.n) + 6LL * N); }
-      b->slab_sum_stride = ((ext + kSlabScalars + 1) / 2) * 2;
+      b->slab_sum_stride = slab_sum_image_stride(b->h_wins);
       ar.zeroed(b->d_slab_sum, (size_t)b->slab_sum_stride * (size_t)B);
     } else
     ar.scratch(b->d_slab_sum, b->slab_sum_stride ? (size_t)b->slab_sum_stride * (size_t)B : 1);
   }
   ar.scratch(b->d_bs_part, std::max<size_t>(1, (size_t)b->nchunk * kBsStride));
   ar.scratch(b->d_cost_part, std::max<size_t>(1, (size_t)b->nchunk));
-  ar.scratch(b->d_ysys, std::max<size_t>(1, room(sys)));
+  ar.scratch(b->d_ysys, std::max<size_t>(1, room(b, plan.sys)));
   ar.scratch(b->d_fstore, b->pol.keep_jacobian ? (size_t)(24 * 64) * cap_tiles        // [tile][12][64] double2
                           : b->opt.reuse_elimination ? (size_t)24 * cap_obs : 2);
   ar.scratch(b->d_line_h, b->pol.keep_jacobian ? (size_t)10 * cap_line : 2);
   b->line_elim_stride = (b->opt.reuse_elimination || b->big_mode) ? kLineElim : kLeU;      // K g is kept for those two paths only
   ar.scratch(b->d_line_elim, std::max<size_t>(1, cap_line * b->line_elim_stride));
-  ar.scratch(b->d_params_out, std::max<size_t>(1, room(param_off)));
+  ar.scratch(b->d_params_out, std::max<size_t>(1, room(b, plan.params)));
   ar.upload(b->d_state, b->h_state0);
   ar.zeroed(b->d_trace, std::max<size_t>(1, (size_t)B * kMaxTrace));
   ar.staged(b->d_param_off, (size_t)std::max(1, B));
-  std::vector<int> big_ob_line, big_cam_ptr, big_cam_obs, big_pair_ptr, big_pair_row, big_pair_col, big_pair_desc;
   if (b->big_mode) {
-    // gather lists of the global-memory path (lba_big.h): per camera its observations, per (window, camera pair r >= c) the
-    // observation pairs of the lines both cameras see - every sum is walked in list order, so results are reproducible
-    if (B > 0xffff) return SLSLAM_ERR_UNSUPPORTED;
-    // a camera-pair descriptor packs (window, row camera, column camera) as wi | r << 16 | c << 24, decoded with & 0xff (lba_big.h):
-    // more than 127 free cameras would spill into the next field (and shift into the sign bit)
-    for (const PackedWindow& P : b->wins) if (P.Cf > 127) return SLSLAM_ERR_UNSUPPORTED;
-    long long sys_cursor = 0, linv_cursor = 0, oc = 0, lc = 0;
-    b->h_big_sys_off.resize(B); b->h_big_linv_off.resize(B);
-    big_ob_line.reserve((size_t)nobs);
-    big_cam_ptr.assign((size_t)ncam + 1, 0);
-    big_cam_obs.resize((size_t)std::max<long long>(1, nobs));
-    std::vector<int> pr_row, pr_col, pr_id;                  // unsorted items with their global pair id
-    {
-      size_t items = 0, pairs = 0;
-      for (const PackedWindow& P : b->wins) {
-        pairs += (size_t)(P.Cf * (P.Cf + 1)) / 2;
-        for (int s2 = 0; s2 < P.L; ++s2) {
-          if (P.line_flags[s2] & 1) continue;
-          const int o0 = P.line_ptr[s2], k = P.line_ptr[s2 + 1] - o0;
-          int kf = 0;
-          while (kf < k && P.cam_cf[P.ob_cam[o0 + kf]] >= 0) ++kf;
-          items += (size_t)(kf * (kf - 1)) / 2;
-        }
-      }
-      pr_row.reserve(items); pr_col.reserve(items); pr_id.reserve(items); big_pair_desc.reserve(pairs);
-    }
-    long long pair_base = 0;
-    for (int wi = 0; wi < B; ++wi) {
-      const PackedWindow& P = b->wins[wi];
-      const int cam_off = b->h_wins[wi].cam_off;
-      b->h_big_sys_off[wi] = sys_cursor; sys_cursor += big_sys_doubles(6 * P.Cf);
-      b->h_big_linv_off[wi] = linv_cursor; linv_cursor += (long long)((6 * P.Cf + kNB - 1) / kNB + 1) * kNB * kNB;
-      for (int o = 0; o < P.M; ++o) big_cam_ptr[(size_t)cam_off + P.ob_cam[o] + 1]++;
-      for (int r = 0; r < P.Cf; ++r)
-        for (int c = 0; c <= r; ++c) big_pair_desc.push_back(wi | (r << 16) | (c << 24));
-      for (int s2 = 0; s2 < P.L; ++s2) {
-        const int o0 = P.line_ptr[s2], k = P.line_ptr[s2 + 1] - o0;
-        for (int j = 0; j < k; ++j) big_ob_line.push_back((int)lc + s2);
-        if (P.line_flags[s2] & 1) continue;
-        int kf = 0;                                        // free-camera observations come first
-        while (kf < k && P.cam_cf[P.ob_cam[o0 + kf]] >= 0) ++kf;
-        for (int i = 0; i < kf; ++i)
-          for (int j = i + 1; j < kf; ++j) {
-            const int ci = P.cam_cf[P.ob_cam[o0 + i]], cj = P.cam_cf[P.ob_cam[o0 + j]];
-            const bool jr = cj >= ci;                      // row: the camera with the larger free index (lower triangle)
-            const int r = jr ? cj : ci, c = jr ? ci : cj;
-            pr_row.push_back((int)(oc + o0 + (jr ? j : i))); pr_col.push_back((int)(oc + o0 + (jr ? i : j)));
-            pr_id.push_back((int)(pair_base + (r * (r + 1)) / 2 + c));
-          }
-      }
-      pair_base += (long long)(P.Cf * (P.Cf + 1)) / 2;
-      oc += P.M; lc += P.L;
-    }
-    for (size_t c = 0; c < (size_t)ncam; ++c) big_cam_ptr[c + 1] += big_cam_ptr[c];
-    {
-      std::vector<int> fill(big_cam_ptr.begin(), big_cam_ptr.end() - 1);
-      long long og = 0;
-      for (int wi = 0; wi < B; ++wi) {
-        const PackedWindow& P = b->wins[wi];
-        for (int o = 0; o < P.M; ++o, ++og) big_cam_obs[(size_t)fill[(size_t)b->h_wins[wi].cam_off + P.ob_cam[o]]++] = (int)og;
-      }
-    }
-    const size_t npairs = big_pair_desc.size();
-    big_pair_ptr.assign(npairs + 1, 0);
-    for (int id : pr_id) big_pair_ptr[(size_t)id + 1]++;
-    for (size_t q = 0; q < npairs; ++q) big_pair_ptr[q + 1] += big_pair_ptr[q];
-    big_pair_row.resize(std::max<size_t>(1, pr_id.size())); big_pair_col.resize(std::max<size_t>(1, pr_id.size()));
-    {
-      std::vector<int> fill(big_pair_ptr.begin(), big_pair_ptr.end() - 1);          // counting sort: items of a pair stay in line order
-      for (size_t q = 0; q < pr_id.size(); ++q) { const int at = fill[(size_t)pr_id[q]]++; big_pair_row[(size_t)at] = pr_row[q]; big_pair_col[(size_t)at] = pr_col[q]; }
-    }
-    if (big_ob_line.empty()) big_ob_line.push_back(0);
-    b->big.npairs = (long long)npairs;
-    if (big_pair_desc.empty()) big_pair_desc.push_back(0);
-    ar.upload(b->d_big_ob_line, big_ob_line);
-    ar.upload(b->d_big_cam_ptr, big_cam_ptr);
-    ar.upload(b->d_big_cam_obs, big_cam_obs);
-    ar.upload(b->d_big_pair_ptr, big_pair_ptr);
-    ar.upload(b->d_big_pair_row, big_pair_row);
-    ar.upload(b->d_big_pair_col, big_pair_col);
-    ar.upload(b->d_big_pair_desc, big_pair_desc);
-    ar.upload(b->d_big_sys_off, b->h_big_sys_off);
-    ar.scratch(b->d_big_J, (size_t)std::max<long long>(1, nobs) * kBigObs);
-    ar.scratch(b->d_big_F, (size_t)std::max<long long>(1, nobs) * kBigF);
-    ar.scratch(b->d_big_cost, (size_t)std::max<long long>(1, nobs) * 2);
-    ar.scratch(b->d_big_camtab, (size_t)std::max<long long>(1, ncam) * 2 * kBigCam);
-    ar.zeroed(b->d_big_line_acc, (size_t)std::max<long long>(1, nline) * kBigLine);
-    ar.zeroed(b->d_big_sys, (size_t)std::max<long long>(1, sys_cursor));
-    ar.zeroed(b->d_big_scal, (size_t)std::max(1, B) * kBgScal);
-    ar.zeroed(b->d_big_flags, (size_t)std::max(1, B) * 2);
-    ar.scratch(b->d_big_linv, (size_t)std::max<long long>(1, linv_cursor));
+    const int rc = big_lists->build(b, plan);
+    if (rc != SLSLAM_OK) return rc;
   }
   ar.zeroed(b->d_iter_counter, 1);
   ar.zeroed(b->d_dbg_cycles, b->pol.debug_flags ? std::max((size_t)32 * std::max(1, b->nchunk), (size_t)16 * std::max(1, B)) : 1);
   ar.zeroed(b->d_active, 1);
-  if ((rc = ar.layout())) return rc;
-  {
-    // every window's slices into the host image, one window per host thread (they are independent), then ONE upload
-    HostImage img = host_image(b);
-    HostPool* pool = batch_pool(b, (int)std::min<long long>(B, b->opt.host_threads > 0 ? b->opt.host_threads : (B >= 64 ? 8 : 1)));
-    auto one = [&](int wi) { fill_window(b, plan, b->wins, wi, img, /*copy_observations=*/true); };
-    if (!run_all(pool, B, one)) return SLSLAM_ERR_NO_MEMORY;
-    fill_tail(b, plan, img);
-  }
-  if ((rc = ar.push())) return rc;
+  return ar.layout();
+}
 
+// every window's slices into the host image, one window per host thread (they are independent), then ONE upload
+int fill_and_push(slslam_lba_batch* b, const LayoutPlan& plan) {
+  const int B = (int)b->wins.size();
+  HostImage img = host_image(b);
+  auto one = [&](int wi) { fill_window(b, plan, b->wins, wi, img, /*copy_observations=*/true); };
+  if (!run_all(batch_pool(b, (size_t)B), B, one)) return SLSLAM_ERR_NO_MEMORY;
+  fill_tail(b, plan, img);
+  return b->arena.push();
+}
+
+// The kernels' view of the batch: BatchPtrs (and BigPtrs for the global-memory path)
+void bind_ptrs(slslam_lba_batch* b, const LayoutPlan& plan) {
   BatchPtrs& p = b->ptrs;
   p.wins = b->d_wins.p; p.tiles = b->d_tiles.p; p.chunks = b->d_chunks.p; p.items = b->d_items.p; p.lane_map = b->d_lane_map.p; p.lane_ctx = b->d_lane_ctx.p;
   p.cam_x = b->d_cam_x.p; p.cam_scale = b->d_cam_scale.p; p.cam_cf = b->d_cam_cf.p;
-  p.cam_tab = share_cam_tab ? b->d_cam_tab.p : nullptr;
+  p.cam_tab = b->share_cam_tab ? b->d_cam_tab.p : nullptr;
   p.line_x = b->d_line_x.p; p.line_scale = b->d_line_scale.p; p.line_ptr = b->d_line_ptr.p;
   p.line_flags = b->d_line_flags.p; p.line_win = b->d_line_win.p;
-  p.ob = b->d_ob.p; p.ob_cam = b->d_ob_cam.p; p.ob_stride = (long long)cap_obs;
+  p.ob = b->d_ob.p; p.ob_cam = b->d_ob_cam.p; p.ob_stride = (long long)(b->d_ob.n / 8);
   p.slab_sum = b->slab_sum_stride ? b->d_slab_sum.p : nullptr; p.slab_sum_stride = b->slab_sum_stride; p.slab_sum_image = b->slab_sum_image ? 1 : 0;
   p.slab = b->d_slab.p; p.bs_part = b->d_bs_part.p; p.cost_part = b->d_cost_part.p; p.ysys = b->d_ysys.p;
   p.fstore = b->d_fstore.p; p.line_elim = b->d_line_elim.p; p.line_elim_stride = b->line_elim_stride; p.line_h = b->d_line_h.p;
   p.state = b->d_state.p; p.trace = b->d_trace.p;
   p.iter_counter = b->d_iter_counter.p; p.active_counter = b->d_active.p; p.cam_x0 = b->d_cam_x0.p; p.line_u0 = b->d_line_x0.p;
-  p.nwin = B; p.nchunk = b->nchunk; p.nline = b->nline; p.ncam = b->ncam;
+  p.nwin = (int)b->wins.size(); p.nchunk = b->nchunk; p.nline = b->nline; p.ncam = b->ncam;
   p.dbg_cycles = b->d_dbg_cycles.p; p.sys_map = b->d_sys_map.p;
   if (b->big_mode) {
     BigPtrs& g = b->big;
     g.ob_line = b->d_big_ob_line.p; g.cam_win = b->d_cam_win.p; g.J = b->d_big_J.p; g.camtab = b->d_big_camtab.p;
     g.line_acc = b->d_big_line_acc.p; g.sys = b->d_big_sys.p; g.sys_off = b->d_big_sys_off.p; g.F = b->d_big_F.p; g.cost = b->d_big_cost.p;
     g.cam_ptr = b->d_big_cam_ptr.p; g.cam_obs = b->d_big_cam_obs.p; g.pair_ptr = b->d_big_pair_ptr.p; g.pair_row = b->d_big_pair_row.p;
-    g.pair_col = b->d_big_pair_col.p; g.pair_desc = b->d_big_pair_desc.p; g.scal = b->d_big_scal.p; g.flags = b->d_big_flags.p; g.nobs = nobs;
+    g.pair_col = b->d_big_pair_col.p; g.pair_desc = b->d_big_pair_desc.p; g.scal = b->d_big_scal.p; g.flags = b->d_big_flags.p; g.nobs = plan.nobs;
   }
   p.line_desc = b->d_line_desc.p; p.elim_mode = b->elim_mode; p.elim_waves = b->elim_waves;
+}
+
+// The LDS sizes of the launches, for the largest window of the batch, and the kernels' limits where they need more than 48 KB
+int set_lds_limits(slslam_lba_batch* b, int maxC, int maxn) {
   b->lds_elim = b->elim_grouped ? (size_t)lds_bytes_eliminate_grouped(maxC, maxn) : (size_t)lds_bytes_eliminate_mfma(maxC, maxn, b->elim_waves);
 
   b->lds_lin = sizeof(double) * (size_t)lds_doubles_linearise(maxC, maxn);
   b->lds_solve = sizeof(double) * (size_t)lds_doubles_solve(maxn);
   // motion-only batches (one free camera, every line constant: SLAM::motion_only_ba): the whole solve in one launch
-  b->fused_motion_only = b->opt.lba_fused_motion_only && !b->opt.reuse_elimination && B > 0;
+  b->fused_motion_only = b->opt.lba_fused_motion_only && !b->opt.reuse_elimination && !b->wins.empty();
   for (const PackedWindow& P : b->wins) if (P.Cf != 1 || P.nfree_params != 6) b->fused_motion_only = false;
   b->lds_motion_only = sizeof(double) * (size_t)lds_doubles_motion_only(maxC);
   b->lds_bs = sizeof(double) * (size_t)lds_doubles_backsub(maxC, maxn);
@@ -1102,33 +1132,51 @@ extern "C" int slslam_lba_batch_finalize(slslam_lba_batch* b, const slslam_solve
   b->lds_cost = sizeof(double) * (size_t)lds_doubles_cost(maxC, maxn);
   const size_t lds_max = std::max(std::max(b->lds_lin, b->lds_solve), std::max(b->lds_bs, b->lds_cost));
   if (lds_max > 160 * 1024 && !b->big_mode) return SLSLAM_ERR_UNSUPPORTED;
-  if (b->lds_lin > 48 * 1024 && !b->big_mode) {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_linearise_schur<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_lin));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_linearise_schur<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_lin));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_linearise_schur<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_lin));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_linearise_schur<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_lin));
-  }
+  if (b->lds_lin > 48 * 1024 && !b->big_mode)
+    HIP_TRY(allow_lds({ (const void*)k_linearise_schur<true>, (const void*)k_linearise_schur<false>, (const void*)k_linearise_schur<false, 0>,
+                        (const void*)k_linearise_schur<false, 1> }, b->lds_lin));
   if (b->elim_mode == 1 && b->lds_elim > 48 * 1024) {
     if (b->lds_elim > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
-    HIP_TRY(hipFuncSetAttribute((const void*)k_eliminate_mfma<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_elim));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_eliminate_mfma<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_elim));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_eliminate_mfma<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_elim));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_eliminate_mfma<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_elim));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_eliminate_grouped<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_elim));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_eliminate_grouped<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_elim));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_eliminate_grouped<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_elim));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_eliminate_grouped<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_elim));
+    HIP_TRY(allow_lds({ (const void*)k_eliminate_mfma<1, false>, (const void*)k_eliminate_mfma<2, false>, (const void*)k_eliminate_mfma<1, true>,
+                        (const void*)k_eliminate_mfma<2, true>, (const void*)k_eliminate_grouped<false>, (const void*)k_eliminate_grouped<true>,
+                        (const void*)k_eliminate_grouped<false, true>, (const void*)k_eliminate_grouped<false, false, true> }, b->lds_elim));
   }
-  if (b->lds_solve > 48 * 1024 && !b->big_mode) {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_reduced_solve<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_solve));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_reduced_solve<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_solve));
+  if (b->lds_solve > 48 * 1024 && !b->big_mode)
+    HIP_TRY(allow_lds({ (const void*)k_reduced_solve<4>, (const void*)k_reduced_solve<1> }, b->lds_solve));
+  return SLSLAM_OK;
+}
+
+}  // namespace
+
+extern "C" int slslam_lba_batch_finalize(slslam_lba_batch* b, const slslam_solver_options* opt) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (b->finalized) return SLSLAM_ERR_STATE;
+  if (opt) b->opt = *opt;
+  if (b->opt.max_num_iterations < 0 || b->opt.max_num_iterations > 100000) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!(b->opt.initial_trust_region_radius > 0.0) || !(b->opt.baseline == b->opt.baseline)) return SLSLAM_ERR_INVALID_ARGUMENT;
+  b->pol = make_policy(b->opt);
+  HIP_TRY(hipSetDevice(b->device));
+  {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) == hipSuccess && cus > 0) b->num_cus = cus;
   }
+  const int B = (int)b->wins.size();
+  bool mixed = false;
+  int rc = choose_sweep(b, &mixed);
+  if (rc != SLSLAM_OK || mixed) return rc;
+  LayoutPlan plan;
+  if ((rc = plan_capacities(b, plan))) return rc;
+  BigLists big_lists;
+  if ((rc = reserve_arena(b, plan, &big_lists))) return rc;
+  if ((rc = fill_and_push(b, plan))) return rc;
+  bind_ptrs(b, plan);
+  if ((rc = set_lds_limits(b, plan.maxC, plan.maxn))) return rc;
   // on the device: the tile contexts from the lane maps, both parameter buffers of cameras and lines from the initial values
   if ((rc = device_init_after_upload(b, nullptr))) return rc;
-  if (!ar.cached) HIP_TRY(hipStreamSynchronize(nullptr));      // (a one-shot solve stays on the null stream: ordered behind this anyway)
+  if (!b->arena.cached) HIP_TRY(hipStreamSynchronize(nullptr));      // (a one-shot solve stays on the null stream: ordered behind this anyway)
   if ((rc = b->h_state.alloc((size_t)B, b->refillable))) return rc;
   if ((rc = b->h_trace.alloc((size_t)B * kMaxTrace, b->refillable))) return rc;
-  if ((rc = b->h_params.alloc(room(param_off), b->refillable))) return rc;
+  if ((rc = b->h_params.alloc(room(b, plan.params), b->refillable))) return rc;
   b->finalized = true;
   return SLSLAM_OK;
 }
@@ -1427,6 +1475,7 @@ extern "C" int slslam_lba_batch_export_device(slslam_lba_batch* b, double* devic
 }
 
 namespace {
+constexpr int kExportWorkgroups = 64;       // k_export_inplace's grid (see there)
 // Results of a device-built refill whose `parameters` arrays are page-locked go straight where the caller wants them (reference
 // src/slam.cpp:957-972 reads them there): thread <-> parameter block, the window's destination from the RawWin table.  A window that ended in
 // NUMERICAL_FAILURE is left untouched, as Ceres leaves the user's parameters.
@@ -1464,9 +1513,8 @@ int download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
   const bool inplace = allow_inplace && b->device_built && b->inplace_export;
   b->results_inplace = inplace;
   if (inplace) {
-    static const int export_wgs = std::getenv("SLSLAM_EXPORT_WORKGROUPS") ? std::max(1, std::atoi(std::getenv("SLSLAM_EXPORT_WORKGROUPS"))) : 64;
     if (b->total_params > 0 && !b->wins.empty())
-      hipLaunchKernelGGL(k_export_inplace, dim3((unsigned)std::min<size_t>(b->wins.size(), (size_t)export_wgs)), dim3(256), 0, s, b->ptrs, (const RawWin*)b->d_rawwin.p,
+      hipLaunchKernelGGL(k_export_inplace, dim3((unsigned)std::min<size_t>(b->wins.size(), (size_t)kExportWorkgroups)), dim3(256), 0, s, b->ptrs, (const RawWin*)b->d_rawwin.p,
                          (const int*)b->d_line_pos.p, (int)b->wins.size());
     HIP_TRY(hipGetLastError());
   } else {
@@ -1481,9 +1529,9 @@ int download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
   }
   if (b->device_built && !b->wins.empty()) {
     // what the device made of the windows: descriptors (free cameras, kept residual blocks, chunk cut) and the per-window build status
-    HIP_TRY(hipMemcpyAsync(b->h_wins_dl, b->d_wins.p, b->wins.size() * sizeof(WinDesc), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_buildwin, b->d_buildwin.p, b->wins.size() * sizeof(BuildWin), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_totals, b->d_totals.p, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_wins_dl.data(), b->d_wins.p, b->wins.size() * sizeof(WinDesc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_buildwin.data(), b->d_buildwin.p, b->wins.size() * sizeof(BuildWin), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_totals.data(), b->d_totals.p, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
   }
   if (!b->ev_results) HIP_TRY(hipEventCreateWithFlags(&b->ev_results, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_results, s));
@@ -1505,6 +1553,17 @@ void adopt_device_build(slslam_lba_batch* b) {
   }
   b->used_tiles = b->h_totals[0]; b->used_items = b->h_totals[1];
 }
+
+// An asynchronous download under way has arrived: its results are adopted (and stay readable)
+int finish_download(slslam_lba_batch* b) {
+  // (a finished event is seen by a query at once; hipEventSynchronize on it was measured at ~2 ms per call in the streamed leg)
+  if (hipEventQuery(b->ev_results) != hipSuccess) HIP_TRY(hipEventSynchronize(b->ev_results));
+  b->results_pending = false;
+  if (b->profiling) b->harvest_events();
+  adopt_device_build(b);
+  b->downloaded = true;
+  return SLSLAM_OK;
+}
 }  // namespace
 
 extern "C" int slslam_lba_batch_download_async(slslam_lba_batch* b, void* stream) { return download_async_impl(b, stream, false); }
@@ -1520,13 +1579,7 @@ extern "C" int slslam_lba_batch_wait(slslam_lba_batch* b) {
     return rc0;
   }
   if (!b->results_pending) return b->downloaded ? SLSLAM_OK : SLSLAM_ERR_STATE;
-  // (a finished event is seen by a query at once; hipEventSynchronize on it was measured at ~2 ms per call in the streamed leg)
-  if (hipEventQuery(b->ev_results) != hipSuccess) HIP_TRY(hipEventSynchronize(b->ev_results));
-  b->results_pending = false;
-  if (b->profiling) b->harvest_events();
-  adopt_device_build(b);
-  b->downloaded = true;
-  return SLSLAM_OK;
+  return finish_download(b);
 }
 
 extern "C" int slslam_lba_batch_download(slslam_lba_batch* b, void* stream) {
@@ -1537,13 +1590,77 @@ extern "C" int slslam_lba_batch_download(slslam_lba_batch* b, void* stream) {
 
 namespace {
 
+// The pinned host mirrors of a device-built refill: [B] each, the totals [8]
 int ensure_build_host_buffers(slslam_lba_batch* b, int B) {
-  if (!b->h_rawwin) HIP_TRY(hipHostMalloc((void**)&b->h_rawwin, sizeof(RawWin) * (size_t)std::max(1, B), hipHostMallocDefault));
-  if (!b->h_buildwin) { HIP_TRY(hipHostMalloc((void**)&b->h_buildwin, sizeof(BuildWin) * (size_t)std::max(1, B), hipHostMallocDefault)); std::memset(b->h_buildwin, 0, sizeof(BuildWin) * (size_t)std::max(1, B)); }
-  if (!b->h_wins_dl) HIP_TRY(hipHostMalloc((void**)&b->h_wins_dl, sizeof(WinDesc) * (size_t)std::max(1, B), hipHostMallocDefault));
-  if (!b->h_totals) { HIP_TRY(hipHostMalloc((void**)&b->h_totals, sizeof(int) * 8, hipHostMallocDefault)); std::memset(b->h_totals, 0, sizeof(int) * 8); }
+  const size_t nb = (size_t)std::max(1, B);
+  int rc = SLSLAM_OK;
+  if (b->h_rawwin.empty()) rc = b->h_rawwin.alloc(nb, true);
+  if (rc == SLSLAM_OK && b->h_buildwin.empty()) rc = b->h_buildwin.alloc(nb, true);
+  if (rc == SLSLAM_OK && b->h_wins_dl.empty()) rc = b->h_wins_dl.alloc(nb, true);
+  if (rc == SLSLAM_OK && b->h_totals.empty()) rc = b->h_totals.alloc(8, true);
+  return rc;
+}
+
+// A refill's staging blocks (pinned: the copy of pageable inputs, or the narrowed indices; device: where the copy engine puts a refill's
+// arrays) grow to what is asked for and an eighth more; their contents are not kept.  The previous refill has read the old one:
+// ev_stage_free / the results were waited for.
+template <typename Block, typename... Flags>
+int grow_stage(Block& block, size_t bytes, Flags... flags) {
+  if (bytes <= block.n) return SLSLAM_OK;
+  return block.alloc(bytes + bytes / 8 + 4096, flags...);
+}
+
+// The host image / the previous refill's sources may still be read by the device; results under way arrive first (and stay readable: a
+// refill that is refused leaves the batch as it was, its results included)
+int wait_stage_free(slslam_lba_batch* b) {
+  if (b->ev_stage_free) HIP_TRY(hipEventSynchronize(b->ev_stage_free));
+  return b->results_pending ? finish_download(b) : SLSLAM_OK;
+}
+
+// What a refilled batch must find zeroed before its solve, as a fresh one does (finalize: the arena's zeroed group), on `s`;
+// device_init_after_upload follows
+int zero_refilled(slslam_lba_batch* b, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(b->d_cam_scale.p, 0, b->d_cam_scale.n * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(b->d_line_scale.p, 0, b->d_line_scale.n * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(b->d_cam_tab.p, 0, b->d_cam_tab.n * sizeof(double), s));
+  if (b->slab_sum_image) HIP_TRY(hipMemsetAsync(b->d_slab_sum.p, 0, b->d_slab_sum.n * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(b->d_active.p, 0, sizeof(unsigned int), s));
   return SLSLAM_OK;
 }
+
+// The build kernels may use up to 158 KB of LDS (lba_device_build.h)
+hipError_t allow_build_lds() {
+  return allow_lds({ (const void*)k_build_lines, (const void*)k_build_rows, (const void*)k_build_order, (const void*)k_build_tiles }, 158 * 1024);
+}
+
+// One window's index words as the device reads them (RawWin::packed): its three index arrays narrowed (index_word), or the caller's words
+// (`packed`) copied.  Nonzero: an index outside [0, C) x [0, L), or a word with a bit above the flags set.
+unsigned narrow_indices(size_t M, const int* cam, const int* line, const int* fixed, const uint32_t* packed, int C, int L, uint32_t* out) {
+  unsigned oob = 0;
+  if (packed) {
+    for (size_t q = 0; q < M; ++q) { const uint32_t v = packed[q]; oob |= word_bad(v, C, L); out[q] = v; }
+    return oob;
+  }
+  for (size_t q = 0; q < M; ++q) {
+    const int c = cam[q], l = line[q];
+    oob |= (unsigned)(c < 0) | (unsigned)(c >= C) | (unsigned)(l < 0) | (unsigned)(l >= L);
+    out[q] = index_word(c, l, fixed[2 * q], fixed[2 * q + 1]);
+  }
+  return oob;
+}
+
+// The three index arrays of M index words, held by `store`, as w's camera_index / line_index / fixed_index
+void expand_indices(const uint32_t* words, size_t M, std::vector<int>& store, slslam_lba_window* w) {
+  store.resize(4 * M);
+  for (size_t q = 0; q < M; ++q) {
+    const uint32_t x = words[q];
+    store[q] = word_camera(x); store[M + q] = word_line(x); store[2 * M + 2 * q] = word_camera_const(x); store[2 * M + 2 * q + 1] = word_line_const(x);
+  }
+  w->camera_index = store.data(); w->line_index = store.data() + M; w->fixed_index = store.data() + 2 * M;
+}
+
+// The SLSLAM_REFILL_TIMING printouts of both refill paths
+double ms_between(std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); }
 
 // Copies `n` doubles (n even or odd) with the NaN / Inf test of lba_pack.cpp::all_finite; non-temporal stores when the destination allows.
 unsigned long long copy_checked(double* dst, const double* src, size_t n) {
@@ -1573,83 +1690,15 @@ unsigned long long copy_checked(double* dst, const double* src, size_t n) {
   return bad;
 }
 
-// The LBAProblem::build stage of a refill ON THE DEVICE (lba_device_build.h).  SLSLAM_OK: taken; SLSLAM_ERR_UNSUPPORTED: not this path's
-// business - nothing was touched, the caller goes on with the host packer; anything else: the refill failed.
-// Two streams: the ingest (the host link's business: few workgroups for ~20 ms per 1024 x 2000-line batch) is enqueued on `s_in`, everything
-// after it on `s` behind an event.  One stream for both (the plain refill entry point) is fine; a STREAM of windows hands ONE ingest stream
-// and ONE solve stream to all its slots, so that batch k + 1 crosses the link while batch k is solved and neither shares its resource
-// (batches that ingest and solve at the same time on streams of their own fall into step: three ingests share the link, then three
-// solves share the chip - measured 37 ms per batch against 20).
-// packed (optional): packed[i] != nullptr replaces window i's three index arrays by the narrowed form (slslam_pack_indices: one 32-bit word per
-// observation) - 68 instead of 80 bytes per observation over the host link.
-// the device block the copy engine fills (refill_device); the previous refill's kernels have read the old one: ev_stage_free / the results were waited for
-int ensure_stage_block(slslam_lba_batch* b, size_t bytes) {
-  if (bytes <= b->d_stage_bytes) return SLSLAM_OK;
-  if (b->d_stage_in) { (void)hipFree(b->d_stage_in); b->d_stage_in = nullptr; b->d_stage_bytes = 0; }
-  const size_t want = bytes + bytes / 8 + 4096;
-  HIP_TRY(hipMalloc((void**)&b->d_stage_in, want));
-  b->d_stage_bytes = want;
-  return SLSLAM_OK;
-}
-
-int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, hipStream_t s, hipStream_t s_in, const unsigned int* const* packed = nullptr) {
-  if (b->opt.device_build < 0 || b->d_rawwin.n < (size_t)std::max(1, B) || !b->d_ob_raw.p) return SLSLAM_ERR_UNSUPPORTED;
-  if (std::getenv("SLSLAM_CHUNK_WEIGHTS")) return SLSLAM_ERR_UNSUPPORTED;          // (an experiment knob of the host-side cut)
-  // (k_build_layout dispatches graded chunks in at most kLayoutMaxRank classes: a batch cut for more rounds of the wave slots - several
-  // thousand 2000-line windows - keeps the host packer)
-  if ((b->opt.chunks_per_window < 0 ? (-b->opt.chunks_per_window) / 1000 : (b->opt.reproducible ? 3 : b->auto_rounds)) > (int)kLayoutMaxRank) return SLSLAM_ERR_UNSUPPORTED;
-  static const bool timing = std::getenv("SLSLAM_REFILL_TIMING") != nullptr;
-  const auto tt0 = std::chrono::steady_clock::now();
-  // ---- what the host knows without reading an array: the windows' sizes, hence their places in the batch
-  std::vector<int> cam_off((size_t)B + 1, 0), line_off((size_t)B + 1, 0);
-  std::vector<long long> obs_off((size_t)B + 1, 0), par_off((size_t)B + 1, 0);
+// What a device-built refill learns on its way through the stages below
+struct RefillPlan {
+  std::vector<int> cam_off, line_off;           // (refill_sizes)
+  std::vector<long long> obs_off, par_off;
   int maxL = 0, maxM = 0, maxC = 1;
-  for (int i = 0; i < B; ++i) {
-    const slslam_lba_window& w = windows[i];
-    if (w.num_cameras < 0 || w.num_lines < 0 || w.num_observations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-    const bool pk = packed && packed[i];
-    if (w.num_observations > 0 && ((!pk && (!w.camera_index || !w.line_index || !w.fixed_index)) || !w.observations)) return SLSLAM_ERR_INVALID_ARGUMENT;
-    if ((w.num_cameras > 0 || w.num_lines > 0) && !w.parameters) return SLSLAM_ERR_INVALID_ARGUMENT;
-    if (w.num_cameras > kMaxCams || w.num_lines > 0xfffe || w.num_observations >= (1 << 24)) return SLSLAM_ERR_UNSUPPORTED;
-    maxL = std::max(maxL, w.num_lines); maxM = std::max(maxM, w.num_observations); maxC = std::max(maxC, w.num_cameras);
-    cam_off[(size_t)i + 1] = cam_off[(size_t)i] + w.num_cameras; line_off[(size_t)i + 1] = line_off[(size_t)i] + w.num_lines;
-    obs_off[(size_t)i + 1] = obs_off[(size_t)i] + w.num_observations;
-    par_off[(size_t)i + 1] = par_off[(size_t)i] + 6LL * w.num_cameras + 4LL * w.num_lines;
-  }
-  size_t lds_tiles = build_tiles_lds_bytes(maxL, maxL);
-  const size_t lds_build = build_lds_bytes(maxL), lds_tiles_staged = build_tiles_lds_bytes(maxL, maxL, maxM, b->elim_grouped ? 1 : 0);
-  if (lds_build > 158 * 1024 || lds_tiles > 158 * 1024) return SLSLAM_ERR_UNSUPPORTED;
-  const int tiles_stage_m = lds_tiles_staged <= 158 * 1024 ? maxM : -1;      // (k_build_tiles: the tile loop's inputs in LDS when they fit)
-  if (tiles_stage_m >= 0) lds_tiles = lds_tiles_staged;
-  const long long ncam = cam_off[(size_t)B], nline = line_off[(size_t)B], nobs = obs_off[(size_t)B], nparams = par_off[(size_t)B];
-  const long long ob_stride = (long long)(b->d_ob.n / 8);
-  if ((size_t)ncam > b->d_cam_cf.n || (size_t)nline > b->d_line_win.n || nobs > ob_stride || (size_t)nparams > b->d_params_out.n ||
-      (size_t)nparams > b->h_params.size() || maxC > b->cap_maxC || nobs > 0x7fffffffLL)
-    return SLSLAM_ERR_UNSUPPORTED;                      // (the host path says the same, before touching anything)
-  int rc = ensure_build_host_buffers(b, B);
-  if (rc != SLSLAM_OK) return rc;
-  // ---- where the device reads the windows: where they are when all their arrays are page-locked (slslam_pinned_alloc /
-  // slslam_pinned_register), else a pinned staging copy made here by the host threads (indices narrowed on the way)
-  bool all_pinned = true, params_pinned = true;
-  const std::vector<PinnedRegistry::Range> rs = PinnedRegistry::get().snapshot();
-  {
-    for (int i = 0; i < B && (all_pinned || params_pinned); ++i) {
-      const slslam_lba_window& w = windows[i];
-      const size_t M = (size_t)w.num_observations, np = (size_t)6 * w.num_cameras + (size_t)4 * w.num_lines;
-      if (np && !PinnedRegistry::contains(rs, w.parameters, 8 * np)) { params_pinned = false; all_pinned = false; }
-      const bool pk = packed && packed[i];
-      if (M && all_pinned && !((pk ? PinnedRegistry::contains(rs, packed[i], 4 * M)
-                                   : (PinnedRegistry::contains(rs, w.camera_index, 4 * M) && PinnedRegistry::contains(rs, w.line_index, 4 * M) && PinnedRegistry::contains(rs, w.fixed_index, 8 * M))) &&
-                               PinnedRegistry::contains(rs, w.observations, 64 * M)))
-        all_pinned = false;
-    }
-  }
-  // the host image / the previous refill's sources may still be read by the device; results under way arrive first (and stay readable)
-  if (b->ev_stage_free) HIP_TRY(hipEventSynchronize(b->ev_stage_free));
-  if (b->results_pending) { HIP_TRY(hipEventSynchronize(b->ev_results)); b->results_pending = false; adopt_device_build(b); b->downloaded = true; if (b->profiling) b->harvest_events(); }
-  const auto tt1 = std::chrono::steady_clock::now();
-  RawWin* rw = b->h_rawwin;
-  b->host_src.assign((size_t)B, RawWin());
+  long long ncam = 0, nline = 0, nobs = 0, nparams = 0;
+  size_t lds_build = 0, lds_tiles = 0;
+  int tiles_stage_m = -1;
+  bool all_pinned = true, params_pinned = true;     // (where_pinned)
   // copies the copy engine is to make before the ingest (host address, device offset in d_stage_in, bytes); empty: the ingest kernel reads
   // the callers' arrays itself (zero copy)
   struct Run { uintptr_t lo, hi; size_t dev_off; };
@@ -1657,156 +1706,188 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
   size_t dev_need = 0;
   int idx_run = -1;                   // the run that holds the indices the host threads narrow (copied after the others)
   bool early_dma = false;             // the other runs are on their way already
-  if (all_pinned) {
-    for (int i = 0; i < B; ++i) {
-      const slslam_lba_window& w = windows[i];
-      RawWin& r = b->host_src[(size_t)i];
-      const bool pk = packed && packed[i];
-      r.cam = pk ? nullptr : w.camera_index; r.line = pk ? nullptr : w.line_index; r.fixed = pk ? nullptr : w.fixed_index; r.packed = pk ? packed[i] : nullptr;
-      r.obs = w.observations; r.params_in = w.parameters; r.params = w.parameters;
-      rw[i] = r;
-    }
-    // Arrays that lie next to each other in host memory (a caller that carves its windows out of an arena) go up in a few large copies of
-    // the copy engine, which does not travel through the shader's L2: a kernel that keeps the link full has ~0.5 MB of host reads
-    // outstanding in the L2 channels, and every latency-bound kernel beside it waits behind them (the window build 2.7 -> 11.6 ms, k_build_tiles
-    // 0.36 -> 6.4 ms measured).  Scattered arrays: zero-copy kernel reads.
-    static const bool no_dma = std::getenv("SLSLAM_INGEST_ZERO_COPY") != nullptr;         // (measurement switch)
-    // The three int32 index arrays are 16 of the 80 bytes an observation sends over the link, which is what a stream of page-locked windows is
-    // bound by (1.085 GB per 1024 x 2000-line batch at 57 GB/s = 19 ms against 15 ms of solve).  The host threads narrow them to one word per
-    // observation into a pinned block on the way (4 B; ~0.25 GB of reads per batch: a few milliseconds on two threads, beside the GPU's work) -
-    // the observations and the parameters still go up from where they are.  Bad indices are reported now, as the host packer does.
-    static const bool no_narrow = std::getenv("SLSLAM_NO_HOST_NARROW") != nullptr;          // (measurement switch)
-    bool any_unpacked = false;
-    for (int i = 0; i < B && !any_unpacked; ++i) any_unpacked = windows[i].num_observations > 0 && !(packed && packed[i]);
-    const bool narrow = !no_dma && !no_narrow && nobs > 0 && any_unpacked;       // (a batch whose caller narrowed every window sends no block of ours)
-    if (narrow) {
-      const size_t need = 4 * (size_t)nobs + 64;
-      if (need > b->raw_stage_bytes) {
-        if (b->h_raw_stage) { (void)hipHostFree(b->h_raw_stage); b->h_raw_stage = nullptr; b->raw_stage_bytes = 0; }
-        const size_t want = need + need / 8 + 4096;
-        HIP_TRY(hipHostMalloc((void**)&b->h_raw_stage, want, hipHostMallocDefault));
-        b->raw_stage_bytes = want;
-      }
-    }
-    // the ranges the copy engine is to move: the callers' arrays and - a run of its own, never merged with a neighbour - the narrowed block
-    using Rg = CopyRange;
-    std::vector<Rg> rg;
-    rg.reserve((size_t)5 * B + 1);
-    size_t payload = 0;
-    if (narrow) { rg.push_back({ (uintptr_t)b->h_raw_stage, (uintptr_t)b->h_raw_stage + 4 * (size_t)nobs, true }); payload += 4 * (size_t)nobs; }
-    for (int i = 0; i < B && !no_dma; ++i) {
-      const slslam_lba_window& w = windows[i];
-      const size_t M = (size_t)w.num_observations, np = (size_t)6 * w.num_cameras + (size_t)4 * w.num_lines;
-      const bool pk = packed && packed[i];
-      if (M && pk) rg.push_back({ (uintptr_t)packed[i], (uintptr_t)packed[i] + 4 * M, false });
-      if (M && !pk && !narrow) { rg.push_back({ (uintptr_t)w.camera_index, (uintptr_t)w.camera_index + 4 * M, false }); rg.push_back({ (uintptr_t)w.line_index, (uintptr_t)w.line_index + 4 * M, false });
-                                 rg.push_back({ (uintptr_t)w.fixed_index, (uintptr_t)w.fixed_index + 8 * M, false }); }
-      if (M) rg.push_back({ (uintptr_t)w.observations, (uintptr_t)w.observations + 64 * M, false });
-      if (np) rg.push_back({ (uintptr_t)w.parameters, (uintptr_t)w.parameters + 8 * np, false });
-      payload += (pk ? 68 : narrow ? 64 : 80) * M + 8 * np;
-    }
-    std::sort(rg.begin(), rg.end(), [](const Rg& x, const Rg& y) { return x.lo < y.lo; });
-    {
-      // (lba_pack.cpp: neighbours within a page of each other, inside one registration, go up as one copy)
-      std::vector<AddrRange> regs(rs.size());
-      for (size_t k = 0; k < rs.size(); ++k) regs[k] = AddrRange{ rs[k].lo, rs[k].hi };
-      for (const AddrRange& a : plan_copy_runs(rg.data(), rg.size(), regs.data(), regs.size(), &idx_run)) runs.push_back(Run{ a.lo, a.hi, 0 });
-    }
-    for (Run& r : runs) { r.dev_off = dev_need + (r.lo & 255); dev_need += ((r.lo & 255) + (r.hi - r.lo) + 255) & ~(size_t)255; }     // (device address = host address modulo 256)
-    if (runs.size() > (size_t)std::max(8, B / 16) || dev_need > payload + payload / 8 + (1u << 20)) { runs.clear(); dev_need = 0; idx_run = -1; }     // scattered: zero copy
-    // The callers' arrays start up the link NOW, the host threads narrow the indices meanwhile: a submit's chain is
-    // max(narrowing, 0.87 GB of copies) + build, not their sum - with three batches in flight the sum (13 + 17 + 4 ms on a slow host thread)
-    // left 2 ms of slack against two solve periods, and a stream at the mercy of the host's jitter (0.70 of resident measured on such a box).
-    if (!runs.empty()) {
-      rc = ensure_stage_block(b, dev_need);
-      if (rc != SLSLAM_OK) return rc;
-      for (size_t k = 0; k < runs.size(); ++k)
-        if ((int)k != idx_run) HIP_TRY(hipMemcpyAsync(b->d_stage_in + runs[k].dev_off, (const void*)runs[k].lo, runs[k].hi - runs[k].lo, hipMemcpyHostToDevice, s_in));
-      early_dma = true;
-    }
-    if (narrow) {
-      std::vector<int> st((size_t)B, SLSLAM_OK);
-      HostPool* pool = batch_pool(b, (int)std::min<long long>(B, b->opt.host_threads > 0 ? b->opt.host_threads : (B >= 64 ? 8 : 1)));
-      auto narrow_one = [&](int i) {
-        if (packed && packed[i]) return;
-        const slslam_lba_window& w = windows[i];
-        const size_t M = (size_t)w.num_observations;
-        uint32_t* ix = reinterpret_cast<uint32_t*>(b->h_raw_stage) + obs_off[(size_t)i];
-        const int C = w.num_cameras, L = w.num_lines;
-        const int* cam = w.camera_index; const int* line = w.line_index; const int* fx = w.fixed_index;
-        unsigned oob = 0;
-        for (size_t q = 0; q < M; ++q) {
-          const int c = cam[q], l = line[q];
-          oob |= (unsigned)(c < 0) | (unsigned)(c >= C) | (unsigned)(l < 0) | (unsigned)(l >= L);
-          ix[q] = ((uint32_t)l & 0xffffu) | ((uint32_t)c & 0xffu) << 16 | (fx[2 * q] ? 1u << 24 : 0u) | (fx[2 * q + 1] ? 1u << 25 : 0u);
-        }
-        if (oob) st[(size_t)i] = SLSLAM_ERR_INVALID_ARGUMENT;
-        RawWin& r = b->host_src[(size_t)i];
-        r.cam = nullptr; r.line = nullptr; r.fixed = nullptr; r.packed = ix;
-        rw[i] = r;
-      };
-      int bad = run_all(pool, B, narrow_one) ? SLSLAM_OK : SLSLAM_ERR_NO_MEMORY;
-      for (int v : st) if (bad == SLSLAM_OK && v != SLSLAM_OK) bad = v;
-      if (bad != SLSLAM_OK) {
-        if (early_dma) (void)hipStreamSynchronize(s_in);            // the copies under way read the callers' arrays: not beyond this call
-        return bad;
-      }
-    }
-  } else {
-    // staging: per window [observations 64 M | narrowed indices 4 M | parameters], 64-byte aligned pieces
-    std::vector<size_t> st_off((size_t)B + 1, 0);
-    for (int i = 0; i < B; ++i) {
-      const size_t M = (size_t)windows[i].num_observations, np = (size_t)6 * windows[i].num_cameras + (size_t)4 * windows[i].num_lines;
-      st_off[(size_t)i + 1] = st_off[(size_t)i] + ((64 * M + 63) & ~(size_t)63) + ((4 * M + 63) & ~(size_t)63) + ((8 * np + 63) & ~(size_t)63);
-    }
-    if (st_off[(size_t)B] > b->raw_stage_bytes) {
-      if (b->h_raw_stage) { (void)hipHostFree(b->h_raw_stage); b->h_raw_stage = nullptr; b->raw_stage_bytes = 0; }
-      const size_t want = st_off[(size_t)B] + st_off[(size_t)B] / 8 + 4096;
-      HIP_TRY(hipHostMalloc((void**)&b->h_raw_stage, want, hipHostMallocDefault));
-      b->raw_stage_bytes = want;
-    }
+};
+
+// ---- what the host knows without reading an array: the windows' sizes, hence their places in the batch
+
+int refill_sizes(const slslam_lba_batch* b, const slslam_lba_window* windows, int B, const unsigned int* const* packed, RefillPlan& z) {
+  z.cam_off.assign((size_t)B + 1, 0); z.line_off.assign((size_t)B + 1, 0);
+  z.obs_off.assign((size_t)B + 1, 0); z.par_off.assign((size_t)B + 1, 0);
+  for (int i = 0; i < B; ++i) {
+    const slslam_lba_window& w = windows[i];
+    if (w.num_cameras < 0 || w.num_lines < 0 || w.num_observations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
+    const bool pk = packed && packed[i];
+    if (w.num_observations > 0 && ((!pk && (!w.camera_index || !w.line_index || !w.fixed_index)) || !w.observations)) return SLSLAM_ERR_INVALID_ARGUMENT;
+    if ((w.num_cameras > 0 || w.num_lines > 0) && !w.parameters) return SLSLAM_ERR_INVALID_ARGUMENT;
+    if (w.num_cameras > kMaxCams || w.num_lines > 0xfffe || w.num_observations >= (1 << 24)) return SLSLAM_ERR_UNSUPPORTED;
+    z.maxL = std::max(z.maxL, w.num_lines); z.maxM = std::max(z.maxM, w.num_observations); z.maxC = std::max(z.maxC, w.num_cameras);
+    z.cam_off[(size_t)i + 1] = z.cam_off[(size_t)i] + w.num_cameras; z.line_off[(size_t)i + 1] = z.line_off[(size_t)i] + w.num_lines;
+    z.obs_off[(size_t)i + 1] = z.obs_off[(size_t)i] + w.num_observations;
+    z.par_off[(size_t)i + 1] = z.par_off[(size_t)i] + 6LL * w.num_cameras + 4LL * w.num_lines;
+  }
+  z.lds_tiles = build_tiles_lds_bytes(z.maxL, z.maxL);
+  z.lds_build = build_lds_bytes(z.maxL);
+  const size_t lds_tiles_staged = build_tiles_lds_bytes(z.maxL, z.maxL, z.maxM, b->elim_grouped ? 1 : 0);
+  if (z.lds_build > 158 * 1024 || z.lds_tiles > 158 * 1024) return SLSLAM_ERR_UNSUPPORTED;
+  z.tiles_stage_m = lds_tiles_staged <= 158 * 1024 ? z.maxM : -1;      // (k_build_tiles: the tile loop's inputs in LDS when they fit)
+  if (z.tiles_stage_m >= 0) z.lds_tiles = lds_tiles_staged;
+  z.ncam = z.cam_off[(size_t)B]; z.nline = z.line_off[(size_t)B]; z.nobs = z.obs_off[(size_t)B]; z.nparams = z.par_off[(size_t)B];
+  const long long ob_stride = (long long)(b->d_ob.n / 8);
+  if ((size_t)z.ncam > b->d_cam_cf.n || (size_t)z.nline > b->d_line_win.n || z.nobs > ob_stride || (size_t)z.nparams > b->d_params_out.n ||
+      (size_t)z.nparams > b->h_params.size() || z.maxC > b->cap_maxC || z.nobs > 0x7fffffffLL)
+    return SLSLAM_ERR_UNSUPPORTED;                      // (the host path says the same, before touching anything)
+  return SLSLAM_OK;
+}
+
+// ---- where the device reads the windows: where they are when all their arrays are page-locked (slslam_pinned_alloc /
+// slslam_pinned_register), else a pinned staging copy made here by the host threads (indices narrowed on the way)
+void where_pinned(const slslam_lba_window* windows, int B, const unsigned int* const* packed, const std::vector<PinnedRegistry::Range>& rs, RefillPlan& z) {
+  for (int i = 0; i < B && (z.all_pinned || z.params_pinned); ++i) {
+    const slslam_lba_window& w = windows[i];
+    const size_t M = (size_t)w.num_observations, np = (size_t)6 * w.num_cameras + (size_t)4 * w.num_lines;
+    if (np && !PinnedRegistry::contains(rs, w.parameters, 8 * np)) { z.params_pinned = false; z.all_pinned = false; }
+    const bool pk = packed && packed[i];
+    if (M && z.all_pinned && !((pk ? PinnedRegistry::contains(rs, packed[i], 4 * M)
+                                 : (PinnedRegistry::contains(rs, w.camera_index, 4 * M) && PinnedRegistry::contains(rs, w.line_index, 4 * M) && PinnedRegistry::contains(rs, w.fixed_index, 8 * M))) &&
+                             PinnedRegistry::contains(rs, w.observations, 64 * M)))
+      z.all_pinned = false;
+  }
+}
+
+// ---- page-locked arrays: read where they are, in few large copies of the copy engine when they lie together
+int plan_pinned_ingest(slslam_lba_batch* b, const slslam_lba_window* windows, int B, const unsigned int* const* packed,
+                       const std::vector<PinnedRegistry::Range>& rs, hipStream_t s_in, RefillPlan& z) {
+  RawWin* rw = b->h_rawwin.data();
+  for (int i = 0; i < B; ++i) {
+    const slslam_lba_window& w = windows[i];
+    RawWin& r = b->host_src[(size_t)i];
+    const bool pk = packed && packed[i];
+    r.cam = pk ? nullptr : w.camera_index; r.line = pk ? nullptr : w.line_index; r.fixed = pk ? nullptr : w.fixed_index; r.packed = pk ? packed[i] : nullptr;
+    r.obs = w.observations; r.params_in = w.parameters; r.params = w.parameters;
+    rw[i] = r;
+  }
+  // Arrays that lie next to each other in host memory (a caller that carves its windows out of an arena) go up in a few large copies of
+  // the copy engine, which does not travel through the shader's L2: a kernel that keeps the link full has ~0.5 MB of host reads
+  // outstanding in the L2 channels, and every latency-bound kernel beside it waits behind them (the window build 2.7 -> 11.6 ms, k_build_tiles
+  // 0.36 -> 6.4 ms measured).  Scattered arrays: zero-copy kernel reads.
+  // The three int32 index arrays are 16 of the 80 bytes an observation sends over the link, which is what a stream of page-locked windows is
+  // bound by (1.085 GB per 1024 x 2000-line batch at 57 GB/s = 19 ms against 15 ms of solve).  The host threads narrow them to one word per
+  // observation into a pinned block on the way (4 B; ~0.25 GB of reads per batch: a few milliseconds on two threads, beside the GPU's work) -
+  // the observations and the parameters still go up from where they are.  Bad indices are reported now, as the host packer does.
+  bool any_unpacked = false;
+  for (int i = 0; i < B && !any_unpacked; ++i) any_unpacked = windows[i].num_observations > 0 && !(packed && packed[i]);
+  const bool narrow = z.nobs > 0 && any_unpacked;       // (a batch whose caller narrowed every window sends no block of ours)
+  if (narrow) {
+    const int rc = grow_stage(b->h_raw_stage, 4 * (size_t)z.nobs + 64, /*pin=*/true, /*zero=*/false);
+    if (rc != SLSLAM_OK) return rc;
+  }
+  // the ranges the copy engine is to move: the callers' arrays and - a run of its own, never merged with a neighbour - the narrowed block
+  using Rg = CopyRange;
+  std::vector<Rg> rg;
+  rg.reserve((size_t)5 * B + 1);
+  size_t payload = 0;
+  if (narrow) { rg.push_back({ (uintptr_t)b->h_raw_stage.data(), (uintptr_t)b->h_raw_stage.data() + 4 * (size_t)z.nobs, true }); payload += 4 * (size_t)z.nobs; }
+  for (int i = 0; i < B; ++i) {
+    const slslam_lba_window& w = windows[i];
+    const size_t M = (size_t)w.num_observations, np = (size_t)6 * w.num_cameras + (size_t)4 * w.num_lines;
+    const bool pk = packed && packed[i];
+    if (M && pk) rg.push_back({ (uintptr_t)packed[i], (uintptr_t)packed[i] + 4 * M, false });
+    if (M && !pk && !narrow) { rg.push_back({ (uintptr_t)w.camera_index, (uintptr_t)w.camera_index + 4 * M, false }); rg.push_back({ (uintptr_t)w.line_index, (uintptr_t)w.line_index + 4 * M, false });
+                               rg.push_back({ (uintptr_t)w.fixed_index, (uintptr_t)w.fixed_index + 8 * M, false }); }
+    if (M) rg.push_back({ (uintptr_t)w.observations, (uintptr_t)w.observations + 64 * M, false });
+    if (np) rg.push_back({ (uintptr_t)w.parameters, (uintptr_t)w.parameters + 8 * np, false });
+    payload += (pk ? 68 : narrow ? 64 : 80) * M + 8 * np;
+  }
+  std::sort(rg.begin(), rg.end(), [](const Rg& x, const Rg& y) { return x.lo < y.lo; });
+  {
+    // (lba_pack.cpp: neighbours within a page of each other, inside one registration, go up as one copy)
+    std::vector<AddrRange> regs(rs.size());
+    for (size_t k = 0; k < rs.size(); ++k) regs[k] = AddrRange{ rs[k].lo, rs[k].hi };
+    for (const AddrRange& a : plan_copy_runs(rg.data(), rg.size(), regs.data(), regs.size(), &z.idx_run)) z.runs.push_back(RefillPlan::Run{ a.lo, a.hi, 0 });
+  }
+  for (RefillPlan::Run& r : z.runs) { r.dev_off = z.dev_need + (r.lo & 255); z.dev_need += ((r.lo & 255) + (r.hi - r.lo) + 255) & ~(size_t)255; }     // (device address = host address modulo 256)
+  if (z.runs.size() > (size_t)std::max(8, B / 16) || z.dev_need > payload + payload / 8 + (1u << 20)) { z.runs.clear(); z.dev_need = 0; z.idx_run = -1; }     // scattered: zero copy
+  // The callers' arrays start up the link NOW, the host threads narrow the indices meanwhile: a submit's chain is
+  // max(narrowing, 0.87 GB of copies) + build, not their sum - with three batches in flight the sum (13 + 17 + 4 ms on a slow host thread)
+  // left 2 ms of slack against two solve periods, and a stream at the mercy of the host's jitter (0.70 of resident measured on such a box).
+  if (!z.runs.empty()) {
+    const int rc = grow_stage(b->d_stage_in, z.dev_need);
+    if (rc != SLSLAM_OK) return rc;
+    for (size_t k = 0; k < z.runs.size(); ++k)
+      if ((int)k != z.idx_run) HIP_TRY(hipMemcpyAsync(b->d_stage_in.p + z.runs[k].dev_off, (const void*)z.runs[k].lo, z.runs[k].hi - z.runs[k].lo, hipMemcpyHostToDevice, s_in));
+    z.early_dma = true;
+  }
+  if (narrow) {
     std::vector<int> st((size_t)B, SLSLAM_OK);
-    HostPool* pool = batch_pool(b, (int)std::min<long long>(B, b->opt.host_threads > 0 ? b->opt.host_threads : (B >= 64 ? 8 : 1)));
-    auto stage_one = [&](int i) {
+    auto narrow_one = [&](int i) {
+      if (packed && packed[i]) return;
       const slslam_lba_window& w = windows[i];
-      const size_t M = (size_t)w.num_observations, np = (size_t)6 * w.num_cameras + (size_t)4 * w.num_lines;
-      char* base = b->h_raw_stage + st_off[(size_t)i];
-      double* ob = reinterpret_cast<double*>(base);
-      uint32_t* ix = reinterpret_cast<uint32_t*>(base + ((64 * M + 63) & ~(size_t)63));
-      double* pr = reinterpret_cast<double*>(base + ((64 * M + 63) & ~(size_t)63) + ((4 * M + 63) & ~(size_t)63));
-      unsigned long long bad = copy_checked(ob, w.observations, 8 * M);
-      bad |= copy_checked(pr, w.parameters, np);
-      const int C = w.num_cameras, L = w.num_lines;
-      unsigned oob = 0;
-      if (packed && packed[i]) {
-        for (size_t q = 0; q < M; ++q) { const uint32_t v = packed[i][q]; oob |= (unsigned)((int)(v & 0xffffu) >= L) | (unsigned)((int)((v >> 16) & 0xffu) >= C) | (v >> 26); ix[q] = v; }
-      } else
-      for (size_t q = 0; q < M; ++q) {
-        const int c = w.camera_index[q], l = w.line_index[q];
-        oob |= (unsigned)(c < 0) | (unsigned)(c >= C) | (unsigned)(l < 0) | (unsigned)(l >= L);
-        ix[q] = ((uint32_t)l & 0xffffu) | ((uint32_t)c & 0xffu) << 16 | (w.fixed_index[2 * q] ? 1u << 24 : 0u) | (w.fixed_index[2 * q + 1] ? 1u << 25 : 0u);
-      }
-      if (bad || oob) st[(size_t)i] = SLSLAM_ERR_INVALID_ARGUMENT;           // reported now, as the host packer does
+      uint32_t* ix = reinterpret_cast<uint32_t*>(b->h_raw_stage.data()) + z.obs_off[(size_t)i];
+      if (narrow_indices((size_t)w.num_observations, w.camera_index, w.line_index, w.fixed_index, nullptr, w.num_cameras, w.num_lines, ix))
+        st[(size_t)i] = SLSLAM_ERR_INVALID_ARGUMENT;
       RawWin& r = b->host_src[(size_t)i];
-      r.cam = nullptr; r.line = nullptr; r.fixed = nullptr; r.packed = ix; r.obs = ob; r.params_in = pr;
-      r.params = params_pinned ? w.parameters : nullptr;                     // (written in place only where the GPU can reach the caller's array)
+      r.cam = nullptr; r.line = nullptr; r.fixed = nullptr; r.packed = ix;
       rw[i] = r;
     };
-    if (!run_all(pool, B, stage_one)) return SLSLAM_ERR_NO_MEMORY;
-    for (int v : st) if (v != SLSLAM_OK) return v;
-    // the whole staging copy goes up in ONE copy of the copy engine
-    if (st_off[(size_t)B] > 0) { runs.push_back(Run{ (uintptr_t)b->h_raw_stage, (uintptr_t)b->h_raw_stage + st_off[(size_t)B], 0 }); dev_need = (st_off[(size_t)B] + 255) & ~(size_t)255; }
+    int bad = run_all(batch_pool(b, (size_t)B), B, narrow_one) ? SLSLAM_OK : SLSLAM_ERR_NO_MEMORY;
+    for (int v : st) if (bad == SLSLAM_OK && v != SLSLAM_OK) bad = v;
+    if (bad != SLSLAM_OK) {
+      if (z.early_dma) (void)hipStreamSynchronize(s_in);            // the copies under way read the callers' arrays: not beyond this call
+      return bad;
+    }
   }
-  if (!runs.empty()) {
-    rc = ensure_stage_block(b, dev_need);
+  return SLSLAM_OK;
+}
+
+// ---- pageable arrays: staging, per window [observations 64 M | narrowed indices 4 M | parameters], 64-byte aligned pieces
+int stage_pageable(slslam_lba_batch* b, const slslam_lba_window* windows, int B, const unsigned int* const* packed, RefillPlan& z) {
+  RawWin* rw = b->h_rawwin.data();
+  std::vector<size_t> st_off((size_t)B + 1, 0);
+  for (int i = 0; i < B; ++i) {
+    const size_t M = (size_t)windows[i].num_observations, np = (size_t)6 * windows[i].num_cameras + (size_t)4 * windows[i].num_lines;
+    st_off[(size_t)i + 1] = st_off[(size_t)i] + ((64 * M + 63) & ~(size_t)63) + ((4 * M + 63) & ~(size_t)63) + ((8 * np + 63) & ~(size_t)63);
+  }
+  const int rc = grow_stage(b->h_raw_stage, st_off[(size_t)B], /*pin=*/true, /*zero=*/false);
+  if (rc != SLSLAM_OK) return rc;
+  std::vector<int> st((size_t)B, SLSLAM_OK);
+  auto stage_one = [&](int i) {
+    const slslam_lba_window& w = windows[i];
+    const size_t M = (size_t)w.num_observations, np = (size_t)6 * w.num_cameras + (size_t)4 * w.num_lines;
+    char* base = b->h_raw_stage.data() + st_off[(size_t)i];
+    double* ob = reinterpret_cast<double*>(base);
+    uint32_t* ix = reinterpret_cast<uint32_t*>(base + ((64 * M + 63) & ~(size_t)63));
+    double* pr = reinterpret_cast<double*>(base + ((64 * M + 63) & ~(size_t)63) + ((4 * M + 63) & ~(size_t)63));
+    unsigned long long bad = copy_checked(ob, w.observations, 8 * M);
+    bad |= copy_checked(pr, w.parameters, np);
+    const unsigned oob = narrow_indices(M, w.camera_index, w.line_index, w.fixed_index, packed ? packed[i] : nullptr, w.num_cameras, w.num_lines, ix);
+    if (bad || oob) st[(size_t)i] = SLSLAM_ERR_INVALID_ARGUMENT;           // reported now, as the host packer does
+    RawWin& r = b->host_src[(size_t)i];
+    r.cam = nullptr; r.line = nullptr; r.fixed = nullptr; r.packed = ix; r.obs = ob; r.params_in = pr;
+    r.params = z.params_pinned ? w.parameters : nullptr;                     // (written in place only where the GPU can reach the caller's array)
+    rw[i] = r;
+  };
+  if (!run_all(batch_pool(b, (size_t)B), B, stage_one)) return SLSLAM_ERR_NO_MEMORY;
+  for (int v : st) if (v != SLSLAM_OK) return v;
+  // the whole staging copy goes up in ONE copy of the copy engine
+  if (st_off[(size_t)B] > 0) {
+    z.runs.push_back(RefillPlan::Run{ (uintptr_t)b->h_raw_stage.data(), (uintptr_t)b->h_raw_stage.data() + st_off[(size_t)B], 0 });
+    z.dev_need = (st_off[(size_t)B] + 255) & ~(size_t)255;
+  }
+  return SLSLAM_OK;
+}
+
+// ---- the device reads every array at its place in the block the copy engine fills; then every window's place in the batch
+int rebase_onto_stage(slslam_lba_batch* b, const slslam_lba_window* windows, int B, const RefillPlan& z) {
+  RawWin* rw = b->h_rawwin.data();
+  if (!z.runs.empty()) {
+    const int rc = grow_stage(b->d_stage_in, z.dev_need);
     if (rc != SLSLAM_OK) return rc;
-    // the device reads every array at its place in the block
     auto to_dev = [&](const void* p) -> const void* {
       if (!p) return nullptr;
       const uintptr_t a = (uintptr_t)p;
-      auto it = std::upper_bound(runs.begin(), runs.end(), a, [](uintptr_t v, const Run& r) { return v < r.lo; });
+      auto it = std::upper_bound(z.runs.begin(), z.runs.end(), a, [](uintptr_t v, const RefillPlan::Run& r) { return v < r.lo; });
       --it;
-      return b->d_stage_in + it->dev_off + (a - it->lo);
+      return b->d_stage_in.p + it->dev_off + (a - it->lo);
     };
     for (int i = 0; i < B; ++i) {
       RawWin& r = rw[i];
@@ -1814,17 +1895,20 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
       r.obs = (const double*)to_dev(r.obs); r.params_in = (const double*)to_dev(r.params_in);
     }
   }
-  b->ingest_mode = runs.empty() ? 0 : 1;
-  b->ingest_pinned = all_pinned;
   for (int i = 0; i < B; ++i) {
     RawWin& r = rw[i];
-    r.param_off = par_off[(size_t)i]; r.C = windows[i].num_cameras; r.L = windows[i].num_lines; r.M = windows[i].num_observations;
-    r.cam_off = cam_off[(size_t)i]; r.line_off = line_off[(size_t)i]; r.obs_off = (int)obs_off[(size_t)i]; r.pad = 0;
+    r.param_off = z.par_off[(size_t)i]; r.C = windows[i].num_cameras; r.L = windows[i].num_lines; r.M = windows[i].num_observations;
+    r.cam_off = z.cam_off[(size_t)i]; r.line_off = z.line_off[(size_t)i]; r.obs_off = (int)z.obs_off[(size_t)i]; r.pad = 0;
     RawWin& h = b->host_src[(size_t)i];
     h.param_off = r.param_off; h.C = r.C; h.L = r.L; h.M = r.M; h.cam_off = r.cam_off; h.line_off = r.line_off; h.obs_off = r.obs_off; h.pad = 0;
   }
-  const auto tt2 = std::chrono::steady_clock::now();
-  // ---- commit: the batch now IS the new windows (what the device makes of them comes back with the results: slslam_lba_batch_wait)
+  return SLSLAM_OK;
+}
+
+// ---- commit: the batch now IS the new windows (what the device makes of them comes back with the results: slslam_lba_batch_wait)
+void refill_commit(slslam_lba_batch* b, const slslam_lba_window* windows, int B, const RefillPlan& z) {
+  const RawWin* rw = b->h_rawwin.data();
+  b->ingest_pinned = z.all_pinned;
   b->wins_spare.resize((size_t)B);
   for (int i = 0; i < B; ++i) {
     PackedWindow& P = b->wins_spare[(size_t)i];
@@ -1834,7 +1918,7 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
   }
   b->wins.swap(b->wins_spare);
   b->h_wins.assign((size_t)B, WinDesc());
-  b->h_param_off.assign(par_off.begin(), par_off.end() - 1);
+  b->h_param_off.assign(z.par_off.begin(), z.par_off.end() - 1);
   b->h_ob_orig_off.resize((size_t)B);
   for (int i = 0; i < B; ++i) {
     WinDesc& wd = b->h_wins[(size_t)i];
@@ -1843,19 +1927,24 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
     b->h_ob_orig_off[(size_t)i] = rw[i].obs_off;
   }
   b->h_win_graded.assign((size_t)std::max(1, B), 0);
-  b->total_params = nparams; b->nobs = nobs;
-  b->used_ncam = ncam; b->used_nline = nline; b->used_nobs = nobs; b->used_tiles = (long long)b->d_tiles.n; b->used_items = (long long)(b->d_items.n / 2);
-  b->device_built = true; b->inplace_export = params_pinned; b->results_inplace = false;
+  b->total_params = z.nparams; b->nobs = z.nobs;
+  b->used_ncam = z.ncam; b->used_nline = z.nline; b->used_nobs = z.nobs; b->used_tiles = (long long)b->d_tiles.n; b->used_items = (long long)(b->d_items.n / 2);
+  b->device_built = true; b->inplace_export = z.params_pinned; b->results_inplace = false;
   b->src_windows.assign(windows, windows + B);
   b->build_status.assign((size_t)B, SLSLAM_OK);
   b->downloaded = false;
-  ++b->n_device_builds; if (all_pinned) ++b->n_zero_copy;
-  // ---- enqueue
+  ++b->n_device_builds; if (z.all_pinned) ++b->n_zero_copy;
+}
+
+constexpr int kIngestWorkgroups = 32;       // k_ingest's grid when it reads the callers' arrays itself (zero copy, below)
+
+// ---- enqueue: the ingest on `s_in`, the build and what the solve needs on `s`
+int refill_enqueue(slslam_lba_batch* b, int B, const RefillPlan& z, hipStream_t s, hipStream_t s_in) {
   BuildPtrs P;
   std::memset(&P, 0, sizeof(P));
   P.raw = b->d_rawwin.p; P.bw = b->d_buildwin.p; P.nwin = B; P.grouping = b->elim_grouped ? 1 : 0;
   P.ob_raw = b->d_ob_raw.p; P.raw_idx = b->d_raw_idx.p; P.line_raw = b->d_line_raw.p; P.lflags = b->d_lflags.p; P.fmask = b->d_fmask.p; P.line_pos = b->d_line_pos.p;
-  P.obs_in_place = runs.empty() ? 0 : 1;       // the copy engine's block is read where it is (k_permute_obs): no second copy of the observations
+  P.obs_in_place = z.runs.empty() ? 0 : 1;       // the copy engine's block is read where it is (k_permute_obs): no second copy of the observations
   P.mid_keys = b->d_mid_keys.p; P.mid_li = b->d_mid_li.p; P.mid_rows = b->d_mid_rows.p; P.mid_next = b->d_mid_next.p; P.mid_trows = b->d_mid_trows.p; P.mid_tptr = b->d_mid_tptr.p; P.mid = b->d_mid.p;
   P.wins = b->d_wins.p; P.tiles = b->d_tiles.p; P.chunks = b->d_chunks.p; P.items = b->d_items.p; P.lane_map = b->d_lane_map.p; P.line_desc = b->d_line_desc.p;
   P.cam_x0 = b->d_cam_x0.p; P.cam_cf = b->d_cam_cf.p; P.cam_win = b->d_cam_win.p;
@@ -1868,61 +1957,86 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
   a.cap_tiles = (int)std::min<size_t>(b->d_tiles.n, 0x7fffffff); a.cap_items = (int)std::min<size_t>(b->d_items.n / 2, 0x7fffffff); a.cap_chunks = b->nchunk;
   a.cap_maxn = b->cap_maxn; a.slab_sum = b->slab_sum_stride ? 1 : 0; a.slab_sum_image = b->slab_sum_image ? 1 : 0;
   a.cap_slab = (long long)b->d_slab.n; a.cap_sys = (long long)b->d_ysys.n; a.slab_sum_stride = b->slab_sum_stride;
-  a.nline = (int)nline; a.nobs = (int)nobs; a.max_free = b->elim_mode == 1 ? (int)kMfmaMaxFree : (int)kMaxFreeCams;
+  a.nline = (int)z.nline; a.nobs = (int)z.nobs; a.max_free = b->elim_mode == 1 ? (int)kMfmaMaxFree : (int)kMaxFreeCams;
   for (int cf = 0; cf < kMaxFreeCams + 2; ++cf) a.sys_map_off[cf] = (size_t)cf < b->sys_map_off_of_cf.size() ? b->sys_map_off_of_cf[(size_t)cf] : -1;
-  {
-    static bool attr_set = false;
-    if (!attr_set) {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_build_lines, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_build_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_build_order, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_build_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-      attr_set = true;
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(b->d_rawwin.p, rw, sizeof(RawWin) * (size_t)B, hipMemcpyHostToDevice, s_in));
+  static bool build_lds_set = false;            // (once per process)
+  if (!build_lds_set) { HIP_TRY(allow_build_lds()); build_lds_set = true; }
+  HIP_TRY(hipMemcpyAsync(b->d_rawwin.p, b->h_rawwin.data(), sizeof(RawWin) * (size_t)B, hipMemcpyHostToDevice, s_in));
   HIP_TRY(hipMemsetAsync(b->d_buildwin.p, 0, sizeof(BuildWin) * (size_t)B, s_in));
-  static const int ingest_wgs = std::getenv("SLSLAM_INGEST_WORKGROUPS") ? std::max(1, std::atoi(std::getenv("SLSLAM_INGEST_WORKGROUPS"))) : 32;
-  for (size_t k = 0; k < runs.size(); ++k)
-    if (!early_dma || (int)k == idx_run) HIP_TRY(hipMemcpyAsync(b->d_stage_in + runs[k].dev_off, (const void*)runs[k].lo, runs[k].hi - runs[k].lo, hipMemcpyHostToDevice, s_in));
+  for (size_t k = 0; k < z.runs.size(); ++k)
+    if (!z.early_dma || (int)k == z.idx_run) HIP_TRY(hipMemcpyAsync(b->d_stage_in.p + z.runs[k].dev_off, (const void*)z.runs[k].lo, z.runs[k].hi - z.runs[k].lo, hipMemcpyHostToDevice, s_in));
   // zero copy: the ingest kernel IS the transfer (32 workgroups keep the link full: tools/micro/zero_copy_bench.hip; more only queue in the L2)
-  if (B > 0 && runs.empty()) hipLaunchKernelGGL(k_ingest, dim3((unsigned)std::min(B, ingest_wgs)), dim3(256), 0, s_in, P);
+  if (B > 0 && z.runs.empty()) hipLaunchKernelGGL(k_ingest, dim3((unsigned)std::min(B, kIngestWorkgroups)), dim3(256), 0, s_in, P);
   if (!b->ev_stage_free) HIP_TRY(hipEventCreateWithFlags(&b->ev_stage_free, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_stage_free, s_in));
   if (s_in != s) HIP_TRY(hipStreamWaitEvent(s, b->ev_stage_free, 0));
   // copy engine: the ingest reads the block in HBM (a fraction of a millisecond), on the solve stream
-  if (B > 0 && !runs.empty()) hipLaunchKernelGGL(k_ingest, dim3((unsigned)std::min(B, 1024)), dim3(256), 0, s, P);
+  if (B > 0 && !z.runs.empty()) hipLaunchKernelGGL(k_ingest, dim3((unsigned)std::min(B, 1024)), dim3(256), 0, s, P);
   // the records beyond the refill's lines / cameras belong to no window
-  if ((size_t)nline < b->d_line_win.n) HIP_TRY(hipMemsetAsync(b->d_line_win.p + nline, 0xFF, (b->d_line_win.n - (size_t)nline) * sizeof(int), s));
-  if ((size_t)ncam < b->d_cam_win.n) {
-    HIP_TRY(hipMemsetAsync(b->d_cam_win.p + ncam, 0xFF, (b->d_cam_win.n - (size_t)ncam) * sizeof(int), s));
-    HIP_TRY(hipMemsetAsync(b->d_cam_cf.p + ncam, 0xFF, (b->d_cam_cf.n - (size_t)ncam) * sizeof(int), s));
+  if ((size_t)z.nline < b->d_line_win.n) HIP_TRY(hipMemsetAsync(b->d_line_win.p + z.nline, 0xFF, (b->d_line_win.n - (size_t)z.nline) * sizeof(int), s));
+  if ((size_t)z.ncam < b->d_cam_win.n) {
+    HIP_TRY(hipMemsetAsync(b->d_cam_win.p + z.ncam, 0xFF, (b->d_cam_win.n - (size_t)z.ncam) * sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(b->d_cam_cf.p + z.ncam, 0xFF, (b->d_cam_cf.n - (size_t)z.ncam) * sizeof(int), s));
   }
   if (B > 0) {
-    hipLaunchKernelGGL(k_build_lines, dim3((unsigned)B), dim3(256), build_lines_lds_bytes(maxL), s, P);
-    hipLaunchKernelGGL(k_build_rows, dim3((unsigned)B), dim3(128), build_rows_lds_bytes(maxL), s, P);
-    hipLaunchKernelGGL(k_build_order, dim3((unsigned)B), dim3(256), lds_build, s, P);
+    hipLaunchKernelGGL(k_build_lines, dim3((unsigned)B), dim3(256), build_lines_lds_bytes(z.maxL), s, P);
+    hipLaunchKernelGGL(k_build_rows, dim3((unsigned)B), dim3(128), build_rows_lds_bytes(z.maxL), s, P);
+    hipLaunchKernelGGL(k_build_order, dim3((unsigned)B), dim3(256), z.lds_build, s, P);
     hipLaunchKernelGGL(k_build_layout, dim3(1), dim3(256), 0, s, P, a);
-    hipLaunchKernelGGL(k_build_tiles, dim3((unsigned)B), dim3(256), lds_tiles, s, P, (const int*)b->d_cam_cf.p, tiles_stage_m);
+    hipLaunchKernelGGL(k_build_tiles, dim3((unsigned)B), dim3(256), z.lds_tiles, s, P, (const int*)b->d_cam_cf.p, z.tiles_stage_m);
   }
   HIP_TRY(hipGetLastError());
-  // what a fresh batch finds zeroed
-  HIP_TRY(hipMemsetAsync(b->d_cam_scale.p, 0, b->d_cam_scale.n * sizeof(double), s));
-  HIP_TRY(hipMemsetAsync(b->d_line_scale.p, 0, b->d_line_scale.n * sizeof(double), s));
-  HIP_TRY(hipMemsetAsync(b->d_cam_tab.p, 0, b->d_cam_tab.n * sizeof(double), s));
-  if (b->slab_sum_image) HIP_TRY(hipMemsetAsync(b->d_slab_sum.p, 0, b->d_slab_sum.n * sizeof(double), s));
-  HIP_TRY(hipMemsetAsync(b->d_active.p, 0, sizeof(unsigned int), s));
-  if (nobs > 0 && maxM > 0)
-    hipLaunchKernelGGL(k_permute_obs, dim3((unsigned)((maxM + 255) / 256), (unsigned)B), dim3(256), 0, s, b->ptrs, (const double*)b->d_ob_raw.p, (const int*)b->d_ob_orig.p, b->d_ob.p,
-                       (const RawWin*)(runs.empty() ? nullptr : b->d_rawwin.p));
-  rc = device_init_after_upload(b, s);
+  const int rc = zero_refilled(b, s);
+  if (rc != SLSLAM_OK) return rc;
+  if (z.nobs > 0 && z.maxM > 0)
+    hipLaunchKernelGGL(k_permute_obs, dim3((unsigned)((z.maxM + 255) / 256), (unsigned)B), dim3(256), 0, s, b->ptrs, (const double*)b->d_ob_raw.p, (const int*)b->d_ob_orig.p, b->d_ob.p,
+                       (const RawWin*)(z.runs.empty() ? nullptr : b->d_rawwin.p));
+  return device_init_after_upload(b, s);
+}
+
+// The LBAProblem::build stage of a refill ON THE DEVICE (lba_device_build.h).  SLSLAM_OK: taken; SLSLAM_ERR_UNSUPPORTED: not this path's
+// business - nothing was touched, the caller goes on with the host packer; anything else: the refill failed.
+// Two streams: the ingest (the host link's business: few workgroups for ~20 ms per 1024 x 2000-line batch) is enqueued on `s_in`, everything
+// after it on `s` behind an event.  One stream for both (the plain refill entry point) is fine; a STREAM of windows hands ONE ingest stream
+// and ONE solve stream to all its slots, so that batch k + 1 crosses the link while batch k is solved and neither shares its resource
+// (batches that ingest and solve at the same time on streams of their own fall into step: three ingests share the link, then three
+// solves share the chip - measured 37 ms per batch against 20).
+// packed (optional): packed[i] != nullptr replaces window i's three index arrays by the narrowed form (slslam_pack_indices: one 32-bit word per
+// observation) - 68 instead of 80 bytes per observation over the host link.
+int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, hipStream_t s, hipStream_t s_in, const unsigned int* const* packed = nullptr) {
+  if (b->opt.device_build < 0 || b->d_rawwin.n < (size_t)std::max(1, B) || !b->d_ob_raw.p) return SLSLAM_ERR_UNSUPPORTED;
+  if (std::getenv("SLSLAM_CHUNK_WEIGHTS")) return SLSLAM_ERR_UNSUPPORTED;          // (an experiment knob of the host-side cut)
+  // (k_build_layout dispatches graded chunks in at most kLayoutMaxRank classes: a batch cut for more rounds of the wave slots - several
+  // thousand 2000-line windows - keeps the host packer)
+  if ((b->opt.chunks_per_window < 0 ? (-b->opt.chunks_per_window) / 1000 : (b->opt.reproducible ? 3 : b->auto_rounds)) > (int)kLayoutMaxRank) return SLSLAM_ERR_UNSUPPORTED;
+  static const bool timing = std::getenv("SLSLAM_REFILL_TIMING") != nullptr;
+  const auto tt0 = std::chrono::steady_clock::now();
+  RefillPlan z;
+  int rc = refill_sizes(b, windows, B, packed, z);
+  if (rc != SLSLAM_OK) return rc;
+  if ((rc = ensure_build_host_buffers(b, B)) != SLSLAM_OK) return rc;
+  const std::vector<PinnedRegistry::Range> rs = PinnedRegistry::get().snapshot();
+  where_pinned(windows, B, packed, rs, z);
+  if ((rc = wait_stage_free(b)) != SLSLAM_OK) return rc;
+  const auto tt1 = std::chrono::steady_clock::now();
+  b->host_src.assign((size_t)B, RawWin());
+  rc = z.all_pinned ? plan_pinned_ingest(b, windows, B, packed, rs, s_in, z) : stage_pageable(b, windows, B, packed, z);
+  if (rc != SLSLAM_OK) return rc;
+  if ((rc = rebase_onto_stage(b, windows, B, z)) != SLSLAM_OK) return rc;
+  const auto tt2 = std::chrono::steady_clock::now();
+  refill_commit(b, windows, B, z);
+  rc = refill_enqueue(b, B, z, s, s_in);
   if (timing) {
     const auto tt3 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
     std::fprintf(stderr, "slslam refill (device build, %s): sizes + wait %.2f  stage %.2f  commit + enqueue %.2f ms  (%d windows)\n",
-                 all_pinned ? (runs.empty() ? "zero copy" : "pinned arrays, copy engine") : "staged", ms(tt0, tt1), ms(tt1, tt2), ms(tt2, tt3), B);
+                 z.all_pinned ? (z.runs.empty() ? "zero copy" : "pinned arrays, copy engine") : "staged", ms_between(tt0, tt1), ms_between(tt1, tt2), ms_between(tt2, tt3), B);
   }
   return rc;
+}
+
+// "Can this batch be refilled as it is": the captured solve's launches were made for this many windows of the tiled sweeps
+bool refillable_as_is(const slslam_lba_batch* b, int n) {
+  return b->finalized && b->refillable && !b->part[0] && !b->big_mode && !b->fused_motion_only && !b->opt.reuse_elimination && (int)b->wins.size() == n;
 }
 
 }  // namespace
@@ -1932,9 +2046,8 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
 extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_window* windows, int n, void* stream) {
   if (!b || (!windows && n > 0)) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (!b->finalized) return SLSLAM_ERR_STATE;
-  if (!b->refillable || b->part[0] || b->big_mode || b->fused_motion_only || b->opt.reuse_elimination) return SLSLAM_ERR_UNSUPPORTED;
-  const int B = (int)b->wins.size();
-  if (n != B) return SLSLAM_ERR_UNSUPPORTED;              // the launches of the captured solve were made for this many windows
+  if (!refillable_as_is(b, n)) return SLSLAM_ERR_UNSUPPORTED;
+  const int B = n;
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t s = (hipStream_t)stream;
   {
@@ -1944,10 +2057,8 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   }
   static const bool timing = std::getenv("SLSLAM_REFILL_TIMING") != nullptr;      // host-side split of a refill on stderr
   const auto tt0 = std::chrono::steady_clock::now();
-  if (b->ev_stage_free) HIP_TRY(hipEventSynchronize(b->ev_stage_free));      // the host image may still feed the previous refill's copies
-  // (an asynchronous download still under way has arrived before the host image is touched - and stays readable: a refill that is refused
-  // below leaves the batch as it was, its results included)
-  if (b->results_pending) { HIP_TRY(hipEventSynchronize(b->ev_results)); b->results_pending = false; adopt_device_build(b); b->downloaded = true; if (b->profiling) b->harvest_events(); }
+  int rc = wait_stage_free(b);      // (the host image may still feed the previous refill's copies)
+  if (rc != SLSLAM_OK) return rc;
   const auto tt1 = std::chrono::steady_clock::now();
   // ---- pack (the LBAProblem::build stage, one window per host thread), the observations straight into the host image: where a window's
   // observations go only depends on the counts before it
@@ -1962,14 +2073,12 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   std::vector<PackedWindow>& wins = b->wins_spare;      // (the windows of the refill before last: their vectors are reused)
   wins.resize((size_t)B);
   std::vector<int> st((size_t)B, SLSLAM_OK);
-  HostPool* pool = batch_pool(b, (int)std::min<long long>(B, b->opt.host_threads > 0 ? b->opt.host_threads : (B >= 64 ? 8 : 1)));
+  HostPool* pool = batch_pool(b, (size_t)B);
   // (the observation region of the pinned image holds the windows' RAW observations, one after the other, after a refill: the device permutes)
-  static const bool host_gather = std::getenv("SLSLAM_REFILL_HOST_GATHER") != nullptr;      // (measurement switch: the gather on the host threads, as a fresh batch is built)
-  const bool device_gather = b->d_ob_raw.n >= (size_t)8 * (size_t)obs_off[(size_t)B] && b->d_ob_raw.p && !host_gather;
   auto pack_one = [&](int i) {
     ObPlanes dest;
     for (int q = 0; q < 4; ++q) dest.plane[q] = img.ob + ((size_t)q * (size_t)img.ob_stride + (size_t)obs_off[(size_t)i]) * 2;
-    if (device_gather) dest.raw = img.ob + (size_t)obs_off[(size_t)i] * 8;
+    dest.raw = img.ob + (size_t)obs_off[(size_t)i] * 8;
     st[(size_t)i] = pack_window(&windows[i], &wins[(size_t)i], grouping, &dest);
   };
   if (!run_all(pool, B, pack_one)) return SLSLAM_ERR_NO_MEMORY;
@@ -1981,18 +2090,15 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   }
   // ---- layout, cut like the batch's first windows, and does it fit
   LayoutPlan plan;
-  int rc = plan_layout(b, wins, /*frozen=*/true, &plan);
+  rc = plan_layout(b, wins, /*frozen=*/true, &plan);
   if (rc != SLSLAM_OK) return rc;
   bool fits = (size_t)plan.ncam <= b->d_cam_cf.n && (size_t)plan.nline <= b->d_line_win.n && plan.nobs <= img.ob_stride &&
               (size_t)plan.ntiles <= b->d_tiles.n && (size_t)plan.nitems * 2 <= b->d_items.n && (int)plan.chunks.size() <= b->nchunk &&
               (size_t)plan.slab <= b->d_slab.n && (size_t)plan.sys <= b->d_ysys.n && (size_t)plan.params <= b->d_params_out.n &&
               (size_t)plan.params <= b->h_params.size() && plan.maxC <= b->cap_maxC && plan.maxn <= b->cap_maxn;
   if (b->slab_sum_stride) {
-    if (b->slab_sum_image) {
-      long long ext = 0;
-      for (const WinDesc& wd : plan.wins) { const int N = solve_pad(wd.n); ext = std::max<long long>(ext, (long long)N * solve_stride(wd.n) + 6LL * N); }
-      fits = fits && ((ext + kSlabScalars + 1) / 2) * 2 <= b->slab_sum_stride;
-    } else fits = fits && (long long)plan.max_sys + kSlabScalars <= b->slab_sum_stride;
+    if (b->slab_sum_image) fits = fits && slab_sum_image_stride(plan.wins) <= b->slab_sum_stride;
+    else fits = fits && (long long)plan.max_sys + kSlabScalars <= b->slab_sum_stride;
   } else fits = fits && plan.max_chunks <= 8;            // (more chunks per window would need k_slab_reduce in the captured solve)
   for (WinDesc& wd : plan.wins) {
     const int off = (size_t)(wd.n / 6) < b->sys_map_off_of_cf.size() ? b->sys_map_off_of_cf[(size_t)wd.n / 6] : -1;
@@ -2022,29 +2128,20 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   SLS_UP(b->d_line_x0, 4 * plan.nline); SLS_UP(b->d_line_ptr, plan.nline + 1); SLS_UP(b->d_line_flags, std::max<long long>(1, plan.nline));
   SLS_UP(b->d_line_win, b->d_line_win.n); SLS_UP(b->d_line_orig, plan.nline);
   SLS_UP(b->d_ob_cam, plan.nobs); SLS_UP(b->d_ob_orig, plan.nobs); SLS_UP(b->d_param_off, B);
-  if (device_gather && plan.nobs > 0) {
+  if (plan.nobs > 0) {
     int maxM = 0;
     for (int i = 0; i < B; ++i) maxM = std::max(maxM, windows[i].num_observations);
     HIP_TRY(hipMemcpyAsync(b->d_ob_raw.p, img.ob, (size_t)plan.nobs * 8 * sizeof(double), hipMemcpyHostToDevice, s));
     if (maxM > 0) hipLaunchKernelGGL(k_permute_obs, dim3((unsigned)((maxM + 255) / 256), (unsigned)B), dim3(256), 0, s, b->ptrs, (const double*)b->d_ob_raw.p, (const int*)b->d_ob_orig.p, b->d_ob.p);
-  } else {
-    for (int q = 0; q < 4 && plan.nobs > 0; ++q)
-      HIP_TRY(hipMemcpyAsync(b->d_ob.p + (size_t)q * (size_t)img.ob_stride * 2, img.ob + (size_t)q * (size_t)img.ob_stride * 2, (size_t)plan.nobs * 2 * sizeof(double), hipMemcpyHostToDevice, s));
   }
 #undef SLS_UP
   if (!b->ev_stage_free) HIP_TRY(hipEventCreateWithFlags(&b->ev_stage_free, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_stage_free, s));
-  // what a fresh batch finds zeroed
-  HIP_TRY(hipMemsetAsync(b->d_cam_scale.p, 0, b->d_cam_scale.n * sizeof(double), s));
-  HIP_TRY(hipMemsetAsync(b->d_line_scale.p, 0, b->d_line_scale.n * sizeof(double), s));
-  HIP_TRY(hipMemsetAsync(b->d_cam_tab.p, 0, b->d_cam_tab.n * sizeof(double), s));
-  if (b->slab_sum_image) HIP_TRY(hipMemsetAsync(b->d_slab_sum.p, 0, b->d_slab_sum.n * sizeof(double), s));
-  HIP_TRY(hipMemsetAsync(b->d_active.p, 0, sizeof(unsigned int), s));
-  rc = device_init_after_upload(b, s);
+  rc = zero_refilled(b, s);
+  if (rc == SLSLAM_OK) rc = device_init_after_upload(b, s);
   if (timing) {
     const auto tt4 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
-    std::fprintf(stderr, "slslam refill: wait %.2f  pack %.2f  plan+fill %.2f  enqueue %.2f ms  (%d windows, %d threads)\n", ms(tt0, tt1), ms(tt1, tt2), ms(tt2, tt3), ms(tt3, tt4), B, pool ? pool->threads() : 1);
+    std::fprintf(stderr, "slslam refill: wait %.2f  pack %.2f  plan+fill %.2f  enqueue %.2f ms  (%d windows, %d threads)\n", ms_between(tt0, tt1), ms_between(tt1, tt2), ms_between(tt2, tt3), ms_between(tt3, tt4), B, pool ? pool->threads() : 1);
   }
   return rc;
 }
@@ -2194,10 +2291,8 @@ extern "C" int slslam_lba_batch_linearise(slslam_lba_batch* b, int index, double
   DevBuf<double> dr, djc, djl, dc;
   int rc;
   if ((rc = dr.alloc(std::max<size_t>(1, 4 * M))) || (rc = djc.alloc(std::max<size_t>(1, 24 * M))) ||
-      (rc = djl.alloc(std::max<size_t>(1, 16 * M))) || (rc = dc.alloc(1))) {
-    dr.release(); djc.release(); djl.release(); dc.release();
+      (rc = djl.alloc(std::max<size_t>(1, 16 * M))) || (rc = dc.alloc(1)))
     return rc;
-  }
   // make sure the trig table of the current buffer is valid
   if (b->nline > 0) hipLaunchKernelGGL(k_line_trig, dim3((unsigned)((b->nline + 255) / 256)), dim3(256), 0, 0, b->ptrs, 0);
   hipLaunchKernelGGL(k_debug_linearise, dim3(1), dim3(64), b->lds_cost, 0, b->ptrs, b->pol, index,
@@ -2209,7 +2304,6 @@ extern "C" int slslam_lba_batch_linearise(slslam_lba_batch* b, int index, double
     if (e == hipSuccess) e = hipMemcpy(j_line, djl.p, 16 * M * sizeof(double), hipMemcpyDeviceToHost);
   }
   if (e == hipSuccess) e = hipMemcpy(cost, dc.p, sizeof(double), hipMemcpyDeviceToHost);
-  dr.release(); djc.release(); djl.release(); dc.release();
   HIP_TRY(e);
   return SLSLAM_OK;
 }
@@ -2272,12 +2366,9 @@ extern "C" int slslam_pinned_unregister(void* p) {
 extern "C" int slslam_pinned_contains(const void* p, size_t bytes) { return PinnedRegistry::get().contains(p, bytes) ? 1 : 0; }
 extern "C" int slslam_pack_indices(int n, const int* camera_index, const int* line_index, const int* fixed_index, unsigned int* packed) {
   if (n < 0 || (n > 0 && (!camera_index || !line_index || !fixed_index || !packed))) return SLSLAM_ERR_INVALID_ARGUMENT;
-  for (int i = 0; i < n; ++i) {
-    const int c = camera_index[i], l = line_index[i];
-    if (c < 0 || c > 0xff || l < 0 || l > 0xfffe) return SLSLAM_ERR_UNSUPPORTED;
-    packed[i] = (unsigned)l | (unsigned)c << 16 | (fixed_index[2 * i] ? 1u << 24 : 0u) | (fixed_index[2 * i + 1] ? 1u << 25 : 0u);
-  }
-  return SLSLAM_OK;
+  // (what the word's fields hold: cameras 0 - 255, lines 0 - 65534)
+  const unsigned oob = narrow_indices((size_t)n, camera_index, line_index, fixed_index, nullptr, 0x100, 0xffff, packed);
+  return oob ? SLSLAM_ERR_UNSUPPORTED : SLSLAM_OK;
 }
 
 // Test hook (tests/test_gpu_device_build.py): ONE window through the device build alone - k_ingest, k_build_lines / _rows / _order, k_build_layout,
@@ -2322,7 +2413,7 @@ extern "C" int slslam_debug_device_pack_timed(const slslam_lba_window* w, int gr
   ar.scratch(d_raw, 1); ar.zeroed(d_bw, 1); ar.zeroed(d_dbg, 16);
   ar.scratch(d_mid_keys, Lq); ar.scratch(d_mid_li, Lq); ar.scratch(d_mid_rows, Lq); ar.scratch(d_mid_next, Lq); ar.scratch(d_mid_trows, Lq + 8); ar.scratch(d_mid_tptr, Lq + 8); ar.scratch(d_mid, 1);
   int rc = ar.commit();
-  if (rc != SLSLAM_OK) { ar.release(); return rc; }
+  if (rc != SLSLAM_OK) return rc;
   RawWin r;
   std::memset(&r, 0, sizeof(r));
   r.cam = d_cam.p; r.line = d_line.p; r.fixed = d_fixed.p; r.packed = nullptr; r.obs = d_obs.p; r.params_in = d_params.p; r.params = d_params.p;
@@ -2342,10 +2433,7 @@ extern "C" int slslam_debug_device_pack_timed(const slslam_lba_window* w, int gr
   std::memset(&a, 0, sizeof(a));
   a.chunks_per_window = 1; a.elim_waves = 1; a.cap_tiles = (int)cap_tiles; a.cap_items = (int)cap_items; a.cap_chunks = 16; a.cap_maxn = 6 * kMaxFreeCams;
   a.slab_sum = 0; a.cap_slab = 1LL << 40; a.cap_sys = 1LL << 40; a.nline = L; a.nobs = M; a.max_free = kMaxFreeCams;
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_build_lines, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_build_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_build_order, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_build_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
+  if (e == hipSuccess) e = allow_build_lds();
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_ingest, dim3(1), dim3(256), 0, 0, P);
     hipLaunchKernelGGL(k_build_lines, dim3(1), dim3(256), build_lines_lds_bytes(L), 0, P);
@@ -2364,7 +2452,7 @@ extern "C" int slslam_debug_device_pack_timed(const slslam_lba_window* w, int gr
   if (e == hipSuccess && phase_clocks) e = hipMemcpy(phase_clocks, d_dbg.p, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
   if (e == hipSuccess && bw.status == 0) {
     out_counts[0] = bw.Cf; out_counts[1] = bw.ntiles; out_counts[2] = bw.nitems; out_counts[3] = bw.nfree_params; out_counts[4] = bw.nkept;
-    if (bw.ntiles > max_tiles || bw.nitems > max_items) { ar.release(); return SLSLAM_ERR_UNSUPPORTED; }
+    if (bw.ntiles > max_tiles || bw.nitems > max_items) return SLSLAM_ERR_UNSUPPORTED;
     auto dl = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && dst && bytes) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); };
     dl(line_order, d_line_orig.p, sizeof(int) * (size_t)L); dl(line_ptr, d_line_ptr.p, sizeof(int) * ((size_t)L + 1));
     dl(ob_orig, d_ob_orig.p, sizeof(int) * (size_t)M); dl(ob_cam, d_ob_cam.p, sizeof(int) * (size_t)M); dl(cam_cf, d_cam_cf.p, sizeof(int) * (size_t)C);
@@ -2373,7 +2461,6 @@ extern "C" int slslam_debug_device_pack_timed(const slslam_lba_window* w, int gr
     dl(ht.data(), d_tiles.p, sizeof(Tile) * ht.size());
     for (size_t t = 0; t < ht.size() && tiles; ++t) { tiles[4 * t] = ht[t].line_begin; tiles[4 * t + 1] = ht[t].nlines; tiles[4 * t + 2] = ht[t].flags; tiles[4 * t + 3] = ht[t].nitems; }
   }
-  ar.release();
   HIP_TRY(e);
   return SLSLAM_OK;
 }
@@ -2409,6 +2496,39 @@ struct slslam_lba_stream {
   long long n_device_builds = 0, n_zero_copy = 0, n_fallback_windows = 0;
 };
 
+namespace {
+// A batch the stream's host threads were lent to
+void destroy_lent(slslam_lba_batch* b) {
+  b->ext_pool = nullptr;
+  slslam_lba_batch_destroy(b);
+}
+
+// A new batch for a slot: the set packed by the stream's host threads, finalized with the stream's options
+int make_slot_batch(slslam_lba_stream* st, const slslam_lba_window* ws, int n, slslam_lba_batch** out) {
+  slslam_lba_batch* b = nullptr;
+  int rc = slslam_lba_batch_create(st->device, &b);
+  if (rc != SLSLAM_OK) return rc;
+  b->ext_pool = st->pool.get();
+  b->wins.resize((size_t)n);
+  std::vector<int> ps((size_t)n, SLSLAM_OK);
+  if (!st->pool->run(n, [&](int i) { ps[(size_t)i] = pack_window(&ws[i], &b->wins[(size_t)i]); })) rc = SLSLAM_ERR_NO_MEMORY;
+  for (int r : ps) if (r != SLSLAM_OK) rc = r;
+  if (rc == SLSLAM_OK) rc = slslam_lba_batch_finalize(b, &st->opt);
+  if (rc != SLSLAM_OK) { destroy_lent(b); return rc; }
+  *out = b;
+  return SLSLAM_OK;
+}
+
+// The slot's batch destroyed, once every stream that may still use it has drained
+int drop_slot_batch(slslam_lba_stream* st, slslam_lba_stream::Slot& sl) {
+  if (sl.stream) HIP_TRY(hipStreamSynchronize(sl.stream));
+  HIP_TRY(hipStreamSynchronize(st->solve_stream)); HIP_TRY(hipStreamSynchronize(st->build_stream)); HIP_TRY(hipStreamSynchronize(st->result_stream));
+  destroy_lent(sl.batch);
+  sl.batch = nullptr;
+  return SLSLAM_OK;
+}
+}  // namespace
+
 extern "C" int slslam_lba_stream_create(int device, const slslam_solver_options* opt, int depth, slslam_lba_stream** out) {
   if (!out) return SLSLAM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
@@ -2434,27 +2554,11 @@ extern "C" int slslam_lba_stream_create(int device, const slslam_solver_options*
   // The ingest stream gets the highest priority: its few workgroups must find wave slots while a solve's thousands are queued.
   int pr_lo = 0, pr_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
-  // (experiment: SLSLAM_BUILD_CUS = n confines the build stream to n compute units spread over the chip)
-  auto make_build_stream = [&](hipStream_t* out) -> hipError_t {
-    const int ncu = std::getenv("SLSLAM_BUILD_CUS") ? std::atoi(std::getenv("SLSLAM_BUILD_CUS")) : 0;
-    hipDeviceProp_t prop;
-    if (ncu > 0 && hipGetDeviceProperties(&prop, device) == hipSuccess && ncu < prop.multiProcessorCount) {
-      const int total = prop.multiProcessorCount;
-      std::vector<uint32_t> mask((size_t)(total + 31) / 32, 0u);
-      for (int k = 0; k < ncu; ++k) { const int cu = (int)((long long)k * total / ncu); mask[(size_t)cu / 32] |= 1u << (cu % 32); }
-      return hipExtStreamCreateWithCUMask(out, (uint32_t)mask.size(), mask.data());
-    }
-    return hipStreamCreateWithPriority(out, hipStreamNonBlocking, std::getenv("SLSLAM_BUILD_STREAM_PRIORITY") ? std::atoi(std::getenv("SLSLAM_BUILD_STREAM_PRIORITY")) : 0);
-  };
   if (hipStreamCreateWithPriority(&st->ingest_stream, hipStreamNonBlocking, pr_hi) != hipSuccess || hipStreamCreateWithFlags(&st->solve_stream, hipStreamNonBlocking) != hipSuccess ||
-      make_build_stream(&st->build_stream) != hipSuccess ||
+      hipStreamCreateWithPriority(&st->build_stream, hipStreamNonBlocking, 0) != hipSuccess ||
       hipStreamCreateWithFlags(&st->result_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&st->ev_solved, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&st->ev_built, hipEventDisableTiming) != hipSuccess) {
-    if (st->ingest_stream) (void)hipStreamDestroy(st->ingest_stream);
-    if (st->solve_stream) (void)hipStreamDestroy(st->solve_stream);
-    if (st->build_stream) (void)hipStreamDestroy(st->build_stream);
-    if (st->result_stream) (void)hipStreamDestroy(st->result_stream);
-    delete st;
+    slslam_lba_stream_destroy(st);
     return SLSLAM_ERR_HIP;
   }
   *out = st;
@@ -2464,19 +2568,14 @@ extern "C" int slslam_lba_stream_create(int device, const slslam_solver_options*
 extern "C" void slslam_lba_stream_destroy(slslam_lba_stream* st) {
   if (!st) return;
   (void)hipSetDevice(st->device);
-  if (st->ingest_stream) (void)hipStreamSynchronize(st->ingest_stream);
-  if (st->solve_stream) (void)hipStreamSynchronize(st->solve_stream);
-  if (st->build_stream) (void)hipStreamSynchronize(st->build_stream);
-  if (st->result_stream) (void)hipStreamSynchronize(st->result_stream);
+  const hipStream_t shared[] = { st->ingest_stream, st->solve_stream, st->build_stream, st->result_stream };
+  for (hipStream_t q : shared) if (q) (void)hipStreamSynchronize(q);
   for (auto& sl : st->slots) {
     if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-    if (sl.batch) { sl.batch->ext_pool = nullptr; slslam_lba_batch_destroy(sl.batch); }
+    if (sl.batch) destroy_lent(sl.batch);
     if (sl.stream) (void)hipStreamDestroy(sl.stream);
   }
-  if (st->ingest_stream) (void)hipStreamDestroy(st->ingest_stream);
-  if (st->solve_stream) (void)hipStreamDestroy(st->solve_stream);
-  if (st->build_stream) (void)hipStreamDestroy(st->build_stream);
-  if (st->result_stream) (void)hipStreamDestroy(st->result_stream);
+  for (hipStream_t q : shared) if (q) (void)hipStreamDestroy(q);
   if (st->ev_solved) (void)hipEventDestroy(st->ev_solved);
   if (st->ev_built) (void)hipEventDestroy(st->ev_built);
   delete st;
@@ -2504,14 +2603,8 @@ int stream_submit_impl(slslam_lba_stream* st, const slslam_lba_window* windows, 
     if (!expanded.empty()) return expanded.data();
     expanded.assign(windows, windows + n);
     exp_idx.resize((size_t)n);
-    for (int i = 0; i < n; ++i) {
-      if (!packed[i]) continue;
-      const size_t M = (size_t)std::max(0, windows[i].num_observations);
-      std::vector<int>& v = exp_idx[(size_t)i];
-      v.resize(4 * M);
-      for (size_t q = 0; q < M; ++q) { const unsigned int x = packed[i][q]; v[q] = (int)((x >> 16) & 0xffu); v[M + q] = (int)(x & 0xffffu); v[2 * M + 2 * q] = (int)((x >> 24) & 1u); v[2 * M + 2 * q + 1] = (int)((x >> 25) & 1u); }
-      expanded[(size_t)i].camera_index = v.data(); expanded[(size_t)i].line_index = v.data() + M; expanded[(size_t)i].fixed_index = v.data() + 2 * M;
-    }
+    for (int i = 0; i < n; ++i)
+      if (packed[i]) expand_indices(packed[i], (size_t)std::max(0, windows[i].num_observations), exp_idx[(size_t)i], &expanded[(size_t)i]);
     return expanded.data();
   };
   auto& sl = st->slots[(size_t)(st->next_ticket % st->depth)];
@@ -2522,13 +2615,12 @@ int stream_submit_impl(slslam_lba_stream* st, const slslam_lba_window* windows, 
   if (sl.batch && sl.n == n) {
     slslam_lba_batch* b = sl.batch;
     // the build stage on the device: ingest on the stream's ONE ingest stream, build + solve + results on its ONE solve stream
-    if (b->finalized && b->refillable && !b->part[0] && !b->big_mode && !b->fused_motion_only && !b->opt.reuse_elimination && (int)b->wins.size() == n) {
-      static const bool serial_build = std::getenv("SLSLAM_STREAM_SERIAL_BUILD") != nullptr;      // (measurement switch: build and solve on one stream)
-      hipStream_t bs = serial_build ? st->solve_stream : st->build_stream;
-      rc = refill_device(b, windows, n, bs, st->ingest_stream, packed);
+    if (refillable_as_is(b, n)) {
+      rc = refill_device(b, windows, n, st->build_stream, st->ingest_stream, packed);
       if (rc == SLSLAM_OK) {
         run = st->solve_stream;
-        if (bs != run) { HIP_TRY(hipEventRecord(st->ev_built, bs)); HIP_TRY(hipStreamWaitEvent(run, st->ev_built, 0)); }
+        HIP_TRY(hipEventRecord(st->ev_built, st->build_stream));
+        HIP_TRY(hipStreamWaitEvent(run, st->ev_built, 0));
       }
     }
     if (rc == SLSLAM_ERR_UNSUPPORTED) {
@@ -2541,17 +2633,9 @@ int stream_submit_impl(slslam_lba_stream* st, const slslam_lba_window* windows, 
   if (rc == SLSLAM_OK) { ++st->n_refills; if (sl.batch->device_built) { ++st->n_device_builds; if (sl.batch->ingest_pinned) ++st->n_zero_copy; } }
   else if (rc == SLSLAM_ERR_UNSUPPORTED) {
     // the first batch of the slot, another number of windows, or windows that do not fit the room the slot's arrays have: a new batch
-    if (sl.batch) { if (sl.stream) HIP_TRY(hipStreamSynchronize(sl.stream)); HIP_TRY(hipStreamSynchronize(st->solve_stream)); HIP_TRY(hipStreamSynchronize(st->build_stream)); HIP_TRY(hipStreamSynchronize(st->result_stream)); sl.batch->ext_pool = nullptr; slslam_lba_batch_destroy(sl.batch); sl.batch = nullptr; }
+    if (sl.batch && (rc = drop_slot_batch(st, sl)) != SLSLAM_OK) return rc;
     slslam_lba_batch* b = nullptr;
-    if ((rc = slslam_lba_batch_create(st->device, &b)) != SLSLAM_OK) return rc;
-    b->ext_pool = st->pool.get();
-    b->wins.resize((size_t)n);
-    std::vector<int> ps((size_t)n, SLSLAM_OK);
-    const slslam_lba_window* ew = expand();
-    if (!st->pool->run(n, [&](int i) { ps[(size_t)i] = pack_window(&ew[i], &b->wins[(size_t)i]); })) rc = SLSLAM_ERR_NO_MEMORY;
-    for (int r : ps) if (r != SLSLAM_OK) rc = r;
-    if (rc == SLSLAM_OK) rc = slslam_lba_batch_finalize(b, &st->opt);
-    if (rc != SLSLAM_OK) { b->ext_pool = nullptr; slslam_lba_batch_destroy(b); return rc; }
+    if ((rc = make_slot_batch(st, expand(), n, &b)) != SLSLAM_OK) return rc;
     sl.batch = b; sl.n = n;
     ++st->n_builds;
   } else return rc;
@@ -2600,13 +2684,8 @@ extern "C" int slslam_lba_stream_collect(slslam_lba_stream* st, int ticket, slsl
     w.num_cameras = r.C; w.num_lines = r.L; w.num_observations = r.M; w.observations = r.obs; w.parameters = sl.out_params[(size_t)i];
     const size_t np = (size_t)6 * r.C + (size_t)4 * r.L;
     if (np && r.params_in != w.parameters) std::memcpy(w.parameters, r.params_in, np * sizeof(double));
-    if (r.packed) {
-      const size_t M = (size_t)r.M;
-      std::vector<int>& v = idx[(size_t)i];
-      v.resize(4 * M);
-      for (size_t q = 0; q < M; ++q) { const uint32_t x = r.packed[q]; v[q] = (int)((x >> 16) & 0xffu); v[M + q] = (int)(x & 0xffffu); v[2 * M + 2 * q] = (int)((x >> 24) & 1u); v[2 * M + 2 * q + 1] = (int)((x >> 25) & 1u); }
-      w.camera_index = v.data(); w.line_index = v.data() + M; w.fixed_index = v.data() + 2 * M;
-    } else { w.camera_index = r.cam; w.line_index = r.line; w.fixed_index = r.fixed; }
+    if (r.packed) expand_indices(r.packed, (size_t)r.M, idx[(size_t)i], &w);
+    else { w.camera_index = r.cam; w.line_index = r.line; w.fixed_index = r.fixed; }
     return w;
   };
   // A refill that did not fit the room the slot's arrays have (only the device knows the tiles a set needs: k_build_layout flags the refill as
@@ -2615,27 +2694,19 @@ extern "C" int slslam_lba_stream_collect(slslam_lba_stream* st, int ticket, slsl
   // (Solving 1024 flagged windows one by one would take a second, and the next set of that shape would be flagged again.)  The layout's fit flag
   // decides, whatever else the windows were flagged for: the host packer takes a window for the host path (a camera that sees a line twice)
   // in its stride - only a window with bad input, which the packer refuses, keeps the set on the per-window path below.
-  bool whole_nofit = dev && sl.n > 0 && bt->h_buildwin && bt->h_totals && bt->h_totals[3] == 0 && (int)bt->host_src.size() == sl.n;
+  bool whole_nofit = dev && sl.n > 0 && !bt->h_buildwin.empty() && !bt->h_totals.empty() && bt->h_totals[3] == 0 && (int)bt->host_src.size() == sl.n;
   for (int i = 0; whole_nofit && i < sl.n; ++i) if (bt->h_buildwin[i].status & kBuildInvalid) whole_nofit = false;
   if (whole_nofit) {
     const int n = sl.n;
     std::vector<slslam_lba_window> ws((size_t)n);
     for (int i = 0; i < n; ++i) ws[(size_t)i] = as_submitted(i);
     slslam_lba_batch* nb = nullptr;
-    if ((rc = slslam_lba_batch_create(st->device, &nb)) != SLSLAM_OK) return rc;
-    nb->ext_pool = st->pool.get();
-    nb->wins.resize((size_t)n);
-    std::vector<int> ps((size_t)n, SLSLAM_OK);
-    if (!st->pool->run(n, [&](int i) { ps[(size_t)i] = pack_window(&ws[(size_t)i], &nb->wins[(size_t)i]); })) rc = SLSLAM_ERR_NO_MEMORY;
-    for (int r : ps) if (r != SLSLAM_OK) rc = r;
-    if (rc == SLSLAM_OK) rc = slslam_lba_batch_finalize(nb, &st->opt);
-    if (rc == SLSLAM_OK) rc = slslam_lba_batch_solve(nb, (void*)st->solve_stream);
+    if ((rc = make_slot_batch(st, ws.data(), n, &nb)) != SLSLAM_OK) return rc;
+    rc = slslam_lba_batch_solve(nb, (void*)st->solve_stream);
     if (rc == SLSLAM_OK) rc = download_async_impl(nb, (void*)st->solve_stream, /*allow_inplace=*/false);
     if (rc == SLSLAM_OK) rc = slslam_lba_batch_wait(nb);
-    if (rc != SLSLAM_OK) { nb->ext_pool = nullptr; slslam_lba_batch_destroy(nb); return rc; }
-    if (sl.stream) HIP_TRY(hipStreamSynchronize(sl.stream));
-    HIP_TRY(hipStreamSynchronize(st->solve_stream)); HIP_TRY(hipStreamSynchronize(st->build_stream)); HIP_TRY(hipStreamSynchronize(st->result_stream));
-    bt->ext_pool = nullptr; slslam_lba_batch_destroy(bt);
+    if (rc != SLSLAM_OK) { destroy_lent(nb); return rc; }
+    if ((rc = drop_slot_batch(st, sl)) != SLSLAM_OK) return rc;
     sl.batch = bt = nb;
     ++st->n_builds; st->n_fallback_windows += n;
     dev = false; flagged.clear();

@@ -52,6 +52,20 @@ struct RawWin {
   int pad;
 };
 
+// The narrowed index word of an observation (RawWin::packed, slslam_pack_indices): line | camera << 16 | camera constant << 24 | line
+// constant << 25.
+__host__ __device__ inline uint32_t index_word(int camera, int line, int camera_const, int line_const) {
+  return ((uint32_t)line & 0xffffu) | ((uint32_t)camera & 0xffu) << 16 | (camera_const ? 1u << 24 : 0u) | (line_const ? 1u << 25 : 0u);
+}
+__host__ __device__ inline int word_line(uint32_t v) { return (int)(v & 0xffffu); }
+__host__ __device__ inline int word_camera(uint32_t v) { return (int)((v >> 16) & 0xffu); }
+__host__ __device__ inline int word_camera_const(uint32_t v) { return (int)((v >> 24) & 1u); }
+__host__ __device__ inline int word_line_const(uint32_t v) { return (int)((v >> 25) & 1u); }
+// nonzero: a caller's word names a line >= L or a camera >= C, or sets a bit above the flags
+__host__ __device__ inline unsigned word_bad(uint32_t v, int C, int L) {
+  return (unsigned)(word_line(v) >= L) | (unsigned)(word_camera(v) >= C) | (v >> 26);
+}
+
 enum { kBuildInvalid = 1, kBuildHostPath = 2, kBuildNoFit = 4 };     // BuildWin.status bits
 struct BuildWin {
   int status;                 // 0, or why the window was not built (emitted empty)
@@ -151,7 +165,7 @@ __global__ __launch_bounds__(256) void k_ingest(BuildPtrs P) {
       if (r.packed) {
         for (int i = tid; i < r.M; i += 256) {
           const uint32_t v = r.packed[i];
-          if ((int)(v & 0xffffu) >= r.L || (int)((v >> 16) & 0xffu) >= r.C || (v >> 26)) bad = 1;
+          if ((int)(v & 0xffffu) >= r.L || (int)((v >> 16) & 0xffu) >= r.C || (v >> 26)) bad = 1;     // (word_bad, short-circuited: it branches here)
           dst[i] = v;
         }
       } else {
@@ -162,7 +176,7 @@ __global__ __launch_bounds__(256) void k_ingest(BuildPtrs P) {
           int f0, f1;
           if (fx8) { const int2 f = fx[i]; f0 = f.x; f1 = f.y; } else { f0 = r.fixed[2 * i]; f1 = r.fixed[2 * i + 1]; }
           if (c < 0 || c >= r.C || l < 0 || l >= r.L) bad = 1;
-          dst[i] = ((uint32_t)l & 0xffffu) | ((uint32_t)c & 0xffu) << 16 | (f0 ? 1u << 24 : 0u) | (f1 ? 1u << 25 : 0u);
+          dst[i] = index_word(c, l, f0, f1);
         }
       }
     }
