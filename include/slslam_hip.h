@@ -228,6 +228,10 @@ int  slslam_lba_batch_wait(slslam_lba_batch* b);
  * solve graph stays valid.  The windows are cut into chunks by the policy finalize resolved, so a refilled batch returns the bytes a
  * fresh batch of the same windows returns.  SLSLAM_ERR_UNSUPPORTED (batch unchanged, still solvable): the windows do not fit the
  * room the arrays have, or need another path / sweep - build a new batch then.
+ * A batch finalized on the fused motion-only path (slslam_lba_batch_path = SLSLAM_PATH_FUSED_MOTION_ONLY: SLAM::motion_only_ba, reference
+ * src/slam.cpp:578-675) is refilled in place too, by the same two builds, with windows of that shape only: every window must have exactly one
+ * observed camera that no observation flags constant and no observed line that is left free - anything else is SLSLAM_ERR_UNSUPPORTED,
+ * checked on the host before the batch is touched (a stream builds a new batch for such a set).
  * Host arrays are read before the call returns - EXCEPT arrays in page-locked memory (slslam_pinned_alloc / _register) when the device
  * builds (options.device_build = 0): those are read by the GPU after the call returns and must stay valid until the results have been
  * waited for.  For arrays in ordinary (pageable) memory the results depend only on what the arrays held when this call was made.  When the device builds, what only the build can find out arrives with the results: a window with bad input, of a shape

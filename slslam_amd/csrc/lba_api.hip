@@ -2034,9 +2034,44 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
   return rc;
 }
 
-// "Can this batch be refilled as it is": the captured solve's launches were made for this many windows of the tiled sweeps
+// "Can this batch be refilled as it is": the captured solve's launches were made for this many windows of the tiled sweeps or of the
+// fused motion-only solve
 bool refillable_as_is(const slslam_lba_batch* b, int n) {
-  return b->finalized && b->refillable && !b->part[0] && !b->big_mode && !b->fused_motion_only && !b->opt.reuse_elimination && (int)b->wins.size() == n;
+  return b->finalized && b->refillable && !b->part[0] && !b->big_mode && !b->opt.reuse_elimination && (int)b->wins.size() == n;
+}
+
+// The motion_only_ba shape (reference src/slam.cpp:578-675) of ONE window, from its index arrays (or its narrowed words): exactly one
+// camera that is observed and never flagged constant, and every observed line flagged constant - what set_lds_limits asks of every
+// window before it gives a batch the fused solve (pack_window's Cf == 1 and nfree_params == 6; a block is constant when one of its
+// observations flags it, lba_problem.cpp:88-91).  False for malformed input too (missing arrays, an index out of range).
+bool motion_only_shape(const slslam_lba_window& w, const unsigned int* packed) {
+  const int C = w.num_cameras, L = w.num_lines, M = w.num_observations;
+  if (C <= 0 || L < 0 || M < 0) return false;
+  if (M > 0 && !packed && (!w.camera_index || !w.line_index || !w.fixed_index)) return false;
+  std::vector<char> cam_used((size_t)C, 0), cam_const((size_t)C, 0), line_seen((size_t)L, 0), line_const((size_t)L, 0);
+  for (int i = 0; i < M; ++i) {
+    int c, l, cc, lc;
+    if (packed) { const uint32_t v = packed[i]; c = word_camera(v); l = word_line(v); cc = word_camera_const(v); lc = word_line_const(v); }
+    else { c = w.camera_index[i]; l = w.line_index[i]; cc = w.fixed_index[2 * i]; lc = w.fixed_index[2 * i + 1]; }
+    if (c < 0 || c >= C || l < 0 || l >= L) return false;
+    cam_used[(size_t)c] = 1; line_seen[(size_t)l] = 1;
+    if (cc) cam_const[(size_t)c] = 1;
+    if (lc) line_const[(size_t)l] = 1;
+  }
+  int free_cams = 0;
+  for (int c = 0; c < C; ++c) free_cams += cam_used[(size_t)c] && !cam_const[(size_t)c];
+  if (free_cams != 1) return false;
+  for (int l = 0; l < L; ++l) if (line_seen[(size_t)l] && !line_const[(size_t)l]) return false;
+  return true;
+}
+
+// A batch that takes the fused motion-only solve runs one wave per window on the 6 x 6 system of ONE free camera: refilled, it can only
+// take windows of that shape (anything else would be solved wrong) - checked on the host before anything is touched
+bool fits_batch_path(const slslam_lba_batch* b, const slslam_lba_window* windows, const unsigned int* const* packed, int n) {
+  if (!b->fused_motion_only) return true;
+  for (int i = 0; i < n; ++i)
+    if (!motion_only_shape(windows[i], packed ? packed[i] : nullptr)) return false;
+  return true;
 }
 
 }  // namespace
@@ -2046,7 +2081,7 @@ bool refillable_as_is(const slslam_lba_batch* b, int n) {
 extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_window* windows, int n, void* stream) {
   if (!b || (!windows && n > 0)) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (!b->finalized) return SLSLAM_ERR_STATE;
-  if (!refillable_as_is(b, n)) return SLSLAM_ERR_UNSUPPORTED;
+  if (!refillable_as_is(b, n) || !fits_batch_path(b, windows, nullptr, n)) return SLSLAM_ERR_UNSUPPORTED;
   const int B = n;
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t s = (hipStream_t)stream;
@@ -2615,7 +2650,7 @@ int stream_submit_impl(slslam_lba_stream* st, const slslam_lba_window* windows, 
   if (sl.batch && sl.n == n) {
     slslam_lba_batch* b = sl.batch;
     // the build stage on the device: ingest on the stream's ONE ingest stream, build + solve + results on its ONE solve stream
-    if (refillable_as_is(b, n)) {
+    if (refillable_as_is(b, n) && fits_batch_path(b, windows, packed, n)) {
       rc = refill_device(b, windows, n, st->build_stream, st->ingest_stream, packed);
       if (rc == SLSLAM_OK) {
         run = st->solve_stream;
