@@ -411,7 +411,8 @@ typedef struct slslam_ransac_trials {
 int slslam_ransac_generate(const slslam_ransac_trials* trials, double baseline, double* poses, int* valid);
 
 /* Whole ransac_motion.  lines [6 K] as in slslam_ransac_frame.  *best_score_io: in = the caller's running best
- * (reference: 0), out = best score; *trial_cnt = trials executed; best_pose[12] and best_inlier_bits[(K+63)/64]
+ * (SLAM::pose_estimation starts it at -1, reference src/slam.cpp:283: a trial that scores 0 then becomes the best, and the
+ * re-estimated trial count lets the loop run to max_trials), out = best score; *trial_cnt = trials executed; best_pose[12] and best_inlier_bits[(K+63)/64]
  * (may be NULL) are written only when some trial beat the incoming best score. */
 int slslam_ransac_motion(const slslam_ransac_trials* trials, const double* lines, double baseline, double error_thr,
                          double prob_free_outliers, int max_trials, int* best_score_io, int* trial_cnt,
@@ -424,6 +425,55 @@ int slslam_ransac_motion_batch(int num_frames, const slslam_ransac_trials* frame
                                double baseline, double error_thr, double prob_free_outliers, int max_trials,
                                int* best_score_io, int* trial_cnt, double* best_pose,
                                unsigned long long* const* best_inlier_bits);
+
+/* ------------------------------------------------------------------ per-frame pose estimation
+ * Replaces: SLAM::pose_estimation (reference src/slam.cpp:244-319) after its merge by feature id (:250-272; the host layer's
+ * slslam_pose_estimation_inputs, slslam_amd/host/window_packer.h, restates it), for many independent frames per call.  Per frame:
+ *   1. fewer than 5 common lines (:275): SLSLAM_POSE_TOO_FEW_FEATURES, nothing else runs;
+ *   2. RANSAC exactly as slslam_ransac_motion_batch with best_score starting at -1 (:283) and the start pose at identity;
+ *   3. best score < 5 = max_feat_num (:295): SLSLAM_POSE_RANSAC_FAILED, no motion-only solve;
+ *   4. motion-only bundle adjustment on the RANSAC inliers (:303, :578-675), packed as slslam_pack_motion_only documents, solved with
+ *      the estimator's options on the fused motion-only path; pose = gc_wt_to_Rt of the solved camera;
+ *   5. final inliers (:305-312): the common lines whose reprojection error under the refined pose is below error_thr (every line:
+ *      no |t| > 1 test), with the float/double arithmetic of slslam_ransac_score.
+ * Frames are independent: a frame's results do not depend on the others in the call.
+ * The whole chain stays on the device: one upload, two launches for the RANSAC of every frame, one download of the scores (the adaptive
+ * trial loop runs on the host), one launch that packs every motion-only window, a refill of the estimator's batch from those device
+ * windows and its solve, one launch that finishes every frame, one download - two host round trips per call whatever the frame count. */
+typedef struct slslam_pose_estimator slslam_pose_estimator;
+enum { SLSLAM_POSE_OK = 0, SLSLAM_POSE_TOO_FEW_FEATURES = 1, SLSLAM_POSE_RANSAC_FAILED = 2 };
+typedef struct slslam_pose_estimate {
+  int    status;                  /* SLSLAM_POSE_*                                                                         */
+  int    trial_cnt;               /* RANSAC trials executed (0 for TOO_FEW_FEATURES)                                       */
+  int    ransac_score;            /* best RANSAC score (-1 when no trial beat the start)                                   */
+  double ransac_pose[12];         /* the RANSAC winner, R row-major | t (identity when no trial won)                       */
+  unsigned long long* ransac_inlier_bits;  /* in: caller-owned [(K + 63) / 64] or NULL; out: the winner's inlier bits (0 when none)  */
+  slslam_summary summary;         /* of the motion-only solve (zeroed unless status is OK)                                  */
+  double pose[12];                /* the refined pose (status OK), else ransac_pose                                         */
+  int    num_inliers;             /* final inliers (0 unless status is OK)                                                  */
+  unsigned long long* inlier_bits;         /* in: caller-owned [(K + 63) / 64] or NULL; out: bit k of word k / 64 = line k is a final inlier */
+} slslam_pose_estimate;
+
+/* device < 0 selects the current HIP device.  opt: the motion-only solve's options (NULL = slslam_default_options); the estimator's
+ * batch always takes the fused motion-only path, refillable (refill_headroom_percent 0 becomes 10), built on the device.
+ * max_frames / max_lines: the capacity its device buffers and batch are made for (at the first run); a run that needs more frames with
+ * a motion-only solve, or more common lines, makes them anew.  Touches no device: a machine without one fails at run. */
+int  slslam_pose_estimator_create(int device, const slslam_solver_options* opt, int max_frames, int max_lines, slslam_pose_estimator** out);
+void slslam_pose_estimator_destroy(slslam_pose_estimator* est);
+/* frames[F], lines[F] and the thresholds as slslam_ransac_motion_batch (samples of frame f index its K common lines; observations0 =
+ * obs0, the previous frame, observations1 = obs1, the current one; lines [6 K] in the previous frame's coordinates); out[F].
+ * Every argument is validated before an output is written or the device is asked: SLSLAM_ERR_INVALID_ARGUMENT, outputs untouched.
+ * Synchronous; host pointers. */
+int  slslam_pose_estimator_run(slslam_pose_estimator* est, int num_frames, const slslam_ransac_trials* frames, const double* const* lines,
+                               double baseline, double error_thr, double prob_free_outliers, int max_trials, slslam_pose_estimate* out);
+/* Since create: runs, device / page-locked buffer allocations of the estimator, batches finalized, batch refills.  Any pointer may be NULL. */
+int  slslam_pose_estimator_stats(const slslam_pose_estimator* est, long long* calls, long long* allocations, long long* finalizes,
+                                 long long* refills);
+/* Test hook: the motion-only window the last run packed on the device for `frame` (status OK only, else SLSLAM_ERR_STATE) -
+ * *num_lines = n inliers, index_words[2n] (slslam_pack_indices form), observations[16n], parameters[12 + 4n] - and solved_camera[6],
+ * the solved (angle-axis, t) of camera 0.  Any array may be NULL. */
+int  slslam_pose_estimator_window(const slslam_pose_estimator* est, int frame, unsigned int* index_words, double* observations,
+                                  double* parameters, double* solved_camera, int* num_lines);
 
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls

@@ -71,6 +71,15 @@ class RansacFrame(C.Structure):
                 ("observations", C.POINTER(C.c_double)), ("lines", C.POINTER(C.c_double))]
 
 
+class PoseEstimate(C.Structure):
+    _fields_ = [("status", C.c_int), ("trial_cnt", C.c_int), ("ransac_score", C.c_int), ("ransac_pose", C.c_double * 12),
+                ("ransac_inlier_bits", C.POINTER(C.c_ulonglong)), ("summary", Summary), ("pose", C.c_double * 12),
+                ("num_inliers", C.c_int), ("inlier_bits", C.POINTER(C.c_ulonglong))]
+
+
+POSE_STATUS = {0: "OK", 1: "TOO_FEW_FEATURES", 2: "RANSAC_FAILED"}
+
+
 class POGraph(C.Structure):
     _fields_ = [("num_poses", C.c_int), ("num_edges", C.c_int),
                 ("pose_index_1", C.POINTER(C.c_int)), ("pose_index_2", C.POINTER(C.c_int)),
@@ -88,7 +97,7 @@ EXPORTS = [
     "slslam_lba_batch_get_parameters", "slslam_lba_batch_get_summary",
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
-    "slslam_po_solve", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -159,6 +168,13 @@ def lib():
                                        C.POINTER(C.c_ulonglong)]
     L.slslam_ransac_motion_batch.argtypes = [C.c_int, C.POINTER(RansacTrials), C.POINTER(dp), C.c_double, C.c_double, C.c_double,
                                              C.c_int, ip, ip, dp, C.POINTER(C.POINTER(C.c_ulonglong))]
+    L.slslam_pose_estimator_create.argtypes = [C.c_int, C.POINTER(SolverOptions), C.c_int, C.c_int, C.POINTER(vp)]
+    L.slslam_pose_estimator_destroy.argtypes = [vp]
+    L.slslam_pose_estimator_destroy.restype = None
+    L.slslam_pose_estimator_run.argtypes = [vp, C.c_int, C.POINTER(RansacTrials), C.POINTER(dp), C.c_double, C.c_double, C.c_double, C.c_int,
+                                            C.POINTER(PoseEstimate)]
+    L.slslam_pose_estimator_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 4
+    L.slslam_pose_estimator_window.argtypes = [vp, C.c_int, C.POINTER(C.c_uint), dp, dp, dp, ip]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -691,8 +707,9 @@ def po_structure(g, max_chains=4096):
             "num_chain_unknowns": int(ncu[0]), "num_unknowns": int(nu[0]), "level1_chains": int(lib().slslam_po_structure_level1())}
 
 
-def ransac_motion_batch(frames, baseline=0.12, error_thr=5.0 / 406.05, prob_free_outliers=0.999, max_trials=1000):
+def ransac_motion_batch(frames, baseline=0.12, error_thr=5.0 / 406.05, prob_free_outliers=0.999, max_trials=1000, best_score=0):
     """slslam_ransac_motion_batch: frames = list of dicts with obs0, obs1, lines, samples (as make_ransac_pair returns).
+    best_score: every frame's incoming running best (SLAM::pose_estimation starts at -1).
     Returns a list of (trial_cnt, best_score, best_pose [12], inlier mask [K]) per frame."""
     n = len(frames)
     keep, trs, lns, bitbufs = [], (RansacTrials * max(n, 1))(), (C.POINTER(C.c_double) * max(n, 1))(), []
@@ -706,7 +723,7 @@ def ransac_motion_batch(frames, baseline=0.12, error_thr=5.0 / 406.05, prob_free
         bits = np.zeros(max((tr.num_lines + 63) // 64, 1), dtype=np.uint64)
         bitbufs.append(bits)
         bitptrs[i] = bits.ctypes.data_as(C.POINTER(C.c_ulonglong))
-    bs = np.zeros(max(n, 1), dtype=np.int32)
+    bs = np.full(max(n, 1), best_score, dtype=np.int32)
     tc = np.zeros(max(n, 1), dtype=np.int32)
     poses = np.zeros((max(n, 1), 12))
     _check(lib().slslam_ransac_motion_batch(n, trs, lns, float(baseline), float(error_thr), float(prob_free_outliers), int(max_trials),
@@ -720,3 +737,82 @@ def ransac_motion_batch(frames, baseline=0.12, error_thr=5.0 / 406.05, prob_free
             mask[64 * w:64 * w + m] = ((bitbufs[i][w] >> np.arange(m, dtype=np.uint64)) & np.uint64(1)).astype(bool)
         out.append((int(tc[i]), int(bs[i]), poses[i].copy(), mask))
     return out
+
+
+def _bits_to_mask(bits, k):
+    mask = np.zeros(k, dtype=bool)
+    for w in range((k + 63) // 64):
+        m = min(64, k - 64 * w)
+        mask[64 * w:64 * w + m] = ((bits[w] >> np.arange(m, dtype=np.uint64)) & np.uint64(1)).astype(bool)
+    return mask
+
+
+class PoseEstimator:
+    """SLAM::pose_estimation for many frames per call (slslam_pose_estimator_*): RANSAC, motion-only BA on its inliers, final inliers.
+    Keeps its device buffers and its refillable motion-only batch between calls."""
+
+    def __init__(self, max_frames=16, max_lines=512, device=-1, **opt):
+        self._h = C.c_void_p()
+        o = default_options(**opt)
+        _check(lib().slslam_pose_estimator_create(int(device), C.byref(o), int(max_frames), int(max_lines), C.byref(self._h)),
+               "slslam_pose_estimator_create")
+
+    def close(self):
+        if self._h:
+            lib().slslam_pose_estimator_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, frames, baseline=0.12, error_thr=5.0 / 406.05, prob_free_outliers=0.999, max_trials=1000):
+        """frames = list of dicts with obs0, obs1, lines, samples (as make_ransac_pair returns).  Returns one dict per frame:
+        status, trial_cnt, ransac_score, ransac_pose [12], ransac_mask [K], summary, pose [12], num_inliers, mask [K]
+        (the RANSAC fields in the shape ransac_motion_batch returns them)."""
+        n = len(frames)
+        keep, trs, lns = [], (RansacTrials * max(n, 1))(), (C.POINTER(C.c_double) * max(n, 1))()
+        outs = (PoseEstimate * max(n, 1))()
+        bitbufs = []
+        for i, fr in enumerate(frames):
+            tr, k = _trials(fr["obs0"], fr["obs1"], fr["samples"])
+            ln = np.ascontiguousarray(fr["lines"], dtype=np.float64).reshape(-1, 6)
+            keep.append((k, ln))
+            trs[i] = tr
+            lns[i] = _dp(ln)
+            words = max((tr.num_lines + 63) // 64, 1)
+            rb, fb = np.zeros(words, dtype=np.uint64), np.zeros(words, dtype=np.uint64)
+            bitbufs.append((rb, fb))
+            outs[i].ransac_inlier_bits = rb.ctypes.data_as(C.POINTER(C.c_ulonglong))
+            outs[i].inlier_bits = fb.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        _check(lib().slslam_pose_estimator_run(self._h, n, trs, lns, float(baseline), float(error_thr), float(prob_free_outliers),
+                                               int(max_trials), outs), "slslam_pose_estimator_run")
+        res = []
+        for i in range(n):
+            o, k = outs[i], trs[i].num_lines
+            res.append({"status": POSE_STATUS[o.status], "trial_cnt": o.trial_cnt, "ransac_score": o.ransac_score,
+                        "ransac_pose": np.array(o.ransac_pose[:]), "ransac_mask": _bits_to_mask(bitbufs[i][0], k),
+                        "summary": _summary_dict(o.summary), "pose": np.array(o.pose[:]), "num_inliers": o.num_inliers,
+                        "mask": _bits_to_mask(bitbufs[i][1], k)})
+        return res
+
+    def stats(self):
+        v = [C.c_longlong() for _ in range(4)]
+        _check(lib().slslam_pose_estimator_stats(self._h, *[C.byref(x) for x in v]), "slslam_pose_estimator_stats")
+        return dict(zip(("calls", "allocations", "finalizes", "refills"), (x.value for x in v)))
+
+    def window(self, frame):
+        """The motion-only window the last run packed on the device for `frame` (test hook): dict of index_words [2n],
+        observations [2n, 8], parameters [12 + 4n], solved_camera [6]."""
+        nl = C.c_int()
+        _check(lib().slslam_pose_estimator_window(self._h, int(frame), None, None, None, None, C.byref(nl)), "slslam_pose_estimator_window")
+        n = nl.value
+        words = np.zeros(max(2 * n, 1), dtype=np.uint32)
+        obs = np.zeros(max(16 * n, 1))
+        par = np.zeros(12 + 4 * n)
+        cam = np.zeros(6)
+        _check(lib().slslam_pose_estimator_window(self._h, int(frame), words.ctypes.data_as(C.POINTER(C.c_uint)), _dp(obs), _dp(par), _dp(cam),
+                                                  C.byref(nl)), "slslam_pose_estimator_window")
+        return {"index_words": words[:2 * n], "observations": obs[:16 * n].reshape(-1, 8), "parameters": par, "solved_camera": cam}

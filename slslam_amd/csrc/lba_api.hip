@@ -23,6 +23,7 @@
 #include "lba_motion_only.h"
 #include "lba_pack.h"
 #include "lba_device_build.h"
+#include "lba_resident.h"
 #include "host_pool.h"
 #include "pinned_registry.h"
 
@@ -2074,7 +2075,49 @@ bool fits_batch_path(const slslam_lba_batch* b, const slslam_lba_window* windows
   return true;
 }
 
+// The placeholders of a resident refill (lba_refill_resident): k_reset made them kRunning, nothing is to run
+__global__ __launch_bounds__(256) void k_park_windows(LMState* state, int from, int to) {
+  const int w = from + (int)(blockIdx.x * 256 + threadIdx.x);
+  if (w < to) state[w].status = SLSLAM_NO_CONVERGENCE;
+}
+
 }  // namespace
+
+// The pose estimator's refill (lba_resident.h): what refill_device does after its host stages, with the windows' device addresses in RawWin
+int slslam::lba_refill_resident(slslam_lba_batch* b, const slslam_lba_window* windows, const unsigned int* const* packed, int n, int n_used,
+                                hipStream_t s) {
+  if (!b || !windows || !packed || n_used < 0 || n_used > n) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!refillable_as_is(b, n) || !b->fused_motion_only || b->d_rawwin.n < (size_t)std::max(1, n) || !b->d_ob_raw.p) return SLSLAM_ERR_UNSUPPORTED;
+  if ((b->opt.chunks_per_window < 0 ? (-b->opt.chunks_per_window) / 1000 : (b->opt.reproducible ? 3 : b->auto_rounds)) > (int)kLayoutMaxRank) return SLSLAM_ERR_UNSUPPORTED;
+  HIP_TRY(hipSetDevice(b->device));
+  RefillPlan z;
+  int rc = refill_sizes(b, windows, n, packed, z);
+  if (rc != SLSLAM_OK) return rc;
+  if ((rc = ensure_build_host_buffers(b, n)) != SLSLAM_OK) return rc;
+  z.all_pinned = false; z.params_pinned = false;          // (nothing is written back in place: the results stay on the device)
+  if ((rc = wait_stage_free(b)) != SLSLAM_OK) return rc;
+  b->host_src.assign((size_t)n, RawWin());
+  RawWin* rw = b->h_rawwin.data();
+  for (int i = 0; i < n; ++i) {
+    RawWin r;
+    std::memset(&r, 0, sizeof(r));
+    r.packed = packed[i]; r.obs = windows[i].observations; r.params_in = windows[i].parameters;
+    rw[i] = r; b->host_src[(size_t)i] = r;
+  }
+  if ((rc = rebase_onto_stage(b, windows, n, z)) != SLSLAM_OK) return rc;       // (no copy runs: only the windows' places in the batch)
+  refill_commit(b, windows, n, z);
+  if ((rc = refill_enqueue(b, n, z, s, s)) != SLSLAM_OK) return rc;            // (no runs: k_ingest reads the device arrays where they are)
+  if (n_used < n) hipLaunchKernelGGL(k_park_windows, dim3((unsigned)((n - n_used + 255) / 256)), dim3(256), 0, s, b->d_state.p, n_used, n);
+  HIP_TRY(hipGetLastError());
+  return SLSLAM_OK;
+}
+
+int slslam::lba_device_results(const slslam_lba_batch* b, const LMState** state, const WinDesc** wins) {
+  if (!b || !state || !wins) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized || b->part[0]) return SLSLAM_ERR_STATE;
+  *state = b->d_state.p; *wins = b->d_wins.p;
+  return SLSLAM_OK;
+}
 
 // ------------------------------------------------------------------------------------------
 // A batch for a stream of windows: every window replaced, nothing allocated, nothing captured again (include/slslam_hip.h).

@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "lba_types.h"
+#include "index_word.h"
 #include "lba_kernels.h"
 #include "lba_eliminate_grouped_maps.h"
 #include "lba_eliminate_mfma_maps.h"
@@ -51,20 +52,6 @@ struct RawWin {
   int cam_off, line_off, obs_off;     // the window's place in the batch arrays
   int pad;
 };
-
-// The narrowed index word of an observation (RawWin::packed, slslam_pack_indices): line | camera << 16 | camera constant << 24 | line
-// constant << 25.
-__host__ __device__ inline uint32_t index_word(int camera, int line, int camera_const, int line_const) {
-  return ((uint32_t)line & 0xffffu) | ((uint32_t)camera & 0xffu) << 16 | (camera_const ? 1u << 24 : 0u) | (line_const ? 1u << 25 : 0u);
-}
-__host__ __device__ inline int word_line(uint32_t v) { return (int)(v & 0xffffu); }
-__host__ __device__ inline int word_camera(uint32_t v) { return (int)((v >> 16) & 0xffu); }
-__host__ __device__ inline int word_camera_const(uint32_t v) { return (int)((v >> 24) & 1u); }
-__host__ __device__ inline int word_line_const(uint32_t v) { return (int)((v >> 25) & 1u); }
-// nonzero: a caller's word names a line >= L or a camera >= C, or sets a bit above the flags
-__host__ __device__ inline unsigned word_bad(uint32_t v, int C, int L) {
-  return (unsigned)(word_line(v) >= L) | (unsigned)(word_camera(v) >= C) | (v >> 26);
-}
 
 enum { kBuildInvalid = 1, kBuildHostPath = 2, kBuildNoFit = 4 };     // BuildWin.status bits
 struct BuildWin {

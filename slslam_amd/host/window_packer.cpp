@@ -198,3 +198,38 @@ extern "C" int slslam_pack_motion_only(const slslam_pose* T, const double* obs_c
 extern "C" void slslam_unpack_motion_only(const slslam_packed_window* w, slslam_pose* T) {
   if (w && T && w->parameters) slslam_gc_wt_to_Rt(w->parameters, T);  // slam.cpp:668-674
 }
+
+// ---- per-frame pose estimation inputs (SLAM::pose_estimation, reference src/slam.cpp:250-272)
+extern "C" int slslam_pose_estimation_inputs(const slslam_feature_obs* obs0, int n0, const slslam_feature_obs* obs1, int n1,
+                                             const slslam_landmark* lms, int num_lms, const slslam_keyframe* kfs, int num_kfs,
+                                             int* ids, double* obs0_out, double* obs1_out, double* lines_out, int* num_common) {
+  if (n0 < 0 || n1 < 0 || num_lms < 0 || num_kfs < 0 || !num_common || (n0 > 0 && !obs0) || (n1 > 0 && !obs1)) return 1;
+  for (int i = 1; i < n0; ++i) if (obs0[i].id <= obs0[i - 1].id) return 1;
+  for (int i = 1; i < n1; ++i) if (obs1[i].id <= obs1[i - 1].id) return 1;
+  std::map<int, const slslam_landmark*> lm_of;
+  for (int i = 0; i < num_lms; ++i) lm_of[lms[i].id] = &lms[i];
+  std::map<int, const slslam_keyframe*> kf_of;
+  for (int i = 0; i < num_kfs; ++i) kf_of[kfs[i].id] = &kfs[i];
+  int K = 0, a = 0, b = 0;
+  while (a < n0 && b < n1) {                                             // :255-270
+    if (obs0[a].id == obs1[b].id) {
+      const int id = obs0[a].id;
+      auto lm = lm_of.find(id);
+      if (lm == lm_of.end()) return 1;
+      auto kf = kf_of.find(lm->second->init_kf_id);
+      if (kf == kf_of.end()) return 1;
+      if (!ids || !obs0_out || !obs1_out || !lines_out) return 1;
+      ids[K] = id;
+      std::memcpy(obs0_out + 8 * (size_t)K, obs0[a].obs, 8 * sizeof(double));
+      std::memcpy(obs1_out + 8 * (size_t)K, obs1[b].obs, 8 * sizeof(double));
+      slslam_gc_line_from_pose(lm->second->line, &kf->second->T, lines_out + 6 * (size_t)K);   // :262-263
+      ++K; ++a; ++b;
+    } else if (obs0[a].id < obs1[b].id) {
+      ++a;
+    } else {
+      ++b;
+    }
+  }
+  *num_common = K;
+  return 0;
+}

@@ -71,6 +71,19 @@ int slslam_pack_motion_only(const slslam_pose* T, const double* obs_cur, const d
                             int num_inliers, slslam_packed_window* out);
 void slslam_unpack_motion_only(const slslam_packed_window* w, slslam_pose* T);
 
+/* ---- per-frame pose estimation: what SLAM::pose_estimation does before RANSAC (reference src/slam.cpp:250-272), for
+ * slslam_pose_estimator_run (include/slslam_hip.h)
+ *   merge   the two frames' observation maps (ob_map: std::map, ascending feature id) walked side by side; every id in both is a
+ *           common line, in ascending id: its id, obs0 (previous frame), obs1 (current frame), and its line in the previous frame's
+ *           coordinates = gc_line_from_pose(lm.line, kfs[lm.init_kf_id].T)
+ * obs0 / obs1 must be sorted by strictly ascending id.  ids[K], obs0_out[8 K], obs1_out[8 K], lines_out[6 K] have room for
+ * min(n0, n1) entries; *num_common = K.  ids map the estimator's inlier bits back to feature ids (SLAM::final_inliers).
+ * Returns 0, or 1 on unsorted input or a common id without a landmark / a landmark whose init keyframe is unknown. */
+typedef struct slslam_feature_obs { int id; double obs[8]; } slslam_feature_obs;   /* one entry of ob_map */
+int slslam_pose_estimation_inputs(const slslam_feature_obs* obs0, int n0, const slslam_feature_obs* obs1, int n1,
+                                  const slslam_landmark* lms, int num_lms, const slslam_keyframe* kfs, int num_kfs,
+                                  int* ids, double* obs0_out, double* obs1_out, double* lines_out, int* num_common);
+
 /* ---- pose graph: what SLAM::pose_optimization does before and after ceres::Solve
  *   pack    reference src/slam.cpp:1248-1280   edge_set (std::set<pii>: ascending (n1, n2)) -> pose_index_1 / pose_index_2,
  *           constraints[6 i] = gc_Rt_to_wt(edges[(n1, n2)].C), parameters[6 k] = gc_Rt_to_wt(kfs[k]->T) for k = 0..N-1
