@@ -367,6 +367,38 @@ int slslam_po_structure(const slslam_po_graph* graph, int* slot, int max_chains,
  * chains (consecutive poses are cut poses of one path; left / right = a cut pose of a still higher level or the path's junction). */
 int slslam_po_structure_level1(void);
 
+/* ---- batched form: many independent pose graphs (sequence shards, cameras, replayed sessions) solved by one launch sequence.
+ * Each graph goes through exactly the per-graph algorithm of slslam_po_solve's default path (structured fp64 factorisation): the
+ * same slots, chain order and operation order; only the order of fp64 atomic sums can differ, so a graph's result does not depend
+ * on the other graphs of the batch beyond that round-off.  Every launch of an LM iteration (~14) covers every graph.
+ * create and add touch no device (a machine without one can validate); finalize is the first call that needs one
+ * (SLSLAM_ERR_NO_DEVICE without).  device < 0 selects the device current at finalize. */
+typedef struct slslam_po_batch slslam_po_batch;
+int  slslam_po_batch_create(int device, slslam_po_batch** out);
+void slslam_po_batch_destroy(slslam_po_batch* b);
+/* Copies the graph's arrays and runs slslam_po_solve's validation (SLSLAM_ERR_INVALID_ARGUMENT, nothing added) and symbolic
+ * analysis (slslam_po_structure).  Returns the graph's index in *index.  SLSLAM_ERR_STATE after finalize. */
+int  slslam_po_batch_add(slslam_po_batch* b, const slslam_po_graph* graph, int* index);
+/* One options struct for every graph, as for slslam_po_solve (huber_delta, baseline ignored); po_dense_factor = 1 or
+ * po_factor_fp32 = 1: SLSLAM_ERR_UNSUPPORTED.  Allocates and uploads.  Device memory per graph of n = 6 x (free poses) unknowns
+ * with nj of them on junction poses: the n x ld normal matrix plus the nj x ld junction factor in doubles, ld = n rounded up to 8,
+ * plus 8 (about 20 MB for a 260-pose graph with 8 loop closures), and a few vectors.  A failed allocation returns SLSLAM_ERR_HIP
+ * and leaves the batch unfinalized. */
+int  slslam_po_batch_finalize(slslam_po_batch* b, const slslam_solver_options* opt);
+/* Enqueues the complete LM solve of every graph on `stream` (a hipStream_t passed as void*, NULL = default stream).  Like
+ * slslam_po_solve it asks the device, now and then, whether every graph has finished and then stops enqueueing: that question
+ * synchronises the stream. */
+int  slslam_po_batch_solve(slslam_po_batch* b, void* stream);
+/* Initial poses back, LM state fresh (asynchronous on `stream`): the next solve starts over. */
+int  slslam_po_batch_reset(slslam_po_batch* b, void* stream);
+/* Blocks until the stream's work is done and copies every graph's poses, summary and trace back to the host. */
+int  slslam_po_batch_download(slslam_po_batch* b, void* stream);
+/* After download (SLSLAM_ERR_STATE before it, and after a reset or solve that followed it): what slslam_po_solve returns for the
+ * graph - parameters[6N] (untouched for NUMERICAL_FAILURE, a graph without edges, unreferenced poses), summary, trace. */
+int  slslam_po_batch_get_parameters(const slslam_po_batch* b, int index, double* parameters);
+int  slslam_po_batch_get_summary(const slslam_po_batch* b, int index, slslam_summary* summary);
+int  slslam_po_batch_get_trace(const slslam_po_batch* b, int index, slslam_iteration* trace, int trace_cap, int* trace_len);
+
 /* ------------------------------------------------------------------ RANSAC hypothesis scoring
  * (the per-frame cost centre next to the hot path.)
  * Replaces: the scoring loop of SLAM::ransac_motion (reference src/slam.cpp:396-413) with

@@ -97,7 +97,7 @@ EXPORTS = [
     "slslam_lba_batch_get_parameters", "slslam_lba_batch_get_summary",
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
-    "slslam_po_solve", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -161,6 +161,17 @@ def lib():
     L.slslam_lba_batch_linearise.argtypes = [vp, C.c_int, dp, dp, dp, dp]
     L.slslam_po_solve.argtypes = [C.POINTER(POGraph), C.POINTER(SolverOptions), C.POINTER(Summary),
                                   C.POINTER(Iteration), C.c_int, ip]
+    L.slslam_po_batch_create.argtypes = [C.c_int, C.POINTER(vp)]
+    L.slslam_po_batch_destroy.argtypes = [vp]
+    L.slslam_po_batch_destroy.restype = None
+    L.slslam_po_batch_add.argtypes = [vp, C.POINTER(POGraph), ip]
+    L.slslam_po_batch_finalize.argtypes = [vp, C.POINTER(SolverOptions)]
+    L.slslam_po_batch_solve.argtypes = [vp, vp]
+    L.slslam_po_batch_reset.argtypes = [vp, vp]
+    L.slslam_po_batch_download.argtypes = [vp, vp]
+    L.slslam_po_batch_get_parameters.argtypes = [vp, C.c_int, dp]
+    L.slslam_po_batch_get_summary.argtypes = [vp, C.c_int, C.POINTER(Summary)]
+    L.slslam_po_batch_get_trace.argtypes = [vp, C.c_int, C.POINTER(Iteration), C.c_int, ip]
     L.slslam_ransac_score.argtypes = [C.POINTER(RansacFrame), C.c_double, C.c_double, ip, C.POINTER(C.c_ulonglong)]
     L.slslam_po_structure.argtypes = [C.POINTER(POGraph), ip, C.c_int, ip, ip, ip, ip, ip, ip, ip]
     L.slslam_ransac_generate.argtypes = [C.POINTER(RansacTrials), C.c_double, dp, ip]
@@ -607,6 +618,91 @@ def po_solve(g, params=None, trace_cap=64, **opt):
     n = C.c_int(0)
     _check(lib().slslam_po_solve(C.byref(cg), C.byref(o), C.byref(s), tr, trace_cap, C.byref(n)), "slslam_po_solve")
     return x, _summary_dict(s), _trace_list(tr, min(n.value, trace_cap))
+
+
+def _po_arrays(g, params=None):
+    i1 = np.ascontiguousarray(g["pose_index_1"], dtype=np.int32)
+    i2 = np.ascontiguousarray(g["pose_index_2"], dtype=np.int32)
+    cons = np.ascontiguousarray(g["constraints"], dtype=np.float64).reshape(-1)
+    x = np.array(g["parameters"] if params is None else params, dtype=np.float64).reshape(-1).copy()
+    if len(i2) != len(i1) or len(cons) != 6 * len(i1) or len(x) != 6 * int(g["num_poses"]):
+        raise ValueError("inconsistent pose-graph arrays")
+    return i1, i2, cons, x
+
+
+class POBatch:
+    """Many pose graphs solved together (slslam_po_batch_*): each graph gets what po_solve gives it.  add() copies the graph,
+    finalize() uploads (the first call that needs a device), solve() enqueues, download() waits and brings the results back."""
+
+    def __init__(self, device=-1):
+        self._h = C.c_void_p()
+        _check(lib().slslam_po_batch_create(int(device), C.byref(self._h)), "slslam_po_batch_create")
+        self._n = []
+
+    def add(self, g, params=None):
+        i1, i2, cons, x = _po_arrays(g, params)
+        cg = POGraph(int(g["num_poses"]), len(i1), _ip(i1), _ip(i2), _dp(cons), _dp(x))
+        idx = C.c_int(-1)
+        _check(lib().slslam_po_batch_add(self._h, C.byref(cg), C.byref(idx)), "slslam_po_batch_add")
+        self._n.append(int(g["num_poses"]))
+        return idx.value
+
+    def __len__(self):
+        return len(self._n)
+
+    def finalize(self, **opt):
+        o = default_options(**opt)
+        _check(lib().slslam_po_batch_finalize(self._h, C.byref(o)), "slslam_po_batch_finalize")
+
+    def solve(self, stream=None):
+        _check(lib().slslam_po_batch_solve(self._h, C.c_void_p(stream or 0)), "slslam_po_batch_solve")
+
+    def reset(self, stream=None):
+        _check(lib().slslam_po_batch_reset(self._h, C.c_void_p(stream or 0)), "slslam_po_batch_reset")
+
+    def download(self, stream=None):
+        _check(lib().slslam_po_batch_download(self._h, C.c_void_p(stream or 0)), "slslam_po_batch_download")
+
+    def parameters(self, i):
+        out = np.zeros(6 * self._n[i])
+        _check(lib().slslam_po_batch_get_parameters(self._h, int(i), _dp(out)), "slslam_po_batch_get_parameters")
+        return out
+
+    def summary(self, i):
+        s = Summary()
+        _check(lib().slslam_po_batch_get_summary(self._h, int(i), C.byref(s)), "slslam_po_batch_get_summary")
+        return _summary_dict(s)
+
+    def trace(self, i, cap=64):
+        tr = (Iteration * cap)()
+        n = C.c_int(0)
+        _check(lib().slslam_po_batch_get_trace(self._h, int(i), tr, cap, C.byref(n)), "slslam_po_batch_get_trace")
+        return _trace_list(tr, min(n.value, cap))
+
+    def close(self):
+        if self._h:
+            lib().slslam_po_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def po_solve_batch(graphs, trace_cap=64, stream=None, **opt):
+    """The graphs through one POBatch: a list of (x, summary, trace), as po_solve returns for each."""
+    b = POBatch()
+    try:
+        for g in graphs:
+            b.add(g)
+        b.finalize(**opt)
+        b.solve(stream)
+        b.download(stream)
+        return [(b.parameters(i), b.summary(i), b.trace(i, trace_cap)) for i in range(len(b))]
+    finally:
+        b.close()
 
 
 def po_solve_timed(g, **opt):

@@ -548,3 +548,6 @@ extern "C" int slslam_po_structure(const slslam_po_graph* g, int* slot_out, int 
   }
   return SLSLAM_OK;
 }
+
+// many graphs per call: slslam_po_batch_* (the same kernels' bodies, the same symbolic analysis)
+#include "po_batch.h"

@@ -151,12 +151,13 @@ enum { kPoCost = 0, kPoCandCost = 1, kPoModel = 2, kPoDn2 = 3, kPoXn2 = 4, kPoFi
 // lane <-> (edge, column of [J1|J2]); 5 edges per wave.
 // mode 0: accumulate H, g, cost at the accepted point (scaled columns)
 // mode 1: cost only at the candidate point
-__global__ __launch_bounds__(64) void k_po_linearise(PoPtrs p, int mode) {
+// (the bodies below take their workgroup's index as an argument: the batched kernels of po_batch.hip map it from a work list)
+__device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned blk) {
   const LMState* st = p.st;
   if (st->status != kRunning) return;
   const int lane = threadIdx.x;
   const int el = lane / 12, d = lane - 12 * el;
-  const int e = blockIdx.x * 5 + el;
+  const int e = blk * 5 + el;
   const bool ok = el < 5 && e < p.E;
   const int buf = mode ? 1 - st->cur : st->cur;
   const double* X = p.x + (long long)buf * 6 * p.N;
@@ -204,14 +205,15 @@ __global__ __launch_bounds__(64) void k_po_linearise(PoPtrs p, int mode) {
   for (int o = 32; o > 0; o >>= 1) cost += __shfl_xor(cost, o);
   if (lane == 0) atomicAdd(&p.scal[kPoCost], cost);
 }
+__global__ __launch_bounds__(64) void k_po_linearise(PoPtrs p, int mode) { po_linearise_body(p, mode, blockIdx.x); }
 
 // Structured factorisation only: zeroes what the linearisation is about to add into - the lower-triangle entries of every edge's two
 // pose blocks and their coupling (the same index rule as k_po_linearise), the junction block (the dense factorisation reads all of it),
 // the gradient and the cost - instead of a memset of the whole dense matrix (20 MB at 1554 unknowns, a third of a structured solve
 // in fill kernels).  Everything else the structured path reads from H it has written itself (k_po_chain_eliminate: factor and fill).
-__global__ __launch_bounds__(256) void k_po_zero_structured(PoPtrs p, int n_chain /* unknowns of the level-1 chains: the square behind them is zeroed */) {
+__device__ __forceinline__ void po_zero_structured_body(const PoPtrs& p, int n_chain /* unknowns of the level-1 chains: the square behind them is zeroed */, unsigned blk) {
   if (p.st->status != kRunning) return;
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long t = (long long)blk * 256 + threadIdx.x;
   const long long n_edge = (long long)p.E * 144;
   const int nj = p.n - n_chain;
   const long long n_junc = (long long)nj * nj;
@@ -231,10 +233,11 @@ __global__ __launch_bounds__(256) void k_po_zero_structured(PoPtrs p, int n_chai
     p.scal[kPoCost] = 0.0;
   }
 }
+__global__ __launch_bounds__(256) void k_po_zero_structured(PoPtrs p, int n_chain) { po_zero_structured_body(p, n_chain, blockIdx.x); }
 
 // one workgroup: gradient max-norm, Jacobi scale on the first call, damping, rhs.
 // first = 1: H holds the UNSCALED J^T J (scale == 1); compute scale, rescale H and g in place.
-__global__ __launch_bounds__(256) void k_po_prepare(PoPtrs p, Policy pol, int first) {
+__device__ __forceinline__ void po_prepare_body(const PoPtrs& p, const Policy& pol, int first) {
   LMState* st = p.st;
   if (st->status != kRunning) return;
   __shared__ double red[256];
@@ -332,6 +335,7 @@ __global__ __launch_bounds__(256) void k_po_prepare(PoPtrs p, Policy pol, int fi
   }
   if (tid == 0) { p.flags[0] = 0; p.scal[kPoCandCost] = 0.0; }
 }
+__global__ __launch_bounds__(256) void k_po_prepare(PoPtrs p, Policy pol, int first) { po_prepare_body(p, pol, first); }
 
 #endif
 // ---- blocked Cholesky, block size 64 --------------------------------------------------------
@@ -439,7 +443,7 @@ __device__ __forceinline__ void po_potrf_lds(PoPtrs& p, T* Tt, T* Li, int tid) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void k_po_potrf_diag(PoPtrs p, T* A, T* linv, int k0, T* Aout = nullptr) {     // Aout: where the factor goes (default: in place)
+__device__ __forceinline__ void po_potrf_diag_body(PoPtrs& p, T* A, T* linv, int k0, T* Aout) {
   if (p.st->status != kRunning) return;
   if (!Aout) Aout = A;
   __shared__ T Tt[kNB * kLdT];
@@ -461,6 +465,10 @@ __global__ __launch_bounds__(256) void k_po_potrf_diag(PoPtrs p, T* A, T* linv, 
     linv[q] = (c <= r) ? Li[r * kLdT + c] : T(0);
     if (r < nb && c <= r) Aout[(long long)(k0 + r) * p.ld + k0 + c] = Tt[r * kLdT + c];
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_po_potrf_diag(PoPtrs p, T* A, T* linv, int k0, T* Aout = nullptr) {     // Aout: where the factor goes (default: in place)
+  po_potrf_diag_body<T>(p, A, linv, k0, Aout);
 }
 
 // C(64x64) = B(64x64) * M(64x64)^T on the 16x16x4 MFMA of T; 4 waves, wave w owns tile row w.
@@ -534,7 +542,7 @@ __global__ __launch_bounds__(256) void k_po_panel_update(PoPtrs p, T* A, const T
 //     linv_all[bk + 1]: the next launch starts from there.
 // Dynamic LDS: three 64 x 66 tiles of T.
 template <typename T>
-__global__ __launch_bounds__(256) void k_po_step(PoPtrs p, T* A, T* Lf, T* linv_all, int bk) {
+__device__ __forceinline__ void po_step_body(PoPtrs& p, T* A, T* Lf, T* linv_all, int bk, unsigned blk) {
   if (p.st->status != kRunning) return;
   extern __shared__ __attribute__((aligned(16))) unsigned char po_step_smem[];
   T* Bi = reinterpret_cast<T*>(po_step_smem);
@@ -545,7 +553,7 @@ __global__ __launch_bounds__(256) void k_po_step(PoPtrs p, T* A, T* Lf, T* linv_
   const T* linv = linv_all + (size_t)bk * kNB * kNB;
   int bi, bj;
   {
-    const int t = blockIdx.x;
+    const int t = blk;
     bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
     while ((bi * (bi + 1)) / 2 > t) --bi;
     while (((bi + 1) * (bi + 2)) / 2 <= t) ++bi;
@@ -609,13 +617,15 @@ __global__ __launch_bounds__(256) void k_po_step(PoPtrs p, T* A, T* Lf, T* linv_
     if (r < nb && c <= r) Lf[(long long)(t0 + r) * p.ld + t0 + c] = Tt[r * kLdT + c];
   }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void k_po_step(PoPtrs p, T* A, T* Lf, T* linv_all, int bk) { po_step_body<T>(p, A, Lf, linv_all, bk, blockIdx.x); }
 enum { kPoStepLdsTiles = 3 };
 
 // forward then backward substitution with the factor in A and the inverted diagonal blocks in
 // linv_all (one 64x64 block per block column, kept by k_po_potrf_diag): every step is a parallel
 // matrix-vector product - no serial pivot loop.  rhs / solution stay fp64.  One workgroup.
 template <typename T>
-__global__ __launch_bounds__(1024) void k_po_trisolve(PoPtrs p, const T* A, const T* linv_all) {
+__device__ __forceinline__ void po_trisolve_body(const PoPtrs& p, const T* A, const T* linv_all) {
   if (p.st->status != kRunning) return;
   __shared__ double yb[kNB], yn[kNB];
   __shared__ T Ls[kNB * (kNB + 1)];
@@ -674,6 +684,8 @@ __global__ __launch_bounds__(1024) void k_po_trisolve(PoPtrs p, const T* A, cons
     __syncthreads();
   }
 }
+template <typename T>
+__global__ __launch_bounds__(1024) void k_po_trisolve(PoPtrs p, const T* A, const T* linv_all) { po_trisolve_body<T>(p, A, linv_all); }
 
 // The same two substitutions spread over the chip: one workgroup per 64-row block, all resident (the host checks), forward
 // then backward in ONE launch.  k_po_trisolve walks the whole factor (10 MB at 1554 unknowns) with a single workgroup - bound by
@@ -823,10 +835,10 @@ __device__ __forceinline__ bool chol6_and_inverse(const double* Ds /* LDS, 6x6 s
   return ok;
 }
 
-__global__ __launch_bounds__(64) void k_po_chain_eliminate(PoPtrs p, const PoChain* chains) {
+__device__ __forceinline__ void po_chain_eliminate_body(const PoPtrs& p, const PoChain* chain) {
   if (p.st->status != kRunning) return;
   __shared__ double Ds[36], Bs[36], Cs[36], Rs[36], Lis[36], Bt[36], Ct[36], Rt[36], gs[6], gt[6];
-  const PoChain ch = chains[blockIdx.x];
+  const PoChain ch = *chain;
   const int lane = threadIdx.x;
   const int r = lane / 6, c = lane - 6 * r;
   const bool el = lane < 36;
@@ -929,13 +941,14 @@ __global__ __launch_bounds__(64) void k_po_chain_eliminate(PoPtrs p, const PoCha
   }
   if (__any(fail) && lane == 0) p.flags[0] = 1;
 }
+__global__ __launch_bounds__(64) void k_po_chain_eliminate(PoPtrs p, const PoChain* chains) { po_chain_eliminate_body(p, chains + blockIdx.x); }
 
 // y_i = L_i^-T ( g~_i - B~_i^T y_{i+1} - C~_i^T y_jl - [last] R~^T y_jr ), from the end of the chain to its start.
 // The three 6x6 blocks of the next step are requested while the current one is solved.
-__global__ __launch_bounds__(64) void k_po_chain_backsub(PoPtrs p, const PoChain* chains) {
+__device__ __forceinline__ void po_chain_backsub_body(const PoPtrs& p, const PoChain* chain) {
   if (p.st->status != kRunning) return;
   __shared__ double Ls[36], Xs[36], Cs[36], gsh[6], rhs[6], ysol[6], ylr[12], idiag[6];
-  const PoChain ch = chains[blockIdx.x];
+  const PoChain ch = *chain;
   const int lane = threadIdx.x;
   const int r = lane / 6, c = lane - 6 * r;
   const bool el = lane < 36;
@@ -988,9 +1001,10 @@ __global__ __launch_bounds__(64) void k_po_chain_backsub(PoPtrs p, const PoChain
     if (lane < 6) p.y[si + lane] = ysol[lane];
   }
 }
+__global__ __launch_bounds__(64) void k_po_chain_backsub(PoPtrs p, const PoChain* chains) { po_chain_backsub_body(p, chains + blockIdx.x); }
 
 // candidate poses and step statistics; one workgroup.
-__global__ __launch_bounds__(256) void k_po_candidate(PoPtrs p) {
+__device__ __forceinline__ void po_candidate_body(const PoPtrs& p) {
   LMState* st = p.st;
   if (st->status != kRunning) return;
   __shared__ double red[3][256];
@@ -1032,11 +1046,12 @@ __global__ __launch_bounds__(256) void k_po_candidate(PoPtrs p) {
     st->solve_failed = (any_bad || p.flags[0]) ? 1 : 0;
   }
 }
+__global__ __launch_bounds__(256) void k_po_candidate(PoPtrs p) { po_candidate_body(p); }
 
 // trust-region bookkeeping (one thread); same policy as k_lm_update.
-__global__ void k_po_update(PoPtrs p, Policy pol) {
+__device__ __forceinline__ void po_update_body(const PoPtrs& p, const Policy& pol) {
   LMState* st = p.st;
-  if (st->status != kRunning || threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (st->status != kRunning || threadIdx.x != 0) return;
   double new_cost = p.scal[kPoCandCost];
   const double model = p.scal[kPoModel], cost = st->cost;
   IterRec rec;
@@ -1082,6 +1097,7 @@ __global__ void k_po_update(PoPtrs p, Policy pol) {
   if (st->radius < pol.min_radius) { st->status = 5; return; }
   if (st->iter >= pol.max_num_iterations) { st->status = 0; return; }
 }
+__global__ void k_po_update(PoPtrs p, Policy pol) { if (blockIdx.x == 0) po_update_body(p, pol); }
 
 #endif
 }  // namespace slslam
