@@ -1,6 +1,7 @@
 // slslam_amd/csrc/po_batch.h — many pose graphs per call: slslam_po_batch_* runs slslam_po_solve's structured path
 // (POProblem::build + ceres::Solve, reference src/slam.cpp:1236-1313, src/po_problem.cpp:40-77) for G graphs at once.
-// Part of po_api.hip's translation unit (included at its end: the one-graph kernels and order_chains_first live there).
+// Part of po_api.hip's translation unit (included at its end: the one-graph kernels, the symbolic analysis and the host helpers both
+// paths share - validation, policy, PoSymbolic, results, PO_TRY, PoCarve - live there).
 //
 // Every launch of the one-graph sequence covers every graph of the batch: the kernels below are the one-graph kernels'
 // bodies (po_kernels.h) behind a graph index taken from the grid (one workgroup per graph) or from a flattened work list
@@ -73,8 +74,6 @@ __global__ __launch_bounds__(64) void k_pob_update(const PoBatchGraph* gs, Polic
 
 constexpr size_t kStepLds = kPoStepLdsTiles * kNB * kLdT * sizeof(double);
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 struct slslam_po_batch {
@@ -82,10 +81,7 @@ struct slslam_po_batch {
     int N = 0, E = 0;
     std::vector<int> p1, p2;
     std::vector<double> cons, x0;
-    // symbolic analysis (slslam_po_solve's, done by add)
-    std::vector<int> slot, level_counts;
-    std::vector<PoChain> chains;
-    int n_chain = 0, n = 0, kept = 0, n_l1 = 0, nj = 0, nblk_j = 0, ld = 0;
+    PoSymbolic sym;                         // slslam_po_solve's structured analysis, done by add
     int active = -1;                        // index among the graphs the device solves (E > 0), -1 otherwise
     // results (download)
     LMState st{};
@@ -119,15 +115,6 @@ struct slslam_po_batch {
   }
 };
 
-#define POB_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      std::fprintf(stderr, "slslam: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return (_e == hipErrorNoDevice || _e == hipErrorInvalidDevice) ? SLSLAM_ERR_NO_DEVICE : SLSLAM_ERR_HIP; \
-    }                                                                                   \
-  } while (0)
-
 extern "C" int slslam_po_batch_create(int device, slslam_po_batch** out) {
   if (!out) return SLSLAM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
@@ -147,36 +134,15 @@ extern "C" void slslam_po_batch_destroy(slslam_po_batch* b) {
 extern "C" int slslam_po_batch_add(slslam_po_batch* b, const slslam_po_graph* g, int* index) {
   if (!b || !g) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (b->finalized) return SLSLAM_ERR_STATE;
-  // the validation of slslam_po_solve
+  if (!po_graph_arrays_ok(g, true) || !po_graph_entries_ok(g, true)) return SLSLAM_ERR_INVALID_ARGUMENT;
   const int N = g->num_poses, E = g->num_edges;
-  if (N < 0 || E < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (E > 0 && (!g->pose_index_1 || !g->pose_index_2 || !g->constraints)) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (N > 0 && !g->parameters) return SLSLAM_ERR_INVALID_ARGUMENT;
-  for (int e = 0; e < E; ++e) {
-    const int a = g->pose_index_1[e], c = g->pose_index_2[e];
-    if (a < 0 || a >= N || c < 0 || c >= N || a == c) return SLSLAM_ERR_INVALID_ARGUMENT;
-    for (int q = 0; q < 6; ++q) if (!std::isfinite(g->constraints[6 * (size_t)e + q])) return SLSLAM_ERR_INVALID_ARGUMENT;
-  }
-  for (size_t i = 0; i < (size_t)6 * N; ++i) if (!std::isfinite(g->parameters[i])) return SLSLAM_ERR_INVALID_ARGUMENT;
   try {
     slslam_po_batch::Graph G;
     G.N = N; G.E = E;
     G.p1.assign(g->pose_index_1, g->pose_index_1 + E); G.p2.assign(g->pose_index_2, g->pose_index_2 + E);
     G.cons.assign(g->constraints, g->constraints + 6 * (size_t)E);
     G.x0.assign(g->parameters, g->parameters + 6 * (size_t)N);
-    if (E > 0) {
-      // the symbolic analysis of slslam_po_solve's structured path: pose1 of edge 0 is constant, unreferenced poses are not in the problem
-      std::vector<int> used(N, 0);
-      G.slot.assign(N, -1);
-      for (int e = 0; e < E; ++e) { used[G.p1[e]] = 1; used[G.p2[e]] = 1; }
-      order_chains_first(N, E, G.p1.data(), G.p2.data(), used, G.p1[0], G.slot, G.chains, &G.n_chain, &G.n, &G.level_counts);
-      for (int e = 0; e < E; ++e) if (G.slot[G.p1[e]] >= 0 || G.slot[G.p2[e]] >= 0) ++G.kept;
-      G.ld = ((G.n + 7) / 8) * 8 + 8;
-      G.nj = G.n - G.n_chain;
-      G.nblk_j = (G.nj + kNB - 1) / kNB;
-      const int n_level1 = G.level_counts.empty() ? 0 : G.level_counts[0];
-      G.n_l1 = n_level1 > 0 ? G.chains[(size_t)n_level1 - 1].start + 6 * G.chains[(size_t)n_level1 - 1].len : 0;
-    }
+    po_analyse(N, E, G.p1.data(), G.p2.data(), true, &G.sym);
     if (index) *index = (int)b->graphs.size();
     b->graphs.push_back(std::move(G));
   } catch (const std::bad_alloc&) {
@@ -189,16 +155,15 @@ namespace {
 // Lays the arena out, fills the pinned image and the work lists.  arena == nullptr: sizes only.
 void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* down_bytes, size_t* total_bytes) {
   const int A = (int)b->active.size();
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+  PoCarve carve;
   char* img = b->h_up;
   auto put = [&](size_t o, const void* src, size_t bytes) { if (img && bytes) std::memcpy(img + o, src, bytes); };
   // what comes back: the LM states (also what solve polls), the traces, the poses
-  const size_t o_st = take(sizeof(LMState) * (size_t)A);
-  b->o_trace = take(sizeof(IterRec) * kMaxTrace * (size_t)A);
+  const size_t o_st = carve.take(sizeof(LMState) * (size_t)A);
+  b->o_trace = carve.take(sizeof(IterRec) * kMaxTrace * (size_t)A);
   b->o_x.assign((size_t)A, 0);
-  for (int a = 0; a < A; ++a) b->o_x[(size_t)a] = take(sizeof(double) * 12 * (size_t)b->graphs[(size_t)b->active[(size_t)a]].N);
-  *down_bytes = off;
+  for (int a = 0; a < A; ++a) b->o_x[(size_t)a] = carve.take(sizeof(double) * 12 * (size_t)b->graphs[(size_t)b->active[(size_t)a]].N);
+  *down_bytes = carve.off;
   // the work lists
   std::vector<PoItem> items;
   std::vector<int> jgraphs;
@@ -206,8 +171,7 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
   list(b->zero_off, b->zero_cnt, [&] {
     for (int a = 0; a < A; ++a) {
       const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
-      const long long nz = G.n - G.n_l1, zero_items = (long long)G.E * 144 + nz * nz + G.n + 1;
-      for (long long k = 0; k < (zero_items + 255) / 256; ++k) items.push_back(PoItem{ a, (int)k });
+      for (long long k = 0; k < po_zero_blocks(G.sym, G.E); ++k) items.push_back(PoItem{ a, (int)k });
     }
   });
   list(b->edge_off, b->edge_cnt, [&] {
@@ -217,63 +181,63 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
   size_t levels = 0;
   int steps = 0;
   for (int gi : b->active) {
-    const auto& G = b->graphs[(size_t)gi];
-    levels = std::max(levels, G.level_counts.size());
-    steps = std::max(steps, G.nblk_j - 1);
+    const PoSymbolic& S = b->graphs[(size_t)gi].sym;
+    levels = std::max(levels, S.level_counts.size());
+    steps = std::max(steps, S.nblk_j - 1);
   }
-  for (int a = 0; a < A; ++a) if (b->graphs[(size_t)b->active[(size_t)a]].nj > 0) jgraphs.push_back(a);
+  for (int a = 0; a < A; ++a) if (b->graphs[(size_t)b->active[(size_t)a]].sym.nj > 0) jgraphs.push_back(a);
   b->jgraph_cnt = (int)jgraphs.size();
   b->level_off.assign(levels, 0); b->level_cnt.assign(levels, 0);
   for (size_t lv = 0; lv < levels; ++lv)
     list(b->level_off[lv], b->level_cnt[lv], [&] {
       for (int a = 0; a < A; ++a) {
-        const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
-        if (lv >= G.level_counts.size()) continue;
+        const PoSymbolic& S = b->graphs[(size_t)b->active[(size_t)a]].sym;
+        if (lv >= S.level_counts.size()) continue;
         size_t first = 0;
-        for (size_t q = 0; q < lv; ++q) first += (size_t)G.level_counts[q];
-        for (int c = 0; c < G.level_counts[lv]; ++c) items.push_back(PoItem{ a, (int)first + c });
+        for (size_t q = 0; q < lv; ++q) first += (size_t)S.level_counts[q];
+        for (int c = 0; c < S.level_counts[lv]; ++c) items.push_back(PoItem{ a, (int)first + c });
       }
     });
   b->step_off.assign((size_t)std::max(steps, 0), 0); b->step_cnt.assign((size_t)std::max(steps, 0), 0);
   for (int bk = 0; bk < steps; ++bk)
     list(b->step_off[(size_t)bk], b->step_cnt[(size_t)bk], [&] {
       for (int a = 0; a < A; ++a) {
-        const int tb = b->graphs[(size_t)b->active[(size_t)a]].nblk_j - 1 - bk;
+        const int tb = b->graphs[(size_t)b->active[(size_t)a]].sym.nblk_j - 1 - bk;
         for (int t = 0; tb > 0 && t < tb * (tb + 1) / 2; ++t) items.push_back(PoItem{ a, t });
       }
     });
-  const size_t o_graphs = take(sizeof(PoBatchGraph) * (size_t)A), o_items = take(sizeof(PoItem) * items.size()),
-               o_jg = take(sizeof(int) * jgraphs.size());
+  const size_t o_graphs = carve.take(sizeof(PoBatchGraph) * (size_t)A), o_items = carve.take(sizeof(PoItem) * items.size()),
+               o_jg = carve.take(sizeof(int) * jgraphs.size());
   put(o_items, items.data(), sizeof(PoItem) * items.size());
   put(o_jg, jgraphs.data(), sizeof(int) * jgraphs.size());
   // per graph: the inputs, then (after every graph's inputs) the work arrays
   std::vector<PoBatchGraph> desc((size_t)A);
   std::vector<size_t> o_in((size_t)A * 8);
+  const LMState st = po_initial_state(b->pol);
   for (int a = 0; a < A; ++a) {
     const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
+    const PoSymbolic& S = G.sym;
     size_t* o = &o_in[(size_t)a * 8];
-    o[0] = take(sizeof(int) * G.E); o[1] = take(sizeof(int) * G.E); o[2] = take(sizeof(int) * G.N); o[3] = take(sizeof(double) * 6 * G.E);
-    o[4] = take(sizeof(double) * G.n); o[5] = take(sizeof(PoChain) * (G.chains.size() + 1)); o[6] = take(sizeof(double) * 8); o[7] = take(sizeof(int) * 2);
+    o[0] = carve.take(sizeof(int) * G.E); o[1] = carve.take(sizeof(int) * G.E); o[2] = carve.take(sizeof(int) * G.N); o[3] = carve.take(sizeof(double) * 6 * G.E);
+    o[4] = carve.take(sizeof(double) * S.n); o[5] = carve.take(sizeof(PoChain) * (S.chains.size() + 1)); o[6] = carve.take(sizeof(double) * 8); o[7] = carve.take(sizeof(int) * 2);
     if (img) {
-      LMState st;
-      std::memset(&st, 0, sizeof(st));
-      st.radius = b->pol.initial_radius; st.decrease_factor = 2.0; st.status = kRunning;
       put(o_st + sizeof(LMState) * a, &st, sizeof(st));
       put(b->o_x[(size_t)a], G.x0.data(), sizeof(double) * 6 * G.N);
       put(b->o_x[(size_t)a] + sizeof(double) * 6 * G.N, G.x0.data(), sizeof(double) * 6 * G.N);
-      put(o[0], G.p1.data(), sizeof(int) * G.E); put(o[1], G.p2.data(), sizeof(int) * G.E); put(o[2], G.slot.data(), sizeof(int) * G.N);
+      put(o[0], G.p1.data(), sizeof(int) * G.E); put(o[1], G.p2.data(), sizeof(int) * G.E); put(o[2], S.slot.data(), sizeof(int) * G.N);
       put(o[3], G.cons.data(), sizeof(double) * 6 * G.E);
-      for (int i = 0; i < G.n; ++i) { const double one = 1.0; put(o[4] + sizeof(double) * i, &one, sizeof(double)); }
-      put(o[5], G.chains.data(), sizeof(PoChain) * G.chains.size());
+      for (int i = 0; i < S.n; ++i) { const double one = 1.0; put(o[4] + sizeof(double) * i, &one, sizeof(double)); }
+      put(o[5], S.chains.data(), sizeof(PoChain) * S.chains.size());
     }
   }
-  *up_bytes = off;
+  *up_bytes = carve.off;
   for (int a = 0; a < A; ++a) {
     const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
+    const PoSymbolic& S = G.sym;
     const size_t* o = &o_in[(size_t)a * 8];
-    const size_t o_H = take(sizeof(double) * (size_t)G.n * G.ld), o_g = take(sizeof(double) * G.n), o_d2 = take(sizeof(double) * G.n),
-                 o_y = take(sizeof(double) * G.n), o_linv = take(sizeof(double) * kNB * kNB * (size_t)std::max(G.nblk_j, 1)),
-                 o_Lf = take(sizeof(double) * (size_t)std::max(G.nj, 1) * G.ld);
+    const size_t o_H = carve.take(sizeof(double) * (size_t)S.n * S.ld), o_g = carve.take(sizeof(double) * S.n), o_d2 = carve.take(sizeof(double) * S.n),
+                 o_y = carve.take(sizeof(double) * S.n), o_linv = carve.take(sizeof(double) * kNB * kNB * (size_t)std::max(S.nblk_j, 1)),
+                 o_Lf = carve.take(sizeof(double) * (size_t)std::max(S.nj, 1) * S.ld);
     if (!arena) continue;
     PoBatchGraph& D = desc[(size_t)a];
     std::memset(&D, 0, sizeof(D));
@@ -282,19 +246,19 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
     p.scale = (double*)(arena + o[4]); p.scal = (double*)(arena + o[6]); p.flags = (int*)(arena + o[7]);
     p.x = (double*)(arena + b->o_x[(size_t)a]); p.st = (LMState*)(arena + o_st) + a; p.trace = (IterRec*)(arena + b->o_trace) + (size_t)kMaxTrace * a;
     p.H = (double*)(arena + o_H); p.g = (double*)(arena + o_g); p.d2 = (double*)(arena + o_d2); p.y = (double*)(arena + o_y);
-    p.N = G.N; p.E = G.E; p.n = G.n; p.ld = G.ld;
+    p.N = G.N; p.E = G.E; p.n = S.n; p.ld = S.ld;
     D.pj = p;                               // the junction block as a matrix of its own (same leading dimension)
-    D.pj.n = G.nj; D.pj.H = p.H + (size_t)G.n_chain * G.ld + G.n_chain; D.pj.y = p.y + G.n_chain;
+    D.pj.n = S.nj; D.pj.H = p.H + (size_t)S.n_chain * S.ld + S.n_chain; D.pj.y = p.y + S.n_chain;
     D.chains = (const PoChain*)(arena + o[5]);
     D.Lf_j = (double*)(arena + o_Lf);
     D.linv = (double*)(arena + o_linv);
-    D.n_l1 = G.n_l1;
+    D.n_l1 = S.n_l1;
   }
   put(o_graphs, desc.data(), sizeof(PoBatchGraph) * desc.size());
   if (arena) {
     b->d_graphs = (PoBatchGraph*)(arena + o_graphs); b->d_items = (PoItem*)(arena + o_items); b->d_jgraphs = (int*)(arena + o_jg);
   }
-  *total_bytes = off;
+  *total_bytes = carve.off;
 }
 }  // namespace
 
@@ -302,23 +266,13 @@ extern "C" int slslam_po_batch_finalize(slslam_po_batch* b, const slslam_solver_
   if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (b->finalized) return SLSLAM_ERR_STATE;
   slslam_solver_options opt;
-  if (opt_in) opt = *opt_in; else slslam_default_options(&opt);
-  if (opt.max_num_iterations < 0 || opt.max_num_iterations > 100000) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!po_policy(opt_in, &opt, &b->pol)) return SLSLAM_ERR_INVALID_ARGUMENT;      // (slslam_po_solve's policy)
   if (opt.po_dense_factor || opt.po_factor_fp32) return SLSLAM_ERR_UNSUPPORTED;      // the structured fp64 factorisation only
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
   if (b->device < 0) { if (hipGetDevice(&b->device) != hipSuccess) return SLSLAM_ERR_NO_DEVICE; }
   if (b->device >= ndev) return SLSLAM_ERR_INVALID_ARGUMENT;
-  POB_TRY(hipSetDevice(b->device));
-  Policy& pol = b->pol;                     // (slslam_po_solve's policy)
-  std::memset(&pol, 0, sizeof(pol));
-  pol.huber_delta = 0.0; pol.baseline = 0.0;
-  pol.initial_radius = opt.initial_trust_region_radius; pol.max_radius = opt.max_trust_region_radius;
-  pol.min_radius = opt.min_trust_region_radius; pol.min_relative_decrease = opt.min_relative_decrease;
-  pol.min_lm_diagonal = opt.min_lm_diagonal; pol.max_lm_diagonal = opt.max_lm_diagonal;
-  pol.function_tolerance = opt.function_tolerance; pol.gradient_tolerance = opt.gradient_tolerance;
-  pol.parameter_tolerance = opt.parameter_tolerance; pol.max_num_iterations = opt.max_num_iterations;
-  pol.max_invalid = opt.max_num_consecutive_invalid_steps; pol.jacobi_scaling = opt.jacobi_scaling; pol.keep_jacobian = 0;
+  PO_TRY(hipSetDevice(b->device));
   b->active.clear();
   for (size_t i = 0; i < b->graphs.size(); ++i) {
     b->graphs[i].active = b->graphs[i].E > 0 ? (int)b->active.size() : -1;
@@ -352,8 +306,8 @@ extern "C" int slslam_po_batch_reset(slslam_po_batch* b, void* stream) {
   if (!b->finalized) return SLSLAM_ERR_STATE;
   b->have_results = false;
   if (b->active.empty()) return SLSLAM_OK;
-  POB_TRY(hipSetDevice(b->device));
-  POB_TRY(hipMemcpyAsync(b->arena, b->h_up, b->up_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  PO_TRY(hipSetDevice(b->device));
+  PO_TRY(hipMemcpyAsync(b->arena, b->h_up, b->up_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
   return SLSLAM_OK;
 }
 
@@ -363,7 +317,7 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
   b->have_results = false;
   const int A = (int)b->active.size();
   if (A == 0) return SLSLAM_OK;
-  POB_TRY(hipSetDevice(b->device));
+  PO_TRY(hipSetDevice(b->device));
   hipStream_t s = (hipStream_t)stream;
   const PoBatchGraph* gs = b->d_graphs;
   const PoItem* items = b->d_items;
@@ -381,8 +335,8 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
   int next_check = b->iter_hint >= 0 ? std::min(b->iter_hint + 1, 8) : 8;
   for (int it = 0; it < pol.max_num_iterations; ++it) {
     if (it == next_check) {
-      POB_TRY(hipMemcpyAsync(b->h_down, b->arena, sizeof(LMState) * (size_t)A, hipMemcpyDeviceToHost, s));
-      POB_TRY(hipStreamSynchronize(s));
+      PO_TRY(hipMemcpyAsync(b->h_down, b->arena, sizeof(LMState) * (size_t)A, hipMemcpyDeviceToHost, s));
+      PO_TRY(hipStreamSynchronize(s));
       const LMState* st = (const LMState*)b->h_down;
       bool running = false;
       int steps = 0;
@@ -409,7 +363,7 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
     hipLaunchKernelGGL(k_pob_linearise, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, gs, items + b->edge_off, 1);
     hipLaunchKernelGGL(k_pob_update, dim3((unsigned)A), dim3(64), 0, s, gs, pol);
   }
-  POB_TRY(hipGetLastError());
+  PO_TRY(hipGetLastError());
   return SLSLAM_OK;
 }
 
@@ -418,10 +372,10 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
   if (!b->finalized) return SLSLAM_ERR_STATE;
   const int A = (int)b->active.size();
   if (A > 0) {
-    POB_TRY(hipSetDevice(b->device));
+    PO_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
-    POB_TRY(hipMemcpyAsync(b->h_down, b->arena, b->down_bytes, hipMemcpyDeviceToHost, s));
-    POB_TRY(hipStreamSynchronize(s));
+    PO_TRY(hipMemcpyAsync(b->h_down, b->arena, b->down_bytes, hipMemcpyDeviceToHost, s));
+    PO_TRY(hipStreamSynchronize(s));
   }
   int steps = 0;
   try {
@@ -449,10 +403,6 @@ int po_batch_graph(const slslam_po_batch* b, int index, const slslam_po_batch::G
   *G = &b->graphs[(size_t)index];
   return SLSLAM_OK;
 }
-int po_termination(const slslam_po_batch::Graph& G) {
-  if (G.active < 0) return SLSLAM_FUNCTION_TOLERANCE;              // no edges: nothing to solve
-  return G.st.status == kRunning ? SLSLAM_NO_CONVERGENCE : G.st.status;
-}
 }  // namespace
 
 extern "C" int slslam_po_batch_get_parameters(const slslam_po_batch* b, int index, double* parameters) {
@@ -461,7 +411,7 @@ extern "C" int slslam_po_batch_get_parameters(const slslam_po_batch* b, int inde
   if (rc != SLSLAM_OK) return rc;
   if (G->N > 0 && !parameters) return SLSLAM_ERR_INVALID_ARGUMENT;
   // a numerical failure leaves the parameters untouched (slslam_po_solve)
-  const bool solved = G->active >= 0 && po_termination(*G) != SLSLAM_NUMERICAL_FAILURE;
+  const bool solved = G->active >= 0 && po_termination(&G->st) != SLSLAM_NUMERICAL_FAILURE;
   if (G->N > 0) std::memcpy(parameters, solved ? G->x.data() : G->x0.data(), sizeof(double) * 6 * (size_t)G->N);
   return SLSLAM_OK;
 }
@@ -472,14 +422,8 @@ extern "C" int slslam_po_batch_get_summary(const slslam_po_batch* b, int index, 
   if (rc != SLSLAM_OK) return rc;
   if (!s) return SLSLAM_ERR_INVALID_ARGUMENT;
   std::memset(s, 0, sizeof(*s));
-  s->termination_type = po_termination(*G);
-  if (G->active < 0) return SLSLAM_OK;
-  const LMState& st = G->st;
-  s->num_successful_steps = st.n_success; s->num_unsuccessful_steps = st.n_unsuccess;
-  s->initial_cost = st.initial_cost;
-  s->final_cost = st.min_cost < st.initial_cost ? st.min_cost : st.initial_cost;
-  s->fixed_cost = st.fixed_cost;
-  s->num_free_parameters = G->n; s->num_residual_blocks = G->kept;
+  s->termination_type = po_termination(G->active < 0 ? nullptr : &G->st);              // (no edges: nothing was solved)
+  if (G->active >= 0) po_fill_summary(G->st, s->termination_type, G->sym, s);
   return SLSLAM_OK;
 }
 
@@ -487,16 +431,7 @@ extern "C" int slslam_po_batch_get_trace(const slslam_po_batch* b, int index, sl
   const slslam_po_batch::Graph* G = nullptr;
   const int rc = po_batch_graph(b, index, &G);
   if (rc != SLSLAM_OK) return rc;
-  const int nt = G->active < 0 ? 0 : (G->st.ntrace < kMaxTrace ? G->st.ntrace : kMaxTrace);
-  if (len) *len = nt;
-  for (int i = 0; trace && i < nt && i < cap; ++i) {
-    const IterRec& r = G->trace[(size_t)i];
-    slslam_iteration& o = trace[i];
-    o.iteration = r.iteration; o.step_is_valid = r.step_is_valid; o.step_is_successful = r.step_is_successful;
-    o.cost = r.cost; o.cost_change = r.cost_change; o.gradient_max_norm = r.gradient_max_norm;
-    o.step_norm = r.step_norm; o.relative_decrease = r.relative_decrease;
-    o.trust_region_radius = r.trust_region_radius; o.model_cost_change = r.model_cost_change;
-  }
+  po_export_trace(G->st, G->trace.data(), trace, cap, len);      // (a graph without edges: its state is all zero, no records)
   return SLSLAM_OK;
 }
 
