@@ -137,6 +137,14 @@ typedef struct slslam_solver_options {
                                            slslam_pinned_register - else from a pinned staging copy the host threads make), with the host
                                            packer as the fallback; -1 = always the host packer (lba_pack.cpp, options.host_threads
                                            threads).  Same layout, same solved bytes either way                                          */
+  double po_huber_delta;                /* pose graph only: 0 (default) = no loss function, the reference as it ships (robustify = false,
+                                           src/po_problem.cpp:27); a > 0 = ceres::HuberLoss(a) on every edge, the other arm of the same
+                                           switch (src/po_problem.cpp:55: robustify ? new HuberLoss(0.001) : NULL) - the reference's value
+                                           is 0.001.  With s = |Te|^2 of an edge: s <= a^2 leaves the block alone, otherwise its residuals
+                                           and both Jacobian blocks are scaled by sqrt(a / sqrt(s)) (Ceres 1.7's corrector for rho'' <= 0)
+                                           and its cost is (2 a sqrt(s) - a^2) / 2.  For graphs whose loop closures may be false matches:
+                                           one wrong edge wrecks the unweighted solve.  Negative or not finite:
+                                           SLSLAM_ERR_INVALID_ARGUMENT.  Last field: the offsets of the others did not move              */
 } slslam_solver_options;
 
 /* Fills every field with the configuration the reference runs (robust loss on, 10 iterations). */
@@ -350,9 +358,18 @@ typedef struct slslam_po_graph {
 
 /* Replaces: POProblem::build + POProblem::set_options + ceres::Solve
  * (reference src/slam.cpp:1283-1293).  Synchronous; parameters solved in place.
- * opt->huber_delta and opt->baseline are ignored (no loss function: src/po_problem.cpp:27,55). */
+ * opt->huber_delta (the LBA loss) and opt->baseline are ignored; the edges' loss is opt->po_huber_delta, 0 by default
+ * (robustify ? new HuberLoss(0.001) : NULL with robustify = false: src/po_problem.cpp:27,55). */
 int slslam_po_solve(const slslam_po_graph* graph, const slslam_solver_options* opt,
                     slslam_summary* summary, slslam_iteration* trace, int trace_cap, int* trace_len);
+
+/* Per-edge report at graph->parameters - which slslam_po_solve has just updated in place -: sq_norm[e] = |Te|^2 of edge e (its six
+ * residuals, src/po_problem.h:74-105) and weight[e] = rho'(sq_norm[e]) under ceres::HuberLoss(po_huber_delta), the loss of
+ * src/po_problem.cpp:27,55: 1 for an inlier (sq_norm <= delta^2) and whenever po_huber_delta is 0, else delta / sqrt(sq_norm).  The edge
+ * with the smallest weight is the loop closure to drop.  sq_norm, weight: [num_edges] host arrays, either may be NULL.  Synchronous;
+ * validates as slslam_po_solve does (SLSLAM_ERR_INVALID_ARGUMENT also for a negative or non-finite po_huber_delta), then needs a
+ * device (SLSLAM_ERR_NO_DEVICE). */
+int slslam_po_edge_report(const slslam_po_graph* graph, double po_huber_delta, double* sq_norm, double* weight);
 
 /* The symbolic analysis behind the structured pose-graph factorisation (host only, no device needed), for
  * inspection and tests: slot[N] = offset of each pose in the reduced vector (-1: the constant pose of edge 0 or a
@@ -379,7 +396,7 @@ void slslam_po_batch_destroy(slslam_po_batch* b);
 /* Copies the graph's arrays and runs slslam_po_solve's validation (SLSLAM_ERR_INVALID_ARGUMENT, nothing added) and symbolic
  * analysis (slslam_po_structure).  Returns the graph's index in *index.  SLSLAM_ERR_STATE after finalize. */
 int  slslam_po_batch_add(slslam_po_batch* b, const slslam_po_graph* graph, int* index);
-/* One options struct for every graph, as for slslam_po_solve (huber_delta, baseline ignored); po_dense_factor = 1 or
+/* One options struct for every graph, as for slslam_po_solve (huber_delta, baseline ignored; po_huber_delta honoured and checked); po_dense_factor = 1 or
  * po_factor_fp32 = 1: SLSLAM_ERR_UNSUPPORTED.  Allocates and uploads.  Device memory per graph of n = 6 x (free poses) unknowns
  * with nj of them on junction poses: the n x ld normal matrix plus the nj x ld junction factor in doubles, ld = n rounded up to 8,
  * plus 8 (about 20 MB for a 260-pose graph with 8 loop closures), and a few vectors.  A failed allocation returns SLSLAM_ERR_HIP
@@ -398,6 +415,10 @@ int  slslam_po_batch_download(slslam_po_batch* b, void* stream);
 int  slslam_po_batch_get_parameters(const slslam_po_batch* b, int index, double* parameters);
 int  slslam_po_batch_get_summary(const slslam_po_batch* b, int index, slslam_summary* summary);
 int  slslam_po_batch_get_trace(const slslam_po_batch* b, int index, slslam_iteration* trace, int trace_cap, int* trace_len);
+/* slslam_po_edge_report for the graph, in the same states as slslam_po_batch_get_parameters and at the parameters it returns (a graph
+ * whose solve ended in NUMERICAL_FAILURE: its untouched ones), under the po_huber_delta the batch was finalized with (the loss of
+ * src/po_problem.cpp:27,55).  download computes every graph's report in one launch ahead of its copy.  Either output may be NULL. */
+int  slslam_po_batch_get_edge_report(const slslam_po_batch* b, int index, double* sq_norm, double* weight);
 
 /* ------------------------------------------------------------------ RANSAC hypothesis scoring
  * (the per-frame cost centre next to the hot path.)

@@ -37,7 +37,8 @@ class SolverOptions(C.Structure):
                 ("jacobi_scaling", C.c_int), ("use_graph", C.c_int), ("chunks_per_window", C.c_int),
                 ("reuse_elimination", C.c_int), ("po_factor_fp32", C.c_int), ("po_dense_factor", C.c_int), ("lba_fused_motion_only", C.c_int),
                 ("lba_elimination", C.c_int), ("lba_keep_jacobian", C.c_int), ("refill_headroom_percent", C.c_int),
-                ("host_threads", C.c_int), ("reproducible", C.c_int), ("lba_precision", C.c_int), ("device_build", C.c_int)]
+                ("host_threads", C.c_int), ("reproducible", C.c_int), ("lba_precision", C.c_int), ("device_build", C.c_int),
+                ("po_huber_delta", C.c_double)]
 
 
 class Summary(C.Structure):
@@ -97,7 +98,7 @@ EXPORTS = [
     "slslam_lba_batch_get_parameters", "slslam_lba_batch_get_summary",
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
-    "slslam_po_solve", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -172,6 +173,8 @@ def lib():
     L.slslam_po_batch_get_parameters.argtypes = [vp, C.c_int, dp]
     L.slslam_po_batch_get_summary.argtypes = [vp, C.c_int, C.POINTER(Summary)]
     L.slslam_po_batch_get_trace.argtypes = [vp, C.c_int, C.POINTER(Iteration), C.c_int, ip]
+    L.slslam_po_edge_report.argtypes = [C.POINTER(POGraph), C.c_double, dp, dp]
+    L.slslam_po_batch_get_edge_report.argtypes = [vp, C.c_int, dp, dp]
     L.slslam_ransac_score.argtypes = [C.POINTER(RansacFrame), C.c_double, C.c_double, ip, C.POINTER(C.c_ulonglong)]
     L.slslam_po_structure.argtypes = [C.POINTER(POGraph), ip, C.c_int, ip, ip, ip, ip, ip, ip, ip]
     L.slslam_ransac_generate.argtypes = [C.POINTER(RansacTrials), C.c_double, dp, ip]
@@ -620,6 +623,16 @@ def po_solve(g, params=None, trace_cap=64, **opt):
     return x, _summary_dict(s), _trace_list(tr, min(n.value, trace_cap))
 
 
+def po_edge_report(g, params=None, po_huber_delta=0.0):
+    """Per-edge (sq_norm, weight) at the graph's parameters (slslam_po_edge_report): |Te|^2 of every edge and the weight rho' that
+    HuberLoss(po_huber_delta) gives it (1 for inliers and without a loss); the smallest weight marks the loop closure to drop."""
+    i1, i2, cons, x = _po_arrays(g, params)
+    cg = POGraph(int(g["num_poses"]), len(i1), _ip(i1), _ip(i2), _dp(cons), _dp(x))
+    sq, wt = np.zeros(len(i1)), np.zeros(len(i1))
+    _check(lib().slslam_po_edge_report(C.byref(cg), float(po_huber_delta), _dp(sq), _dp(wt)), "slslam_po_edge_report")
+    return sq, wt
+
+
 def _po_arrays(g, params=None):
     i1 = np.ascontiguousarray(g["pose_index_1"], dtype=np.int32)
     i2 = np.ascontiguousarray(g["pose_index_2"], dtype=np.int32)
@@ -638,6 +651,7 @@ class POBatch:
         self._h = C.c_void_p()
         _check(lib().slslam_po_batch_create(int(device), C.byref(self._h)), "slslam_po_batch_create")
         self._n = []
+        self._e = []
 
     def add(self, g, params=None):
         i1, i2, cons, x = _po_arrays(g, params)
@@ -645,6 +659,7 @@ class POBatch:
         idx = C.c_int(-1)
         _check(lib().slslam_po_batch_add(self._h, C.byref(cg), C.byref(idx)), "slslam_po_batch_add")
         self._n.append(int(g["num_poses"]))
+        self._e.append(len(i1))
         return idx.value
 
     def __len__(self):
@@ -667,6 +682,12 @@ class POBatch:
         out = np.zeros(6 * self._n[i])
         _check(lib().slslam_po_batch_get_parameters(self._h, int(i), _dp(out)), "slslam_po_batch_get_parameters")
         return out
+
+    def edge_report(self, i):
+        """(sq_norm, weight) of graph i's edges at its returned parameters, under the batch's po_huber_delta."""
+        sq, wt = np.zeros(self._e[i]), np.zeros(self._e[i])
+        _check(lib().slslam_po_batch_get_edge_report(self._h, int(i), _dp(sq), _dp(wt)), "slslam_po_batch_get_edge_report")
+        return sq, wt
 
     def summary(self, i):
         s = Summary()

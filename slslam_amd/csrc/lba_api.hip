@@ -74,6 +74,7 @@ extern "C" void slslam_default_options(slslam_solver_options* o) {
   o->reproducible = 0;
   o->lba_precision = 0;
   o->device_build = 0;
+  o->po_huber_delta = 0.0;                    // robustify = false, reference src/po_problem.cpp:27
 }
 
 extern "C" void slslam_release_cached_memory(void) { DeviceBlockCache::drop(); }

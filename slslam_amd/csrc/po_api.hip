@@ -179,10 +179,15 @@ bool po_graph_entries_ok(const slslam_po_graph* g, bool values) {
   return true;
 }
 
-// The caller's options (the defaults when there are none) and the numeric policy the kernels take.  false: max_num_iterations out of range.
+// po_huber_delta as the C ABI takes it: 0 (no loss) or a finite positive scale.
+bool po_huber_ok(double delta) { return std::isfinite(delta) && delta >= 0.0; }
+
+// The caller's options (the defaults when there are none) and the numeric policy the kernels take.  false: max_num_iterations out of range
+// or po_huber_delta negative / not finite.  (The edges' loss travels in PoPtrs.huber; Policy.huber_delta is the LBA path's and stays 0.)
 bool po_policy(const slslam_solver_options* opt_in, slslam_solver_options* opt, Policy* pol) {
   if (opt_in) *opt = *opt_in; else slslam_default_options(opt);
   if (opt->max_num_iterations < 0 || opt->max_num_iterations > 100000) return false;
+  if (!po_huber_ok(opt->po_huber_delta)) return false;
   std::memset(pol, 0, sizeof(*pol));
   pol->huber_delta = 0.0; pol->baseline = 0.0;
   pol->initial_radius = opt->initial_trust_region_radius; pol->max_radius = opt->max_trust_region_radius;
@@ -451,6 +456,7 @@ int po_solve_upload(PoSolve& c) {
   p.scal = (double*)(arena + o_scal); p.flags = (int*)(arena + o_flags); p.st = (LMState*)(arena + o_st);
   p.trace = (IterRec*)(arena + o_trace); c.d_chains = (PoChain*)(arena + o_chains);
   p.N = N; p.E = E; p.n = n; p.ld = ld;
+  p.huber = c.opt.po_huber_delta;
   c.pj = p;                                // the junction block as a matrix of its own (same leading dimension)
   c.pj.n = S.nj; c.pj.H = p.H + (size_t)S.n_chain * ld + S.n_chain; c.pj.y = p.y + S.n_chain;
   // the pinned image (kept per calling thread, grown on demand)
@@ -478,6 +484,12 @@ int po_solve_upload(PoSolve& c) {
   return SLSLAM_OK;
 }
 
+// k_po_linearise with the loss (po_huber_delta > 0) or, as before there was one, without
+void po_launch_linearise(const PoSolve& c, int mode) {
+  if (c.p.huber > 0.0) hipLaunchKernelGGL(k_po_linearise<true>, c.g_edges, dim3(64), 0, 0, c.p, mode);
+  else hipLaunchKernelGGL(k_po_linearise<false>, c.g_edges, dim3(64), 0, 0, c.p, mode);
+}
+
 // ---- initial evaluation: cost, gradient, column norms -> Jacobi scale
 int po_solve_enqueue_initial(PoSolve& c) {
   if (po_step_lds_attributes() != hipSuccess) { PO_TRY(hipErrorInvalidValue); }
@@ -491,7 +503,7 @@ int po_solve_enqueue_initial(PoSolve& c) {
     PO_TRY(hipMemsetAsync(p.H, 0, c.hbytes, 0));
     PO_TRY(hipMemsetAsync(p.g, 0, sizeof(double) * c.nn, 0));
   }
-  hipLaunchKernelGGL(k_po_linearise, c.g_edges, dim3(64), 0, 0, p, 0);
+  po_launch_linearise(c, 0);
   hipLaunchKernelGGL(k_po_prepare, dim3(1), dim3(256), 0, 0, p, c.pol, 1);
   return SLSLAM_OK;
 }
@@ -519,7 +531,7 @@ int po_solve_enqueue_iteration(PoSolve& c) {
     PO_TRY(hipMemsetAsync(p.g, 0, sizeof(double) * c.nn, 0));
     PO_TRY(hipMemsetAsync(p.scal, 0, sizeof(double), 0));            // kPoCost
   }
-  hipLaunchKernelGGL(k_po_linearise, c.g_edges, dim3(64), 0, 0, p, 0);
+  po_launch_linearise(c, 0);
   hipLaunchKernelGGL(k_po_prepare, dim3(1), dim3(256), 0, 0, p, c.pol, 0);
   if (c.f32) hipLaunchKernelGGL(k_po_to_f32, dim3(256), dim3(256), 0, 0, p, c.d_Hf);
   c.stamp();
@@ -544,7 +556,7 @@ int po_solve_enqueue_iteration(PoSolve& c) {
   }
   c.stamp();
   hipLaunchKernelGGL(k_po_candidate, dim3(1), dim3(256), 0, 0, p);
-  hipLaunchKernelGGL(k_po_linearise, c.g_edges, dim3(64), 0, 0, p, 1);
+  po_launch_linearise(c, 1);
   hipLaunchKernelGGL(k_po_update, dim3(1), dim3(64), 0, 0, p, c.pol);
   return SLSLAM_OK;
 }
@@ -616,6 +628,41 @@ extern "C" int slslam_po_solve(const slslam_po_graph* g, const slslam_solver_opt
   return po_solve_report(c, summary, trace, trace_cap, trace_len);
 }
 
+
+// Per-edge report at graph->parameters (what a solve has just updated in place): sq_norm[e] = |Te|^2, weight[e] = rho'(s) under
+// HuberLoss(po_huber_delta) - the switch of reference src/po_problem.cpp:27,55.  One launch, one lane per edge.
+extern "C" int slslam_po_edge_report(const slslam_po_graph* g, double po_huber_delta, double* sq_norm, double* weight) {
+  if (!g || !po_graph_arrays_ok(g, true) || !po_huber_ok(po_huber_delta) || !po_graph_entries_ok(g, true)) return SLSLAM_ERR_INVALID_ARGUMENT;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  const int N = g->num_poses, E = g->num_edges;
+  if (E == 0 || (!sq_norm && !weight)) return SLSLAM_OK;
+  PoCarve a;
+  const size_t o_p1 = a.take(sizeof(int) * E), o_p2 = a.take(sizeof(int) * E), o_cons = a.take(sizeof(double) * 6 * E),
+               o_x = a.take(sizeof(double) * 6 * N), up_bytes = a.off, o_out = a.take(sizeof(double) * 2 * E);
+  struct Block {                          // the calling thread's cached device block, handed back on every path
+    char* p = nullptr; size_t bytes = 0; int device = 0;
+    ~Block() { DeviceBlockCache::give_back(p, bytes, device); }
+  } blk;
+  blk.bytes = a.off;
+  PO_TRY(hipGetDevice(&blk.device));
+  PO_TRY(DeviceBlockCache::acquire(blk.bytes, blk.device, &blk.p));
+  std::vector<char> img(up_bytes > sizeof(double) * 2 * E ? up_bytes : sizeof(double) * 2 * E);
+  std::memcpy(img.data() + o_p1, g->pose_index_1, sizeof(int) * E); std::memcpy(img.data() + o_p2, g->pose_index_2, sizeof(int) * E);
+  std::memcpy(img.data() + o_cons, g->constraints, sizeof(double) * 6 * E); std::memcpy(img.data() + o_x, g->parameters, sizeof(double) * 6 * N);
+  PO_TRY(hipMemcpy(blk.p, img.data(), up_bytes, hipMemcpyHostToDevice));
+  PoPtrs p;
+  std::memset(&p, 0, sizeof(p));
+  p.p1 = (const int*)(blk.p + o_p1); p.p2 = (const int*)(blk.p + o_p2); p.cons = (const double*)(blk.p + o_cons);
+  p.N = N; p.E = E; p.huber = po_huber_delta;
+  double* d_out = (double*)(blk.p + o_out);
+  hipLaunchKernelGGL(k_po_edge_report, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, 0, p, (const double*)(blk.p + o_x), d_out, d_out + E);
+  PO_TRY(hipGetLastError());
+  PO_TRY(hipMemcpy(img.data(), d_out, sizeof(double) * 2 * E, hipMemcpyDeviceToHost));
+  if (sq_norm) std::memcpy(sq_norm, img.data(), sizeof(double) * E);
+  if (weight) std::memcpy(weight, img.data() + sizeof(double) * E, sizeof(double) * E);
+  return SLSLAM_OK;
+}
 
 namespace { thread_local int g_last_level1 = 0; }
 /* (inspection, beside slslam_po_structure: how many of the chains it listed - the first ones - are level-1 chains; the rest are the chains

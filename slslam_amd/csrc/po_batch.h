@@ -23,15 +23,27 @@ struct PoBatchGraph {
   double* Lf_j;                             // the junction block's factor: nj rows, leading dimension ld
   double* linv;                             // inverses of its 64 x 64 diagonal blocks
   int n_l1;                                 // unknowns of the level-1 chains (k_po_zero_structured)
+  const double* x0;                         // the poses as added (the edge report of a graph whose solve failed numerically)
+  double* report;                           // [2E] per edge |Te|^2, then rho' (k_pob_edge_report)
 };
 
 __global__ __launch_bounds__(256) void k_pob_zero(const PoBatchGraph* gs, const PoItem* items) {
   const PoItem it = items[blockIdx.x];
   po_zero_structured_body(gs[it.graph].p, gs[it.graph].n_l1, (unsigned)it.local);
 }
+template <bool kRobust>
 __global__ __launch_bounds__(64) void k_pob_linearise(const PoBatchGraph* gs, const PoItem* items, int mode) {
   const PoItem it = items[blockIdx.x];
-  po_linearise_body(gs[it.graph].p, mode, (unsigned)it.local);
+  po_linearise_body<kRobust>(gs[it.graph].p, mode, (unsigned)it.local);
+}
+// every graph's edge report over the linearisation's work list (5 edges per workgroup), at what slslam_po_batch_get_parameters returns:
+// the accepted poses, or the poses as added when the solve ended in a numerical failure
+__global__ __launch_bounds__(64) void k_pob_edge_report(const PoBatchGraph* gs, const PoItem* items) {
+  const PoItem it = items[blockIdx.x];
+  const PoBatchGraph& G = gs[it.graph];
+  const LMState* st = G.p.st;
+  const double* X = st->status == SLSLAM_NUMERICAL_FAILURE ? G.x0 : G.p.x + (long long)st->cur * 6 * G.p.N;
+  po_edge_report_body(G.p, X, G.report, G.report + G.p.E, (unsigned)it.local, 5);
 }
 __global__ __launch_bounds__(256) void k_pob_prepare(const PoBatchGraph* gs, Policy pol, int first) {
   const PoPtrs p = gs[blockIdx.x].p;
@@ -87,19 +99,23 @@ struct slslam_po_batch {
     LMState st{};
     std::vector<IterRec> trace;
     std::vector<double> x;
+    std::vector<double> report;             // [2E] per edge |Te|^2, then rho'
   };
   int device = -1;
   bool finalized = false, have_results = false;
   std::vector<Graph> graphs;
   std::vector<int> active;                  // batch index of each graph the device solves
   Policy pol{};
-  // device arena: [ states | traces | poses ] (what comes back) [ descriptors | work lists | per-graph inputs ] (what reset restores)
-  // [ per-graph work arrays ]
+  double huber = 0.0;                       // po_huber_delta of finalize: HuberLoss on every edge of every graph, 0 = none
+  // device arena: [ states | traces | poses | edge reports ] (what comes back) [ descriptors | work lists | per-graph inputs ] (what reset
+  // restores) [ poses as added ] (uploaded once) [ per-graph work arrays ]
   char* arena = nullptr;
-  char* h_up = nullptr;                     // pinned image of the first two regions, as uploaded at finalize (reset copies it again)
+  char* h_up = nullptr;                     // pinned image of the first three regions, as uploaded at finalize (reset copies the first two again)
   char* h_down = nullptr;                   // pinned landing area of the first region
   size_t up_bytes = 0, down_bytes = 0;
+  size_t init_bytes = 0;                    // what finalize uploads: the image reset restores (up_bytes) and, behind it, what stays as it is
   std::vector<size_t> o_x;                  // per active graph: offset of its poses in the arena
+  std::vector<size_t> o_report;             // ... and of its edge report
   size_t o_trace = 0;
   PoBatchGraph* d_graphs = nullptr;
   PoItem* d_items = nullptr;
@@ -163,6 +179,8 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
   b->o_trace = carve.take(sizeof(IterRec) * kMaxTrace * (size_t)A);
   b->o_x.assign((size_t)A, 0);
   for (int a = 0; a < A; ++a) b->o_x[(size_t)a] = carve.take(sizeof(double) * 12 * (size_t)b->graphs[(size_t)b->active[(size_t)a]].N);
+  b->o_report.assign((size_t)A, 0);
+  for (int a = 0; a < A; ++a) b->o_report[(size_t)a] = carve.take(sizeof(double) * 2 * (size_t)b->graphs[(size_t)b->active[(size_t)a]].E);
   *down_bytes = carve.off;
   // the work lists
   std::vector<PoItem> items;
@@ -212,12 +230,12 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
   put(o_jg, jgraphs.data(), sizeof(int) * jgraphs.size());
   // per graph: the inputs, then (after every graph's inputs) the work arrays
   std::vector<PoBatchGraph> desc((size_t)A);
-  std::vector<size_t> o_in((size_t)A * 8);
+  std::vector<size_t> o_in((size_t)A * 9);     // (the ninth: the poses as added, behind what reset restores)
   const LMState st = po_initial_state(b->pol);
   for (int a = 0; a < A; ++a) {
     const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
     const PoSymbolic& S = G.sym;
-    size_t* o = &o_in[(size_t)a * 8];
+    size_t* o = &o_in[(size_t)a * 9];
     o[0] = carve.take(sizeof(int) * G.E); o[1] = carve.take(sizeof(int) * G.E); o[2] = carve.take(sizeof(int) * G.N); o[3] = carve.take(sizeof(double) * 6 * G.E);
     o[4] = carve.take(sizeof(double) * S.n); o[5] = carve.take(sizeof(PoChain) * (S.chains.size() + 1)); o[6] = carve.take(sizeof(double) * 8); o[7] = carve.take(sizeof(int) * 2);
     if (img) {
@@ -231,10 +249,17 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
     }
   }
   *up_bytes = carve.off;
+  // uploaded once, by finalize: the poses as added, which no kernel writes (the edge report of a graph whose solve failed numerically)
+  for (int a = 0; a < A; ++a) {
+    const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
+    o_in[(size_t)a * 9 + 8] = carve.take(sizeof(double) * 6 * G.N);
+    put(o_in[(size_t)a * 9 + 8], G.x0.data(), sizeof(double) * 6 * G.N);
+  }
+  b->init_bytes = carve.off;
   for (int a = 0; a < A; ++a) {
     const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
     const PoSymbolic& S = G.sym;
-    const size_t* o = &o_in[(size_t)a * 8];
+    const size_t* o = &o_in[(size_t)a * 9];
     const size_t o_H = carve.take(sizeof(double) * (size_t)S.n * S.ld), o_g = carve.take(sizeof(double) * S.n), o_d2 = carve.take(sizeof(double) * S.n),
                  o_y = carve.take(sizeof(double) * S.n), o_linv = carve.take(sizeof(double) * kNB * kNB * (size_t)std::max(S.nblk_j, 1)),
                  o_Lf = carve.take(sizeof(double) * (size_t)std::max(S.nj, 1) * S.ld);
@@ -247,12 +272,15 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
     p.x = (double*)(arena + b->o_x[(size_t)a]); p.st = (LMState*)(arena + o_st) + a; p.trace = (IterRec*)(arena + b->o_trace) + (size_t)kMaxTrace * a;
     p.H = (double*)(arena + o_H); p.g = (double*)(arena + o_g); p.d2 = (double*)(arena + o_d2); p.y = (double*)(arena + o_y);
     p.N = G.N; p.E = G.E; p.n = S.n; p.ld = S.ld;
+    p.huber = b->huber;
     D.pj = p;                               // the junction block as a matrix of its own (same leading dimension)
     D.pj.n = S.nj; D.pj.H = p.H + (size_t)S.n_chain * S.ld + S.n_chain; D.pj.y = p.y + S.n_chain;
     D.chains = (const PoChain*)(arena + o[5]);
     D.Lf_j = (double*)(arena + o_Lf);
     D.linv = (double*)(arena + o_linv);
     D.n_l1 = S.n_l1;
+    D.x0 = (const double*)(arena + o[8]);
+    D.report = (double*)(arena + b->o_report[(size_t)a]);
   }
   put(o_graphs, desc.data(), sizeof(PoBatchGraph) * desc.size());
   if (arena) {
@@ -268,6 +296,7 @@ extern "C" int slslam_po_batch_finalize(slslam_po_batch* b, const slslam_solver_
   slslam_solver_options opt;
   if (!po_policy(opt_in, &opt, &b->pol)) return SLSLAM_ERR_INVALID_ARGUMENT;      // (slslam_po_solve's policy)
   if (opt.po_dense_factor || opt.po_factor_fp32) return SLSLAM_ERR_UNSUPPORTED;      // the structured fp64 factorisation only
+  b->huber = opt.po_huber_delta;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
   if (b->device < 0) { if (hipGetDevice(&b->device) != hipSuccess) return SLSLAM_ERR_NO_DEVICE; }
@@ -283,12 +312,12 @@ extern "C" int slslam_po_batch_finalize(slslam_po_batch* b, const slslam_solver_
     po_batch_layout(b, nullptr, &up, &down, &total);
     hipError_t e = hipFuncSetAttribute((const void*)k_pob_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStepLds);
     if (e == hipSuccess) e = hipMalloc((void**)&b->arena, total);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_up, up, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_up, b->init_bytes, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_down, down, hipHostMallocDefault);
     if (e == hipSuccess) {
-      std::memset(b->h_up, 0, up);
+      std::memset(b->h_up, 0, b->init_bytes);
       po_batch_layout(b, b->arena, &b->up_bytes, &b->down_bytes, &total);
-      e = hipMemcpy(b->arena, b->h_up, b->up_bytes, hipMemcpyHostToDevice);
+      e = hipMemcpy(b->arena, b->h_up, b->init_bytes, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
       std::fprintf(stderr, "slslam: slslam_po_batch_finalize: %s (%zu bytes of device memory)\n", hipGetErrorString(e), total);
@@ -322,9 +351,13 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
   const PoBatchGraph* gs = b->d_graphs;
   const PoItem* items = b->d_items;
   const Policy pol = b->pol;
+  auto linearise = [&](int mode) {          // with the loss (po_huber_delta > 0) or, as before there was one, without
+    if (b->huber > 0.0) hipLaunchKernelGGL(k_pob_linearise<true>, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, gs, items + b->edge_off, mode);
+    else hipLaunchKernelGGL(k_pob_linearise<false>, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, gs, items + b->edge_off, mode);
+  };
   auto zero_and_linearise = [&]() {
     hipLaunchKernelGGL(k_pob_zero, dim3((unsigned)b->zero_cnt), dim3(256), 0, s, gs, items + b->zero_off);
-    hipLaunchKernelGGL(k_pob_linearise, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, gs, items + b->edge_off, 0);
+    linearise(0);
   };
   // initial evaluation: cost, gradient, column norms -> Jacobi scale
   zero_and_linearise();
@@ -360,7 +393,7 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
       if (b->level_cnt[lv] > 0)
         hipLaunchKernelGGL(k_pob_chain_backsub, dim3((unsigned)b->level_cnt[lv]), dim3(64), 0, s, gs, items + b->level_off[lv]);
     hipLaunchKernelGGL(k_pob_candidate, dim3((unsigned)A), dim3(256), 0, s, gs);
-    hipLaunchKernelGGL(k_pob_linearise, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, gs, items + b->edge_off, 1);
+    linearise(1);
     hipLaunchKernelGGL(k_pob_update, dim3((unsigned)A), dim3(64), 0, s, gs, pol);
   }
   PO_TRY(hipGetLastError());
@@ -374,6 +407,9 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
   if (A > 0) {
     PO_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
+    // every graph's edge report (slslam_po_batch_get_edge_report), at the batch's own po_huber_delta, in one launch ahead of the copy
+    hipLaunchKernelGGL(k_pob_edge_report, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, (const PoBatchGraph*)b->d_graphs, (const PoItem*)(b->d_items + b->edge_off));
+    PO_TRY(hipGetLastError());
     PO_TRY(hipMemcpyAsync(b->h_down, b->arena, b->down_bytes, hipMemcpyDeviceToHost, s));
     PO_TRY(hipStreamSynchronize(s));
   }
@@ -386,6 +422,8 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
       std::memcpy(G.trace.data(), b->h_down + b->o_trace + sizeof(IterRec) * kMaxTrace * (size_t)a, sizeof(IterRec) * kMaxTrace);
       G.x.resize((size_t)6 * G.N);
       std::memcpy(G.x.data(), b->h_down + b->o_x[(size_t)a] + sizeof(double) * 6 * G.N * (size_t)G.st.cur, sizeof(double) * 6 * G.N);
+      G.report.resize((size_t)2 * G.E);
+      std::memcpy(G.report.data(), b->h_down + b->o_report[(size_t)a], sizeof(double) * 2 * (size_t)G.E);
       steps = std::max(steps, G.st.n_success + G.st.n_unsuccess);
     }
   } catch (const std::bad_alloc&) {
@@ -413,6 +451,16 @@ extern "C" int slslam_po_batch_get_parameters(const slslam_po_batch* b, int inde
   // a numerical failure leaves the parameters untouched (slslam_po_solve)
   const bool solved = G->active >= 0 && po_termination(&G->st) != SLSLAM_NUMERICAL_FAILURE;
   if (G->N > 0) std::memcpy(parameters, solved ? G->x.data() : G->x0.data(), sizeof(double) * 6 * (size_t)G->N);
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_po_batch_get_edge_report(const slslam_po_batch* b, int index, double* sq_norm, double* weight) {
+  const slslam_po_batch::Graph* G = nullptr;
+  const int rc = po_batch_graph(b, index, &G);
+  if (rc != SLSLAM_OK) return rc;
+  const size_t E = (size_t)G->E;             // (a graph without edges: nothing to report)
+  if (sq_norm && E) std::memcpy(sq_norm, G->report.data(), sizeof(double) * E);
+  if (weight && E) std::memcpy(weight, G->report.data() + E, sizeof(double) * E);
   return SLSLAM_OK;
 }
 

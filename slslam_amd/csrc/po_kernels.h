@@ -3,7 +3,8 @@
 // What this replaces: ceres::Solve on the problem POProblem::build wires up (reference
 // src/po_problem.cpp:40-77, call site src/slam.cpp:1283-1293): one <6,6,6> residual block per edge,
 // Te = T2^-1 * (C * T1) in (angle-axis, translation) form (src/po_problem.h:68-108), pose1 of
-// edge 0 constant, no loss function, SPARSE_NORMAL_CHOLESKY.
+// edge 0 constant, SPARSE_NORMAL_CHOLESKY; the loss of src/po_problem.cpp:27,55 (robustify ? new HuberLoss(0.001) : NULL, shipped off)
+// is slslam_solver_options.po_huber_delta: off by default, applied by k_po_linearise<true> where the residual blocks are formed.
 //
 //   k_po_linearise   lane <-> (edge, seed direction): the templated SE(3) functor is evaluated on
 //                    a one-direction dual number per lane (12 lanes = the 12 columns of [J1|J2]),
@@ -17,6 +18,7 @@
 //   k_po_trisolve    forward / backward substitution
 //   k_po_candidate   x+ = x - scale*y and the step statistics;  k_po_cost  cost at x+
 //   k_po_update      trust-region bookkeeping (same policy as the LBA path)
+//   k_po_edge_report per-edge |Te|^2 and Huber weight at the solution (slslam_po_edge_report)
 #ifndef SLSLAM_PO_KERNELS_H_
 #define SLSLAM_PO_KERNELS_H_
 
@@ -144,14 +146,33 @@ struct PoPtrs {
   LMState* st;
   IterRec* trace;
   int N, E, n, ld;
+  double huber;                      // po_huber_delta: HuberLoss(huber) on every edge; <= 0: no loss (k_po_linearise<false>)
 };
 enum { kPoCost = 0, kPoCandCost = 1, kPoModel = 2, kPoDn2 = 3, kPoXn2 = 4, kPoFixed = 5 };
 
 #ifndef SLSLAM_PO_FACTOR_ONLY    // (lba_api.hip includes this header for the blocked Cholesky kernels only: lba_big.h)
+// ceres::HuberLoss(a) on one edge - the switch the reference has and ships off (robustify ? new HuberLoss(0.001) : NULL, reference
+// src/po_problem.cpp:27,55) - with Ceres 1.7's corrector for rho'' <= 0, as huber_scale (lba_math.h) applies it to line blocks:
+// s = |Te|^2 -> sqrt(rho'), the factor of the six residuals and of both 6 x 6 Jacobian blocks, and the block cost rho / 2.
+// The test comes before any division by sqrt(s): a consistent graph has s == 0 exactly.
+__device__ __forceinline__ double po_huber_scale(double s, double a, double* cost) {
+  if (s > a * a) {
+    const double r = sqrt(s);
+    *cost = 0.5 * (2.0 * a * r - a * a);
+    return sqrt(a / r);
+  }
+  *cost = 0.5 * s;
+  return 1.0;
+}
+
 // lane <-> (edge, column of [J1|J2]); 5 edges per wave.
 // mode 0: accumulate H, g, cost at the accepted point (scaled columns)
 // mode 1: cost only at the candidate point
+// kRobust: the Huber loss of p.huber > 0 on every block - residuals and Jacobian columns scaled by sqrt(rho'), block cost rho / 2 (both
+// modes and the fixed cost).  Every lane of an edge holds all six Te[q].v, so s takes no cross-lane traffic; what consumes the blocks
+// (Jacobi scale, damping, gradient, model cost change) sees scaled blocks and is unchanged.  kRobust = false is the code as it was.
 // (the bodies below take their workgroup's index as an argument: the batched kernels of po_batch.hip map it from a work list)
+template <bool kRobust>
 __device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned blk) {
   const LMState* st = p.st;
   if (st->status != kRunning) return;
@@ -170,7 +191,15 @@ __device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned b
       for (int i = 0; i < 6; ++i) { T1[i] = X[6 * a + i]; T2[i] = X[6 * b + i]; C[i] = p.cons[6 * es + i]; }
       pose_constraint_error<double>(T1, T2, C, Te);
       const bool kept = p.slot[a] >= 0 || p.slot[b] >= 0;
-      if (kept) for (int i = 0; i < 6; ++i) cost += 0.5 * Te[i] * Te[i];
+      if (kRobust) {
+        double s = 0.0;
+        for (int i = 0; i < 6; ++i) s += Te[i] * Te[i];
+        double c;
+        po_huber_scale(s, p.huber, &c);
+        if (kept) cost += c;
+      } else {
+        if (kept) for (int i = 0; i < 6; ++i) cost += 0.5 * Te[i] * Te[i];
+      }
     }
     for (int o = 32; o > 0; o >>= 1) cost += __shfl_xor(cost, o);
     if (lane == 0) atomicAdd(&p.scal[kPoCandCost], cost);
@@ -183,6 +212,13 @@ __device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned b
     C[i] = mk(p.cons[6 * es + i]);
   }
   pose_constraint_error<Dual>(T1, T2, C, Te);
+  double block_cost = 0.0;
+  if (kRobust) {
+    double s = 0.0;
+    for (int q = 0; q < 6; ++q) s += Te[q].v * Te[q].v;
+    const double w = po_huber_scale(s, p.huber, &block_cost);
+    for (int q = 0; q < 6; ++q) { Te[q].v *= w; Te[q].d *= w; }
+  }
   const int sa = p.slot[a], sb = p.slot[b];
   const int my = d < 6 ? (sa >= 0 ? sa + d : -1) : (sb >= 0 ? sb + d - 6 : -1);
   const bool kept = sa >= 0 || sb >= 0;
@@ -198,14 +234,35 @@ __device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned b
   }
   if (ok && my >= 0) atomicAdd(&p.g[my], gsum);
   if (ok && d == 0) {
-    double c = 0.0;
-    for (int q = 0; q < 6; ++q) c += 0.5 * Te[q].v * Te[q].v;
+    double c = block_cost;
+    if (!kRobust) for (int q = 0; q < 6; ++q) c += 0.5 * Te[q].v * Te[q].v;
     if (kept) cost = c; else atomicAdd(&p.scal[kPoFixed], c);
   }
   for (int o = 32; o > 0; o >>= 1) cost += __shfl_xor(cost, o);
   if (lane == 0) atomicAdd(&p.scal[kPoCost], cost);
 }
-__global__ __launch_bounds__(64) void k_po_linearise(PoPtrs p, int mode) { po_linearise_body(p, mode, blockIdx.x); }
+template <bool kRobust>
+__global__ __launch_bounds__(64) void k_po_linearise(PoPtrs p, int mode) { po_linearise_body<kRobust>(p, mode, blockIdx.x); }
+
+// Per-edge report at the poses X: sq[e] = |Te|^2 and wt[e] = rho'(s), the weight the loss of p.huber gives the edge (1 for an inlier and
+// whenever there is no loss) - what tells the caller which loop closure to drop.  One lane per edge, `per_block` edges per workgroup
+// (the batched launch reuses the linearisation's work list: 5); nothing is summed, so no atomics.
+__device__ __forceinline__ void po_edge_report_body(const PoPtrs& p, const double* X, double* sq, double* wt, unsigned blk, int per_block) {
+  const int lane = threadIdx.x;
+  const int e = blk * per_block + lane;
+  if (lane >= per_block || e >= p.E) return;
+  const int a = p.p1[e], b = p.p2[e];
+  double T1[6], T2[6], C[6], Te[6];
+  for (int i = 0; i < 6; ++i) { T1[i] = X[6 * a + i]; T2[i] = X[6 * b + i]; C[i] = p.cons[6 * e + i]; }
+  pose_constraint_error<double>(T1, T2, C, Te);
+  double s = 0.0;
+  for (int i = 0; i < 6; ++i) s += Te[i] * Te[i];
+  sq[e] = s;
+  wt[e] = (p.huber > 0.0 && s > p.huber * p.huber) ? p.huber / sqrt(s) : 1.0;
+}
+__global__ __launch_bounds__(64) void k_po_edge_report(PoPtrs p, const double* X, double* sq, double* wt) {
+  po_edge_report_body(p, X, sq, wt, blockIdx.x, 64);
+}
 
 // Structured factorisation only: zeroes what the linearisation is about to add into - the lower-triangle entries of every edge's two
 // pose blocks and their coupling (the same index rule as k_po_linearise), the junction block (the dense factorisation reads all of it),

@@ -74,6 +74,10 @@ class POProblem {
   // the back-end needs the count to size the dense system, so by default it is inferred as
   // 1 + max pose index over the edges; a caller with trailing unreferenced poses may set it.
   inline void set_num_poses(int n)        { num_poses_ = n;      }
+  // robustify is a constructor constant of the reference (false, src/po_problem.cpp:27) that selects the edges' loss at :55
+  // (robustify ? new HuberLoss(0.001) : NULL).  A caller whose loop closures may be false matches switches it on here.
+  inline void set_robustify(bool r)       { robustify = r;       }
+  bool robust() const { return robustify; }
   int num_poses() const;
 
   void build(Problem* problem);

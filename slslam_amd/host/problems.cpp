@@ -177,6 +177,7 @@ void Solve(const Solver::Options& options, Problem* problem, Solver::Summary* su
     g.num_poses = p->num_poses(); g.num_edges = p->num_size();
     g.pose_index_1 = p->pose_index_1(); g.pose_index_2 = p->pose_index_2();
     g.constraints = p->constraints(); g.parameters = p->parameters();
+    o.po_huber_delta = p->robust() ? 0.001 : 0.0;      // robustify ? new HuberLoss(0.001) : NULL  (po_problem.cpp:55)
     rc = slslam_po_solve(&g, &o, &r, nullptr, 0, nullptr);
   }
   s->backend_status = rc;
