@@ -285,6 +285,42 @@ int  slslam_lba_batch_window_chunks(const slslam_lba_batch* b, int index, int* n
 int  slslam_lba_batch_set_profiling(slslam_lba_batch* b, int enable);
 int  slslam_lba_batch_kernel_times(const slslam_lba_batch* b, double ms[8], int launches[8]);
 
+/* ---- posterior covariances of solved windows (csrc/lba_covariance.h).
+ * Replaces nothing in the reference - its odometry edges are identity-weighted -; the Ceres counterpart is ceres::Covariance.
+ * For a window at its CURRENT device parameters x (the solved ones after _solve, the initial ones after _finalize / _reset / _refill:
+ * the point slslam_lba_batch_linearise evaluates), with J the Jacobian of all residual blocks w.r.t. the free blocks after the Huber
+ * corrector (huber_delta <= 0: none), without Jacobi scaling or damping, and H = J^T J split into cameras (c) and lines (l):
+ *   S = H_cc - sum_lines H_cl H_ll^-1 H_lc,  cov_cameras = S^-1 (the joint covariance of all free cameras, cross blocks included),
+ *   cov_lines[l] = H_ll^-1 + K S^-1 K^T with K = H_ll^-1 H_lc (the line's own 4 x 4 marginal; no line-line or line-camera blocks).
+ * A camera / line is free iff it is observed and no observation flags it constant (the rule of the solve); constant lines add to
+ * H_cc only.  Units are Ceres': unit-variance residuals - multiply by the noise variance.
+ * SLSLAM_COV_SINGULAR: a pivot <= 1e-10 in the Cholesky factorisation of S or of a line's H_ll, each scaled to unit diagonal (a
+ * window without a constant camera has a 6-dimensional gauge null space): every output of that window is zero; the other windows
+ * of the batch are not affected. */
+enum { SLSLAM_COV_OK = 0, SLSLAM_COV_SINGULAR = 1 };
+/* ceres::Covariance::Compute for every window of the batch: enqueues one launch on `stream` and returns.  with_lines = 0 skips the
+ * lines' blocks and their buffer.  Changes nothing the solve reads or writes.  The result buffers are allocated by the first call
+ * (the lines' by the first call that asks for them) and kept: a batch that never asks pays nothing.  Works on refilled batches and,
+ * through slslam_lba_stream_batch, on a stream's.  SLSLAM_ERR_UNSUPPORTED (batch untouched): the batch takes
+ * SLSLAM_PATH_GLOBAL_MEMORY or SLSLAM_PATH_MIXED - the reduced system of such a window (up to 240 x 240) does not fit LDS. */
+int  slslam_lba_batch_covariance(slslam_lba_batch* b, void* stream, int with_lines);
+/* ceres::Covariance::GetCovarianceBlock, after slslam_lba_batch_download / _wait (which bring the covariances enqueued since the last
+ * download back with the other results): *status = SLSLAM_COV_*; *num_free_cameras = F; free_camera[C]: the free cameras' caller
+ * indices, ascending, in [0, F), -1 behind; cov_cameras[(6F)^2] row-major, block order = free_camera[]; cov_lines[16 L]: row-major
+ * 4 x 4 per caller line index, zeros for constant or unobserved lines.  Any output pointer may be NULL.
+ * SLSLAM_ERR_INVALID_ARGUMENT: the last slslam_lba_batch_covariance call has not been downloaded - none was made, a newer one is
+ * still on the device, or a refill has replaced the windows since;
+ * SLSLAM_ERR_STATE: cov_lines asked for, but the downloaded call had with_lines = 0; a window a device-built refill flagged
+ * returns that window's error, as slslam_lba_batch_get_parameters does. */
+int  slslam_lba_batch_get_covariance(const slslam_lba_batch* b, int index, int* status, int* num_free_cameras, int* free_camera,
+                                     double* cov_cameras, double* cov_lines);
+/* Since create: slslam_lba_batch_covariance calls, and the device / host buffers they allocated.  Any pointer may be NULL. */
+int  slslam_lba_batch_covariance_stats(const slslam_lba_batch* b, long long* calls, long long* allocations);
+/* ceres::Covariance for ONE window, no solve: the covariance at window->parameters (validates as slslam_lba_solve does, then needs
+ * a device).  opt: huber_delta and baseline are what matters (NULL = slslam_default_options).  cov_lines = NULL skips the lines. */
+int  slslam_lba_covariance(const slslam_lba_window* window, const slslam_solver_options* opt, int* status, int* num_free_cameras,
+                           int* free_camera, double* cov_cameras, double* cov_lines);
+
 /* Test hook: evaluate residuals / Jacobians (after the Huber corrector, before Jacobi scaling)
  * of window `index` at its CURRENT device parameters, returned in the caller's observation order:
  * residuals[4M], j_cam[24M] (row-major 4x6), j_line[16M] (row-major 4x4), cost[1]. */

@@ -79,6 +79,7 @@ class PoseEstimate(C.Structure):
 
 
 POSE_STATUS = {0: "OK", 1: "TOO_FEW_FEATURES", 2: "RANSAC_FAILED"}
+COV_OK, COV_SINGULAR = 0, 1
 
 
 class POGraph(C.Structure):
@@ -98,6 +99,7 @@ EXPORTS = [
     "slslam_lba_batch_get_parameters", "slslam_lba_batch_get_summary",
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
+    "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
     "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -160,6 +162,10 @@ def lib():
     L.slslam_lba_batch_set_profiling.argtypes = [vp, C.c_int]
     L.slslam_lba_batch_kernel_times.argtypes = [vp, dp, ip]
     L.slslam_lba_batch_linearise.argtypes = [vp, C.c_int, dp, dp, dp, dp]
+    L.slslam_lba_batch_covariance.argtypes = [vp, vp, C.c_int]
+    L.slslam_lba_batch_get_covariance.argtypes = [vp, C.c_int, ip, ip, ip, dp, dp]
+    L.slslam_lba_batch_covariance_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+    L.slslam_lba_covariance.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), ip, ip, ip, dp, dp]
     L.slslam_po_solve.argtypes = [C.POINTER(POGraph), C.POINTER(SolverOptions), C.POINTER(Summary),
                                   C.POINTER(Iteration), C.c_int, ip]
     L.slslam_po_batch_create.argtypes = [C.c_int, C.POINTER(vp)]
@@ -304,6 +310,26 @@ class _WindowArrays:
                            _ip(self.fixed), _dp(self.obs), _dp(self.params))
 
 
+def _cov_result(fn, where, num_cameras, num_lines, with_lines):
+    """Calls fn(status, F, free_camera, cov_cameras, cov_lines) and trims the outputs to the window's free cameras."""
+    st, nf = C.c_int(-1), C.c_int(0)
+    free = np.full(max(num_cameras, 1), -1, dtype=np.int32)
+    cc = np.zeros(36 * num_cameras * num_cameras)
+    cl = np.zeros((num_lines, 4, 4)) if with_lines else None
+    _check(fn(C.byref(st), C.byref(nf), _ip(free), _dp(cc), _dp(cl) if with_lines else None), where)
+    n = 6 * nf.value
+    return st.value, free[:nf.value].copy(), cc[:n * n].reshape(n, n).copy(), cl
+
+
+def lba_covariance(w, params=None, with_lines=True, **opt):
+    """Posterior covariance of one window at its parameters, no solve (slslam_lba_covariance; Ceres: ceres::Covariance).
+    Returns (status, free_camera, cov_cameras[6F, 6F], cov_lines[L, 4, 4] or None)."""
+    arr = _WindowArrays(w, params)
+    o = default_options(**opt)
+    return _cov_result(lambda *a: lib().slslam_lba_covariance(C.byref(arr.c), C.byref(o), *a), "slslam_lba_covariance",
+                       int(w["num_cameras"]), int(w["num_lines"]), with_lines)
+
+
 def lba_solve(w, params=None, trace_cap=64, **opt):
     """One window through slslam_lba_solve (LBAProblem::build + set_options + ceres::Solve).
     Returns (solved parameters, summary dict, trace list)."""
@@ -429,6 +455,23 @@ class LBABatch:
         n = np.zeros(8, dtype=np.int32)
         _check(lib().slslam_lba_batch_kernel_times(self._h, _dp(ms), _ip(n)), "slslam_lba_batch_kernel_times")
         return {KERNEL_FAMILIES[i]: (float(ms[i]), int(n[i])) for i in range(8)}
+
+    def covariance(self, stream=None, with_lines=True):
+        """Enqueues the posterior covariances of every window at its current device parameters (slslam_lba_batch_covariance);
+        download() brings them back."""
+        _check(lib().slslam_lba_batch_covariance(self._h, C.c_void_p(stream or 0), int(bool(with_lines))), "slslam_lba_batch_covariance")
+        self._cov_lines = bool(with_lines)
+
+    def get_covariance(self, i):
+        """(status, free_camera, cov_cameras[6F, 6F], cov_lines[L, 4, 4] or None) of window i, after download()."""
+        c, l = self.sizes[i]
+        return _cov_result(lambda *a: lib().slslam_lba_batch_get_covariance(self._h, int(i), *a), "slslam_lba_batch_get_covariance",
+                           c, l, getattr(self, "_cov_lines", False))
+
+    def covariance_stats(self):
+        v = [C.c_longlong(0) for _ in range(2)]
+        _check(lib().slslam_lba_batch_covariance_stats(self._h, *[C.byref(x) for x in v]), "slslam_lba_batch_covariance_stats")
+        return dict(zip(["calls", "allocations"], [x.value for x in v]))
 
     def linearise(self, i, num_observations):
         m = int(num_observations)

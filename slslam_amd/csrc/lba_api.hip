@@ -21,6 +21,7 @@
 #include "lba_big_solve.h"
 #include "device_cache.h"
 #include "lba_motion_only.h"
+#include "lba_covariance.h"
 #include "lba_pack.h"
 #include "lba_device_build.h"
 #include "lba_resident.h"
@@ -346,6 +347,15 @@ struct slslam_lba_batch {
   hipEvent_t part_fork = nullptr, part_join = nullptr;
   DevBuf<double> d_part_out[2];
   int num_windows() const { return part[0] ? (int)route.size() : (int)wins.size(); }
+  // posterior covariances (lba_covariance.h): buffers made by the first slslam_lba_batch_covariance call and kept
+  DevBuf<int> d_cov_hdr; DevBuf<double> d_cov_cam, d_cov_line;
+  HostArr<int> h_cov_hdr; HostArr<double> h_cov_cam, h_cov_line;
+  long long cov_cam_stride = 0;
+  // where the result of the LAST slslam_lba_batch_covariance call is: enqueued on the device, part of the download under way, on the host
+  enum CovState { COV_NONE, COV_ENQUEUED, COV_COPYING, COV_READY };
+  CovState cov_state = COV_NONE;
+  bool cov_lines = false;                                // ... and whether that call asked for the lines' blocks
+  long long cov_calls = 0, cov_allocations = 0;
   // profiling
   bool profiling = false;
   double fam_ms[FAM_N] = { 0 };
@@ -1535,6 +1545,15 @@ int download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
     HIP_TRY(hipMemcpyAsync(b->h_buildwin.data(), b->d_buildwin.p, b->wins.size() * sizeof(BuildWin), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(b->h_totals.data(), b->d_totals.p, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
   }
+  if (b->cov_state == slslam_lba_batch::COV_ENQUEUED) {
+    // the covariances enqueued since the last download come back with it
+    const size_t B = b->wins.size();
+    HIP_TRY(hipMemcpyAsync(b->h_cov_hdr.data(), b->d_cov_hdr.p, B * kCovHdr * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_cov_cam.data(), b->d_cov_cam.p, B * (size_t)b->cov_cam_stride * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (b->cov_lines && b->h_cov_line.size() > 0)
+      HIP_TRY(hipMemcpyAsync(b->h_cov_line.data(), b->d_cov_line.p, b->h_cov_line.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    b->cov_state = slslam_lba_batch::COV_COPYING;
+  }
   if (!b->ev_results) HIP_TRY(hipEventCreateWithFlags(&b->ev_results, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_results, s));
   b->results_pending = true;
@@ -1563,6 +1582,7 @@ int finish_download(slslam_lba_batch* b) {
   b->results_pending = false;
   if (b->profiling) b->harvest_events();
   adopt_device_build(b);
+  if (b->cov_state == slslam_lba_batch::COV_COPYING) b->cov_state = slslam_lba_batch::COV_READY;
   b->downloaded = true;
   return SLSLAM_OK;
 }
@@ -1932,6 +1952,7 @@ void refill_commit(slslam_lba_batch* b, const slslam_lba_window* windows, int B,
   b->total_params = z.nparams; b->nobs = z.nobs;
   b->used_ncam = z.ncam; b->used_nline = z.nline; b->used_nobs = z.nobs; b->used_tiles = (long long)b->d_tiles.n; b->used_items = (long long)(b->d_items.n / 2);
   b->device_built = true; b->inplace_export = z.params_pinned; b->results_inplace = false;
+  b->cov_state = slslam_lba_batch::COV_NONE;
   b->src_windows.assign(windows, windows + B);
   b->build_status.assign((size_t)B, SLSLAM_OK);
   b->downloaded = false;
@@ -2193,6 +2214,7 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   b->wins.swap(wins);
   b->downloaded = false;
   b->device_built = false; b->inplace_export = false; b->results_inplace = false; b->src_windows.clear(); b->build_status.clear();
+  b->cov_state = slslam_lba_batch::COV_NONE;
   auto fill_one = [&](int wi) { fill_window(b, plan, b->wins, wi, img, /*copy_observations=*/false); };
   (void)run_all(pool, B, fill_one);                      // (fill_window copies into the image: it allocates nothing)
   fill_tail(b, plan, img);
@@ -2385,6 +2407,100 @@ extern "C" int slslam_lba_batch_linearise(slslam_lba_batch* b, int index, double
   if (e == hipSuccess) e = hipMemcpy(cost, dc.p, sizeof(double), hipMemcpyDeviceToHost);
   HIP_TRY(e);
   return SLSLAM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Posterior covariances of the windows at their current device parameters (lba_covariance.h)
+extern "C" int slslam_lba_batch_covariance(slslam_lba_batch* b, void* stream, int with_lines) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized) return SLSLAM_ERR_STATE;
+  if (b->part[0] || b->big_mode) return SLSLAM_ERR_UNSUPPORTED;      // (a 240 x 240 reduced system does not fit LDS)
+  const size_t B = b->wins.size();
+  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
+  if (maxC > kMaxCams || maxn > 6 * kMaxFreeCams) return SLSLAM_ERR_UNSUPPORTED;
+  const size_t lds = lds_bytes_covariance(maxC, maxn);
+  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  ++b->cov_calls;
+  int rc;
+  if (!b->d_cov_hdr.p) {
+    b->cov_cam_stride = std::max<long long>(1, (long long)maxn * maxn);
+    if ((rc = b->d_cov_hdr.alloc(std::max<size_t>(1, B) * kCovHdr)) || (rc = b->d_cov_cam.alloc(std::max<size_t>(1, B) * (size_t)b->cov_cam_stride)) ||
+        (rc = b->h_cov_hdr.alloc(std::max<size_t>(1, B) * kCovHdr, b->refillable)) ||
+        (rc = b->h_cov_cam.alloc(std::max<size_t>(1, B) * (size_t)b->cov_cam_stride, b->refillable))) {
+      b->d_cov_hdr.release();
+      return rc;
+    }
+    b->cov_allocations += 4;
+    // (the kernel's limit is a property of the process, not of this batch: always the ceiling, so that no batch lowers it for another)
+    HIP_TRY(allow_lds({ (const void*)k_lba_covariance }, 160 * 1024));
+  }
+  if (with_lines && !b->d_cov_line.p) {
+    const size_t cap_line = std::max<size_t>(1, b->d_line_flags.n);
+    if ((rc = b->d_cov_line.alloc(16 * cap_line)) || (rc = b->h_cov_line.alloc(16 * cap_line, b->refillable))) { b->d_cov_line.release(); return rc; }
+    b->cov_allocations += 2;
+  }
+  if (B > 0)
+    hipLaunchKernelGGL(k_lba_covariance, dim3((unsigned)B), dim3(kCovThreads), lds, s, b->ptrs, b->pol, (const int*)b->d_line_orig.p, b->d_cov_hdr.p,
+                       b->d_cov_cam.p, b->cov_cam_stride, with_lines ? b->d_cov_line.p : (double*)nullptr, maxC, maxn);
+  HIP_TRY(hipGetLastError());
+  b->cov_state = slslam_lba_batch::COV_ENQUEUED; b->cov_lines = with_lines != 0;
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_lba_batch_covariance_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (calls) *calls = b->cov_calls;
+  if (allocations) *allocations = b->cov_allocations;
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_lba_batch_get_covariance(const slslam_lba_batch* b, int index, int* status, int* num_free_cameras, int* free_camera,
+                                               double* cov_cameras, double* cov_lines) {
+  if (!b || index < 0 || index >= b->num_windows()) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (b->part[0] || b->cov_state != slslam_lba_batch::COV_READY) return SLSLAM_ERR_INVALID_ARGUMENT;      // the last covariance call (if any) has not been downloaded
+  if (b->device_built && b->build_status[(size_t)index] != SLSLAM_OK) return b->build_status[(size_t)index];
+  if (cov_lines && !b->cov_lines) return SLSLAM_ERR_STATE;            // (the call that was downloaded skipped the lines)
+  const WinDesc& wd = b->h_wins[(size_t)index];
+  const int* hdr = b->h_cov_hdr.data() + (size_t)index * kCovHdr;
+  const int F = std::min(std::max(hdr[1], 0), (int)kMaxFreeCams);
+  if (status) *status = hdr[0];
+  if (num_free_cameras) *num_free_cameras = F;
+  if (free_camera) {
+    for (int c = 0; c < wd.C; ++c) free_camera[c] = -1;
+    for (int f = 0; f < F && f < wd.C; ++f) free_camera[f] = hdr[2 + f];
+  }
+  if (cov_cameras && F > 0) std::memcpy(cov_cameras, b->h_cov_cam.data() + (size_t)index * (size_t)b->cov_cam_stride, (size_t)(6 * F) * (6 * F) * sizeof(double));
+  if (cov_lines && wd.L > 0) std::memcpy(cov_lines, b->h_cov_line.data() + 16 * (size_t)wd.line_off, 16 * (size_t)wd.L * sizeof(double));
+  return SLSLAM_OK;
+}
+
+// One window, no solve: the covariance at window->parameters
+extern "C" int slslam_lba_covariance(const slslam_lba_window* w, const slslam_solver_options* opt, int* status, int* num_free_cameras,
+                                     int* free_camera, double* cov_cameras, double* cov_lines) {
+  if (!w) return SLSLAM_ERR_INVALID_ARGUMENT;
+  slslam_solver_options o;
+  if (opt) o = *opt; else slslam_default_options(&o);
+  if (o.max_num_iterations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
+  PackedWindow pw;   // malformed input is reported as such on any machine, before the device is looked for
+  {
+    const int prc = pack_window(w, &pw);
+    if (prc != SLSLAM_OK) return prc;
+  }
+  slslam_lba_batch* b = nullptr;
+  int rc = slslam_lba_batch_create(-1, &b);
+  if (rc) return rc;
+  o.use_graph = 0;
+  o.refill_headroom_percent = 0;
+  b->wins.push_back(std::move(pw));
+  b->arena.cached = true;
+  if ((rc = slslam_lba_batch_finalize(b, &o)) == SLSLAM_OK &&
+      (rc = slslam_lba_batch_covariance(b, nullptr, cov_lines ? 1 : 0)) == SLSLAM_OK &&
+      (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
+    rc = slslam_lba_batch_get_covariance(b, 0, status, num_free_cameras, free_camera, cov_cameras, cov_lines);
+  slslam_lba_batch_destroy(b);
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------------
