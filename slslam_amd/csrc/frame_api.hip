@@ -1,8 +1,8 @@
 // slslam_amd/csrc/frame_api.hip — the per-frame pose estimator (include/slslam_hip.h: slslam_pose_estimator_*).
 //
 // SLAM::pose_estimation (reference src/slam.cpp:244-319) after its merge by feature id, for many frames per call:
-//   RANSAC      generate + score every frame's trials, one launch each (frame index in the grid; bodies of ransac_device.h),
-//               one download of the scores, the adaptive trial loop on the host (ransac_loop.h), best_score starting at -1 (:283)
+//   RANSAC      the library's one RANSAC front (ransac_front.h, compiled in ransac_api.hip) on the estimator's buffers and stream: two
+//               launches for all frames, one download of the scores, the adaptive trial loops on the host, best_score starting at -1 (:283)
 //   pack        k_frame_pack: one wave per solvable frame writes its motion-only window (:590-640) into device memory
 //   solve       the estimator's refillable fused motion-only LBA batch, refilled from those device windows (lba_resident.h)
 //   finish      k_frame_finish: gc_wt_to_Rt of the solved camera (:668-674) and the final inlier set under it (:305-312), with the
@@ -11,35 +11,32 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/slslam_hip.h"
+#include "hip_status.h"
 #include "ransac_device.h"
-#include "ransac_loop.h"
+#include "ransac_front.h"
 #include "gc_convert.h"
 #include "index_word.h"
 #include "lba_resident.h"
 
 using namespace slslam_ransac;
+using slslam::align256;
+using slslam::GrowBuf;
+using slslam::Mem;
 
 namespace {
 
 constexpr int kMaxFeatNum = 5;          // max_feat_num (reference src/parameter.h:25): the fewest common lines / RANSAC inliers accepted
 
-// Per frame, where its inputs and RANSAC work lie (uploaded with the inputs)
-struct FrameDesc {
-  long long o0, o1, ln;                 // doubles: obs0 [8K], obs1 [8K], lines [6K]
-  long long smp;                        // ints: samples [H s]
-  long long hyp;                        // first hypothesis of the frame in poses [12] / valid / scores
-  long long bits;                       // first 64-bit word of the frame's hypothesis inlier bits ([H words])
-  long long outb;                       // first word of the frame's bits in the result block (RANSAC winner, then final set: 2 words each)
-  int H, K, s, words;                   // trials scored (<= max_trials + 1), common lines, sample size, (K + 63) / 64
-};
 // Per frame, what the trial loop decided (uploaded after it)
-struct FramePlan { int best_h, slot; };
+struct FramePlan {
+  int best_h, slot;
+  long long outb;                       // first word of the frame's bits in the result block (RANSAC winner, then final set: words each)
+};
 // Per slot of the batch: its frame (-1: a placeholder) and where its window lies
 struct SlotDesc {
   int frame, n, best_h, pad;            // frame, inliers = lines of the window, the winning trial
@@ -55,40 +52,6 @@ struct FrameOut {
 
 // Window slot i lies at a fixed stride in the window buffers: words [2 Lcap], observations [16 Lcap], parameters [12 + 4 Lcap]
 struct WinBufs { unsigned* words; double* obs; double* par; int cap_lines; };
-
-__global__ __launch_bounds__(64) void k_frames_generate(const FrameDesc* __restrict__ fr, const double* __restrict__ dd,
-                                                        const int* __restrict__ di, double baseline, double* poses, int* valid) {
-  const FrameDesc fd = fr[blockIdx.y];
-  const int h = blockIdx.x * 64 + threadIdx.x;
-  if (h >= fd.H) return;
-  valid[fd.hyp + h] = generate_trial(fd.s, di + fd.smp + (long long)h * fd.s, dd + fd.o0, dd + fd.o1, baseline, poses + 12 * (fd.hyp + h));
-}
-
-// k_ransac_score of every frame: blockIdx = (64-line block, hypothesis, frame)
-__global__ __launch_bounds__(64) void k_frames_score(const FrameDesc* __restrict__ fr, const double* __restrict__ dd, const double* __restrict__ poses,
-                                                     const int* __restrict__ valid, double baseline, double thr, int* scores,
-                                                     unsigned long long* bits) {
-  const FrameDesc fd = fr[blockIdx.z];
-  const int blk = blockIdx.x, lane = threadIdx.x;
-  if (blk >= fd.words) return;
-  const int k = blk * 64 + lane;
-  for (int h = blockIdx.y; h < fd.H; h += gridDim.y) {
-    const long long g = fd.hyp + h;
-    const double* T = poses + 12 * g;
-    // `if ( num_sol == 0 ) continue;` (slam.cpp:394) and `if ( motion[j].t.norm() > 1 ) continue;` (:398-399)
-    if (!valid[g] || pose_skipped(T)) {
-      if (blk == 0 && lane == 0) scores[g] = -1;
-      if (lane == 0) bits[fd.bits + (long long)h * fd.words + blk] = 0ull;
-      continue;
-    }
-    const bool inlier = k < fd.K && line_inlier(T, dd + fd.o1 + 8 * (long long)k, dd + fd.ln + 6 * (long long)k, baseline, thr);
-    const unsigned long long m = __ballot(inlier);
-    if (lane == 0) {
-      bits[fd.bits + (long long)h * fd.words + blk] = m;
-      atomicAdd(&scores[g], __popcll(m));
-    }
-  }
-}
 
 // One wave per slot: the motion-only window of the slot's frame (reference src/slam.cpp:590-640, slslam_pack_motion_only) -
 // camera 0 = gc_Rt_to_wt(RANSAC pose), free; camera 1 = identity, constant; per inlier in ascending line order (camera 0, obs1) then
@@ -146,7 +109,7 @@ __global__ __launch_bounds__(64) void k_frame_finish(const FrameDesc* __restrict
   const FramePlan pl = plans[f];
   if (blk >= fd.words || pl.best_h < 0) return;
   FrameOut& o = out[f];
-  if (lane == 0) out_bits[fd.outb + blk] = bits[fd.bits + (long long)pl.best_h * fd.words + blk];
+  if (lane == 0) out_bits[pl.outb + blk] = bits[fd.bits + (long long)pl.best_h * fd.words + blk];
   if (blk == 0 && lane < 12) o.ransac_pose[lane] = poses[12 * (fd.hyp + pl.best_h) + lane];
   if (pl.slot < 0) return;
   const SlotDesc sd = slots[pl.slot];
@@ -168,43 +131,10 @@ __global__ __launch_bounds__(64) void k_frame_finish(const FrameDesc* __restrict
   const bool inlier = k < fd.K && line_inlier(T, dd + fd.o1 + 8 * (long long)k, dd + fd.ln + 6 * (long long)k, baseline, thr);
   const unsigned long long m = __ballot(inlier);
   if (lane == 0) {
-    out_bits[fd.outb + fd.words + blk] = m;
+    out_bits[pl.outb + fd.words + blk] = m;
     atomicAdd(&o.num_inliers, __popcll(m));
   }
 }
-
-// A device buffer that only grows (its contents are not kept); every allocation is counted
-struct DBuf {
-  char* p = nullptr;
-  size_t n = 0;
-  ~DBuf() { if (p) (void)hipFree(p); }
-  hipError_t need(size_t bytes, long long* allocs) {
-    if (bytes <= n && p) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-    const size_t want = std::max<size_t>(bytes + bytes / 8, 256);
-    const hipError_t e = hipMalloc((void**)&p, want);
-    if (e == hipSuccess) { n = want; ++*allocs; }
-    return e;
-  }
-  template <typename T> T* at(size_t byte_off) const { return reinterpret_cast<T*>(p + byte_off); }
-};
-// ... and its page-locked host counterpart
-struct HBuf {
-  char* p = nullptr;
-  size_t n = 0;
-  ~HBuf() { if (p) (void)hipHostFree(p); }
-  hipError_t need(size_t bytes, long long* allocs) {
-    if (bytes <= n && p) return hipSuccess;
-    if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
-    const size_t want = std::max<size_t>(bytes + bytes / 8, 256);
-    const hipError_t e = hipHostMalloc((void**)&p, want, hipHostMallocDefault);
-    if (e == hipSuccess) { n = want; ++*allocs; }
-    return e;
-  }
-  template <typename T> T* at(size_t byte_off) const { return reinterpret_cast<T*>(p + byte_off); }
-};
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -213,22 +143,19 @@ struct slslam_pose_estimator {
   slslam_solver_options opt;
   int cap_frames = 0, cap_lines = 0;               // what the batch and the window buffers hold
   slslam_lba_batch* batch = nullptr;
-  hipStream_t stream = nullptr;
-  DBuf d_in, d_work, d_win, d_export, d_small, d_out;
-  HBuf h_in, h_small, h_out;
-  long long calls = 0, allocations = 0, finalizes = 0, refills = 0;
+  Workspace ws{Mem::kPinned};                      // the RANSAC front's buffers, the stream of every call, the allocation counter
+  GrowBuf d_win{Mem::kDevice}, d_export{Mem::kDevice}, d_small{Mem::kDevice}, d_out{Mem::kDevice};
+  GrowBuf h_small{Mem::kPinned}, h_out{Mem::kPinned};
+  long long calls = 0, finalizes = 0, refills = 0;
   // the last call, for slslam_pose_estimator_window
   std::vector<int> slot_of_frame, n_of_frame;
   std::vector<long long> exp_off_of_frame;
   void drop_batch() { if (batch) { slslam_lba_batch_destroy(batch); batch = nullptr; } }
   ~slslam_pose_estimator() {
     drop_batch();
-    if (stream) (void)hipStreamDestroy(stream);
+    if (ws.stream) (void)hipStreamDestroy(ws.stream);
   }
 };
-
-#define FE_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { std::fprintf(stderr, "slslam: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    return (_e == hipErrorNoDevice || _e == hipErrorInvalidDevice) ? SLSLAM_ERR_NO_DEVICE : SLSLAM_ERR_HIP; } } while (0)
 
 extern "C" int slslam_pose_estimator_create(int device, const slslam_solver_options* opt, int max_frames, int max_lines,
                                             slslam_pose_estimator** out) {
@@ -253,7 +180,7 @@ extern "C" int slslam_pose_estimator_stats(const slslam_pose_estimator* e, long 
                                            long long* refills) {
   if (!e) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (calls) *calls = e->calls;
-  if (allocations) *allocations = e->allocations;
+  if (allocations) *allocations = e->ws.allocations;
   if (finalizes) *finalizes = e->finalizes;
   if (refills) *refills = e->refills;
   return SLSLAM_OK;
@@ -301,94 +228,44 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
   // ---- every argument before anything is written or the device is asked (as slslam_ransac_motion_batch)
   if (!e || num_frames < 0 || (num_frames > 0 && (!frames || !lines || !out))) return SLSLAM_ERR_INVALID_ARGUMENT;
   const int F = num_frames;
-  for (int f = 0; f < F; ++f) {
-    const slslam_ransac_trials& tr = frames[f];
-    if (tr.num_trials < 0 || tr.num_lines < 0 || tr.num_lines > 0xfffe || tr.sample_size < 1 || tr.sample_size > 16) return SLSLAM_ERR_INVALID_ARGUMENT;
-    const int H = tr.num_trials, K = tr.num_lines, s = tr.sample_size;
-    if (H > 0 && K > 0 && (!tr.samples || !tr.observations0 || !tr.observations1 || !lines[f])) return SLSLAM_ERR_INVALID_ARGUMENT;
-    for (long long i = 0; K > 0 && i < (long long)H * s; ++i)
-      if (tr.samples[i] < 0 || tr.samples[i] >= K) return SLSLAM_ERR_INVALID_ARGUMENT;
-  }
+  for (int f = 0; f < F; ++f)
+    if (frames[f].num_lines > 0xfffe) return SLSLAM_ERR_INVALID_ARGUMENT;        // (the windows' index words hold 16-bit line indices)
+  if (!trials_valid(F, frames, lines, true)) return SLSLAM_ERR_INVALID_ARGUMENT;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
-  if (e->device >= 0) FE_TRY(hipSetDevice(e->device));
-  else FE_TRY(hipGetDevice(&e->device));
-  if (!e->stream) FE_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  hipStream_t s = e->stream;
+  if (e->device >= 0) HIP_TRY(hipSetDevice(e->device));
+  else HIP_TRY(hipGetDevice(&e->device));
+  if (!e->ws.stream) HIP_TRY(hipStreamCreateWithFlags(&e->ws.stream, hipStreamNonBlocking));
+  hipStream_t s = e->ws.stream;
   ++e->calls;
   e->slot_of_frame.assign((size_t)F, -1); e->n_of_frame.assign((size_t)F, 0); e->exp_off_of_frame.assign((size_t)F, 0);
 
-  // ---- layout of the inputs: one block [FrameDesc F | doubles | ints], one upload
-  // (a frame with fewer than 5 common lines runs nothing (:275); of the others only the trials the loop can reach are scored)
-  std::vector<FrameDesc> fd((size_t)F);
-  long long nd = 0, ni = 0, nh = 0, nb = 0, nob = 0;
-  int maxH = 0, maxW = 0, maxK = 0;
-  for (int f = 0; f < F; ++f) {
-    const slslam_ransac_trials& tr = frames[f];
-    FrameDesc& d = fd[(size_t)f];
-    const int K = tr.num_lines;
-    const bool runs = K >= kMaxFeatNum;
-    d.K = runs ? K : 0; d.s = tr.sample_size; d.words = (d.K + 63) / 64;
-    d.H = runs ? std::max(0, (int)std::min<long long>(tr.num_trials, (long long)max_trials + 1)) : 0;
-    d.o0 = nd; nd += 8LL * d.K; d.o1 = nd; nd += 8LL * d.K; d.ln = nd; nd += 6LL * d.K;
-    d.smp = ni; ni += (long long)d.H * d.s;
-    d.hyp = nh; nh += d.H;
-    d.bits = nb; nb += (long long)d.H * d.words;
-    d.outb = nob; nob += 2LL * d.words;
-    maxH = std::max(maxH, d.H); maxW = std::max(maxW, d.words); maxK = std::max(maxK, d.K);
-  }
-  const size_t off_d = align256(sizeof(FrameDesc) * (size_t)F), off_i = off_d + align256(8 * (size_t)nd), in_bytes = off_i + 4 * (size_t)ni;
-  const size_t w_poses = 0, w_bits = align256(96 * (size_t)nh), w_valid = w_bits + align256(8 * (size_t)nb), w_scores = w_valid + align256(4 * (size_t)nh),
-               work_bytes = w_scores + 4 * (size_t)nh;
-  FE_TRY(e->h_in.need(in_bytes, &e->allocations));
-  FE_TRY(e->d_in.need(in_bytes, &e->allocations));
-  FE_TRY(e->d_work.need(work_bytes, &e->allocations));
-  if (F > 0) std::memcpy(e->h_in.p, fd.data(), sizeof(FrameDesc) * (size_t)F);
-  for (int f = 0; f < F; ++f) {
-    const slslam_ransac_trials& tr = frames[f];
-    const FrameDesc& d = fd[(size_t)f];
-    if (d.K > 0 && d.H > 0) {
-      std::memcpy(e->h_in.at<double>(off_d) + d.o0, tr.observations0, 64 * (size_t)d.K);
-      std::memcpy(e->h_in.at<double>(off_d) + d.o1, tr.observations1, 64 * (size_t)d.K);
-      std::memcpy(e->h_in.at<double>(off_d) + d.ln, lines[f], 48 * (size_t)d.K);
-      std::memcpy(e->h_in.at<int>(off_i) + d.smp, tr.samples, 4 * (size_t)d.H * d.s);
-    }
-  }
-  const FrameDesc* d_fd = e->d_in.at<FrameDesc>(0);
-  const double* d_dd = e->d_in.at<double>(off_d);
-  const int* d_di = e->d_in.at<int>(off_i);
-  double* d_poses = e->d_work.at<double>(w_poses);
-  unsigned long long* d_bits = e->d_work.at<unsigned long long>(w_bits);
-  int* d_valid = e->d_work.at<int>(w_valid);
-  int* d_scores = e->d_work.at<int>(w_scores);
+  // ---- RANSAC of every frame (best_score = -1, slam.cpp:283); a frame with fewer than 5 common lines runs nothing (:275)
+  std::vector<slslam_ransac_trials> gated(frames, frames + F);
+  for (slslam_ransac_trials& tr : gated)
+    if (tr.num_lines < kMaxFeatNum) tr.num_trials = 0;
+  Front fr;
+  int rc = front_ransac(e->ws, F, gated.data(), lines, baseline, error_thr, prob_free_outliers, max_trials, nullptr, &fr);
+  if (rc != SLSLAM_OK) return rc;
+  const std::vector<FrameDesc>& fd = fr.fd;
+  const std::vector<TrialLoop>& loop = fr.loop;
+  const FrameDesc* d_fd = fr.d_fd;
+  const double *d_dd = fr.d_dd, *d_poses = fr.d_poses;
+  const unsigned long long* d_bits = fr.d_bits;
+  const int maxW = fr.maxW, maxK = fr.maxK;
 
-  // ---- RANSAC of every frame: two launches, one download of the scores
-  std::vector<int> scores((size_t)std::max<long long>(nh, 1), 0);
-  if (F > 0) FE_TRY(hipMemcpyAsync(e->d_in.p, e->h_in.p, in_bytes, hipMemcpyHostToDevice, s));
-  if (nh > 0) {
-    FE_TRY(hipMemsetAsync(d_scores, 0, 4 * (size_t)nh, s));
-    // the reference passes -baseline to the generator (slam.cpp:391-392)
-    hipLaunchKernelGGL(k_frames_generate, dim3((unsigned)((maxH + 63) / 64), (unsigned)F), dim3(64), 0, s, d_fd, d_dd, d_di, -baseline, d_poses, d_valid);
-    hipLaunchKernelGGL(k_frames_score, dim3((unsigned)maxW, (unsigned)std::min(maxH, 65535), (unsigned)F), dim3(64), 0, s, d_fd, d_dd, (const double*)d_poses,
-                       (const int*)d_valid, baseline, error_thr, d_scores, d_bits);
-    FE_TRY(hipGetLastError());
-    FE_TRY(hipMemcpyAsync(scores.data(), d_scores, 4 * (size_t)nh, hipMemcpyDeviceToHost, s));
-    FE_TRY(hipStreamSynchronize(s));
-  }
-
-  // ---- the trial loops (best_score = -1, slam.cpp:283), statuses, the solvable frames' slots
+  // ---- statuses, the solvable frames' slots, where each frame's bits lie in the result block
   std::vector<FramePlan> plan((size_t)F);
-  std::vector<TrialLoop> loop((size_t)F);
   std::vector<int> slot_frame;
+  long long nob = 0;
   for (int f = 0; f < F; ++f) {
-    const FrameDesc& d = fd[(size_t)f];
-    loop[(size_t)f] = d.K > 0 ? run_trial_loop(scores.data() + d.hyp, d.H, d.K, d.s, prob_free_outliers, max_trials, -1) : TrialLoop{ -1, -1, 0 };
-    plan[(size_t)f].best_h = loop[(size_t)f].best_h;
-    plan[(size_t)f].slot = -1;
-    if (d.K > 0 && loop[(size_t)f].best >= kMaxFeatNum) { plan[(size_t)f].slot = (int)slot_frame.size(); slot_frame.push_back(f); }
+    FramePlan& pl = plan[(size_t)f];
+    pl.best_h = loop[(size_t)f].best_h;
+    pl.slot = -1;
+    pl.outb = nob; nob += 2LL * fd[(size_t)f].words;
+    if (loop[(size_t)f].best >= kMaxFeatNum) { pl.slot = (int)slot_frame.size(); slot_frame.push_back(f); }
   }
   const int S = (int)slot_frame.size();
-  int rc = SLSLAM_OK;
   if (S > 0) rc = ensure_batch(e, S, maxK);
   if (rc != SLSLAM_OK) return rc;
   const int B = S > 0 ? e->cap_frames : 0;
@@ -405,15 +282,15 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
   // ---- the small tables (plans, slots) up, the result block [FrameOut F | bits] zeroed
   const size_t off_slots = align256(sizeof(FramePlan) * (size_t)F), small_bytes = off_slots + sizeof(SlotDesc) * (size_t)B;
   const size_t off_bits = align256(sizeof(FrameOut) * (size_t)F), out_bytes = off_bits + 8 * (size_t)nob;
-  FE_TRY(e->h_small.need(small_bytes, &e->allocations));
-  FE_TRY(e->d_small.need(small_bytes, &e->allocations));
-  FE_TRY(e->h_out.need(out_bytes, &e->allocations));
-  FE_TRY(e->d_out.need(out_bytes, &e->allocations));
+  HIP_TRY(e->h_small.need(small_bytes, &e->ws.allocations));
+  HIP_TRY(e->d_small.need(small_bytes, &e->ws.allocations));
+  HIP_TRY(e->h_out.need(out_bytes, &e->ws.allocations));
+  HIP_TRY(e->d_out.need(out_bytes, &e->ws.allocations));
   if (F > 0) std::memcpy(e->h_small.p, plan.data(), sizeof(FramePlan) * (size_t)F);
   if (B > 0) std::memcpy(e->h_small.p + off_slots, slot.data(), sizeof(SlotDesc) * (size_t)B);
   if (F > 0) {
-    FE_TRY(hipMemcpyAsync(e->d_small.p, e->h_small.p, small_bytes, hipMemcpyHostToDevice, s));
-    FE_TRY(hipMemsetAsync(e->d_out.p, 0, out_bytes, s));
+    HIP_TRY(hipMemcpyAsync(e->d_small.p, e->h_small.p, small_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->d_out.p, 0, out_bytes, s));
   }
   const FramePlan* d_plan = e->d_small.at<FramePlan>(0);
   const SlotDesc* d_slot = e->d_small.at<SlotDesc>(off_slots);
@@ -424,11 +301,11 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
   if (S > 0) {
     const size_t Lc = (size_t)e->cap_lines, nw = (size_t)B;
     const size_t o_obs = align256(4 * 2 * Lc * nw), o_par = o_obs + align256(8 * 16 * Lc * nw), win_bytes = o_par + 8 * (12 + 4 * Lc) * nw;
-    FE_TRY(e->d_win.need(win_bytes, &e->allocations));
-    FE_TRY(e->d_export.need(8 * (size_t)exp_total, &e->allocations));
+    HIP_TRY(e->d_win.need(win_bytes, &e->ws.allocations));
+    HIP_TRY(e->d_export.need(8 * (size_t)exp_total, &e->ws.allocations));
     WinBufs wb{ e->d_win.at<unsigned>(0), e->d_win.at<double>(o_obs), e->d_win.at<double>(o_par), e->cap_lines };
-    hipLaunchKernelGGL(k_frame_pack, dim3((unsigned)B), dim3(64), 0, s, d_slot, d_fd, d_dd, (const double*)d_poses, (const unsigned long long*)d_bits, wb);
-    FE_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_frame_pack, dim3((unsigned)B), dim3(64), 0, s, d_slot, d_fd, d_dd, d_poses, d_bits, wb);
+    HIP_TRY(hipGetLastError());
     std::vector<slslam_lba_window> wins((size_t)B);
     std::vector<const unsigned*> packed((size_t)B);
     for (int i = 0; i < B; ++i) {
@@ -450,12 +327,11 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
   // ---- finish every frame in one launch, one download
   FrameOut* d_o = e->d_out.at<FrameOut>(0);
   if (F > 0 && maxW > 0)
-    hipLaunchKernelGGL(k_frame_finish, dim3((unsigned)maxW, (unsigned)F), dim3(64), 0, s, d_fd, d_plan, d_slot, d_dd, (const double*)d_poses,
-                       (const unsigned long long*)d_bits, (const double*)e->d_export.at<double>(0), d_state, d_wins, baseline, error_thr, d_o,
-                       e->d_out.at<unsigned long long>(off_bits));
-  FE_TRY(hipGetLastError());
-  if (F > 0) FE_TRY(hipMemcpyAsync(e->h_out.p, e->d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
-  FE_TRY(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(k_frame_finish, dim3((unsigned)maxW, (unsigned)F), dim3(64), 0, s, d_fd, d_plan, d_slot, d_dd, d_poses, d_bits,
+                       e->d_export.at<const double>(0), d_state, d_wins, baseline, error_thr, d_o, e->d_out.at<unsigned long long>(off_bits));
+  HIP_TRY(hipGetLastError());
+  if (F > 0) HIP_TRY(hipMemcpyAsync(e->h_out.p, e->d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   for (int f = 0; f < F; ++f)
     if (plan[(size_t)f].slot >= 0 && !e->h_out.at<FrameOut>(0)[f].built) return SLSLAM_ERR_UNSUPPORTED;     // (the device build refused a window)
 
@@ -470,7 +346,7 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
     r.trial_cnt = tl.trial_cnt;
     r.ransac_score = tl.best;
     for (int q = 0; q < 12; ++q) r.ransac_pose[q] = tl.best_h >= 0 ? o.ransac_pose[q] : (q == 0 || q == 4 || q == 8 ? 1.0 : 0.0);
-    const unsigned long long* ob = e->h_out.at<unsigned long long>(off_bits) + d.outb;
+    const unsigned long long* ob = e->h_out.at<unsigned long long>(off_bits) + plan[(size_t)f].outb;
     if (r.ransac_inlier_bits)
       for (int w = 0; w < words_k; ++w) r.ransac_inlier_bits[w] = tl.best_h >= 0 && w < d.words ? ob[w] : 0ull;
     std::memset(&r.summary, 0, sizeof(r.summary));
@@ -499,11 +375,11 @@ extern "C" int slslam_pose_estimator_window(const slslam_pose_estimator* e, int 
   *num_lines = n;
   const size_t Lc = (size_t)e->cap_lines, nw = (size_t)e->cap_frames;
   const size_t o_obs = align256(4 * 2 * Lc * nw), o_par = o_obs + align256(8 * 16 * Lc * nw);
-  FE_TRY(hipSetDevice(e->device));
-  FE_TRY(hipStreamSynchronize(e->stream));
-  if (index_words) FE_TRY(hipMemcpy(index_words, e->d_win.at<unsigned>(0) + (size_t)i * 2 * Lc, 4 * 2 * (size_t)n, hipMemcpyDeviceToHost));
-  if (observations) FE_TRY(hipMemcpy(observations, e->d_win.at<double>(o_obs) + (size_t)i * 16 * Lc, 8 * 16 * (size_t)n, hipMemcpyDeviceToHost));
-  if (parameters) FE_TRY(hipMemcpy(parameters, e->d_win.at<double>(o_par) + (size_t)i * (12 + 4 * Lc), 8 * (12 + 4 * (size_t)n), hipMemcpyDeviceToHost));
-  if (solved_camera) FE_TRY(hipMemcpy(solved_camera, e->d_export.at<double>(0) + e->exp_off_of_frame[(size_t)frame], 8 * 6, hipMemcpyDeviceToHost));
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->ws.stream));
+  if (index_words) HIP_TRY(hipMemcpy(index_words, e->d_win.at<unsigned>(0) + (size_t)i * 2 * Lc, 4 * 2 * (size_t)n, hipMemcpyDeviceToHost));
+  if (observations) HIP_TRY(hipMemcpy(observations, e->d_win.at<double>(o_obs) + (size_t)i * 16 * Lc, 8 * 16 * (size_t)n, hipMemcpyDeviceToHost));
+  if (parameters) HIP_TRY(hipMemcpy(parameters, e->d_win.at<double>(o_par) + (size_t)i * (12 + 4 * Lc), 8 * (12 + 4 * (size_t)n), hipMemcpyDeviceToHost));
+  if (solved_camera) HIP_TRY(hipMemcpy(solved_camera, e->d_export.at<double>(0) + e->exp_off_of_frame[(size_t)frame], 8 * 6, hipMemcpyDeviceToHost));
   return SLSLAM_OK;
 }

@@ -25,6 +25,7 @@
 #include "lba_pack.h"
 #include "lba_device_build.h"
 #include "lba_resident.h"
+#include "hip_status.h"
 #include "host_pool.h"
 #include "pinned_registry.h"
 
@@ -36,15 +37,6 @@
 #include <thread>
 
 using namespace slslam;
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      std::fprintf(stderr, "slslam: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return (_e == hipErrorNoDevice || _e == hipErrorInvalidDevice) ? SLSLAM_ERR_NO_DEVICE : SLSLAM_ERR_HIP; \
-    }                                                                                   \
-  } while (0)
 
 extern "C" void slslam_default_options(slslam_solver_options* o) {
   if (!o) return;

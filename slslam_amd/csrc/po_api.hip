@@ -14,22 +14,9 @@
 #include "../../include/slslam_hip.h"
 #include "po_kernels.h"
 #include "device_cache.h"
+#include "hip_status.h"
 
 using namespace slslam;
-
-namespace {
-// A failed HIP call as the C ABI reports it (the message and the mapping, for every pose-graph entry point).
-int po_hip_status(hipError_t e, const char* what, const char* file, int line) {
-  std::fprintf(stderr, "slslam: %s failed: %s (%s:%d)\n", what, hipGetErrorString(e), file, line);
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? SLSLAM_ERR_NO_DEVICE : SLSLAM_ERR_HIP;
-}
-}  // namespace
-
-#define PO_TRY(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return po_hip_status(_e, #expr, __FILE__, __LINE__);          \
-  } while (0)
 
 namespace {
 
@@ -443,7 +430,7 @@ int po_solve_upload(PoSolve& c) {
                o_linvf = a.take(f32 ? sizeof(float) * nb2 : 0);
   c.arena_bytes = a.off;
   (void)hipGetDevice(&c.arena_device);
-  PO_TRY(DeviceBlockCache::acquire(a.off, c.arena_device, &c.arena));   // the block of the previous one-shot solve, if large enough
+  HIP_TRY(DeviceBlockCache::acquire(a.off, c.arena_device, &c.arena));   // the block of the previous one-shot solve, if large enough
   char* arena = c.arena;
   PoPtrs& p = c.p;
   std::memset(&p, 0, sizeof(p));
@@ -466,7 +453,7 @@ int po_solve_upload(PoSolve& c) {
   if (hs->bytes < c.up_bytes) {
     if (hs->p) (void)hipHostFree(hs->p);
     hs->p = nullptr; hs->bytes = 0;
-    PO_TRY(hipHostMalloc((void**)&hs->p, c.up_bytes + c.up_bytes / 4 + 4096, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&hs->p, c.up_bytes + c.up_bytes / 4 + 4096, hipHostMallocDefault));
     hs->bytes = c.up_bytes + c.up_bytes / 4 + 4096;
   }
   char* stage = c.stage = hs->p;
@@ -479,7 +466,7 @@ int po_solve_upload(PoSolve& c) {
   std::memcpy(stage + o_slot, S.slot.data(), sizeof(int) * N); std::memcpy(stage + o_cons, g->constraints, sizeof(double) * 6 * E);
   std::fill_n((double*)(stage + o_scale), nn, 1.0);
   if (!S.chains.empty()) std::memcpy(stage + o_chains, S.chains.data(), sizeof(PoChain) * S.chains.size());
-  PO_TRY(hipMemcpyAsync(arena, stage, c.up_bytes, hipMemcpyHostToDevice, 0));
+  HIP_TRY(hipMemcpyAsync(arena, stage, c.up_bytes, hipMemcpyHostToDevice, 0));
   c.wide_resident = po_wide_resident(f32, c.arena_device);
   return SLSLAM_OK;
 }
@@ -492,16 +479,16 @@ void po_launch_linearise(const PoSolve& c, int mode) {
 
 // ---- initial evaluation: cost, gradient, column norms -> Jacobi scale
 int po_solve_enqueue_initial(PoSolve& c) {
-  if (po_step_lds_attributes() != hipSuccess) { PO_TRY(hipErrorInvalidValue); }
+  if (po_step_lds_attributes() != hipSuccess) { HIP_TRY(hipErrorInvalidValue); }
   c.stamp(); c.stamp();                   // [1] is re-recorded at the end
   const PoPtrs& p = c.p;
   // (structured: only what the linearisation adds into and the junction block are zeroed, by one small launch: k_po_zero_structured)
   if (c.zero_small) {
-    PO_TRY(hipMemsetAsync(p.g, 0, sizeof(double) * c.nn, 0));             // (once: the padding behind the n gradient entries)
+    HIP_TRY(hipMemsetAsync(p.g, 0, sizeof(double) * c.nn, 0));             // (once: the padding behind the n gradient entries)
     hipLaunchKernelGGL(k_po_zero_structured, c.g_zero, dim3(256), 0, 0, p, c.S->n_l1);
   } else {
-    PO_TRY(hipMemsetAsync(p.H, 0, c.hbytes, 0));
-    PO_TRY(hipMemsetAsync(p.g, 0, sizeof(double) * c.nn, 0));
+    HIP_TRY(hipMemsetAsync(p.H, 0, c.hbytes, 0));
+    HIP_TRY(hipMemsetAsync(p.g, 0, sizeof(double) * c.nn, 0));
   }
   po_launch_linearise(c, 0);
   hipLaunchKernelGGL(k_po_prepare, dim3(1), dim3(256), 0, 0, p, c.pol, 1);
@@ -527,9 +514,9 @@ int po_solve_enqueue_iteration(PoSolve& c) {
   const PoSymbolic& S = *c.S;
   if (c.zero_small) hipLaunchKernelGGL(k_po_zero_structured, c.g_zero, dim3(256), 0, 0, p, S.n_l1);
   else {
-    PO_TRY(hipMemsetAsync(p.H, 0, c.hbytes, 0));
-    PO_TRY(hipMemsetAsync(p.g, 0, sizeof(double) * c.nn, 0));
-    PO_TRY(hipMemsetAsync(p.scal, 0, sizeof(double), 0));            // kPoCost
+    HIP_TRY(hipMemsetAsync(p.H, 0, c.hbytes, 0));
+    HIP_TRY(hipMemsetAsync(p.g, 0, sizeof(double) * c.nn, 0));
+    HIP_TRY(hipMemsetAsync(p.scal, 0, sizeof(double), 0));            // kPoCost
   }
   po_launch_linearise(c, 0);
   hipLaunchKernelGGL(k_po_prepare, dim3(1), dim3(256), 0, 0, p, c.pol, 0);
@@ -563,8 +550,8 @@ int po_solve_enqueue_iteration(PoSolve& c) {
 
 // Asks the device whether the solve has finished (state | trace | poses in one copy: when it has, this IS the download).
 int po_solve_poll(PoSolve& c) {
-  PO_TRY(hipMemcpyAsync(c.stage, c.arena, c.down_bytes, hipMemcpyDeviceToHost, 0));
-  PO_TRY(hipStreamSynchronize(0));
+  HIP_TRY(hipMemcpyAsync(c.stage, c.arena, c.down_bytes, hipMemcpyDeviceToHost, 0));
+  HIP_TRY(hipStreamSynchronize(0));
   std::memcpy(&c.hst, c.landed(c.p.st), sizeof(c.hst));
   c.have_results = c.hst.status != kRunning;
   return SLSLAM_OK;
@@ -581,12 +568,12 @@ void po_solve_read_timing(PoSolve& c) {
 }
 
 int po_solve_report(PoSolve& c, slslam_summary* summary, slslam_iteration* trace, int trace_cap, int* trace_len) {
-  PO_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   if (c.timing && c.tev.size() >= 2) (void)hipEventRecord(c.tev[1], 0);
-  if (!c.have_results || c.timing) PO_TRY(hipDeviceSynchronize());
+  if (!c.have_results || c.timing) HIP_TRY(hipDeviceSynchronize());
   if (c.timing) po_solve_read_timing(c);
   // state | trace | poses come back in ONE copy (they are the first bytes of the block)
-  if (!c.have_results) PO_TRY(hipMemcpy(c.stage, c.arena, c.down_bytes, hipMemcpyDeviceToHost));
+  if (!c.have_results) HIP_TRY(hipMemcpy(c.stage, c.arena, c.down_bytes, hipMemcpyDeviceToHost));
   std::memcpy(&c.hst, c.landed(c.p.st), sizeof(c.hst));
   const LMState& st = c.hst;
   const int N = c.g->num_poses;
@@ -645,20 +632,20 @@ extern "C" int slslam_po_edge_report(const slslam_po_graph* g, double po_huber_d
     ~Block() { DeviceBlockCache::give_back(p, bytes, device); }
   } blk;
   blk.bytes = a.off;
-  PO_TRY(hipGetDevice(&blk.device));
-  PO_TRY(DeviceBlockCache::acquire(blk.bytes, blk.device, &blk.p));
+  HIP_TRY(hipGetDevice(&blk.device));
+  HIP_TRY(DeviceBlockCache::acquire(blk.bytes, blk.device, &blk.p));
   std::vector<char> img(up_bytes > sizeof(double) * 2 * E ? up_bytes : sizeof(double) * 2 * E);
   std::memcpy(img.data() + o_p1, g->pose_index_1, sizeof(int) * E); std::memcpy(img.data() + o_p2, g->pose_index_2, sizeof(int) * E);
   std::memcpy(img.data() + o_cons, g->constraints, sizeof(double) * 6 * E); std::memcpy(img.data() + o_x, g->parameters, sizeof(double) * 6 * N);
-  PO_TRY(hipMemcpy(blk.p, img.data(), up_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(blk.p, img.data(), up_bytes, hipMemcpyHostToDevice));
   PoPtrs p;
   std::memset(&p, 0, sizeof(p));
   p.p1 = (const int*)(blk.p + o_p1); p.p2 = (const int*)(blk.p + o_p2); p.cons = (const double*)(blk.p + o_cons);
   p.N = N; p.E = E; p.huber = po_huber_delta;
   double* d_out = (double*)(blk.p + o_out);
   hipLaunchKernelGGL(k_po_edge_report, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, 0, p, (const double*)(blk.p + o_x), d_out, d_out + E);
-  PO_TRY(hipGetLastError());
-  PO_TRY(hipMemcpy(img.data(), d_out, sizeof(double) * 2 * E, hipMemcpyDeviceToHost));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(img.data(), d_out, sizeof(double) * 2 * E, hipMemcpyDeviceToHost));
   if (sq_norm) std::memcpy(sq_norm, img.data(), sizeof(double) * E);
   if (weight) std::memcpy(weight, img.data() + sizeof(double) * E, sizeof(double) * E);
   return SLSLAM_OK;

@@ -1,7 +1,7 @@
 // slslam_amd/csrc/po_batch.h — many pose graphs per call: slslam_po_batch_* runs slslam_po_solve's structured path
 // (POProblem::build + ceres::Solve, reference src/slam.cpp:1236-1313, src/po_problem.cpp:40-77) for G graphs at once.
 // Part of po_api.hip's translation unit (included at its end: the one-graph kernels, the symbolic analysis and the host helpers both
-// paths share - validation, policy, PoSymbolic, results, PO_TRY, PoCarve - live there).
+// paths share - validation, policy, PoSymbolic, results, PoCarve - live there).
 //
 // Every launch of the one-graph sequence covers every graph of the batch: the kernels below are the one-graph kernels'
 // bodies (po_kernels.h) behind a graph index taken from the grid (one workgroup per graph) or from a flattened work list
@@ -301,7 +301,7 @@ extern "C" int slslam_po_batch_finalize(slslam_po_batch* b, const slslam_solver_
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
   if (b->device < 0) { if (hipGetDevice(&b->device) != hipSuccess) return SLSLAM_ERR_NO_DEVICE; }
   if (b->device >= ndev) return SLSLAM_ERR_INVALID_ARGUMENT;
-  PO_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipSetDevice(b->device));
   b->active.clear();
   for (size_t i = 0; i < b->graphs.size(); ++i) {
     b->graphs[i].active = b->graphs[i].E > 0 ? (int)b->active.size() : -1;
@@ -335,8 +335,8 @@ extern "C" int slslam_po_batch_reset(slslam_po_batch* b, void* stream) {
   if (!b->finalized) return SLSLAM_ERR_STATE;
   b->have_results = false;
   if (b->active.empty()) return SLSLAM_OK;
-  PO_TRY(hipSetDevice(b->device));
-  PO_TRY(hipMemcpyAsync(b->arena, b->h_up, b->up_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipMemcpyAsync(b->arena, b->h_up, b->up_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
   return SLSLAM_OK;
 }
 
@@ -346,7 +346,7 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
   b->have_results = false;
   const int A = (int)b->active.size();
   if (A == 0) return SLSLAM_OK;
-  PO_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipSetDevice(b->device));
   hipStream_t s = (hipStream_t)stream;
   const PoBatchGraph* gs = b->d_graphs;
   const PoItem* items = b->d_items;
@@ -368,8 +368,8 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
   int next_check = b->iter_hint >= 0 ? std::min(b->iter_hint + 1, 8) : 8;
   for (int it = 0; it < pol.max_num_iterations; ++it) {
     if (it == next_check) {
-      PO_TRY(hipMemcpyAsync(b->h_down, b->arena, sizeof(LMState) * (size_t)A, hipMemcpyDeviceToHost, s));
-      PO_TRY(hipStreamSynchronize(s));
+      HIP_TRY(hipMemcpyAsync(b->h_down, b->arena, sizeof(LMState) * (size_t)A, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
       const LMState* st = (const LMState*)b->h_down;
       bool running = false;
       int steps = 0;
@@ -396,7 +396,7 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
     linearise(1);
     hipLaunchKernelGGL(k_pob_update, dim3((unsigned)A), dim3(64), 0, s, gs, pol);
   }
-  PO_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return SLSLAM_OK;
 }
 
@@ -405,13 +405,13 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
   if (!b->finalized) return SLSLAM_ERR_STATE;
   const int A = (int)b->active.size();
   if (A > 0) {
-    PO_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     // every graph's edge report (slslam_po_batch_get_edge_report), at the batch's own po_huber_delta, in one launch ahead of the copy
     hipLaunchKernelGGL(k_pob_edge_report, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, (const PoBatchGraph*)b->d_graphs, (const PoItem*)(b->d_items + b->edge_off));
-    PO_TRY(hipGetLastError());
-    PO_TRY(hipMemcpyAsync(b->h_down, b->arena, b->down_bytes, hipMemcpyDeviceToHost, s));
-    PO_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_down, b->arena, b->down_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
   int steps = 0;
   try {

@@ -1,5 +1,5 @@
-// slslam_amd/csrc/ransac_device.h — the bodies of RANSAC hypothesis scoring and generation, shared by the kernels of
-// ransac_api.hip (one frame per launch) and frame_api.hip (every frame of a pose-estimator call in one launch).
+// slslam_amd/csrc/ransac_device.h — the bodies of RANSAC hypothesis scoring and generation: called by the one kernel pair of
+// ransac_api.hip (every frame of a call in one launch) and, for the final inlier set, by frame_api.hip's k_frame_finish.
 //
 // Scoring: SLAM::reprojection_error (reference src/slam.cpp:691-726) of one line under one pose.  The reference mixes float
 // and double (float `sql = nc.head(2).norm()`, `float error`); the same conversions are applied in the same places so that

@@ -1,6 +1,6 @@
 // slslam_amd/csrc/ransac_loop.h — the adaptive trial loop of SLAM::ransac_motion (reference src/slam.cpp:363, :415-423), replayed
-// on the host in trial order over scores the device computed for every pre-drawn trial.  Shared by slslam_ransac_motion,
-// slslam_ransac_motion_batch and the pose estimator.  It stays on the host: its pow / log feed an int truncation, and device libm
+// on the host in trial order over scores the device computed for every pre-drawn trial.  Called from one place, the RANSAC front
+// (ransac_front.h, ransac_api.hip) that every entry point and the pose estimator run through.  It stays on the host: its pow / log feed an int truncation, and device libm
 // does not promise the host's last bit.
 #ifndef SLSLAM_RANSAC_LOOP_H_
 #define SLSLAM_RANSAC_LOOP_H_

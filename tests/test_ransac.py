@@ -119,3 +119,97 @@ def test_gpu_ransac_motion_batch_equals_single_calls(hip, oracle):
         assert (tc, best) == t1[:2] == t0[:2]
         assert np.array_equal(mask, t1[3]) and np.array_equal(mask, t0[3])
         assert np.array_equal(pose, t1[2])
+
+
+def _ragged_frames():
+    """Frames at the edges of the shared kernels' indexing, each with (frame, incoming best score): K on both sides of a 64-line
+    word and with a partial last word, sample sizes 3 / 4 / 5 side by side, and the frames that run nothing or nearly nothing."""
+    def pair(seed, K, T, s):
+        return synth.make_ransac_pair(seed, num_lines=K, noise_px=0.4, outlier_frac=0.3, num_trials=T, sample_size=s)
+    out = [(pair(71, 63, 90, 3), 0), (pair(72, 64, 70, 4), 0), (pair(73, 65, 130, 5), -1), (pair(74, 129, 200, 4), 0)]
+    f = pair(75, 40, 30, 3)
+    out.append((dict(f, samples=f["samples"][:0]), 0))                                            # H == 0
+    out.append((dict(f, obs0=f["obs0"][:0], obs1=f["obs1"][:0], lines=f["lines"][:0]), 3))       # K == 0, samples not empty
+    out.append((pair(79, 50, 1, 4), -1))                                                          # H == 1
+    f = pair(77, 70, 60, 3)
+    o0 = f["obs0"].copy()
+    k = f["samples"][0][0]
+    o0[k, 2:4] = o0[k, 0:2]                                                                       # trial 0 degenerate: valid == 0
+    out.append((dict(f, obs0=o0), 0))
+    out.append((pair(78, 66, 40, 5), 10 ** 6))                                                    # a best score nothing beats
+    return out
+
+
+@pytest.fixture(scope="module")
+def ragged(oracle):
+    frames = _ragged_frames()
+    ref = [oracle.ransac_motion(f["obs0"], f["obs1"], f["lines"], f["samples"], best_score=b) for f, b in frames]
+    return frames, ref
+
+
+@pytest.fixture(scope="module")
+def ragged_batch(hip, ragged):
+    frames, _ = ragged
+    return hip.ransac_motion_batch([f for f, _ in frames], best_score=[b for _, b in frames])
+
+
+@pytest.mark.gpu
+def test_gpu_ragged_batch_against_oracle(oracle, ragged, ragged_batch):
+    """One slslam_ransac_motion_batch call over the ragged frames: per frame the oracle's sequential loop."""
+    frames, ref = ragged
+    assert len(ragged_batch) == len(frames)
+    for (f, b), (tc0, b0, p0, i0), (tc, best, pose, mask) in zip(frames, ref, ragged_batch):
+        assert (tc, best) == (tc0, b0)
+        assert np.array_equal(mask, i0)
+        assert np.abs(pose - p0).max() < 1e-9                    # device sin / cos, as in test_gpu_motion_generator_and_trial_loop
+    # the cases are what they claim to be
+    tcs = [r[0] for r in ref]
+    assert tcs[4] == 0 and tcs[5] == 0 and ref[5][1] == 3
+    assert tcs[6] == 1 and ref[6][1] > 0                         # the only trial is the winner
+    f7 = frames[7][0]
+    assert oracle.vo_angle_axis_approx(f7["obs0"][f7["samples"][0]], f7["obs1"][f7["samples"][0]])[0] == 0      # trial 0: valid == 0
+    assert ref[8][1] == 10 ** 6 and tcs[8] == 40 and not ref[8][3].any()
+    assert all(t > 0 and r[1] > 0 for t, r in zip(tcs[:4], ref[:4]))
+
+
+@pytest.mark.gpu
+def test_gpu_ragged_frames_one_at_a_time(hip, ragged, ragged_batch):
+    """slslam_ransac_motion per frame: the same kernels on the same inputs as the frame's slot of the batch, so the same tuple."""
+    frames, _ = ragged
+    for (f, b), (tc, best, pose, mask) in zip(frames, ragged_batch):
+        t1 = hip.ransac_motion(f["obs0"], f["obs1"], f["lines"], f["samples"], best_score=b)
+        assert t1[:2] == (tc, best)
+        assert np.array_equal(t1[2], pose) and np.array_equal(t1[3], mask)
+
+
+@pytest.mark.gpu
+def test_gpu_score_beyond_the_grid_limit(hip, oracle):
+    """More hypotheses than a grid dimension holds (65 535): the scorer strides over them."""
+    poses, obs, lines, _ = synth.make_ransac_frame(5, num_lines=8, num_hypotheses=80)
+    poses = np.tile(poses, (820, 1))                             # 65 600 hypotheses, no two alike
+    poses[:, 9:] += np.random.default_rng(5).normal(size=(len(poses), 3)) * 1e-3
+    s0, m0 = oracle.ransac_score(poses, obs, lines)
+    s1, m1 = hip.ransac_score(poses, obs, lines)
+    assert len(s1) == 65600 and len(obs) == 8
+    assert np.array_equal(s0, s1) and np.array_equal(m0, m1)
+    assert (s0[65535:] >= 0).any() and (s0 == -1).any()
+
+
+@pytest.mark.gpu
+def test_gpu_generate_with_lines_beyond_the_samples(hip, oracle):
+    """Generate only: the samples draw from the first 30 of 200 common lines (more than a 64-line block is never indexed), and no
+    lines array is given."""
+    fr = synth.make_ransac_pair(9, num_lines=200, noise_px=0.4, outlier_frac=0.3, num_trials=8)
+    rng = np.random.default_rng(9)
+    smp = np.stack([rng.choice(30, size=5, replace=False) for _ in range(100)]).astype(np.int32)
+    o0 = fr["obs0"].copy()
+    k = smp[0][0]
+    o0[k, 2:4] = o0[k, 0:2]
+    poses, valid = hip.ransac_generate(o0, fr["obs1"], smp)
+    assert smp.max() + 64 < len(o0)
+    assert np.array_equal(valid == 0, (smp == k).any(axis=1))
+    for h in range(100):
+        n, ref = oracle.vo_angle_axis_approx(o0[smp[h]], fr["obs1"][smp[h]])
+        assert n == valid[h]
+        if n:
+            assert np.abs(poses[h] - ref).max() <= 1e-9 * max(1.0, np.abs(ref).max())
