@@ -456,6 +456,47 @@ int  slslam_po_batch_get_trace(const slslam_po_batch* b, int index, slslam_itera
  * src/po_problem.cpp:27,55).  download computes every graph's report in one launch ahead of its copy.  Either output may be NULL. */
 int  slslam_po_batch_get_edge_report(const slslam_po_batch* b, int index, double* sq_norm, double* weight);
 
+/* ---- posterior covariances of pose graphs (csrc/po_covariance.h).
+ * Replace nothing in the reference - consistency_broken() (src/slam.cpp:1215-1232) judges a loop closure by two fixed thresholds -;
+ * the Ceres counterpart is ceres::Covariance on the problem POProblem::build wires up.
+ * For a graph at its CURRENT parameters x (graph->parameters for the one-graph call; what slslam_po_batch_get_parameters would return
+ * for a batch - the poses as added for a graph whose solve ended in NUMERICAL_FAILURE):
+ *   free pose: referenced by at least one edge and not pose_index_1[0] (the rule of the solve: slslam_po_structure's slot >= 0);
+ *   J: the Jacobian of all edges' six residuals (src/po_problem.h:68-108) w.r.t. the free poses, in the global (angle-axis, translation)
+ *      coordinates, after the Huber corrector of po_huber_delta (a block with s = |Te|^2 > delta^2 is scaled by sqrt(delta / sqrt(s));
+ *      0: no loss), without Jacobi scaling or damping;
+ *   H = J^T J, n = 6 x (free poses);  Sigma = H^-1 for unit-variance residuals - multiply by the noise variance.
+ *   cov_poses[36 N]: the row-major 6 x 6 marginal Sigma_aa per caller pose index, zeros for the constant pose and unreferenced poses;
+ *   cov_pairs[36 P]: for the caller's pairs (pair_a[k], pair_b[k]) the row-major block Sigma_ab, rows of a, columns of b; a == b gives
+ *      the marginal; a pair that touches a constant or unreferenced pose gives zeros.
+ * SLSLAM_COV_SINGULAR: a pivot <= 1e-10 in the Cholesky factorisation of H scaled to unit diagonal (the scaling is internal: outputs
+ * are unscaled) - a component not connected to the constant pose has a 6-dimensional null space.  Every output of that graph is zero;
+ * the other graphs of a batch are not affected.  The covariance of an edge error Te follows from Sigma_aa, Sigma_bb, Sigma_ab and the
+ * Jacobians of the caller's functor. */
+/* One graph, no solve, synchronous.  Validates as slslam_po_edge_report does - and SLSLAM_ERR_INVALID_ARGUMENT for a pair index outside
+ * [0, num_poses), num_pairs < 0, or cov_pairs with num_pairs > 0 and a NULL pair array - before it needs a device
+ * (SLSLAM_ERR_NO_DEVICE).  status, cov_poses, cov_pairs: any may be NULL. */
+int  slslam_po_covariance(const slslam_po_graph* graph, double po_huber_delta, int num_pairs, const int* pair_a, const int* pair_b,
+                          int* status, double* cov_poses, double* cov_pairs);
+/* The pairs slslam_po_batch_covariance reports for graph `index` (none until set).  Host only: copies the pairs, replaces the graph's
+ * previous list; allowed before and after finalize.  SLSLAM_ERR_INVALID_ARGUMENT as above.  Results of a covariance call made with
+ * the previous list can no longer be read (slslam_po_batch_get_covariance). */
+int  slslam_po_batch_set_covariance_pairs(slslam_po_batch* b, int index, int num_pairs, const int* pair_a, const int* pair_b);
+/* Enqueues the covariance of every graph on `stream` and returns (after the first call, or a call that follows a replaced pair list:
+ * those build the work lists and wait for their upload).  SLSLAM_ERR_STATE before finalize.  Under the po_huber_delta of finalize.
+ * Changes nothing a solve, reset or download reads or returns.  Its buffers are allocated by the first call and kept; they grow only
+ * when a pair list grew.  Device memory per graph: two n x ld matrices of doubles (the normal matrix, which the inverse factor
+ * overwrites, and the Cholesky factor; ld = n rounded up to 8, plus 8: 39 MB for a 260-pose graph), 32 KB per 64 unknowns for the
+ * diagonal blocks' inverses, 288 bytes per pose and per pair of results, and a few vectors. */
+int  slslam_po_batch_covariance(slslam_po_batch* b, void* stream);
+/* After slslam_po_batch_download, which brings the covariances enqueued since the last download back with the other results:
+ * *status = SLSLAM_COV_*, cov_poses[36 N], cov_pairs[36 P] as above (a graph without edges: SLSLAM_COV_OK and zeros).  Any output
+ * pointer may be NULL.  SLSLAM_ERR_INVALID_ARGUMENT: no covariance call has been downloaded, or a solve, a reset, a newer covariance
+ * call or slslam_po_batch_set_covariance_pairs came after it. */
+int  slslam_po_batch_get_covariance(const slslam_po_batch* b, int index, int* status, double* cov_poses, double* cov_pairs);
+/* Since create: slslam_po_batch_covariance calls, and the device / host buffers they allocated.  Any pointer may be NULL. */
+int  slslam_po_batch_covariance_stats(const slslam_po_batch* b, long long* calls, long long* allocations);
+
 /* ------------------------------------------------------------------ RANSAC hypothesis scoring
  * (the per-frame cost centre next to the hot path.)
  * Replaces: the scoring loop of SLAM::ransac_motion (reference src/slam.cpp:396-413) with

@@ -100,7 +100,7 @@ EXPORTS = [
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
-    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -181,6 +181,11 @@ def lib():
     L.slslam_po_batch_get_trace.argtypes = [vp, C.c_int, C.POINTER(Iteration), C.c_int, ip]
     L.slslam_po_edge_report.argtypes = [C.POINTER(POGraph), C.c_double, dp, dp]
     L.slslam_po_batch_get_edge_report.argtypes = [vp, C.c_int, dp, dp]
+    L.slslam_po_covariance.argtypes = [C.POINTER(POGraph), C.c_double, C.c_int, ip, ip, ip, dp, dp]
+    L.slslam_po_batch_set_covariance_pairs.argtypes = [vp, C.c_int, C.c_int, ip, ip]
+    L.slslam_po_batch_covariance.argtypes = [vp, vp]
+    L.slslam_po_batch_get_covariance.argtypes = [vp, C.c_int, ip, dp, dp]
+    L.slslam_po_batch_covariance_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
     L.slslam_ransac_score.argtypes = [C.POINTER(RansacFrame), C.c_double, C.c_double, ip, C.POINTER(C.c_ulonglong)]
     L.slslam_po_structure.argtypes = [C.POINTER(POGraph), ip, C.c_int, ip, ip, ip, ip, ip, ip, ip]
     L.slslam_ransac_generate.argtypes = [C.POINTER(RansacTrials), C.c_double, dp, ip]
@@ -676,6 +681,25 @@ def po_edge_report(g, params=None, po_huber_delta=0.0):
     return sq, wt
 
 
+def _po_pairs(pairs):
+    pr = np.ascontiguousarray(np.asarray([] if pairs is None else pairs, dtype=np.int32).reshape(-1, 2))
+    return np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+
+
+def po_covariance(g, pairs=None, po_huber_delta=0.0, params=None):
+    """Posterior covariance of one pose graph at its parameters (slslam_po_covariance; ceres::Covariance): (status,
+    cov_poses[N, 6, 6] - the marginal of every pose, zeros for the constant pose and unreferenced ones -, cov_pairs[P, 6, 6] - the
+    cross blocks Sigma_ab of `pairs` [(a, b), ...], rows of a, columns of b).  status COV_SINGULAR: all zeros."""
+    i1, i2, cons, x = _po_arrays(g, params)
+    cg = POGraph(int(g["num_poses"]), len(i1), _ip(i1), _ip(i2), _dp(cons), _dp(x))
+    pa, pb = _po_pairs(pairs)
+    st = C.c_int(-1)
+    cp, cq = np.zeros((int(g["num_poses"]), 6, 6)), np.zeros((len(pa), 6, 6))
+    _check(lib().slslam_po_covariance(C.byref(cg), float(po_huber_delta), len(pa), _ip(pa), _ip(pb), C.byref(st), _dp(cp), _dp(cq)),
+           "slslam_po_covariance")
+    return st.value, cp, cq
+
+
 def _po_arrays(g, params=None):
     i1 = np.ascontiguousarray(g["pose_index_1"], dtype=np.int32)
     i2 = np.ascontiguousarray(g["pose_index_2"], dtype=np.int32)
@@ -695,6 +719,7 @@ class POBatch:
         _check(lib().slslam_po_batch_create(int(device), C.byref(self._h)), "slslam_po_batch_create")
         self._n = []
         self._e = []
+        self._pairs = {}
 
     def add(self, g, params=None):
         i1, i2, cons, x = _po_arrays(g, params)
@@ -731,6 +756,28 @@ class POBatch:
         sq, wt = np.zeros(self._e[i]), np.zeros(self._e[i])
         _check(lib().slslam_po_batch_get_edge_report(self._h, int(i), _dp(sq), _dp(wt)), "slslam_po_batch_get_edge_report")
         return sq, wt
+
+    def set_covariance_pairs(self, i, pairs):
+        """The pairs [(a, b), ...] whose cross blocks covariance() reports for graph i (replaces the previous list)."""
+        pa, pb = _po_pairs(pairs)
+        _check(lib().slslam_po_batch_set_covariance_pairs(self._h, int(i), len(pa), _ip(pa), _ip(pb)), "slslam_po_batch_set_covariance_pairs")
+        self._pairs[int(i)] = len(pa)
+
+    def covariance(self, stream=None):
+        """Enqueue the covariance of every graph at its current poses; download() brings the results back."""
+        _check(lib().slslam_po_batch_covariance(self._h, C.c_void_p(stream or 0)), "slslam_po_batch_covariance")
+
+    def get_covariance(self, i):
+        """(status, cov_poses[N, 6, 6], cov_pairs[P, 6, 6]) of graph i, as po_covariance returns them."""
+        st = C.c_int(-1)
+        cp, cq = np.zeros((self._n[i], 6, 6)), np.zeros((self._pairs.get(int(i), 0), 6, 6))
+        _check(lib().slslam_po_batch_get_covariance(self._h, int(i), C.byref(st), _dp(cp), _dp(cq)), "slslam_po_batch_get_covariance")
+        return st.value, cp, cq
+
+    def covariance_stats(self):
+        c, a = C.c_longlong(0), C.c_longlong(0)
+        _check(lib().slslam_po_batch_covariance_stats(self._h, C.byref(c), C.byref(a)), "slslam_po_batch_covariance_stats")
+        return dict(calls=c.value, allocations=a.value)
 
     def summary(self, i):
         s = Summary()

@@ -100,6 +100,10 @@ struct slslam_po_batch {
     std::vector<IterRec> trace;
     std::vector<double> x;
     std::vector<double> report;             // [2E] per edge |Te|^2, then rho'
+    // covariances (po_covariance.h): the caller's pairs, and what the last downloaded slslam_po_batch_covariance call gave
+    std::vector<int> cov_pa, cov_pb;
+    int cov_status = SLSLAM_COV_OK;
+    std::vector<double> cov_poses, cov_pairs;
   };
   int device = -1;
   bool finalized = false, have_results = false;
@@ -123,11 +127,24 @@ struct slslam_po_batch {
   int zero_off = 0, zero_cnt = 0, edge_off = 0, edge_cnt = 0, jgraph_cnt = 0;
   std::vector<int> level_off, level_cnt, step_off, step_cnt;
   int iter_hint = -1;                       // LM iterations the slowest graph of the previous solve took
+  // covariances: buffers of their own, allocated by the first slslam_po_batch_covariance call and kept (grown when a pair list grew)
+  std::vector<PoBatchGraph> h_desc;         // host copy of the descriptors: where each graph's arrays live in the arena
+  PoCovPlan cov_plan;
+  char* cov_dev = nullptr;
+  char* cov_h_down = nullptr;               // pinned landing area of the plan's results
+  size_t cov_dev_bytes = 0, cov_down_cap = 0;
+  bool cov_dirty = true;                    // the plan has to be (re)built: first call, or a pair list was replaced
+  bool cov_pending = false;                 // a covariance call is on the device, not downloaded, no solve or reset behind it
+  bool cov_valid = false;                   // the graphs hold the results of the latest covariance call
+  long long cov_calls = 0, cov_allocs = 0;
   void release() {
     if (arena) (void)hipFree(arena);
     if (h_up) (void)hipHostFree(h_up);
     if (h_down) (void)hipHostFree(h_down);
-    arena = h_up = h_down = nullptr;
+    if (cov_dev) (void)hipFree(cov_dev);
+    if (cov_h_down) (void)hipHostFree(cov_h_down);
+    arena = h_up = h_down = cov_dev = cov_h_down = nullptr;
+    cov_dev_bytes = cov_down_cap = 0;
   }
 };
 
@@ -143,7 +160,7 @@ extern "C" int slslam_po_batch_create(int device, slslam_po_batch** out) {
 
 extern "C" void slslam_po_batch_destroy(slslam_po_batch* b) {
   if (!b) return;
-  if (b->arena || b->h_up || b->h_down) { (void)hipSetDevice(b->device); b->release(); }
+  if (b->arena || b->h_up || b->h_down || b->cov_dev || b->cov_h_down) { (void)hipSetDevice(b->device); b->release(); }
   delete b;
 }
 
@@ -284,6 +301,7 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
   }
   put(o_graphs, desc.data(), sizeof(PoBatchGraph) * desc.size());
   if (arena) {
+    b->h_desc = desc;
     b->d_graphs = (PoBatchGraph*)(arena + o_graphs); b->d_items = (PoItem*)(arena + o_items); b->d_jgraphs = (int*)(arena + o_jg);
   }
   *total_bytes = carve.off;
@@ -334,6 +352,7 @@ extern "C" int slslam_po_batch_reset(slslam_po_batch* b, void* stream) {
   if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (!b->finalized) return SLSLAM_ERR_STATE;
   b->have_results = false;
+  b->cov_pending = b->cov_valid = false;    // (a covariance enqueued before this call is no longer the covariance at the batch's poses)
   if (b->active.empty()) return SLSLAM_OK;
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipMemcpyAsync(b->arena, b->h_up, b->up_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
@@ -344,6 +363,7 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
   if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (!b->finalized) return SLSLAM_ERR_STATE;
   b->have_results = false;
+  b->cov_pending = b->cov_valid = false;    // (a covariance enqueued before this call is no longer the covariance at the batch's poses)
   const int A = (int)b->active.size();
   if (A == 0) return SLSLAM_OK;
   HIP_TRY(hipSetDevice(b->device));
@@ -411,6 +431,7 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
     hipLaunchKernelGGL(k_pob_edge_report, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, (const PoBatchGraph*)b->d_graphs, (const PoItem*)(b->d_items + b->edge_off));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(b->h_down, b->arena, b->down_bytes, hipMemcpyDeviceToHost, s));
+    if (b->cov_pending) HIP_TRY(hipMemcpyAsync(b->cov_h_down, b->cov_dev + b->cov_plan.down_off, b->cov_plan.down_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   int steps = 0;
@@ -425,11 +446,19 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
       G.report.resize((size_t)2 * G.E);
       std::memcpy(G.report.data(), b->h_down + b->o_report[(size_t)a], sizeof(double) * 2 * (size_t)G.E);
       steps = std::max(steps, G.st.n_success + G.st.n_unsuccess);
+      if (!b->cov_pending) continue;
+      const PoCovPlan& P = b->cov_plan;      // the covariances enqueued since the last download come back with the other results
+      std::memcpy(&G.cov_status, b->cov_h_down + P.o_status + sizeof(int) * (size_t)a, sizeof(int));
+      G.cov_poses.resize((size_t)36 * G.N);
+      std::memcpy(G.cov_poses.data(), b->cov_h_down + P.o_poses[(size_t)a], sizeof(double) * 36 * (size_t)G.N);
+      G.cov_pairs.resize((size_t)36 * G.cov_pa.size());
+      if (!G.cov_pa.empty()) std::memcpy(G.cov_pairs.data(), b->cov_h_down + P.o_pairs[(size_t)a], sizeof(double) * 36 * G.cov_pa.size());
     }
   } catch (const std::bad_alloc&) {
     return SLSLAM_ERR_NO_MEMORY;
   }
   if (A > 0) b->iter_hint = steps;
+  if (b->cov_pending) { b->cov_pending = false; b->cov_valid = true; }
   b->have_results = true;
   return SLSLAM_OK;
 }
@@ -480,6 +509,92 @@ extern "C" int slslam_po_batch_get_trace(const slslam_po_batch* b, int index, sl
   const int rc = po_batch_graph(b, index, &G);
   if (rc != SLSLAM_OK) return rc;
   po_export_trace(G->st, G->trace.data(), trace, cap, len);      // (a graph without edges: its state is all zero, no records)
+  return SLSLAM_OK;
+}
+
+// ---- covariances of the batch's graphs (po_covariance.h: the kernels and the plan)
+extern "C" int slslam_po_batch_set_covariance_pairs(slslam_po_batch* b, int index, int num_pairs, const int* pair_a, const int* pair_b) {
+  if (!b || index < 0 || index >= (int)b->graphs.size()) return SLSLAM_ERR_INVALID_ARGUMENT;
+  slslam_po_batch::Graph& G = b->graphs[(size_t)index];
+  if (!po_cov_pairs_ok(G.N, num_pairs, pair_a, pair_b)) return SLSLAM_ERR_INVALID_ARGUMENT;
+  try {
+    std::vector<int> pa(pair_a, pair_a + num_pairs), pb(pair_b, pair_b + num_pairs);
+    G.cov_pa.swap(pa); G.cov_pb.swap(pb);
+  } catch (const std::bad_alloc&) {
+    return SLSLAM_ERR_NO_MEMORY;
+  }
+  b->cov_dirty = true;
+  b->cov_pending = b->cov_valid = false;    // (results of a call made with the previous list no longer match the list)
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_po_batch_covariance(slslam_po_batch* b, void* stream) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized) return SLSLAM_ERR_STATE;
+  const int A = (int)b->active.size();
+  ++b->cov_calls;
+  b->cov_valid = false;
+  if (A == 0) { b->cov_pending = true; return SLSLAM_OK; }
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (b->cov_dirty) {
+    try {
+      std::vector<PoCovInput> in((size_t)A);
+      for (int a = 0; a < A; ++a) {
+        const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
+        const PoBatchGraph& D = b->h_desc[(size_t)a];
+        PoCovInput& I = in[(size_t)a];
+        I.N = G.N; I.E = G.E; I.n = G.sym.n; I.ld = G.sym.ld;
+        I.d_p1 = D.p.p1; I.d_p2 = D.p.p2; I.d_slot = D.p.slot; I.d_cons = D.p.cons;      // the batch's own arrays: the chains-first slots do as well as any
+        I.d_x_src = D.p.x; I.d_st_src = D.p.st; I.d_x0 = D.x0;
+        I.pa = G.cov_pa.data(); I.pb = G.cov_pb.data(); I.P = (int)G.cov_pa.size();
+      }
+      PoCovPlan plan;
+      const size_t bytes = po_cov_layout(in, b->huber, PoCarve(), nullptr, nullptr, &plan);
+      HIP_TRY(hipStreamSynchronize(s));     // (an earlier covariance call may still read the plan that is about to be replaced)
+      if (bytes > b->cov_dev_bytes) {
+        if (b->cov_dev) (void)hipFree(b->cov_dev);
+        b->cov_dev = nullptr; b->cov_dev_bytes = 0;
+        HIP_TRY(hipMalloc((void**)&b->cov_dev, bytes));
+        b->cov_dev_bytes = bytes; ++b->cov_allocs;
+      }
+      if (plan.down_bytes > b->cov_down_cap) {
+        if (b->cov_h_down) (void)hipHostFree(b->cov_h_down);
+        b->cov_h_down = nullptr; b->cov_down_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&b->cov_h_down, plan.down_bytes, hipHostMallocDefault));
+        b->cov_down_cap = plan.down_bytes; ++b->cov_allocs;
+      }
+      std::vector<char> img;
+      po_cov_layout(in, b->huber, PoCarve(), b->cov_dev, &img, &plan);
+      HIP_TRY(hipMemcpyAsync(b->cov_dev + plan.img_off, img.data(), plan.img_bytes, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipStreamSynchronize(s));     // (img leaves scope)
+      HIP_TRY(po_cov_lds_attribute());
+      b->cov_plan = std::move(plan);
+      b->cov_dirty = false;
+    } catch (const std::bad_alloc&) {
+      return SLSLAM_ERR_NO_MEMORY;
+    }
+  }
+  const int rc = po_cov_enqueue(b->cov_plan, s);
+  if (rc == SLSLAM_OK) b->cov_pending = true;
+  return rc;
+}
+
+extern "C" int slslam_po_batch_get_covariance(const slslam_po_batch* b, int index, int* status, double* cov_poses, double* cov_pairs) {
+  if (!b || index < 0 || index >= (int)b->graphs.size() || !b->cov_valid) return SLSLAM_ERR_INVALID_ARGUMENT;
+  const slslam_po_batch::Graph& G = b->graphs[(size_t)index];
+  const size_t np = 36 * (size_t)G.N, nq = 36 * G.cov_pa.size();
+  const bool have = G.active >= 0;           // (a graph without edges has no free pose: zeros)
+  if (status) *status = have ? G.cov_status : SLSLAM_COV_OK;
+  if (cov_poses && np) { if (have) std::memcpy(cov_poses, G.cov_poses.data(), sizeof(double) * np); else std::memset(cov_poses, 0, sizeof(double) * np); }
+  if (cov_pairs && nq) { if (have) std::memcpy(cov_pairs, G.cov_pairs.data(), sizeof(double) * nq); else std::memset(cov_pairs, 0, sizeof(double) * nq); }
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_po_batch_covariance_stats(const slslam_po_batch* b, long long* calls, long long* allocations) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (calls) *calls = b->cov_calls;
+  if (allocations) *allocations = b->cov_allocs;
   return SLSLAM_OK;
 }
 
