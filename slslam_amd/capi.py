@@ -111,7 +111,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    # SLSLAM_HIP_LIBRARY: a variant build of the same library (kernel experiments, tools/variant_lib.sh); still a HIP library - no fallback
+    # SLSLAM_HIP_LIBRARY: a variant build of the same library (kernel experiments); still a HIP library - no fallback
     path = os.environ.get("SLSLAM_HIP_LIBRARY") or LIB_PATH
     if not os.path.exists(path):
         raise SlslamError(2, "libslslam_hip.so not built (run __graft_entry__.build()): " + path)

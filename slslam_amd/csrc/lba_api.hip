@@ -571,7 +571,7 @@ int plan_layout(slslam_lba_batch* b, const std::vector<PackedWindow>& wins, bool
       // (30 % when there are only two), the rest what is left, and the chunk array - the dispatch order - lists the classes one after
       // the other: a slot that is late with its long chunk takes fewer short ones.  The slab count per window - what the reduced
       // solve reads - does not change.
-      if (rounds >= 2 && cpw >= rounds && cpw < 1000 && b->elim_waves == 1 && wd.ntiles >= 8 * cpw && !std::getenv("SLSLAM_EQUAL_CHUNKS")) {
+      if (rounds >= 2 && cpw >= rounds && cpw < 1000 && b->elim_waves == 1 && wd.ntiles >= 8 * cpw) {
         graded_chunks = (int)cpw; graded_rounds = (int)rounds;
       }
     }
@@ -579,10 +579,6 @@ int plan_layout(slslam_lba_batch* b, const std::vector<PackedWindow>& wins, bool
     for (int c = 0; c < graded_chunks; ++c) {
       const int q = (int)(((long long)c * graded_rounds) / graded_chunks);           // the round of the slots this chunk belongs to
       weights[c] = q == 0 ? 84 : q == 1 ? (graded_rounds == 2 ? 36 : 24) : std::max(1, 12 / (graded_rounds - 2));
-    }
-    if (const char* ws = std::getenv("SLSLAM_CHUNK_WEIGHTS")) {           // (experiments: comma-separated weights of the window's chunks)
-      int c = 0;
-      for (const char* q = ws; *q && c < graded_chunks; ++c) { weights[c] = std::max(1, std::atoi(q)); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
     }
     std::vector<int> bounds = graded_chunks > 0 ? chunk_boundaries_graded(wd.ntiles, graded_chunks, weights) : chunk_boundaries(wd.ntiles, per_chunk);
     L.win_graded[wi] = (graded_chunks > 0 && (int)bounds.size() - 1 == graded_chunks) ? graded_rounds : 0;
@@ -1968,7 +1964,7 @@ int refill_enqueue(slslam_lba_batch* b, int B, const RefillPlan& z, hipStream_t 
   LayoutArgs a;
   std::memset(&a, 0, sizeof(a));
   a.chunks_per_window = b->opt.chunks_per_window; a.reproducible = b->opt.reproducible; a.auto_rounds = b->auto_rounds; a.auto_cpw = b->auto_cpw;
-  a.elim_waves = b->elim_waves; a.elim_mode = b->elim_mode; a.equal_chunks = std::getenv("SLSLAM_EQUAL_CHUNKS") ? 1 : 0;
+  a.elim_waves = b->elim_waves; a.elim_mode = b->elim_mode;
   a.cap_tiles = (int)std::min<size_t>(b->d_tiles.n, 0x7fffffff); a.cap_items = (int)std::min<size_t>(b->d_items.n / 2, 0x7fffffff); a.cap_chunks = b->nchunk;
   a.cap_maxn = b->cap_maxn; a.slab_sum = b->slab_sum_stride ? 1 : 0; a.slab_sum_image = b->slab_sum_image ? 1 : 0;
   a.cap_slab = (long long)b->d_slab.n; a.cap_sys = (long long)b->d_ysys.n; a.slab_sum_stride = b->slab_sum_stride;
@@ -2020,7 +2016,6 @@ int refill_enqueue(slslam_lba_batch* b, int B, const RefillPlan& z, hipStream_t 
 // observation) - 68 instead of 80 bytes per observation over the host link.
 int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, hipStream_t s, hipStream_t s_in, const unsigned int* const* packed = nullptr) {
   if (b->opt.device_build < 0 || b->d_rawwin.n < (size_t)std::max(1, B) || !b->d_ob_raw.p) return SLSLAM_ERR_UNSUPPORTED;
-  if (std::getenv("SLSLAM_CHUNK_WEIGHTS")) return SLSLAM_ERR_UNSUPPORTED;          // (an experiment knob of the host-side cut)
   // (k_build_layout dispatches graded chunks in at most kLayoutMaxRank classes: a batch cut for more rounds of the wave slots - several
   // thousand 2000-line windows - keeps the host packer)
   if ((b->opt.chunks_per_window < 0 ? (-b->opt.chunks_per_window) / 1000 : (b->opt.reproducible ? 3 : b->auto_rounds)) > (int)kLayoutMaxRank) return SLSLAM_ERR_UNSUPPORTED;

@@ -145,10 +145,7 @@ __device__ __forceinline__ void big_F_obs(const BatchPtrs& p, const BigPtrs& bg,
       for (int r = 0; r < 4; ++r) s += J[6 * r + a] * J[24 + 4 * r + b];
       h[b] = s;
     }
-    F[4 * a + 0] = h[0] * K[0];
-    F[4 * a + 1] = h[0] * K[1] + h[1] * K[2];
-    F[4 * a + 2] = h[0] * K[3] + h[1] * K[4] + h[2] * K[5];
-    F[4 * a + 3] = h[0] * K[6] + h[1] * K[7] + h[2] * K[8] + h[3] * K[9];
+    f_row(h, K, F + 4 * a);
   }
 }
 
@@ -230,10 +227,7 @@ __global__ __launch_bounds__(256) void k_big_line(BatchPtrs p, BigPtrs bg, Polic
   if (line_active) ok = chol4_inverse(H, D2, K);
   else { for (int q = 0; q < 10; ++q) K[q] = 0.0; }
   if (line_active) {
-    u[0] = K[0] * g[0];
-    u[1] = K[1] * g[0] + K[2] * g[1];
-    u[2] = K[3] * g[0] + K[4] * g[1] + K[5] * g[2];
-    u[3] = K[6] * g[0] + K[7] * g[1] + K[8] * g[2] + K[9] * g[3];
+    chol4_apply(K, g, u);
     if (st->need_grad_check)
       for (int a = 0; a < 4; ++a) gm = fmax(gm, fabs(g[a] / sl[a]));
   }
@@ -249,7 +243,7 @@ __global__ __launch_bounds__(256) void k_big_line(BatchPtrs p, BigPtrs bg, Polic
   if (lane != 0) return;                                  // every lane holds the same values; one writes
   if (fresh) for (int a = 0; a < 4; ++a) lsc[a] = sl[a];
   la[kBlGmax] = gm; la[kBlXn2] = xn2; la[kBlFail] = ok ? 0.0 : 1.0;
-  double* le = p.line_elim + (long long)ls * p.line_elim_stride;
+  double* le = line_elim_rec(p, ls);
   for (int q = 0; q < 10; ++q) le[q] = K[q];
   for (int q = 0; q < 4; ++q) { le[kLeU + q] = u[q]; le[kLeD2 + q] = D2[q]; le[kLeG + q] = g[q]; }
 }
@@ -271,7 +265,7 @@ __global__ __launch_bounds__(128) void k_big_F(BatchPtrs p, BigPtrs bg) {
   if (o >= bg.nobs) return;
   const int ls = bg.ob_line[o], w = p.line_win[ls];
   if (p.state[w].status != kRunning) return;
-  big_F_obs(p, bg, o, ls, p.wins[w], p.line_elim + (long long)ls * p.line_elim_stride);
+  big_F_obs(p, bg, o, ls, p.wins[w], line_elim_rec(p, ls));
 }
 
 // One workgroup (4 waves) per free camera: its record of the reduced system - diagonal block Jc^T Jc - F F^T (21), b = Jc^T r - F u
@@ -659,14 +653,11 @@ __global__ __launch_bounds__(256) void k_big_backsub_line(BatchPtrs p, BigPtrs b
         wv[m] += wave_sum(cf >= 0 ? v : 0.0);
       }
     }
-    const double* le = p.line_elim + (long long)ls * p.line_elim_stride;
+    const double* le = line_elim_rec(p, ls);
     const double* lsc = p.line_scale + (long long)ls * 4;
-    const double z0 = le[kLeU] - wv[0], z1 = le[kLeU + 1] - wv[1], z2 = le[kLeU + 2] - wv[2], z3 = le[kLeU + 3] - wv[3];
+    const double z[4] = { le[kLeU] - wv[0], le[kLeU + 1] - wv[1], le[kLeU + 2] - wv[2], le[kLeU + 3] - wv[3] };
     double y[4];
-    y[0] = le[0] * z0 + le[1] * z1 + le[3] * z2 + le[6] * z3;
-    y[1] = le[2] * z1 + le[4] * z2 + le[7] * z3;
-    y[2] = le[5] * z2 + le[8] * z3;
-    y[3] = le[9] * z3;
+    chol4_apply_t(le, z, y);
     for (int a = 0; a < 4; ++a) {
       model += 0.5 * y[a] * (le[kLeG + a] + le[kLeD2 + a] * y[a]);
       const double v = xn[a] - y[a] * lsc[a];

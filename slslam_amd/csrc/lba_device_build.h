@@ -106,7 +106,7 @@ struct BuildPtrs {
 
 // How k_build_layout cuts (the batch-wide numbers slslam_lba_batch_finalize resolved: plan_layout with frozen = true) and what has to fit.
 struct LayoutArgs {
-  int chunks_per_window, reproducible, auto_rounds, auto_cpw, elim_waves, elim_mode, equal_chunks;
+  int chunks_per_window, reproducible, auto_rounds, auto_cpw, elim_waves, elim_mode;
   int cap_tiles, cap_items, cap_chunks, cap_maxn, slab_sum, slab_sum_image;
   long long cap_slab, cap_sys, slab_sum_stride;
   int nline, nobs;            // totals of the refill (host-known): the end of the line pointers
@@ -754,7 +754,7 @@ __device__ inline int layout_window_chunks(const LayoutArgs& a, int ntiles, int*
     long long rounds = a.auto_rounds, cpw = a.auto_cpw;
     if (a.reproducible) { cpw = max(1, (ntiles + 33) / 34); rounds = 3; }
     per = (int)max((long long)a.elim_waves, (ntiles + cpw - 1) / cpw);
-    if (rounds >= 2 && cpw >= rounds && cpw < 1000 && a.elim_waves == 1 && ntiles >= 8 * cpw && !a.equal_chunks) { gc = (int)cpw; gr = (int)rounds; }
+    if (rounds >= 2 && cpw >= rounds && cpw < 1000 && a.elim_waves == 1 && ntiles >= 8 * cpw) { gc = (int)cpw; gr = (int)rounds; }
   }
   *graded_chunks = gc; *graded_rounds = gr; *per_chunk = per;
   if (ntiles <= 0) return 0;

@@ -32,26 +32,10 @@
 #include "lba_eliminate_mfma.h"
 #include "lba_eliminate_grouped_maps.h"
 
-// timing experiments (results WRONG when set): 1 no matrix-core phase, 2 operands fetched but no products issued, 4 one product per line only
-#if !defined(GP_ABLATE)
-#define GP_ABLATE 0
-#endif
-// lines fetched together per block count (1: one by one)
-#if !defined(GP_GB1)
-#define GP_GB1 4
-#endif
-#if !defined(GP_GB2)
-#define GP_GB2 4
-#endif
-#if !defined(GP_GB3)
-#define GP_GB3 2
-#endif
-#if !defined(GP_SETPRIO)
-#define GP_SETPRIO 1
-#endif
-
 namespace slslam {
 
+// lines fetched together per block count (1: one by one)
+constexpr int kGpGb1 = 4, kGpGb2 = 4, kGpGb3 = 2;
 
 __host__ __device__ inline int lds_bytes_eliminate_grouped(int C, int n) {
   return (kGpPanel + C * kCamTabG + (n / 6) * kDiagRec) * 8 + ((C + 15) / 16) * 16;
@@ -194,9 +178,7 @@ void k_eliminate_grouped(BatchPtrs p, Policy pol) {
     bool row3_used = false;
     auto products = [&](auto nbtag, const double (&X)[4]) {
       constexpr int NB = decltype(nbtag)::value;
-      if (GP_ABLATE & 2) { for (int r = 0; r < NB; ++r) keep_alive(X[r]); return; }
       acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(X[0], X[0], acc[0], 0, 0, 0);
-      if (GP_ABLATE & 4) { for (int r = 1; r < NB; ++r) keep_alive(X[r]); return; }
       if (NB >= 2) {
         acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(X[1], X[0], acc[1], 0, 0, 0);
         acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(X[1], X[1], acc[2], 0, 0, 0);
@@ -264,8 +246,8 @@ void k_eliminate_grouped(BatchPtrs p, Policy pol) {
       for (int c = 0; c < 4; ++c) { grouped_flush_tile(slab, row3[c], 3, c, a, n, l2); row3[c] = solve_acc_t{ 0.0, 0.0, 0.0, 0.0 }; }
       row3_used = false;
     };
-    if (GP_SETPRIO) __builtin_amdgcn_s_setprio(1);   // the few VALU slots this phase needs come first: they feed the matrix pipe
-    const int nact = (GP_ABLATE & 1) ? 0 : __popcll(__ballot(d_active));
+    __builtin_amdgcn_s_setprio(1);   // the few VALU slots this phase needs come first: they feed the matrix pipe
+    const int nact = __popcll(__ballot(d_active));
     for (int sb = 0; sb < nact;) {                   // a segment: the lines of one group (a tile has one, at a seam two)
       const int a = (int)(((unsigned)__builtin_amdgcn_readlane((int)descv, sb) >> 16) & 15u);
       const bool in_seg = d_active && d_group == (unsigned)a;
@@ -275,16 +257,16 @@ void k_eliminate_grouped(BatchPtrs p, Policy pol) {
         if (cur_a >= 0) { flush_group(cur_a); if (row3_used) flush_row3(cur_a); }
         cur_a = a;
       }
-      run(sb, e1, std::integral_constant<int, 1>(), std::integral_constant<int, GP_GB1>());
-      run(e1, e2, std::integral_constant<int, 2>(), std::integral_constant<int, GP_GB2>());
-      run(e2, e3, std::integral_constant<int, 3>(), std::integral_constant<int, GP_GB3>());
+      run(sb, e1, std::integral_constant<int, 1>(), std::integral_constant<int, kGpGb1>());
+      run(e1, e2, std::integral_constant<int, 2>(), std::integral_constant<int, kGpGb2>());
+      run(e2, e3, std::integral_constant<int, 3>(), std::integral_constant<int, kGpGb3>());
       if (e4 > e3) { run(e3, e4, std::integral_constant<int, 4>(), std::integral_constant<int, 1>()); row3_used = true; }
       sb = e4;
     }
     SLS_K1_STAMP(6);
     SLS_PHASE("row3");
     if (row3_used) flush_row3(cur_a);
-    if (GP_SETPRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     SLS_K1_STAMP(9);
   };
 
@@ -424,6 +406,7 @@ void k_eliminate_grouped(BatchPtrs p, Policy pol) {
       SLS_PHASE("factor4x4");
       double K[10], z[4] = { 0, 0, 0, 0 };
       {
+        // (u and z spelled out, not chol4_apply / chol4_apply_t: the helpers move this sweep's register allocation, profiles/lba_prune_isa.txt)
         double D2[4], u[4];
         lm_diag4(H, pol, inv_radius, D2);
         bool okc = true;
@@ -477,7 +460,7 @@ void k_eliminate_grouped(BatchPtrs p, Policy pol) {
         double* rec = diag + (cam_free ? cf : 0) * kDiagRec;
         // (no skewed adds here - the packer's flag for lanes of a row that share a camera, see the diagonal block of
         // k_linearise_schur: with a third of that sweep's LDS atomics left it measures neutral, 1.224 / 1.222 ms)
-        auto emit = [&](int off, double val) { if (cam_free) lds_add_rec(rec + off, val); };
+        auto emit = [&](int off, double val) { if (cam_free) lds_add(rec + off, val); };
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
           JT gaj = 0, hj[4] = { 0, 0, 0, 0 };
@@ -488,12 +471,10 @@ void k_eliminate_grouped(BatchPtrs p, Policy pol) {
             for (int b = 0; b < 4; ++b) hj[b] += Jc[6 * r + a] * Jl[4 * r + b];
           }
           const double ga = (double)gaj, h[4] = { (double)hj[0], (double)hj[1], (double)hj[2], (double)hj[3] };
-          const double f0 = h[0] * K[0];
-          const double f1 = h[0] * K[1] + h[1] * K[2];
-          const double f2 = h[0] * K[3] + h[1] * K[4] + h[2] * K[5];
-          const double f3 = h[0] * K[6] + h[1] * K[7] + h[2] * K[8] + h[3] * K[9];
-          reinterpret_cast<double2*>(slabF)[2 * a] = make_double2(f0, f1);
-          reinterpret_cast<double2*>(slabF)[2 * a + 1] = make_double2(f2, f3);
+          double f[4];
+          f_row(h, K, f);
+          reinterpret_cast<double2*>(slabF)[2 * a] = make_double2(f[0], f[1]);
+          reinterpret_cast<double2*>(slabF)[2 * a + 1] = make_double2(f[2], f[3]);
           if (keep) {                                    // (every lane: whole 1 KB rows)
             hkeep[(2 * a) * 64] = make_double2(h[0], h[1]);
             hkeep[(2 * a + 1) * 64] = make_double2(h[2], h[3]);
@@ -599,7 +580,7 @@ void k_eliminate_grouped(BatchPtrs p, Policy pol) {
           reinterpret_cast<double2*>(slabF)[2 * a] = make_double2(f0, f1);
           reinterpret_cast<double2*>(slabF)[2 * a + 1] = make_double2(f2, f3);
           const double fu = h0 * z[0] + h1 * z[1] + h2 * z[2] + h3 * z[3];
-          if (cam_free) lds_add_rec(rec + kDiagB + a, -fu);
+          if (cam_free) lds_add(rec + kDiagB + a, -fu);
         }
       }
       SLS_PHASE("replay_request");

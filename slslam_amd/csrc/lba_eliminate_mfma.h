@@ -283,6 +283,7 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
       }
 
       // ---- eliminate the line: A = H + D^2, A^-1 = K^T K
+      // (u = K g spelled out, not chol4_apply: the helper moves this sweep's register allocation, profiles/lba_prune_isa.txt)
       double D2[4], K[10], u[4] = { 0, 0, 0, 0 };
       lm_diag4(H, pol, inv_radius, D2);
       bool okc = true;
@@ -298,13 +299,7 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
         if (need_grad && line_ok && j == 0) {
           for (int a = 0; a < 4; ++a) acc_gmax = fmax(acc_gmax, fabs(g[a] / pf.lsc[a]));
         }
-        if (j == 0) {                                  // the line's factor, for the back-substitution of this iteration
-          double* le = p.line_elim + (long long)ls * p.line_elim_stride;
-#pragma unroll
-          for (int q = 0; q < 10; ++q) le[q] = K[q];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) { le[kLeD2 + q] = D2[q]; le[kLeG + q] = g[q]; }
-        }
+        if (j == 0) store_line_elim(line_elim_rec(p, ls), K, D2, g);      // the line's factor, for the back-substitution of this iteration
       }
       SLS_STAMP(4);
       // ---- Z = Y K^T in place (column m = sum_{b <= m} K[m][b] Y_b), F' = Mc Z to the panel, b' = Mc (w - Z u)

@@ -224,24 +224,6 @@ __device__ __forceinline__ double wave_max(double v) {
 __device__ __forceinline__ void lds_add(double* p, double v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-// Timing experiments of the elimination sweep (SLSLAM_EXTRA_FLAGS=-DSLSLAM_ABLATE=<bits>, tools/gpu_variant_bench.sh; results are
-// WRONG when set): 1 pair-block atomics dropped (products still computed), 4 camera-record atomics dropped, 8 pair-block
-// atomics replaced by plain stores, 16 camera-record atomics replaced by stores, 64 back-substitution: every lane reads the first
-// line's factor record (are those loads waited for?).
-#if !defined(SLSLAM_ABLATE)
-#define SLSLAM_ABLATE 0
-#endif
-__device__ __forceinline__ void keep_alive(double v) { asm volatile("" : : "v"(v)); }
-__device__ __forceinline__ void lds_add_pair(double* p, double v) {
-  if (SLSLAM_ABLATE & 1) keep_alive(v);
-  else if (SLSLAM_ABLATE & 8) *(volatile double*)p = v;
-  else lds_add(p, v);
-}
-__device__ __forceinline__ void lds_add_rec(double* p, double v) {
-  if (SLSLAM_ABLATE & 4) keep_alive(v);
-  else if (SLSLAM_ABLATE & 16) *(volatile double*)p = v;
-  else lds_add(p, v);
-}
 
 // ------------------------------------------------------------------------------------------
 // Everything a lane knows about its observation and its line after linearisation.
@@ -280,9 +262,6 @@ __device__ __forceinline__ TileReq request_tile(const BatchPtrs& p, int t, int t
   const int* tl = reinterpret_cast<const int*>(p.tiles + tt);    // Tile: line_begin | nlines, flags | item_off | nitems (separate loads: a sweep
   q.nl = tl[1];                                                  // that does not use a part does not carry it)
   q.items = *reinterpret_cast<const int2*>(tl + 2);
-#if defined(SLS_BLOCKING_TILE_FETCH)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // timing control: ONE exposed round trip per tile (the old chain had three)
-#endif
   return q;
 }
 __device__ __forceinline__ TileCtx resolve_tile(const TileReq& q) {
@@ -331,13 +310,8 @@ struct ObsPref {
 template <bool WITH_U, bool WITH_ITEMS = false>
 __device__ __forceinline__ void prefetch_obs(const BatchPtrs& p, const TileCtx& c, int cur, int safe_obs, ObsPref& f, int lane = 0) {
   const bool valid = c.line_ok && c.j < c.k;
-#if defined(SLS_ABLATE_OBS_CACHED)
-  const int o = safe_obs + (c.j & 7);                 // timing experiment (results WRONG): every tile reads the same few observations and lines - cache hits
-  const int lsafe = c.j & 7;
-#else
   const int o = valid ? c.o0 + c.j : safe_obs;
   const int lsafe = c.line_ok ? c.ls : 0;
-#endif
 #pragma unroll
   for (int q = 0; q < 4; ++q) {     // (x,y) endpoint pairs: one 16-byte load per plane
     const double2 e = reinterpret_cast<const double2*>(p.ob)[(long long)q * p.ob_stride + o];
@@ -492,11 +466,7 @@ __device__ __forceinline__ void line_block(const LaneLin& L, const SegCtx& sg, d
     for (int r = 0; r < 4; ++r) ga += L.Jl[4 * r + a] * L.rs[r];
     v[10 + a] = ga;
   }
-#if defined(SLSLAM_SEG_TOTAL_BPERMUTE)        // round-2 form, for comparison: 28 ds_bpermute per tile
-  seg_sum_n<14>(v, sg);
-#else
   seg_sum_n<14, false, true>(v, sg);
-#endif
 #pragma unroll
   for (int i = 0; i < 10; ++i) H[i] = v[i];
 #pragma unroll
@@ -541,6 +511,38 @@ __device__ __forceinline__ void lm_diag4(const double H[10], const Policy& pol, 
   for (int a = 0; a < 4; ++a) D2[a] = fmin(fmax(d[a], pol.min_lm_diagonal), pol.max_lm_diagonal) * inv_radius;
 }
 
+// Products with the packed lower-triangular K of chol4_inverse:  out = K v,  out = K^T v,  and one row f = h K^T of a block
+// F = (Jc^T Jl) K^T.  The operation order is part of the contract (the sweeps are compared bit for bit).  A few sites of the
+// register-bound sweeps spell the same lines out where the helper form changed their code (profiles/lba_prune_isa.txt).
+__device__ __forceinline__ void chol4_apply(const double* K, const double v[4], double out[4]) {
+  out[0] = K[0] * v[0];
+  out[1] = K[1] * v[0] + K[2] * v[1];
+  out[2] = K[3] * v[0] + K[4] * v[1] + K[5] * v[2];
+  out[3] = K[6] * v[0] + K[7] * v[1] + K[8] * v[2] + K[9] * v[3];
+}
+__device__ __forceinline__ void chol4_apply_t(const double* K, const double v[4], double out[4]) {
+  out[0] = K[0] * v[0] + K[1] * v[1] + K[3] * v[2] + K[6] * v[3];
+  out[1] = K[2] * v[1] + K[4] * v[2] + K[7] * v[3];
+  out[2] = K[5] * v[2] + K[8] * v[3];
+  out[3] = K[9] * v[3];
+}
+__device__ __forceinline__ void f_row(const double h[4], const double* K, double* f) {
+  f[0] = h[0] * K[0];
+  f[1] = h[0] * K[1] + h[1] * K[2];
+  f[2] = h[0] * K[3] + h[1] * K[4] + h[2] * K[5];
+  f[3] = h[0] * K[6] + h[1] * K[7] + h[2] * K[8] + h[3] * K[9];
+}
+
+// The line's record in BatchPtrs.line_elim (lba_types.h: K[10] | D2[4] at kLeD2 | g[4] at kLeG | u[4] at kLeU where the stride has
+// room for it), written by the line's first lane for the back-substitution of the same iteration.
+__device__ __forceinline__ double* line_elim_rec(const BatchPtrs& p, int ls) { return p.line_elim + (long long)ls * p.line_elim_stride; }
+__device__ __forceinline__ void store_line_elim(double* le, const double K[10], const double D2[4], const double g[4]) {
+#pragma unroll
+  for (int q = 0; q < 10; ++q) le[q] = K[q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { le[kLeD2 + q] = D2[q]; le[kLeG + q] = g[q]; }
+}
+
 // F = (Jc^T Jl) K^T  (6x4, row-major):  the line's share of the elimination, so that
 // H_cl A^-1 H_lc = F F^T  and  H_cl A^-1 g_l = F (K g_l).
 __device__ __forceinline__ void lane_F(const LaneLin& L, const double K[10], double F[24]) {
@@ -554,10 +556,7 @@ __device__ __forceinline__ void lane_F(const LaneLin& L, const double K[10], dou
       for (int r = 0; r < 4; ++r) s += L.Jc[6 * r + a] * L.Jl[4 * r + b];
       h[b] = s;
     }
-    F[4 * a + 0] = h[0] * K[0];
-    F[4 * a + 1] = h[0] * K[1] + h[1] * K[2];
-    F[4 * a + 2] = h[0] * K[3] + h[1] * K[4] + h[2] * K[5];
-    F[4 * a + 3] = h[0] * K[6] + h[1] * K[7] + h[2] * K[8] + h[3] * K[9];
+    f_row(h, K, F + 4 * a);
   }
 }
 
@@ -753,10 +752,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     else { for (int q = 0; q < 10; ++q) K[q] = 0.0; }
     if (!okc) fail = 1;
     if (line_active) {
-      u[0] = K[0] * g[0];
-      u[1] = K[1] * g[0] + K[2] * g[1];
-      u[2] = K[3] * g[0] + K[4] * g[1] + K[5] * g[2];
-      u[3] = K[6] * g[0] + K[7] * g[1] + K[8] * g[2] + K[9] * g[3];
+      chol4_apply(K, g, u);
       if (need_grad && line_ok && j == 0) {       // only the launch after an accepted step tests the gradient
         for (int a = 0; a < 4; ++a) acc_gmax = fmax(acc_gmax, fabs(g[a] * fast_rcp(pf.lsc[a])));
       }
@@ -778,7 +774,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     // the per-line factor is kept for the back-substitution of the same iteration (176 B per line against
     // ~500 B of observations): it does not have to rebuild and refactor the 4x4 block
     if (line_active && j == 0) {
-      double* le = p.line_elim + (long long)ls * p.line_elim_stride;
+      double* le = p.line_elim + (long long)ls * p.line_elim_stride;       // (spelled out, not store_line_elim: see profiles/lba_prune_isa.txt)
 #pragma unroll
       for (int q = 0; q < 10; ++q) le[q] = K[q];
 #pragma unroll
@@ -801,15 +797,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       // delayed value waits in two registers; selects and address arithmetic are VALU work, which this sweep has to spare.
       // (Three levels - the third same-camera lane of a row two steps late - measured slower: 1.26 -> 1.52 ms.)
       double* rec = S + L.cf * kCamAcc;
-#if defined(SLSLAM_NO_SKEW)
-      const bool skew = false;
-#else
       const bool skew = tc.skew;
-#endif
       double pval = 0.0;
       int poff = kRecB;
       auto emit = [&](int off, double val) {
-        lds_add_rec(rec + (skew ? poff : off), skew ? pval : val);
+        lds_add(rec + (skew ? poff : off), skew ? pval : val);
         pval = val; poff = off;
       };
 #pragma unroll
@@ -833,7 +825,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
           emit(tri_index(a, b), v);
         }
       }
-      if (skew) lds_add_rec(rec + poff, pval);             // the marked lanes' last entry
+      if (skew) lds_add(rec + poff, pval);             // the marked lanes' last entry
     }
 
     // ---- off-diagonal camera pairs of the tile, balanced over the lanes
@@ -864,7 +856,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
               double v = 0.0;                       // - F_j F_i^T: the sign rides on the fma's operand modifier
 #pragma unroll
               for (int m = 0; m < 4; ++m) v -= Fj[4 * a + m] * Fi[4 * b + m];
-              lds_add_pair(&blk[6 * a + b], v);
+              lds_add(&blk[6 * a + b], v);
             }
         } else {               // the same camera observes the line twice: symmetric part
           SLS_PHASE("pair_same_camera");
@@ -1668,12 +1660,7 @@ __device__ __forceinline__ void line_trig_step(const double trig0[7], const doub
 }
 
 // One or two waves per chunk workgroup (blockDim.x = 64 or 128): wave w takes the tiles tile_begin + w, + nw, ...
-#if defined(SLSLAM_BACKSUB_WAVES_PER_EU)       // occupancy experiments (SLSLAM_EXTRA_FLAGS=-DSLSLAM_BACKSUB_WAVES_PER_EU=3)
-#define SLS_BACKSUB_OCC __attribute__((amdgpu_waves_per_eu(SLSLAM_BACKSUB_WAVES_PER_EU, SLSLAM_BACKSUB_WAVES_PER_EU)))
-#else
-#define SLS_BACKSUB_OCC
-#endif
-__global__ __launch_bounds__(128) SLS_BACKSUB_OCC void k_backsub(BatchPtrs p, Policy pol) {
+__global__ __launch_bounds__(128) void k_backsub(BatchPtrs p, Policy pol) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   SLS_K1_STAMP_INIT;
@@ -1756,9 +1743,7 @@ __global__ __launch_bounds__(128) SLS_BACKSUB_OCC void k_backsub(BatchPtrs p, Po
     // D^2, g_l (the same values this sweep would recompute); every lane of the line's run reads the same record
     double K[10], D2[4], g[4];
     {
-      // (timing experiment 64: the record read from the chunk's first line only - same instructions, L2 hits: is the sweep waiting
-      // for these loads?)
-      const double* le = p.line_elim + (long long)((SLSLAM_ABLATE & 64) ? 0 : (tc.line_ok ? tc.ls : 0)) * p.line_elim_stride;
+      const double* le = p.line_elim + (long long)(tc.line_ok ? tc.ls : 0) * p.line_elim_stride;
 #pragma unroll
       for (int q = 0; q < 10; ++q) K[q] = le[q];
 #pragma unroll
@@ -1789,16 +1774,10 @@ __global__ __launch_bounds__(128) SLS_BACKSUB_OCC void k_backsub(BatchPtrs p, Po
     const bool head = line_ok && j == 0;
     if (line_active) {
       // z = K (g - w);  y = K^T z
-      const double e0 = g[0] - wv[0], e1 = g[1] - wv[1], e2 = g[2] - wv[2], e3 = g[3] - wv[3];
-      const double z0 = K[0] * e0;
-      const double z1 = K[1] * e0 + K[2] * e1;
-      const double z2 = K[3] * e0 + K[4] * e1 + K[5] * e2;
-      const double z3 = K[6] * e0 + K[7] * e1 + K[8] * e2 + K[9] * e3;
-      double y[4];
-      y[0] = K[0] * z0 + K[1] * z1 + K[3] * z2 + K[6] * z3;
-      y[1] = K[2] * z1 + K[4] * z2 + K[7] * z3;
-      y[2] = K[5] * z2 + K[8] * z3;
-      y[3] = K[9] * z3;
+      const double e[4] = { g[0] - wv[0], g[1] - wv[1], g[2] - wv[2], g[3] - wv[3] };
+      double z[4], y[4];
+      chol4_apply(K, e, z);
+      chol4_apply_t(K, z, y);
       for (int a = 0; a < 4; ++a) {
         const double v = xn[a] - y[a] * pf.lsc[a];
         const double dd = xn[a] - v;
@@ -1915,16 +1894,13 @@ __global__ __launch_bounds__(64) void k_backsub_stream(BatchPtrs p, Policy pol) 
       double* xc = p.line_x + line_rec(p, ls, (1 - cur));
       double xn[4] = { xl[0], xl[1], xl[2], xl[3] };
       if (line_active) {
-        const double* le = p.line_elim + (long long)ls * p.line_elim_stride;
+        const double* le = line_elim_rec(p, ls);
         double K[10];
 #pragma unroll
         for (int q = 0; q < 10; ++q) K[q] = le[q];
-        const double z0 = le[kLeU] - v[0], z1 = le[kLeU + 1] - v[1], z2 = le[kLeU + 2] - v[2], z3 = le[kLeU + 3] - v[3];
+        const double z[4] = { le[kLeU] - v[0], le[kLeU + 1] - v[1], le[kLeU + 2] - v[2], le[kLeU + 3] - v[3] };
         double y[4];
-        y[0] = K[0] * z0 + K[1] * z1 + K[3] * z2 + K[6] * z3;
-        y[1] = K[2] * z1 + K[4] * z2 + K[7] * z3;
-        y[2] = K[5] * z2 + K[8] * z3;
-        y[3] = K[9] * z3;
+        chol4_apply_t(K, z, y);
         const double* lsc = p.line_scale + (long long)ls * 4;
 #pragma unroll
         for (int a = 0; a < 4; ++a) {

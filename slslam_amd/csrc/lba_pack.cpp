@@ -342,8 +342,6 @@ int pack_window(const slslam_lba_window* w, PackedWindow* out, int grouping, con
     // written past the caches (when the four planes are 16-byte aligned, which the image's are)
     bool stream_out = ob_dest != nullptr;
     for (int q = 0; q < 4; ++q) if (reinterpret_cast<uintptr_t>(pl[q]) & 15u) stream_out = false;
-    static const bool no_stream = std::getenv("SLSLAM_PACK_NO_STREAMING_STORES") != nullptr;      // (measurement switch)
-    if (no_stream) stream_out = false;
     uint64_t nonfinite = 0;
     if (ob_dest && ob_dest->raw) {
       // the device gathers (refill): here only the linear copy of the caller's array, tested for NaN / Inf on the way, and the sorted camera ids
@@ -351,7 +349,7 @@ int pack_window(const slslam_lba_window* w, PackedWindow* out, int grouping, con
       double* dst = ob_dest->raw;
       const size_t n8 = (size_t)8 * (size_t)M;
 #if defined(__SSE2__)
-      if (!(reinterpret_cast<uintptr_t>(dst) & 15u) && !no_stream) {
+      if (!(reinterpret_cast<uintptr_t>(dst) & 15u)) {
         // (non-temporal 16-byte stores, the exponent test of all_finite on the same registers)
         const __m128i expo = _mm_set1_epi64x((long long)0x7ff0000000000000ull), one = _mm_set1_epi64x((long long)0x0010000000000000ull);
         __m128i acc = _mm_setzero_si128();
