@@ -390,7 +390,18 @@ typedef struct slslam_po_graph {
   const int*    pose_index_2;     /* [E]                                               */
   const double* constraints;      /* [6E]: (w,t) of C = T_{n2<-n1}                     */
   double*       parameters;       /* [6N] in/out: (w,t) per pose; pose_index_1[0] is held constant */
+  const double* sqrt_information; /* [36E] row-major W_e, or NULL: identity */
 } slslam_po_graph;
+/* sqrt_information (an extension: the reference's edges are unweighted, src/po_problem.h:68-108): W_e is ANY 6 x 6 matrix with
+ * W_e^T W_e = Omega_e, the edge's information matrix - it need not be symmetric or triangular, any finite values are accepted, and a
+ * non-finite entry is SLSLAM_ERR_INVALID_ARGUMENT, found before a device is needed.  The residual block of edge e becomes W_e Te and
+ * its two Jacobian blocks W_e J1, W_e J2; the loss of po_huber_delta acts on s = |W_e Te|^2 (the weight inside the functor, as Ceres
+ * has it), so every cost, the Jacobi scale, the gradient and the model see whitened blocks.  With the edges' true information matrices
+ * s is chi-square with 6 degrees of freedom.  An all-zero W_e removes its edge (the LM damping keeps the solve defined).  NULL runs
+ * the kernels there were before the field existed.  Fill the struct value-initialised (slslam_po_graph g = {0}) so that the field is
+ * NULL unless set.  slslam_po_sqrt_information (below) makes W_e from a covariance block.  Honoured by slslam_po_solve,
+ * slslam_po_edge_report, slslam_po_covariance and slslam_po_batch_add (a batch may mix graphs with and without); slslam_po_structure
+ * ignores it. */
 
 /* Replaces: POProblem::build + POProblem::set_options + ceres::Solve
  * (reference src/slam.cpp:1283-1293).  Synchronous; parameters solved in place.
@@ -400,7 +411,7 @@ int slslam_po_solve(const slslam_po_graph* graph, const slslam_solver_options* o
                     slslam_summary* summary, slslam_iteration* trace, int trace_cap, int* trace_len);
 
 /* Per-edge report at graph->parameters - which slslam_po_solve has just updated in place -: sq_norm[e] = |Te|^2 of edge e (its six
- * residuals, src/po_problem.h:74-105) and weight[e] = rho'(sq_norm[e]) under ceres::HuberLoss(po_huber_delta), the loss of
+ * residuals, src/po_problem.h:74-105; |W_e Te|^2 with graph->sqrt_information) and weight[e] = rho'(sq_norm[e]) under ceres::HuberLoss(po_huber_delta), the loss of
  * src/po_problem.cpp:27,55: 1 for an inlier (sq_norm <= delta^2) and whenever po_huber_delta is 0, else delta / sqrt(sq_norm).  The edge
  * with the smallest weight is the loop closure to drop.  sq_norm, weight: [num_edges] host arrays, either may be NULL.  Synchronous;
  * validates as slslam_po_solve does (SLSLAM_ERR_INVALID_ARGUMENT also for a negative or non-finite po_huber_delta), then needs a
@@ -429,7 +440,7 @@ int slslam_po_structure_level1(void);
 typedef struct slslam_po_batch slslam_po_batch;
 int  slslam_po_batch_create(int device, slslam_po_batch** out);
 void slslam_po_batch_destroy(slslam_po_batch* b);
-/* Copies the graph's arrays and runs slslam_po_solve's validation (SLSLAM_ERR_INVALID_ARGUMENT, nothing added) and symbolic
+/* Copies the graph's arrays (sqrt_information too, or notes its absence: per graph) and runs slslam_po_solve's validation (SLSLAM_ERR_INVALID_ARGUMENT, nothing added) and symbolic
  * analysis (slslam_po_structure).  Returns the graph's index in *index.  SLSLAM_ERR_STATE after finalize. */
 int  slslam_po_batch_add(slslam_po_batch* b, const slslam_po_graph* graph, int* index);
 /* One options struct for every graph, as for slslam_po_solve (huber_delta, baseline ignored; po_huber_delta honoured and checked); po_dense_factor = 1 or
@@ -463,9 +474,10 @@ int  slslam_po_batch_get_edge_report(const slslam_po_batch* b, int index, double
  * for a batch - the poses as added for a graph whose solve ended in NUMERICAL_FAILURE):
  *   free pose: referenced by at least one edge and not pose_index_1[0] (the rule of the solve: slslam_po_structure's slot >= 0);
  *   J: the Jacobian of all edges' six residuals (src/po_problem.h:68-108) w.r.t. the free poses, in the global (angle-axis, translation)
- *      coordinates, after the Huber corrector of po_huber_delta (a block with s = |Te|^2 > delta^2 is scaled by sqrt(delta / sqrt(s));
- *      0: no loss), without Jacobi scaling or damping;
- *   H = J^T J, n = 6 x (free poses);  Sigma = H^-1 for unit-variance residuals - multiply by the noise variance.
+ *      coordinates, every block whitened by its W_e when the graph has sqrt_information, then the Huber corrector of po_huber_delta (a
+ *      block with s = |W_e Te|^2 > delta^2 is scaled by sqrt(delta / sqrt(s)); 0: no loss), without Jacobi scaling or damping;
+ *   H = J^T J, n = 6 x (free poses);  Sigma = H^-1.  Sigma is the covariance when W_e^T W_e are the edges' true information matrices;
+ *   with sqrt_information NULL it is the covariance for unit-variance residuals - multiply by the noise variance.
  *   cov_poses[36 N]: the row-major 6 x 6 marginal Sigma_aa per caller pose index, zeros for the constant pose and unreferenced poses;
  *   cov_pairs[36 P]: for the caller's pairs (pair_a[k], pair_b[k]) the row-major block Sigma_ab, rows of a, columns of b; a == b gives
  *      the marginal; a pair that touches a constant or unreferenced pose gives zeros.
@@ -496,6 +508,14 @@ int  slslam_po_batch_covariance(slslam_po_batch* b, void* stream);
 int  slslam_po_batch_get_covariance(const slslam_po_batch* b, int index, int* status, double* cov_poses, double* cov_pairs);
 /* Since create: slslam_po_batch_covariance calls, and the device / host buffers they allocated.  Any pointer may be NULL. */
 int  slslam_po_batch_covariance_stats(const slslam_po_batch* b, long long* calls, long long* allocations);
+/* Host only, no device: the square-root information of an edge from a covariance.  cov[36]: a symmetric positive-definite 6 x 6 matrix
+ * (row-major; the lower triangle is read), Sigma = L L^T; writes W = L^-1, lower triangular, row-major, so that W^T W = Sigma^-1 - what
+ * slslam_po_graph.sqrt_information takes.  Factored after scaling to unit diagonal, by the rule of slslam_po_covariance: a scaled pivot
+ * <= 1e-10 (or a diagonal entry <= 0) gives *status = SLSLAM_COV_SINGULAR and zeros, else SLSLAM_COV_OK.  Non-finite input, or a NULL cov
+ * or sqrt_information: SLSLAM_ERR_INVALID_ARGUMENT.  status may be NULL.  This is the bridge from the 6 x 6 blocks slslam_lba_covariance,
+ * slslam_lba_batch_get_covariance and slslam_po_covariance return (the covariance of a relative pose, in the edge error's coordinates:
+ * INTEGRATION.md) to edge weights. */
+int  slslam_po_sqrt_information(const double cov[36], double sqrt_information[36], int* status);
 
 /* ------------------------------------------------------------------ RANSAC hypothesis scoring
  * (the per-frame cost centre next to the hot path.)

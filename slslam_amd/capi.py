@@ -85,7 +85,8 @@ COV_OK, COV_SINGULAR = 0, 1
 class POGraph(C.Structure):
     _fields_ = [("num_poses", C.c_int), ("num_edges", C.c_int),
                 ("pose_index_1", C.POINTER(C.c_int)), ("pose_index_2", C.POINTER(C.c_int)),
-                ("constraints", C.POINTER(C.c_double)), ("parameters", C.POINTER(C.c_double))]
+                ("constraints", C.POINTER(C.c_double)), ("parameters", C.POINTER(C.c_double)),
+                ("sqrt_information", C.POINTER(C.c_double))]      # [36E] row-major W_e; NULL (the default): identity
 
 
 # every symbol include/slslam_hip.h declares (checked by the CPU test-suite)
@@ -100,7 +101,7 @@ EXPORTS = [
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
-    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -180,6 +181,7 @@ def lib():
     L.slslam_po_batch_get_summary.argtypes = [vp, C.c_int, C.POINTER(Summary)]
     L.slslam_po_batch_get_trace.argtypes = [vp, C.c_int, C.POINTER(Iteration), C.c_int, ip]
     L.slslam_po_edge_report.argtypes = [C.POINTER(POGraph), C.c_double, dp, dp]
+    L.slslam_po_sqrt_information.argtypes = [dp, dp, ip]
     L.slslam_po_batch_get_edge_report.argtypes = [vp, C.c_int, dp, dp]
     L.slslam_po_covariance.argtypes = [C.POINTER(POGraph), C.c_double, C.c_int, ip, ip, ip, dp, dp]
     L.slslam_po_batch_set_covariance_pairs.argtypes = [vp, C.c_int, C.c_int, ip, ip]
@@ -655,14 +657,9 @@ class LBAStream:
 
 
 def po_solve(g, params=None, trace_cap=64, **opt):
-    """One pose graph through slslam_po_solve (POProblem::build + set_options + ceres::Solve)."""
-    i1 = np.ascontiguousarray(g["pose_index_1"], dtype=np.int32)
-    i2 = np.ascontiguousarray(g["pose_index_2"], dtype=np.int32)
-    cons = np.ascontiguousarray(g["constraints"], dtype=np.float64).reshape(-1)
-    x = np.array(g["parameters"] if params is None else params, dtype=np.float64).reshape(-1).copy()
-    if len(i2) != len(i1) or len(cons) != 6 * len(i1) or len(x) != 6 * int(g["num_poses"]):
-        raise ValueError("inconsistent pose-graph arrays")
-    cg = POGraph(int(g["num_poses"]), len(i1), _ip(i1), _ip(i2), _dp(cons), _dp(x))
+    """One pose graph through slslam_po_solve (POProblem::build + set_options + ceres::Solve).  g["sqrt_information"] ([E, 6, 6] or
+    [36E], optional): the edges' square-root information matrices W_e - blocks are whitened by them; absent or None: identity."""
+    cg, (i1, i2, cons, x, _) = _po_graph(g, params)
     o = default_options(**opt)
     s = Summary()
     tr = (Iteration * trace_cap)()
@@ -672,10 +669,10 @@ def po_solve(g, params=None, trace_cap=64, **opt):
 
 
 def po_edge_report(g, params=None, po_huber_delta=0.0):
-    """Per-edge (sq_norm, weight) at the graph's parameters (slslam_po_edge_report): |Te|^2 of every edge and the weight rho' that
-    HuberLoss(po_huber_delta) gives it (1 for inliers and without a loss); the smallest weight marks the loop closure to drop."""
-    i1, i2, cons, x = _po_arrays(g, params)
-    cg = POGraph(int(g["num_poses"]), len(i1), _ip(i1), _ip(i2), _dp(cons), _dp(x))
+    """Per-edge (sq_norm, weight) at the graph's parameters (slslam_po_edge_report): |Te|^2 of every edge - |W_e Te|^2 when the graph
+    has g["sqrt_information"] - and the weight rho' that HuberLoss(po_huber_delta) gives it (1 for inliers and without a loss); the
+    smallest weight marks the loop closure to drop."""
+    cg, (i1, i2, cons, x, _) = _po_graph(g, params)
     sq, wt = np.zeros(len(i1)), np.zeros(len(i1))
     _check(lib().slslam_po_edge_report(C.byref(cg), float(po_huber_delta), _dp(sq), _dp(wt)), "slslam_po_edge_report")
     return sq, wt
@@ -690,8 +687,7 @@ def po_covariance(g, pairs=None, po_huber_delta=0.0, params=None):
     """Posterior covariance of one pose graph at its parameters (slslam_po_covariance; ceres::Covariance): (status,
     cov_poses[N, 6, 6] - the marginal of every pose, zeros for the constant pose and unreferenced ones -, cov_pairs[P, 6, 6] - the
     cross blocks Sigma_ab of `pairs` [(a, b), ...], rows of a, columns of b).  status COV_SINGULAR: all zeros."""
-    i1, i2, cons, x = _po_arrays(g, params)
-    cg = POGraph(int(g["num_poses"]), len(i1), _ip(i1), _ip(i2), _dp(cons), _dp(x))
+    cg, (i1, i2, cons, x, _) = _po_graph(g, params)
     pa, pb = _po_pairs(pairs)
     st = C.c_int(-1)
     cp, cq = np.zeros((int(g["num_poses"]), 6, 6)), np.zeros((len(pa), 6, 6))
@@ -710,6 +706,37 @@ def _po_arrays(g, params=None):
     return i1, i2, cons, x
 
 
+def _po_weights(g, num_edges):
+    """g["sqrt_information"] as the flat [36E] array the C ABI takes, or None (absent or None: identity on every edge)."""
+    w = g.get("sqrt_information") if hasattr(g, "get") else None
+    if w is None:
+        return None
+    w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if len(w) != 36 * num_edges:
+        raise ValueError("sqrt_information must hold 36 doubles per edge")
+    return w
+
+
+def _po_graph(g, params=None):
+    """The POGraph of a graph dict and the arrays it points into (keep them alive for as long as the struct is used)."""
+    i1, i2, cons, x = _po_arrays(g, params)
+    w = _po_weights(g, len(i1))
+    return POGraph(int(g["num_poses"]), len(i1), _ip(i1), _ip(i2), _dp(cons), _dp(x), None if w is None else _dp(w)), (i1, i2, cons, x, w)
+
+
+def po_sqrt_information(cov):
+    """(status, W[6, 6]) from a symmetric positive-definite 6 x 6 covariance (slslam_po_sqrt_information; host only): W lower
+    triangular with W^T W = cov^-1 - an edge's entry of g["sqrt_information"], e.g. from a block lba_covariance or po_covariance
+    returned.  status COV_SINGULAR: zeros."""
+    cv = np.ascontiguousarray(cov, dtype=np.float64).reshape(-1)
+    if len(cv) != 36:
+        raise ValueError("cov must be 6 x 6")
+    out = np.zeros((6, 6))
+    st = C.c_int(-1)
+    _check(lib().slslam_po_sqrt_information(_dp(cv), _dp(out), C.byref(st)), "slslam_po_sqrt_information")
+    return st.value, out
+
+
 class POBatch:
     """Many pose graphs solved together (slslam_po_batch_*): each graph gets what po_solve gives it.  add() copies the graph,
     finalize() uploads (the first call that needs a device), solve() enqueues, download() waits and brings the results back."""
@@ -722,8 +749,7 @@ class POBatch:
         self._pairs = {}
 
     def add(self, g, params=None):
-        i1, i2, cons, x = _po_arrays(g, params)
-        cg = POGraph(int(g["num_poses"]), len(i1), _ip(i1), _ip(i2), _dp(cons), _dp(x))
+        cg, (i1, i2, cons, x, _) = _po_graph(g, params)
         idx = C.c_int(-1)
         _check(lib().slslam_po_batch_add(self._h, C.byref(cg), C.byref(idx)), "slslam_po_batch_add")
         self._n.append(int(g["num_poses"]))

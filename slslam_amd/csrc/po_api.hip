@@ -163,6 +163,8 @@ bool po_graph_entries_ok(const slslam_po_graph* g, bool values) {
     for (int q = 0; values && q < 6; ++q) if (!std::isfinite(g->constraints[6 * (size_t)e + q])) return false;
   }
   for (size_t i = 0; values && i < (size_t)6 * N; ++i) if (!std::isfinite(g->parameters[i])) return false;
+  // the edges' square-root information matrices, when given: any finite values (an all-zero W_e removes its edge)
+  for (size_t i = 0; values && g->sqrt_information && i < (size_t)36 * E; ++i) if (!std::isfinite(g->sqrt_information[i])) return false;
   return true;
 }
 
@@ -422,7 +424,7 @@ int po_solve_upload(PoSolve& c) {
   const size_t o_st = a.take(sizeof(LMState)), o_trace = a.take(sizeof(IterRec) * kMaxTrace), o_x = a.take(sizeof(double) * 12 * (N > 0 ? N : 1));
   c.down_bytes = a.off;
   const size_t o_p1 = a.take(sizeof(int) * E), o_p2 = a.take(sizeof(int) * E), o_slot = a.take(sizeof(int) * (N > 0 ? N : 1)),
-               o_cons = a.take(sizeof(double) * 6 * E), o_scale = a.take(sizeof(double) * nn), o_chains = a.take(sizeof(PoChain) * (S.chains.size() + 1)),
+               o_cons = a.take(sizeof(double) * 6 * E), o_winfo = a.take(g->sqrt_information ? sizeof(double) * 36 * E : 0), o_scale = a.take(sizeof(double) * nn), o_chains = a.take(sizeof(PoChain) * (S.chains.size() + 1)),
                o_scal = a.take(sizeof(double) * 8), o_flags = a.take(sizeof(int) * 2), o_tri = a.take(sizeof(unsigned) * (size_t)(c.nblk + 1));
   c.up_bytes = a.off;
   const size_t o_H = a.take(c.hbytes), o_g = a.take(sizeof(double) * nn), o_d2 = a.take(sizeof(double) * nn), o_y = a.take(sizeof(double) * nn),
@@ -444,6 +446,7 @@ int po_solve_upload(PoSolve& c) {
   p.trace = (IterRec*)(arena + o_trace); c.d_chains = (PoChain*)(arena + o_chains);
   p.N = N; p.E = E; p.n = n; p.ld = ld;
   p.huber = c.opt.po_huber_delta;
+  p.winfo = g->sqrt_information ? (const double*)(arena + o_winfo) : nullptr;
   c.pj = p;                                // the junction block as a matrix of its own (same leading dimension)
   c.pj.n = S.nj; c.pj.H = p.H + (size_t)S.n_chain * ld + S.n_chain; c.pj.y = p.y + S.n_chain;
   // the pinned image (kept per calling thread, grown on demand)
@@ -464,6 +467,7 @@ int po_solve_upload(PoSolve& c) {
   std::memcpy(stage + o_x + sizeof(double) * 6 * N, g->parameters, sizeof(double) * 6 * N);
   std::memcpy(stage + o_p1, g->pose_index_1, sizeof(int) * E); std::memcpy(stage + o_p2, g->pose_index_2, sizeof(int) * E);
   std::memcpy(stage + o_slot, S.slot.data(), sizeof(int) * N); std::memcpy(stage + o_cons, g->constraints, sizeof(double) * 6 * E);
+  if (g->sqrt_information) std::memcpy(stage + o_winfo, g->sqrt_information, sizeof(double) * 36 * E);
   std::fill_n((double*)(stage + o_scale), nn, 1.0);
   if (!S.chains.empty()) std::memcpy(stage + o_chains, S.chains.data(), sizeof(PoChain) * S.chains.size());
   HIP_TRY(hipMemcpyAsync(arena, stage, c.up_bytes, hipMemcpyHostToDevice, 0));
@@ -471,10 +475,15 @@ int po_solve_upload(PoSolve& c) {
   return SLSLAM_OK;
 }
 
-// k_po_linearise with the loss (po_huber_delta > 0) or, as before there was one, without
+// k_po_linearise with the loss (po_huber_delta > 0) or, as before there was one, without; whitening only for a graph that brings
+// sqrt_information (without it: the two instantiations there were)
 void po_launch_linearise(const PoSolve& c, int mode) {
-  if (c.p.huber > 0.0) hipLaunchKernelGGL(k_po_linearise<true>, c.g_edges, dim3(64), 0, 0, c.p, mode);
-  else hipLaunchKernelGGL(k_po_linearise<false>, c.g_edges, dim3(64), 0, 0, c.p, mode);
+  const bool robust = c.p.huber > 0.0;
+  if (c.p.winfo) {
+    if (robust) hipLaunchKernelGGL((k_po_linearise<true, true>), c.g_edges, dim3(64), 0, 0, c.p, mode);
+    else hipLaunchKernelGGL((k_po_linearise<false, true>), c.g_edges, dim3(64), 0, 0, c.p, mode);
+  } else if (robust) hipLaunchKernelGGL((k_po_linearise<true, false>), c.g_edges, dim3(64), 0, 0, c.p, mode);
+  else hipLaunchKernelGGL((k_po_linearise<false, false>), c.g_edges, dim3(64), 0, 0, c.p, mode);
 }
 
 // ---- initial evaluation: cost, gradient, column norms -> Jacobi scale
@@ -616,7 +625,8 @@ extern "C" int slslam_po_solve(const slslam_po_graph* g, const slslam_solver_opt
 }
 
 
-// Per-edge report at graph->parameters (what a solve has just updated in place): sq_norm[e] = |Te|^2, weight[e] = rho'(s) under
+// Per-edge report at graph->parameters (what a solve has just updated in place): sq_norm[e] = |W_e Te|^2 (W_e = I without
+// graph->sqrt_information), weight[e] = rho'(s) under
 // HuberLoss(po_huber_delta) - the switch of reference src/po_problem.cpp:27,55.  One launch, one lane per edge.
 extern "C" int slslam_po_edge_report(const slslam_po_graph* g, double po_huber_delta, double* sq_norm, double* weight) {
   if (!g || !po_graph_arrays_ok(g, true) || !po_huber_ok(po_huber_delta) || !po_graph_entries_ok(g, true)) return SLSLAM_ERR_INVALID_ARGUMENT;
@@ -626,7 +636,8 @@ extern "C" int slslam_po_edge_report(const slslam_po_graph* g, double po_huber_d
   if (E == 0 || (!sq_norm && !weight)) return SLSLAM_OK;
   PoCarve a;
   const size_t o_p1 = a.take(sizeof(int) * E), o_p2 = a.take(sizeof(int) * E), o_cons = a.take(sizeof(double) * 6 * E),
-               o_x = a.take(sizeof(double) * 6 * N), up_bytes = a.off, o_out = a.take(sizeof(double) * 2 * E);
+               o_x = a.take(sizeof(double) * 6 * N), o_winfo = a.take(g->sqrt_information ? sizeof(double) * 36 * E : 0), up_bytes = a.off,
+               o_out = a.take(sizeof(double) * 2 * E);
   struct Block {                          // the calling thread's cached device block, handed back on every path
     char* p = nullptr; size_t bytes = 0; int device = 0;
     ~Block() { DeviceBlockCache::give_back(p, bytes, device); }
@@ -637,17 +648,57 @@ extern "C" int slslam_po_edge_report(const slslam_po_graph* g, double po_huber_d
   std::vector<char> img(up_bytes > sizeof(double) * 2 * E ? up_bytes : sizeof(double) * 2 * E);
   std::memcpy(img.data() + o_p1, g->pose_index_1, sizeof(int) * E); std::memcpy(img.data() + o_p2, g->pose_index_2, sizeof(int) * E);
   std::memcpy(img.data() + o_cons, g->constraints, sizeof(double) * 6 * E); std::memcpy(img.data() + o_x, g->parameters, sizeof(double) * 6 * N);
+  if (g->sqrt_information) std::memcpy(img.data() + o_winfo, g->sqrt_information, sizeof(double) * 36 * E);
   HIP_TRY(hipMemcpy(blk.p, img.data(), up_bytes, hipMemcpyHostToDevice));
   PoPtrs p;
   std::memset(&p, 0, sizeof(p));
   p.p1 = (const int*)(blk.p + o_p1); p.p2 = (const int*)(blk.p + o_p2); p.cons = (const double*)(blk.p + o_cons);
   p.N = N; p.E = E; p.huber = po_huber_delta;
+  p.winfo = g->sqrt_information ? (const double*)(blk.p + o_winfo) : nullptr;
   double* d_out = (double*)(blk.p + o_out);
-  hipLaunchKernelGGL(k_po_edge_report, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, 0, p, (const double*)(blk.p + o_x), d_out, d_out + E);
+  const dim3 grid((unsigned)((E + 63) / 64));
+  if (p.winfo) hipLaunchKernelGGL(k_po_edge_report<true>, grid, dim3(64), 0, 0, p, (const double*)(blk.p + o_x), d_out, d_out + E);
+  else hipLaunchKernelGGL(k_po_edge_report<false>, grid, dim3(64), 0, 0, p, (const double*)(blk.p + o_x), d_out, d_out + E);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(img.data(), d_out, sizeof(double) * 2 * E, hipMemcpyDeviceToHost));
   if (sq_norm) std::memcpy(sq_norm, img.data(), sizeof(double) * E);
   if (weight) std::memcpy(weight, img.data() + sizeof(double) * E, sizeof(double) * E);
+  return SLSLAM_OK;
+}
+
+// W = L^-1 for cov = L L^T, after scaling to unit diagonal (C = D cov D = Lc Lc^T, L = D^-1 Lc, W = Lc^-1 D): host only.
+extern "C" int slslam_po_sqrt_information(const double* cov, double* W, int* status) {
+  if (!cov || !W) return SLSLAM_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < 36; ++i) if (!std::isfinite(cov[i])) return SLSLAM_ERR_INVALID_ARGUMENT;
+  std::fill_n(W, 36, 0.0);
+  if (status) *status = SLSLAM_COV_SINGULAR;
+  double d[6], Lc[36] = {}, Li[36] = {};
+  for (int i = 0; i < 6; ++i) {
+    if (!(cov[7 * i] > 0.0)) return SLSLAM_OK;
+    d[i] = 1.0 / std::sqrt(cov[7 * i]);
+  }
+  for (int j = 0; j < 6; ++j) {
+    double piv = 1.0;                                        // the unit diagonal
+    for (int k = 0; k < j; ++k) piv -= Lc[6 * j + k] * Lc[6 * j + k];
+    if (!(piv > 1e-10)) return SLSLAM_OK;                    // (a scaled pivot at or below 1e-10: singular, as po_covariance.h rules)
+    const double ljj = std::sqrt(piv);
+    Lc[7 * j] = ljj;
+    for (int i = j + 1; i < 6; ++i) {
+      double v = d[i] * cov[6 * i + j] * d[j];
+      for (int k = 0; k < j; ++k) v -= Lc[6 * i + k] * Lc[6 * j + k];
+      Lc[6 * i + j] = v / ljj;
+    }
+  }
+  for (int j = 0; j < 6; ++j) {                              // Li = Lc^-1, column by column
+    Li[7 * j] = 1.0 / Lc[7 * j];
+    for (int i = j + 1; i < 6; ++i) {
+      double v = 0.0;
+      for (int k = j; k < i; ++k) v -= Lc[6 * i + k] * Li[6 * k + j];
+      Li[6 * i + j] = v / Lc[7 * i];
+    }
+  }
+  for (int i = 0; i < 6; ++i) for (int j = 0; j <= i; ++j) W[6 * i + j] = Li[6 * i + j] * d[j];
+  if (status) *status = SLSLAM_COV_OK;
   return SLSLAM_OK;
 }
 

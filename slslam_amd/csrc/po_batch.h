@@ -31,19 +31,21 @@ __global__ __launch_bounds__(256) void k_pob_zero(const PoBatchGraph* gs, const 
   const PoItem it = items[blockIdx.x];
   po_zero_structured_body(gs[it.graph].p, gs[it.graph].n_l1, (unsigned)it.local);
 }
-template <bool kRobust>
+// kWeighted: launched when some graph of the batch has sqrt_information; a graph without (p.winfo null) keeps identity weights
+template <bool kRobust, bool kWeighted>
 __global__ __launch_bounds__(64) void k_pob_linearise(const PoBatchGraph* gs, const PoItem* items, int mode) {
   const PoItem it = items[blockIdx.x];
-  po_linearise_body<kRobust>(gs[it.graph].p, mode, (unsigned)it.local);
+  po_linearise_body<kRobust, kWeighted>(gs[it.graph].p, mode, (unsigned)it.local);
 }
 // every graph's edge report over the linearisation's work list (5 edges per workgroup), at what slslam_po_batch_get_parameters returns:
 // the accepted poses, or the poses as added when the solve ended in a numerical failure
+template <bool kWeighted>
 __global__ __launch_bounds__(64) void k_pob_edge_report(const PoBatchGraph* gs, const PoItem* items) {
   const PoItem it = items[blockIdx.x];
   const PoBatchGraph& G = gs[it.graph];
   const LMState* st = G.p.st;
   const double* X = st->status == SLSLAM_NUMERICAL_FAILURE ? G.x0 : G.p.x + (long long)st->cur * 6 * G.p.N;
-  po_edge_report_body(G.p, X, G.report, G.report + G.p.E, (unsigned)it.local, 5);
+  po_edge_report_body<kWeighted>(G.p, X, G.report, G.report + G.p.E, (unsigned)it.local, 5);
 }
 __global__ __launch_bounds__(256) void k_pob_prepare(const PoBatchGraph* gs, Policy pol, int first) {
   const PoPtrs p = gs[blockIdx.x].p;
@@ -93,6 +95,8 @@ struct slslam_po_batch {
     int N = 0, E = 0;
     std::vector<int> p1, p2;
     std::vector<double> cons, x0;
+    std::vector<double> winfo;              // [36E] the edges' square-root information; empty: none given (identity)
+    bool weighted = false;
     PoSymbolic sym;                         // slslam_po_solve's structured analysis, done by add
     int active = -1;                        // index among the graphs the device solves (E > 0), -1 otherwise
     // results (download)
@@ -111,6 +115,7 @@ struct slslam_po_batch {
   std::vector<int> active;                  // batch index of each graph the device solves
   Policy pol{};
   double huber = 0.0;                       // po_huber_delta of finalize: HuberLoss on every edge of every graph, 0 = none
+  bool weighted = false;                    // some active graph has sqrt_information: the whitening instantiations run (else: the ones there were)
   // device arena: [ states | traces | poses | edge reports ] (what comes back) [ descriptors | work lists | per-graph inputs ] (what reset
   // restores) [ poses as added ] (uploaded once) [ per-graph work arrays ]
   char* arena = nullptr;
@@ -175,6 +180,8 @@ extern "C" int slslam_po_batch_add(slslam_po_batch* b, const slslam_po_graph* g,
     G.p1.assign(g->pose_index_1, g->pose_index_1 + E); G.p2.assign(g->pose_index_2, g->pose_index_2 + E);
     G.cons.assign(g->constraints, g->constraints + 6 * (size_t)E);
     G.x0.assign(g->parameters, g->parameters + 6 * (size_t)N);
+    G.weighted = g->sqrt_information != nullptr;
+    if (G.weighted) G.winfo.assign(g->sqrt_information, g->sqrt_information + 36 * (size_t)E);
     po_analyse(N, E, G.p1.data(), G.p2.data(), true, &G.sym);
     if (index) *index = (int)b->graphs.size();
     b->graphs.push_back(std::move(G));
@@ -247,12 +254,12 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
   put(o_jg, jgraphs.data(), sizeof(int) * jgraphs.size());
   // per graph: the inputs, then (after every graph's inputs) the work arrays
   std::vector<PoBatchGraph> desc((size_t)A);
-  std::vector<size_t> o_in((size_t)A * 9);     // (the ninth: the poses as added, behind what reset restores)
+  std::vector<size_t> o_in((size_t)A * 10);    // (the ninth and tenth: the poses as added and the edges' weights, behind what reset restores)
   const LMState st = po_initial_state(b->pol);
   for (int a = 0; a < A; ++a) {
     const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
     const PoSymbolic& S = G.sym;
-    size_t* o = &o_in[(size_t)a * 9];
+    size_t* o = &o_in[(size_t)a * 10];
     o[0] = carve.take(sizeof(int) * G.E); o[1] = carve.take(sizeof(int) * G.E); o[2] = carve.take(sizeof(int) * G.N); o[3] = carve.take(sizeof(double) * 6 * G.E);
     o[4] = carve.take(sizeof(double) * S.n); o[5] = carve.take(sizeof(PoChain) * (S.chains.size() + 1)); o[6] = carve.take(sizeof(double) * 8); o[7] = carve.take(sizeof(int) * 2);
     if (img) {
@@ -266,17 +273,20 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
     }
   }
   *up_bytes = carve.off;
-  // uploaded once, by finalize: the poses as added, which no kernel writes (the edge report of a graph whose solve failed numerically)
+  // uploaded once, by finalize: the poses as added, which no kernel writes (the edge report of a graph whose solve failed numerically),
+  // and the square-root information of the graphs that have it
   for (int a = 0; a < A; ++a) {
     const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
-    o_in[(size_t)a * 9 + 8] = carve.take(sizeof(double) * 6 * G.N);
-    put(o_in[(size_t)a * 9 + 8], G.x0.data(), sizeof(double) * 6 * G.N);
+    o_in[(size_t)a * 10 + 8] = carve.take(sizeof(double) * 6 * G.N);
+    put(o_in[(size_t)a * 10 + 8], G.x0.data(), sizeof(double) * 6 * G.N);
+    o_in[(size_t)a * 10 + 9] = carve.take(sizeof(double) * G.winfo.size());
+    put(o_in[(size_t)a * 10 + 9], G.winfo.data(), sizeof(double) * G.winfo.size());
   }
   b->init_bytes = carve.off;
   for (int a = 0; a < A; ++a) {
     const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
     const PoSymbolic& S = G.sym;
-    const size_t* o = &o_in[(size_t)a * 9];
+    const size_t* o = &o_in[(size_t)a * 10];
     const size_t o_H = carve.take(sizeof(double) * (size_t)S.n * S.ld), o_g = carve.take(sizeof(double) * S.n), o_d2 = carve.take(sizeof(double) * S.n),
                  o_y = carve.take(sizeof(double) * S.n), o_linv = carve.take(sizeof(double) * kNB * kNB * (size_t)std::max(S.nblk_j, 1)),
                  o_Lf = carve.take(sizeof(double) * (size_t)std::max(S.nj, 1) * S.ld);
@@ -290,6 +300,7 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
     p.H = (double*)(arena + o_H); p.g = (double*)(arena + o_g); p.d2 = (double*)(arena + o_d2); p.y = (double*)(arena + o_y);
     p.N = G.N; p.E = G.E; p.n = S.n; p.ld = S.ld;
     p.huber = b->huber;
+    p.winfo = G.weighted ? (const double*)(arena + o[9]) : nullptr;
     D.pj = p;                               // the junction block as a matrix of its own (same leading dimension)
     D.pj.n = S.nj; D.pj.H = p.H + (size_t)S.n_chain * S.ld + S.n_chain; D.pj.y = p.y + S.n_chain;
     D.chains = (const PoChain*)(arena + o[5]);
@@ -321,9 +332,10 @@ extern "C" int slslam_po_batch_finalize(slslam_po_batch* b, const slslam_solver_
   if (b->device >= ndev) return SLSLAM_ERR_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(b->device));
   b->active.clear();
+  b->weighted = false;
   for (size_t i = 0; i < b->graphs.size(); ++i) {
     b->graphs[i].active = b->graphs[i].E > 0 ? (int)b->active.size() : -1;
-    if (b->graphs[i].E > 0) b->active.push_back((int)i);
+    if (b->graphs[i].E > 0) { b->active.push_back((int)i); b->weighted = b->weighted || b->graphs[i].weighted; }
   }
   if (!b->active.empty()) {
     size_t up = 0, down = 0, total = 0;
@@ -371,9 +383,14 @@ extern "C" int slslam_po_batch_solve(slslam_po_batch* b, void* stream) {
   const PoBatchGraph* gs = b->d_graphs;
   const PoItem* items = b->d_items;
   const Policy pol = b->pol;
-  auto linearise = [&](int mode) {          // with the loss (po_huber_delta > 0) or, as before there was one, without
-    if (b->huber > 0.0) hipLaunchKernelGGL(k_pob_linearise<true>, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, gs, items + b->edge_off, mode);
-    else hipLaunchKernelGGL(k_pob_linearise<false>, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, gs, items + b->edge_off, mode);
+  auto linearise = [&](int mode) {          // with the loss (po_huber_delta > 0) or, as before there was one, without; whitening only when a graph has weights
+    const dim3 g_edges((unsigned)b->edge_cnt);
+    const bool robust = b->huber > 0.0;
+    if (b->weighted) {
+      if (robust) hipLaunchKernelGGL((k_pob_linearise<true, true>), g_edges, dim3(64), 0, s, gs, items + b->edge_off, mode);
+      else hipLaunchKernelGGL((k_pob_linearise<false, true>), g_edges, dim3(64), 0, s, gs, items + b->edge_off, mode);
+    } else if (robust) hipLaunchKernelGGL((k_pob_linearise<true, false>), g_edges, dim3(64), 0, s, gs, items + b->edge_off, mode);
+    else hipLaunchKernelGGL((k_pob_linearise<false, false>), g_edges, dim3(64), 0, s, gs, items + b->edge_off, mode);
   };
   auto zero_and_linearise = [&]() {
     hipLaunchKernelGGL(k_pob_zero, dim3((unsigned)b->zero_cnt), dim3(256), 0, s, gs, items + b->zero_off);
@@ -428,7 +445,8 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     // every graph's edge report (slslam_po_batch_get_edge_report), at the batch's own po_huber_delta, in one launch ahead of the copy
-    hipLaunchKernelGGL(k_pob_edge_report, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, (const PoBatchGraph*)b->d_graphs, (const PoItem*)(b->d_items + b->edge_off));
+    if (b->weighted) hipLaunchKernelGGL(k_pob_edge_report<true>, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, (const PoBatchGraph*)b->d_graphs, (const PoItem*)(b->d_items + b->edge_off));
+    else hipLaunchKernelGGL(k_pob_edge_report<false>, dim3((unsigned)b->edge_cnt), dim3(64), 0, s, (const PoBatchGraph*)b->d_graphs, (const PoItem*)(b->d_items + b->edge_off));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(b->h_down, b->arena, b->down_bytes, hipMemcpyDeviceToHost, s));
     if (b->cov_pending) HIP_TRY(hipMemcpyAsync(b->cov_h_down, b->cov_dev + b->cov_plan.down_off, b->cov_plan.down_bytes, hipMemcpyDeviceToHost, s));
@@ -545,7 +563,7 @@ extern "C" int slslam_po_batch_covariance(slslam_po_batch* b, void* stream) {
         const PoBatchGraph& D = b->h_desc[(size_t)a];
         PoCovInput& I = in[(size_t)a];
         I.N = G.N; I.E = G.E; I.n = G.sym.n; I.ld = G.sym.ld;
-        I.d_p1 = D.p.p1; I.d_p2 = D.p.p2; I.d_slot = D.p.slot; I.d_cons = D.p.cons;      // the batch's own arrays: the chains-first slots do as well as any
+        I.d_p1 = D.p.p1; I.d_p2 = D.p.p2; I.d_slot = D.p.slot; I.d_cons = D.p.cons; I.d_winfo = D.p.winfo;      // the batch's own arrays: the chains-first slots do as well as any
         I.d_x_src = D.p.x; I.d_st_src = D.p.st; I.d_x0 = D.x0;
         I.pa = G.cov_pa.data(); I.pb = G.cov_pb.data(); I.P = (int)G.cov_pa.size();
       }

@@ -8,7 +8,7 @@
 // (graph, block) items, as po_batch.h); the one-graph entry point runs the same kernels on a list of one.
 //
 //   k_pocov_begin      zeroes H, copies the poses the covariance is taken at, arms the graph's own LMState (the bodies below early-out on it)
-//   k_pocov_linearise  po_linearise_body<kRobust> into the covariance's OWN normal matrix, scale == 1
+//   k_pocov_linearise  po_linearise_body<kRobust, kWeighted> (blocks whitened by the edges' sqrt_information, when a graph has it) into the covariance's OWN normal matrix, scale == 1
 //   k_pocov_diag / k_pocov_scale     d = 1 / sqrt(diag H),  H <- D H D  (unit diagonal: the pivot test is scale free)
 //   k_pocov_potrf_diag / k_pocov_step   the blocked MFMA Cholesky of po_kernels.h (64 x 64 blocks, the diagonal blocks' inverses kept)
 //   k_pocov_check      smallest pivot L_kk^2 of the unit-diagonal matrix <= 1e-10 (or a failed tile) -> SLSLAM_COV_SINGULAR
@@ -63,10 +63,10 @@ __global__ __launch_bounds__(256) void k_pocov_begin(const PoCovGraph* gs, const
   const PoCovItem it = items[blockIdx.x];
   pocov_begin_body(gs[it.graph], (unsigned)it.local);
 }
-template <bool kRobust>
+template <bool kRobust, bool kWeighted>
 __global__ __launch_bounds__(64) void k_pocov_linearise(const PoCovGraph* gs, const PoCovItem* items) {
   const PoCovItem it = items[blockIdx.x];
-  po_linearise_body<kRobust>(gs[it.graph].p, 0, (unsigned)it.local);
+  po_linearise_body<kRobust, kWeighted>(gs[it.graph].p, 0, (unsigned)it.local);
 }
 // d = 1 / sqrt(diag H); a free pose has an edge, so its diagonal is positive - 0 (then a zero pivot: singular) guards the rest
 __global__ __launch_bounds__(256) void k_pocov_diag(const PoCovGraph* gs) {
@@ -228,6 +228,7 @@ struct PoCovInput {
   int N = 0, E = 0, n = 0, ld = 0;
   const int *d_p1 = nullptr, *d_p2 = nullptr, *d_slot = nullptr;   // device arrays of the graph
   const double* d_cons = nullptr;
+  const double* d_winfo = nullptr;                                 // [36E] the edges' square-root information, or null: identity
   const double* d_x_src = nullptr; const LMState* d_st_src = nullptr; const double* d_x0 = nullptr;
   const int *pa = nullptr, *pb = nullptr;                          // host: the pairs
   int P = 0;
@@ -235,6 +236,7 @@ struct PoCovInput {
 struct PoCovPlan {
   int A = 0;
   bool robust = false;
+  bool weighted = false;                      // some graph has sqrt_information: the whitening instantiation of k_pocov_linearise runs
   PoCovGraph* d_graphs = nullptr;
   PoCovItem* d_items = nullptr;
   int fill_off = 0, fill_cnt = 0, edge_off = 0, edge_cnt = 0, block_off = 0, block_cnt = 0;
@@ -253,6 +255,8 @@ size_t po_cov_layout(const std::vector<PoCovInput>& in, double huber, PoCarve ca
   const int A = (int)in.size();
   P->A = A;
   P->robust = huber > 0.0;
+  P->weighted = false;
+  for (const PoCovInput& g : in) P->weighted = P->weighted || g.d_winfo != nullptr;
   P->down_off = carve.off;
   P->o_status = carve.take(sizeof(int) * (size_t)A) - P->down_off;
   P->o_poses.assign((size_t)A, 0); P->o_pairs.assign((size_t)A, 0);
@@ -314,7 +318,7 @@ size_t po_cov_layout(const std::vector<PoCovInput>& in, double huber, PoCarve ca
     p.p1 = g.d_p1; p.p2 = g.d_p2; p.slot = g.d_slot; p.cons = g.d_cons;
     p.x = (double*)(dev + o_x); p.scale = (double*)(dev + o_scale); p.H = (double*)(dev + o_H); p.g = (double*)(dev + o_g);
     p.scal = (double*)(dev + o_scal); p.flags = (int*)(dev + o_flags); p.st = (LMState*)(dev + o_st);
-    p.N = g.N; p.E = g.E; p.n = g.n; p.ld = g.ld; p.huber = huber;
+    p.N = g.N; p.E = g.E; p.n = g.n; p.ld = g.ld; p.huber = huber; p.winfo = g.d_winfo;
     D.x_src = g.d_x_src; D.st_src = g.d_st_src; D.x0 = g.d_x0;
     D.Lf = (double*)(dev + o_Lf); D.linv = (double*)(dev + o_linv); D.dsc = (double*)(dev + o_d);
     D.pa = (const int*)(dev + o_pa[(size_t)a]); D.pb = (const int*)(dev + o_pb[(size_t)a]);
@@ -349,8 +353,12 @@ int po_cov_enqueue(const PoCovPlan& P, hipStream_t s) {
   const PoCovItem* items = P.d_items;
   const dim3 per_graph((unsigned)P.A);
   hipLaunchKernelGGL(k_pocov_begin, dim3((unsigned)P.fill_cnt), dim3(256), 0, s, gs, items + P.fill_off);
-  if (P.robust) hipLaunchKernelGGL(k_pocov_linearise<true>, dim3((unsigned)P.edge_cnt), dim3(64), 0, s, gs, items + P.edge_off);
-  else hipLaunchKernelGGL(k_pocov_linearise<false>, dim3((unsigned)P.edge_cnt), dim3(64), 0, s, gs, items + P.edge_off);
+  const dim3 g_edges((unsigned)P.edge_cnt);
+  if (P.weighted) {
+    if (P.robust) hipLaunchKernelGGL((k_pocov_linearise<true, true>), g_edges, dim3(64), 0, s, gs, items + P.edge_off);
+    else hipLaunchKernelGGL((k_pocov_linearise<false, true>), g_edges, dim3(64), 0, s, gs, items + P.edge_off);
+  } else if (P.robust) hipLaunchKernelGGL((k_pocov_linearise<true, false>), g_edges, dim3(64), 0, s, gs, items + P.edge_off);
+  else hipLaunchKernelGGL((k_pocov_linearise<false, false>), g_edges, dim3(64), 0, s, gs, items + P.edge_off);
   hipLaunchKernelGGL(k_pocov_diag, per_graph, dim3(256), 0, s, gs);
   hipLaunchKernelGGL(k_pocov_scale, dim3((unsigned)P.fill_cnt), dim3(256), 0, s, gs, items + P.fill_off);
   hipLaunchKernelGGL(k_pocov_potrf_diag, per_graph, dim3(256), 0, s, gs);
@@ -392,7 +400,7 @@ extern "C" int slslam_po_covariance(const slslam_po_graph* g, double po_huber_de
     po_analyse(N, E, g->pose_index_1, g->pose_index_2, false, &S);      // the free poses in index order: the inverse needs no chains
     PoCarve a;
     const size_t o_p1 = a.take(sizeof(int) * E), o_p2 = a.take(sizeof(int) * E), o_slot = a.take(sizeof(int) * N), o_cons = a.take(sizeof(double) * 6 * E),
-                 o_x = a.take(sizeof(double) * 6 * N), up_bytes = a.off;
+                 o_x = a.take(sizeof(double) * 6 * N), o_winfo = a.take(g->sqrt_information ? sizeof(double) * 36 * E : 0), up_bytes = a.off;
     std::vector<PoCovInput> in(1);
     PoCovInput& I = in[0];
     I.N = N; I.E = E; I.n = S.n; I.ld = S.ld; I.pa = pair_a; I.pb = pair_b; I.P = P;
@@ -407,11 +415,13 @@ extern "C" int slslam_po_covariance(const slslam_po_graph* g, double po_huber_de
     HIP_TRY(po_cov_lds_attribute());
     I.d_p1 = (const int*)(blk.p + o_p1); I.d_p2 = (const int*)(blk.p + o_p2); I.d_slot = (const int*)(blk.p + o_slot);
     I.d_cons = (const double*)(blk.p + o_cons); I.d_x0 = (const double*)(blk.p + o_x);
+    if (g->sqrt_information) I.d_winfo = (const double*)(blk.p + o_winfo);
     std::vector<char> img, up(up_bytes);
     po_cov_layout(in, po_huber_delta, a, blk.p, &img, &plan);
     std::memcpy(up.data() + o_p1, g->pose_index_1, sizeof(int) * E); std::memcpy(up.data() + o_p2, g->pose_index_2, sizeof(int) * E);
     std::memcpy(up.data() + o_slot, S.slot.data(), sizeof(int) * N); std::memcpy(up.data() + o_cons, g->constraints, sizeof(double) * 6 * E);
     std::memcpy(up.data() + o_x, g->parameters, sizeof(double) * 6 * N);
+    if (g->sqrt_information) std::memcpy(up.data() + o_winfo, g->sqrt_information, sizeof(double) * 36 * E);
     HIP_TRY(hipMemcpy(blk.p, up.data(), up_bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(blk.p + plan.img_off, img.data(), plan.img_bytes, hipMemcpyHostToDevice));
     const int rc = po_cov_enqueue(plan, 0);

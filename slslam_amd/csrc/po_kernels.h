@@ -147,6 +147,7 @@ struct PoPtrs {
   IterRec* trace;
   int N, E, n, ld;
   double huber;                      // po_huber_delta: HuberLoss(huber) on every edge; <= 0: no loss (k_po_linearise<false>)
+  const double* winfo;               // [36E] row-major square-root information W_e of every edge, or null: identity (kWeighted = false)
 };
 enum { kPoCost = 0, kPoCandCost = 1, kPoModel = 2, kPoDn2 = 3, kPoXn2 = 4, kPoFixed = 5 };
 
@@ -165,14 +166,45 @@ __device__ __forceinline__ double po_huber_scale(double s, double a, double* cos
   return 1.0;
 }
 
+// Whitening by an edge's square-root information W (row-major 6 x 6, W^T W = the edge's information matrix): Te <- W Te, on the six
+// values and, for a Dual, on the lane's column of [J1|J2] as well.  W is streamed a row at a time (the lanes of an edge read the same
+// 36 doubles: a broadcast load) beside the six inputs and six outputs; no cross-lane traffic.
+__device__ __forceinline__ void po_whiten(const double* __restrict__ W, double Te[6]) {
+  double out[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v += W[6 * q + k] * Te[k];
+    out[q] = v;
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) Te[q] = out[q];
+}
+__device__ __forceinline__ void po_whiten(const double* __restrict__ W, Dual Te[6]) {
+  Dual out[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    double v = 0.0, d = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { const double w = W[6 * q + k]; v += w * Te[k].v; d += w * Te[k].d; }
+    out[q] = mk(v, d);
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) Te[q] = out[q];
+}
+
 // lane <-> (edge, column of [J1|J2]); 5 edges per wave.
 // mode 0: accumulate H, g, cost at the accepted point (scaled columns)
 // mode 1: cost only at the candidate point
 // kRobust: the Huber loss of p.huber > 0 on every block - residuals and Jacobian columns scaled by sqrt(rho'), block cost rho / 2 (both
 // modes and the fixed cost).  Every lane of an edge holds all six Te[q].v, so s takes no cross-lane traffic; what consumes the blocks
 // (Jacobi scale, damping, gradient, model cost change) sees scaled blocks and is unchanged.  kRobust = false is the code as it was.
+// kWeighted: every block is whitened by its edge's W_e (p.winfo) BEFORE the loss, so s = |W_e Te|^2 and the corrector follows the whitening
+// (the weight inside the functor, as Ceres has it); a graph whose p.winfo is null keeps identity weights (a batched launch mixes both: the
+// test is uniform over the workgroup).  Launched only when some graph has weights; kWeighted = false is the code as it was.
 // (the bodies below take their workgroup's index as an argument: the batched kernels of po_batch.hip map it from a work list)
-template <bool kRobust>
+template <bool kRobust, bool kWeighted>
 __device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned blk) {
   const LMState* st = p.st;
   if (st->status != kRunning) return;
@@ -190,6 +222,7 @@ __device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned b
       double T1[6], T2[6], C[6], Te[6];
       for (int i = 0; i < 6; ++i) { T1[i] = X[6 * a + i]; T2[i] = X[6 * b + i]; C[i] = p.cons[6 * es + i]; }
       pose_constraint_error<double>(T1, T2, C, Te);
+      if (kWeighted) { if (p.winfo) po_whiten(p.winfo + 36 * (long long)es, Te); }
       const bool kept = p.slot[a] >= 0 || p.slot[b] >= 0;
       if (kRobust) {
         double s = 0.0;
@@ -212,6 +245,7 @@ __device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned b
     C[i] = mk(p.cons[6 * es + i]);
   }
   pose_constraint_error<Dual>(T1, T2, C, Te);
+  if (kWeighted) { if (p.winfo) po_whiten(p.winfo + 36 * (long long)es, Te); }
   double block_cost = 0.0;
   if (kRobust) {
     double s = 0.0;
@@ -241,12 +275,14 @@ __device__ __forceinline__ void po_linearise_body(PoPtrs p, int mode, unsigned b
   for (int o = 32; o > 0; o >>= 1) cost += __shfl_xor(cost, o);
   if (lane == 0) atomicAdd(&p.scal[kPoCost], cost);
 }
-template <bool kRobust>
-__global__ __launch_bounds__(64) void k_po_linearise(PoPtrs p, int mode) { po_linearise_body<kRobust>(p, mode, blockIdx.x); }
+template <bool kRobust, bool kWeighted>
+__global__ __launch_bounds__(64) void k_po_linearise(PoPtrs p, int mode) { po_linearise_body<kRobust, kWeighted>(p, mode, blockIdx.x); }
 
 // Per-edge report at the poses X: sq[e] = |Te|^2 and wt[e] = rho'(s), the weight the loss of p.huber gives the edge (1 for an inlier and
 // whenever there is no loss) - what tells the caller which loop closure to drop.  One lane per edge, `per_block` edges per workgroup
-// (the batched launch reuses the linearisation's work list: 5); nothing is summed, so no atomics.
+// (the batched launch reuses the linearisation's work list: 5); nothing is summed, so no atomics.  kWeighted: s = |W_e Te|^2 (p.winfo, as
+// the linearisation whitens; a graph with a null p.winfo keeps identity).
+template <bool kWeighted>
 __device__ __forceinline__ void po_edge_report_body(const PoPtrs& p, const double* X, double* sq, double* wt, unsigned blk, int per_block) {
   const int lane = threadIdx.x;
   const int e = blk * per_block + lane;
@@ -255,13 +291,15 @@ __device__ __forceinline__ void po_edge_report_body(const PoPtrs& p, const doubl
   double T1[6], T2[6], C[6], Te[6];
   for (int i = 0; i < 6; ++i) { T1[i] = X[6 * a + i]; T2[i] = X[6 * b + i]; C[i] = p.cons[6 * e + i]; }
   pose_constraint_error<double>(T1, T2, C, Te);
+  if (kWeighted) { if (p.winfo) po_whiten(p.winfo + 36 * (long long)e, Te); }
   double s = 0.0;
   for (int i = 0; i < 6; ++i) s += Te[i] * Te[i];
   sq[e] = s;
   wt[e] = (p.huber > 0.0 && s > p.huber * p.huber) ? p.huber / sqrt(s) : 1.0;
 }
+template <bool kWeighted>
 __global__ __launch_bounds__(64) void k_po_edge_report(PoPtrs p, const double* X, double* sq, double* wt) {
-  po_edge_report_body(p, X, sq, wt, blockIdx.x, 64);
+  po_edge_report_body<kWeighted>(p, X, sq, wt, blockIdx.x, 64);
 }
 
 // Structured factorisation only: zeroes what the linearisation is about to add into - the lower-triangle entries of every edge's two

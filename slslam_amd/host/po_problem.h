@@ -70,6 +70,11 @@ class POProblem {
   inline void set_pose_index_2(int* idx)  { pose_index_2_ = idx; }
   inline void set_constraints(double* d)  { constraints_ = d;    }
   inline void set_parameters(double* d)   { parameters_ = d;     }
+  // An extension the reference does not have (its edges are unweighted): [36 * num_size()] row-major square-root information
+  // matrices W_e, W_e^T W_e = the edge's information matrix (slslam_po_graph.sqrt_information; slslam_po_sqrt_information makes one
+  // from a covariance block).  Ownership as for the other setters: delete[]d by the destructor.  Null until set: identity.
+  inline void set_sqrt_information(double* d) { sqrt_information_ = d; }
+  const double* sqrt_information() const { return sqrt_information_; }
   // The reference sizes `parameters` by kfs.size() and never tells POProblem (slam.cpp:1265,1276-1280);
   // the back-end needs the count to size the dense system, so by default it is inferred as
   // 1 + max pose index over the edges; a caller with trailing unreferenced poses may set it.
@@ -95,6 +100,7 @@ class POProblem {
   int* pose_index_2_;
   double* constraints_;
   double* parameters_;
+  double* sqrt_information_;
 };
 
 }  // namespace ceres

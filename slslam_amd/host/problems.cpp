@@ -55,13 +55,14 @@ void LBAProblem::set_options(Solver::Options* options) {
 // ---------------------------------------------------------------- POProblem (src/po_problem.cpp)
 POProblem::POProblem(int a, int n)
     : num_iterations(n), num_threads(1), eta(1e-2), robustify(false), size_(a), num_poses_(-1),
-      pose_index_1_(nullptr), pose_index_2_(nullptr), constraints_(nullptr), parameters_(nullptr) {}
+      pose_index_1_(nullptr), pose_index_2_(nullptr), constraints_(nullptr), parameters_(nullptr), sqrt_information_(nullptr) {}
 
 POProblem::~POProblem() {
   delete[] pose_index_1_;
   delete[] pose_index_2_;
   delete[] constraints_;
   delete[] parameters_;
+  delete[] sqrt_information_;
 }
 
 int POProblem::num_poses() const {
@@ -173,10 +174,11 @@ void Solve(const Solver::Options& options, Problem* problem, Solver::Summary* su
     rc = slslam_lba_solve(&w, &o, &r, nullptr, 0, nullptr);
   } else if (problem && problem->po()) {
     POProblem* p = problem->po();
-    slslam_po_graph g;
+    slslam_po_graph g = {};
     g.num_poses = p->num_poses(); g.num_edges = p->num_size();
     g.pose_index_1 = p->pose_index_1(); g.pose_index_2 = p->pose_index_2();
     g.constraints = p->constraints(); g.parameters = p->parameters();
+    g.sqrt_information = p->sqrt_information();
     o.po_huber_delta = p->robust() ? 0.001 : 0.0;      // robustify ? new HuberLoss(0.001) : NULL  (po_problem.cpp:55)
     rc = slslam_po_solve(&g, &o, &r, nullptr, 0, nullptr);
   }

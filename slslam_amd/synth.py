@@ -360,6 +360,22 @@ def make_pose_graph(seed, num_poses=260, num_loops=8, sigma_t=0.01, sigma_r_deg=
             "parameters": params.reshape(-1), "true_parameters": truth.reshape(-1), "seed": int(seed)}
 
 
+def make_edge_information(seed, g, s_min=0.5, s_max=2.0, off_diagonal=0.3):
+    """Square-root information matrices for the edges of a pose graph (g["sqrt_information"]; an extension the reference does not
+    have): [E, 6, 6], W_e = R_e diag(s_e) T_e with R_e a random orthogonal 6 x 6, s_e in [s_min, s_max] and T_e unit lower triangular
+    with off-diagonals in [-off_diagonal, off_diagonal].  Full, NOT symmetric and O(1): a transposed or column-major read is a
+    different problem, and the conditioning of the graph stays what it was."""
+    rng = np.random.default_rng(np.random.SeedSequence([11, int(seed)]))
+    E = len(g["pose_index_1"])
+    W = np.zeros((E, 6, 6))
+    for e in range(E):
+        q, r = np.linalg.qr(rng.normal(size=(6, 6)))
+        q = q * np.sign(np.diag(r))                                        # (the factorisation's sign convention taken out)
+        t = np.eye(6) + np.tril(rng.uniform(-off_diagonal, off_diagonal, (6, 6)), -1)
+        W[e] = q @ np.diag(rng.uniform(s_min, s_max, 6)) @ t
+    return W
+
+
 def camera_centers(cams):
     """camera centres c = -R^T t of a [C,6] pose array (for trajectory-error reporting,
     reference matlab_script/calc_traj_err.m:28-40)."""

@@ -12,9 +12,9 @@ with tempfile.TemporaryDirectory() as d:
 txt = r.stderr
 if r.returncode:
     print(txt[-3000:]); sys.exit(1)
-K = {"v": r"VGPRs", "a": r"AGPRs", "s": r"ScratchSize \[bytes/lane\]", "o": r"Occupancy \[waves/SIMD\]", "l": r"LDS Size \[bytes/block\]"}
+K = {"v": r"VGPRs", "g": r"SGPRs", "a": r"AGPRs", "s": r"ScratchSize \[bytes/lane\]", "o": r"Occupancy \[waves/SIMD\]", "l": r"LDS Size \[bytes/block\]"}
 for b in txt.split("Function Name: ")[1:]:
     name = subprocess.run(["c++filt", b.split()[0]], capture_output=True, text=True).stdout.strip()
     name = re.sub(r"\(slslam::BatchPtrs.*", "", name).replace("void ", "").replace("slslam::", "")
     g = {k: (re.search(p + r": (\d+)", b).group(1) if re.search(p + r": (\d+)", b) else "?") for k, p in K.items()}
-    print("%-52s VGPR %4s AGPR %4s scratch %5s occ %2s LDS %s" % (name[:52], g["v"], g["a"], g["s"], g["o"], g["l"]))
+    print("%-72s VGPR %4s SGPR %4s AGPR %4s scratch %5s occ %2s LDS %s" % (name[:72], g["v"], g["g"], g["a"], g["s"], g["o"], g["l"]))
