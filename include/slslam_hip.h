@@ -517,6 +517,71 @@ int  slslam_po_batch_covariance_stats(const slslam_po_batch* b, long long* calls
  * INTEGRATION.md) to edge weights. */
 int  slslam_po_sqrt_information(const double cov[36], double sqrt_information[36], int* status);
 
+/* ---- statistics of an edge under the posterior covariance of its two poses (csrc/po_gate.h).
+ * Serves the two places where the reference has an edge and no uncertainty for it: consistency_broken() (src/slam.cpp:1215-1232), which
+ * judges a loop closure by two fixed thresholds on |w| and |t| of the edge error, and the odometry constraints built at
+ * src/slam.cpp:1403-1416 (C = T_b o T_a^-1 at :1410-1412), which enter the graph unweighted.
+ * One item: two poses x_a, x_b (angle-axis, translation), a constraint C, the joint covariance blocks Sigma_aa, Sigma_bb, Sigma_ab (row-major,
+ * Sigma_ab = rows of a, columns of b) and a measurement covariance R (its lower triangle is read).  With
+ *   Te = the edge error of the solve (src/po_problem.h:74-105; T1 = x_a, T2 = x_b), unwhitened;  Ja = dTe/dx_a, Jb = dTe/dx_b;
+ *   S  = sigma2 (Ja Saa Ja^T + Jb Sbb Jb^T + Ja Sab Jb^T + Jb Sab^T Ja^T) + R;
+ *   W  = slslam_po_sqrt_information(S): lower triangular, W^T W = S^-1;   m2 = Te^T S^-1 Te = |W Te|^2,
+ * the outputs per item are status[1] (SLSLAM_COV_*), error[6] = Te, cov[36] = S, sqrt_information[36] = W, mahalanobis2[1] = m2.
+ * SLSLAM_COV_SINGULAR by the rule of slslam_po_sqrt_information (a pivot <= 1e-10 of S scaled to unit diagonal, or a diagonal entry
+ * <= 0): that item gets zeros for cov, sqrt_information and mahalanobis2, its error is still written, the other items are unaffected.
+ * |w| and |t| of error are what consistency_broken() thresholds; m2 is chi-square with 6 degrees of freedom for a consistent edge.
+ * sigma2: finite and positive, for the whole call - the noise variance that multiplies unit-variance covariances (slslam_po_covariance of
+ * an unweighted graph), 1 for covariances of weighted graphs and for slslam_lba_batch_get_covariance blocks already scaled. */
+typedef struct slslam_po_edge_items {
+  int n;
+  const double* pose_a;        /* [6 n]  */
+  const double* pose_b;        /* [6 n]  */
+  const double* constraints;   /* [6 n]  */
+  const double* cov_aa;        /* [36 n] or NULL = zeros (a constant pose) */
+  const double* cov_bb;        /* [36 n] or NULL */
+  const double* cov_ab;        /* [36 n] or NULL */
+  const double* cov_meas;      /* [36 n] R, or NULL = zeros */
+  double sigma2;
+} slslam_po_edge_items;
+/* n independent items, host pointers, synchronous: one upload, one launch, one download.  Any output may be NULL.
+ * SLSLAM_ERR_INVALID_ARGUMENT - found before an output is written or a device is needed -: items NULL, n < 0, sigma2 not finite or <= 0,
+ * a NULL pose or constraint array with n > 0, a non-finite input.  n == 0 succeeds and does nothing.  With x_a, x_b two cameras of a
+ * solved LBA window, C = T_b o T_a^-1 and the camera blocks of slslam_lba_batch_get_covariance, sqrt_information is the odometry
+ * edge's W_e for slslam_po_graph.sqrt_information. */
+int  slslam_po_edge_statistics(const slslam_po_edge_items* items, int* status, double* error, double* cov, double* sqrt_information,
+                               double* mahalanobis2);
+/* Candidate edges between poses of a graph: item k is (x[pose_a[k]], x[pose_b[k]], constraints[k], the graph's own Sigma blocks, cov_meas[k]). */
+typedef struct slslam_po_candidates {
+  int num;
+  const int* pose_a;           /* [num] pose indices of the graph, a != b */
+  const int* pose_b;           /* [num] */
+  const double* constraints;   /* [6 num] */
+  const double* cov_meas;      /* [36 num] or NULL */
+  double sigma2;
+} slslam_po_candidates;
+/* One graph at graph->parameters, no solve, synchronous: the launch sequence of slslam_po_covariance (weights and po_huber_delta
+ * honoured) with the candidates as its pairs, then one launch that reads Sigma_aa, Sigma_bb, Sigma_ab and the poses where they are on the
+ * device; only the statistics come back.  *cov_status: the graph's SLSLAM_COV_*; when it is SLSLAM_COV_SINGULAR every candidate is
+ * singular (zeros, error written).  A candidate that touches the constant pose has zero blocks for it.  Outputs as above, [num] items;
+ * any may be NULL.  Validates as slslam_po_covariance does, and the candidates (NULL, num < 0, an index outside [0, num_poses), a == b,
+ * sigma2, non-finite values): SLSLAM_ERR_INVALID_ARGUMENT before an output is written or a device is needed. */
+int  slslam_po_gate(const slslam_po_graph* graph, double po_huber_delta, const slslam_po_candidates* candidates, int* cov_status, int* status,
+                    double* error, double* cov, double* sqrt_information, double* mahalanobis2);
+/* The candidates slslam_po_batch_gate judges for graph `index` (none until set).  Host only: copies them, replaces the previous list
+ * (num == 0 clears it); before or after finalize.  Results of an earlier gate or covariance call can no longer be read. */
+int  slslam_po_batch_set_candidates(slslam_po_batch* b, int index, const slslam_po_candidates* candidates);
+/* slslam_po_batch_covariance with, per graph, the caller's pairs followed by the candidates, plus one launch over every (graph,
+ * candidate).  Same states, same invalidation rules, counted by slslam_po_batch_covariance_stats; slslam_po_batch_get_covariance
+ * returns afterwards what it would after slslam_po_batch_covariance.  A second call with unchanged lists allocates nothing.  A graph
+ * without edges is not on the device (no free pose: S = R): its candidates, if it has any, are judged inside this call through
+ * slslam_po_edge_statistics - a synchronous upload, launch and download on the default stream, not on `stream`. */
+int  slslam_po_batch_gate(slslam_po_batch* b, void* stream);
+/* After slslam_po_batch_download: graph `index`'s statistics, [num] items (any output may be NULL).  SLSLAM_ERR_INVALID_ARGUMENT under
+ * the rules of slslam_po_batch_get_covariance - no gate call has been downloaded, or a solve, a reset, a newer covariance or gate call,
+ * or a replaced pair or candidate list came after it. */
+int  slslam_po_batch_get_gate(const slslam_po_batch* b, int index, int* status, double* error, double* cov, double* sqrt_information,
+                              double* mahalanobis2);
+
 /* ------------------------------------------------------------------ RANSAC hypothesis scoring
  * (the per-frame cost centre next to the hot path.)
  * Replaces: the scoring loop of SLAM::ransac_motion (reference src/slam.cpp:396-413) with

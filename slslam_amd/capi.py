@@ -89,6 +89,17 @@ class POGraph(C.Structure):
                 ("sqrt_information", C.POINTER(C.c_double))]      # [36E] row-major W_e; NULL (the default): identity
 
 
+class POEdgeItems(C.Structure):
+    _fields_ = [("n", C.c_int), ("pose_a", C.POINTER(C.c_double)), ("pose_b", C.POINTER(C.c_double)), ("constraints", C.POINTER(C.c_double)),
+                ("cov_aa", C.POINTER(C.c_double)), ("cov_bb", C.POINTER(C.c_double)), ("cov_ab", C.POINTER(C.c_double)),
+                ("cov_meas", C.POINTER(C.c_double)), ("sigma2", C.c_double)]
+
+
+class POCandidates(C.Structure):
+    _fields_ = [("num", C.c_int), ("pose_a", C.POINTER(C.c_int)), ("pose_b", C.POINTER(C.c_int)), ("constraints", C.POINTER(C.c_double)),
+                ("cov_meas", C.POINTER(C.c_double)), ("sigma2", C.c_double)]
+
+
 # every symbol include/slslam_hip.h declares (checked by the CPU test-suite)
 EXPORTS = [
     "slslam_default_options", "slslam_lba_solve", "slslam_lba_batch_create", "slslam_lba_batch_destroy",
@@ -101,7 +112,7 @@ EXPORTS = [
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
-    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -188,6 +199,12 @@ def lib():
     L.slslam_po_batch_covariance.argtypes = [vp, vp]
     L.slslam_po_batch_get_covariance.argtypes = [vp, C.c_int, ip, dp, dp]
     L.slslam_po_batch_covariance_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+    if hasattr(L, "slslam_po_gate"):         # (a SLSLAM_HIP_LIBRARY built before the edge statistics existed still loads: tools time it)
+        L.slslam_po_edge_statistics.argtypes = [C.POINTER(POEdgeItems), ip, dp, dp, dp, dp]
+        L.slslam_po_gate.argtypes = [C.POINTER(POGraph), C.c_double, C.POINTER(POCandidates), ip, ip, dp, dp, dp, dp]
+        L.slslam_po_batch_set_candidates.argtypes = [vp, C.c_int, C.POINTER(POCandidates)]
+        L.slslam_po_batch_gate.argtypes = [vp, vp]
+        L.slslam_po_batch_get_gate.argtypes = [vp, C.c_int, ip, dp, dp, dp, dp]
     L.slslam_ransac_score.argtypes = [C.POINTER(RansacFrame), C.c_double, C.c_double, ip, C.POINTER(C.c_ulonglong)]
     L.slslam_po_structure.argtypes = [C.POINTER(POGraph), ip, C.c_int, ip, ip, ip, ip, ip, ip, ip]
     L.slslam_ransac_generate.argtypes = [C.POINTER(RansacTrials), C.c_double, dp, ip]
@@ -737,6 +754,121 @@ def po_sqrt_information(cov):
     return st.value, out
 
 
+def _opt36(a, n):
+    """An optional [n, 6, 6] array as the flat array the C ABI takes, or None."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    if len(a) != 36 * n:
+        raise ValueError("a covariance array must hold 36 doubles per item")
+    return a
+
+
+def _edge_outputs(n):
+    return np.full(n, -1, dtype=np.int32), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6, 6)), np.zeros(n)
+
+
+def _edge_dict(st, err, cov, w, m2):
+    return dict(status=st, error=err, cov=cov, sqrt_information=w, mahalanobis2=m2)
+
+
+def po_edge_statistics(pose_a, pose_b, constraints, cov_aa=None, cov_bb=None, cov_ab=None, cov_meas=None, sigma2=1.0):
+    """Statistics of n edges under the covariance of their poses (slslam_po_edge_statistics): dict(status[n], error[n, 6] = Te,
+    cov[n, 6, 6] = S = sigma2 J Sigma J^T + R, sqrt_information[n, 6, 6] = W with W^T W = S^-1, mahalanobis2[n] = |W Te|^2).  Any
+    covariance array may be None (zeros).  A COV_SINGULAR item has zeros but for its error."""
+    xa = np.ascontiguousarray(pose_a, dtype=np.float64).reshape(-1)
+    xb = np.ascontiguousarray(pose_b, dtype=np.float64).reshape(-1)
+    cc = np.ascontiguousarray(constraints, dtype=np.float64).reshape(-1)
+    n = len(xa) // 6
+    if len(xa) != 6 * n or len(xb) != 6 * n or len(cc) != 6 * n:
+        raise ValueError("inconsistent edge arrays")
+    blocks = [_opt36(a, n) for a in (cov_aa, cov_bb, cov_ab, cov_meas)]
+    it = POEdgeItems(n, _dp(xa), _dp(xb), _dp(cc), *[None if a is None else _dp(a) for a in blocks], float(sigma2))
+    out = _edge_outputs(n)
+    _check(lib().slslam_po_edge_statistics(C.byref(it), _ip(out[0]), *[_dp(a) for a in out[1:]]), "slslam_po_edge_statistics")
+    return _edge_dict(*out)
+
+
+def _po_candidates(candidates):
+    """The POCandidates of dict(pose_a, pose_b, constraints, cov_meas (optional), sigma2 (default 1)) and the arrays it points into."""
+    pa = np.ascontiguousarray(candidates["pose_a"], dtype=np.int32).reshape(-1)
+    pb = np.ascontiguousarray(candidates["pose_b"], dtype=np.int32).reshape(-1)
+    cc = np.ascontiguousarray(candidates["constraints"], dtype=np.float64).reshape(-1)
+    if len(pb) != len(pa) or len(cc) != 6 * len(pa):
+        raise ValueError("inconsistent candidate arrays")
+    r = _opt36(candidates.get("cov_meas"), len(pa))
+    return POCandidates(len(pa), _ip(pa), _ip(pb), _dp(cc), None if r is None else _dp(r), float(candidates.get("sigma2", 1.0))), (pa, pb, cc, r)
+
+
+def po_gate(g, candidates, po_huber_delta=0.0, params=None):
+    """Candidate edges against one graph at its parameters (slslam_po_gate): (cov_status, dict as po_edge_statistics returns).
+    candidates: dict(pose_a[M], pose_b[M], constraints[M, 6], cov_meas[M, 6, 6] or absent, sigma2)."""
+    cg, keep = _po_graph(g, params)
+    cc, keep2 = _po_candidates(candidates)
+    out = _edge_outputs(cc.num)
+    st = C.c_int(-1)
+    _check(lib().slslam_po_gate(C.byref(cg), float(po_huber_delta), C.byref(cc), C.byref(st), _ip(out[0]), *[_dp(a) for a in out[1:]]), "slslam_po_gate")
+    return st.value, _edge_dict(*out)
+
+
+def se3_inverse(p):
+    """P^-1 of a pose [angle-axis | translation] (the reference's gc_T_inv)."""
+    p = np.asarray(p, dtype=np.float64)
+    return np.concatenate([-p[:3], -_aa_rotate(-p[:3], p[3:])])
+
+
+def _aa_rotate(w, v):
+    th = np.linalg.norm(w)
+    if th < 1e-300:
+        return v + np.cross(w, v)
+    k = w / th
+    return v * np.cos(th) + np.cross(k, v) * np.sin(th) + k * np.dot(k, v) * (1.0 - np.cos(th))
+
+
+def _aa_to_quat(w):
+    th = np.linalg.norm(w)
+    if th < 1e-300:
+        return np.array([1.0, 0.5 * w[0], 0.5 * w[1], 0.5 * w[2]])
+    return np.concatenate([[np.cos(0.5 * th)], np.sin(0.5 * th) / th * w])
+
+
+def se3_compose(t21, t10):
+    """T20 = T21 T10 on [angle-axis | translation] (the reference's gc_T_20)."""
+    t21, t10 = np.asarray(t21, dtype=np.float64), np.asarray(t10, dtype=np.float64)
+    a, b = _aa_to_quat(t21[:3]), _aa_to_quat(t10[:3])
+    q = np.array([a[0] * b[0] - a[1:] @ b[1:], *(a[0] * b[1:] + b[0] * a[1:] + np.cross(a[1:], b[1:]))])
+    s = np.linalg.norm(q[1:])
+    w = 2.0 * q[1:] if s < 1e-300 else 2.0 * np.arctan2(s, q[0]) / s * q[1:] if q[0] >= 0 else 2.0 * np.arctan2(-s, -q[0]) / s * q[1:]
+    return np.concatenate([w, _aa_rotate(t21[:3], t10[3:]) + t21[3:]])
+
+
+def lba_odometry_edges(cov_result, cameras, pairs, sigma2=1.0):
+    """Odometry edges between cameras of ONE solved LBA window, weighted by the window's posterior covariance.  cov_result: what
+    lba_covariance / LBABatch.get_covariance returned for the window - (status, free_camera[F], cov_cameras[6F, 6F], cov_lines);
+    cameras [C, 6]: the solved camera parameters; pairs [(a, b), ...].  Returns (constraints [P, 6] with
+    C = T_b o T_a^-1, the reference's src/slam.cpp:1410-1412, dict as po_edge_statistics returns): sqrt_information[k] is edge k's W_e.
+    A constant camera contributes zero blocks; a pair of two constant cameras is COV_SINGULAR."""
+    cams = np.asarray(cameras, dtype=np.float64).reshape(-1, 6)
+    free = [int(c) for c in cov_result[1]] if cov_result[0] == COV_OK else []
+    F = len(free)
+    sig = np.asarray(cov_result[2], dtype=np.float64)[:6 * F, :6 * F].reshape(F, 6, F, 6).transpose(0, 2, 1, 3)
+    pos = {c: k for k, c in enumerate(free)}
+    P = len(pairs)
+    xa, xb, cc = np.zeros((P, 6)), np.zeros((P, 6)), np.zeros((P, 6))
+    saa, sbb, sab = np.zeros((P, 6, 6)), np.zeros((P, 6, 6)), np.zeros((P, 6, 6))
+    for k, (a, b) in enumerate(pairs):
+        xa[k], xb[k] = cams[a], cams[b]
+        cc[k] = se3_compose(cams[b], se3_inverse(cams[a]))
+        ka, kb = pos.get(int(a)), pos.get(int(b))
+        if ka is not None:
+            saa[k] = sig[ka, ka]
+        if kb is not None:
+            sbb[k] = sig[kb, kb]
+        if ka is not None and kb is not None:
+            sab[k] = sig[ka, kb]
+    return cc, po_edge_statistics(xa, xb, cc, saa, sbb, sab, None, sigma2)
+
+
 class POBatch:
     """Many pose graphs solved together (slslam_po_batch_*): each graph gets what po_solve gives it.  add() copies the graph,
     finalize() uploads (the first call that needs a device), solve() enqueues, download() waits and brings the results back."""
@@ -747,6 +879,7 @@ class POBatch:
         self._n = []
         self._e = []
         self._pairs = {}
+        self._cands = {}
 
     def add(self, g, params=None):
         cg, (i1, i2, cons, x, _) = _po_graph(g, params)
@@ -799,6 +932,24 @@ class POBatch:
         cp, cq = np.zeros((self._n[i], 6, 6)), np.zeros((self._pairs.get(int(i), 0), 6, 6))
         _check(lib().slslam_po_batch_get_covariance(self._h, int(i), C.byref(st), _dp(cp), _dp(cq)), "slslam_po_batch_get_covariance")
         return st.value, cp, cq
+
+    def set_candidates(self, i, candidates):
+        """The candidate edges gate() judges for graph i (replaces the previous list; None or an empty list clears it)."""
+        if candidates is None:
+            candidates = dict(pose_a=[], pose_b=[], constraints=[])
+        cc, keep = _po_candidates(candidates)
+        _check(lib().slslam_po_batch_set_candidates(self._h, int(i), C.byref(cc)), "slslam_po_batch_set_candidates")
+        self._cands[int(i)] = cc.num
+
+    def gate(self, stream=None):
+        """covariance() plus the statistics of every graph's candidates; download() brings both back."""
+        _check(lib().slslam_po_batch_gate(self._h, C.c_void_p(stream or 0)), "slslam_po_batch_gate")
+
+    def get_gate(self, i):
+        """dict as po_edge_statistics returns, for graph i's candidates."""
+        out = _edge_outputs(self._cands.get(int(i), 0))
+        _check(lib().slslam_po_batch_get_gate(self._h, int(i), _ip(out[0]), *[_dp(a) for a in out[1:]]), "slslam_po_batch_get_gate")
+        return _edge_dict(*out)
 
     def covariance_stats(self):
         c, a = C.c_longlong(0), C.c_longlong(0)

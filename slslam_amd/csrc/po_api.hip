@@ -729,5 +729,7 @@ extern "C" int slslam_po_structure(const slslam_po_graph* g, int* slot_out, int 
 
 // posterior covariances of one graph or of a batch's graphs: the kernels, the plan, slslam_po_covariance
 #include "po_covariance.h"
+// edge statistics under those covariances: slslam_po_edge_statistics, slslam_po_gate and the gate's plan
+#include "po_gate.h"
 // many graphs per call: slslam_po_batch_* (the same kernels' bodies, the same symbolic analysis)
 #include "po_batch.h"

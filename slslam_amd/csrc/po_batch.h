@@ -108,6 +108,13 @@ struct slslam_po_batch {
     std::vector<int> cov_pa, cov_pb;
     int cov_status = SLSLAM_COV_OK;
     std::vector<double> cov_poses, cov_pairs;
+    // the gate (po_gate.h): the caller's candidates, the pair lists of the covariance plan (the caller's pairs, then the candidates),
+    // and what the last downloaded slslam_po_batch_gate call gave
+    std::vector<int> gate_pa, gate_pb, plan_pa, plan_pb;
+    std::vector<double> gate_cons, gate_r;
+    double gate_sigma2 = 1.0;
+    std::vector<int> gate_status;
+    std::vector<double> gate_err, gate_cov, gate_W, gate_m2;
   };
   int device = -1;
   bool finalized = false, have_results = false;
@@ -142,14 +149,19 @@ struct slslam_po_batch {
   bool cov_pending = false;                 // a covariance call is on the device, not downloaded, no solve or reset behind it
   bool cov_valid = false;                   // the graphs hold the results of the latest covariance call
   long long cov_calls = 0, cov_allocs = 0;
+  PoGatePlan gate_plan;                     // laid out behind cov_plan in cov_dev, rebuilt with it
+  char* gate_h_down = nullptr;              // pinned landing area of the gate's results
+  size_t gate_down_cap = 0;
+  bool gate_call = false;                   // the covariance call that is pending (or, after its download, valid) was a gate call
   void release() {
     if (arena) (void)hipFree(arena);
     if (h_up) (void)hipHostFree(h_up);
     if (h_down) (void)hipHostFree(h_down);
     if (cov_dev) (void)hipFree(cov_dev);
     if (cov_h_down) (void)hipHostFree(cov_h_down);
-    arena = h_up = h_down = cov_dev = cov_h_down = nullptr;
-    cov_dev_bytes = cov_down_cap = 0;
+    if (gate_h_down) (void)hipHostFree(gate_h_down);
+    arena = h_up = h_down = cov_dev = cov_h_down = gate_h_down = nullptr;
+    cov_dev_bytes = cov_down_cap = gate_down_cap = 0;
   }
 };
 
@@ -450,6 +462,7 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(b->h_down, b->arena, b->down_bytes, hipMemcpyDeviceToHost, s));
     if (b->cov_pending) HIP_TRY(hipMemcpyAsync(b->cov_h_down, b->cov_dev + b->cov_plan.down_off, b->cov_plan.down_bytes, hipMemcpyDeviceToHost, s));
+    if (b->cov_pending && b->gate_call && b->gate_plan.down_bytes > 0) HIP_TRY(hipMemcpyAsync(b->gate_h_down, b->cov_dev + b->gate_plan.down_off, b->gate_plan.down_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   int steps = 0;
@@ -471,6 +484,10 @@ extern "C" int slslam_po_batch_download(slslam_po_batch* b, void* stream) {
       std::memcpy(G.cov_poses.data(), b->cov_h_down + P.o_poses[(size_t)a], sizeof(double) * 36 * (size_t)G.N);
       G.cov_pairs.resize((size_t)36 * G.cov_pa.size());
       if (!G.cov_pa.empty()) std::memcpy(G.cov_pairs.data(), b->cov_h_down + P.o_pairs[(size_t)a], sizeof(double) * 36 * G.cov_pa.size());
+      if (!b->gate_call || b->gate_plan.down_bytes == 0) continue;
+      const size_t m = G.gate_pa.size();     // the gate's results, likewise
+      G.gate_status.resize(m); G.gate_err.resize(6 * m); G.gate_cov.resize(36 * m); G.gate_W.resize(36 * m); G.gate_m2.resize(m);
+      po_gate_read(b->gate_plan, b->gate_h_down, a, (int)m, nullptr, G.gate_status.data(), G.gate_err.data(), G.gate_cov.data(), G.gate_W.data(), G.gate_m2.data());
     }
   } catch (const std::bad_alloc&) {
     return SLSLAM_ERR_NO_MEMORY;
@@ -546,29 +563,44 @@ extern "C" int slslam_po_batch_set_covariance_pairs(slslam_po_batch* b, int inde
   return SLSLAM_OK;
 }
 
-extern "C" int slslam_po_batch_covariance(slslam_po_batch* b, void* stream) {
+namespace {
+// slslam_po_batch_covariance and slslam_po_batch_gate: the covariance launch sequence and, for the gate, k_po_gate behind it
+int po_batch_covariance_call(slslam_po_batch* b, void* stream, bool gate) {
   if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (!b->finalized) return SLSLAM_ERR_STATE;
   const int A = (int)b->active.size();
   ++b->cov_calls;
   b->cov_valid = false;
+  b->gate_call = gate;
   if (A == 0) { b->cov_pending = true; return SLSLAM_OK; }
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t s = (hipStream_t)stream;
   if (b->cov_dirty) {
     try {
       std::vector<PoCovInput> in((size_t)A);
+      bool any_candidates = false;          // without any, the plan is slslam_po_batch_covariance's as it always was: no gate region
+      for (int a = 0; a < A; ++a) any_candidates = any_candidates || !b->graphs[(size_t)b->active[(size_t)a]].gate_pa.empty();
+      std::vector<PoGateInput> gin(any_candidates ? (size_t)A : 0);
       for (int a = 0; a < A; ++a) {
-        const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
+        auto& G = b->graphs[(size_t)b->active[(size_t)a]];
+        G.plan_pa = G.cov_pa; G.plan_pa.insert(G.plan_pa.end(), G.gate_pa.begin(), G.gate_pa.end());
+        G.plan_pb = G.cov_pb; G.plan_pb.insert(G.plan_pb.end(), G.gate_pb.begin(), G.gate_pb.end());
         const PoBatchGraph& D = b->h_desc[(size_t)a];
         PoCovInput& I = in[(size_t)a];
         I.N = G.N; I.E = G.E; I.n = G.sym.n; I.ld = G.sym.ld;
         I.d_p1 = D.p.p1; I.d_p2 = D.p.p2; I.d_slot = D.p.slot; I.d_cons = D.p.cons; I.d_winfo = D.p.winfo;      // the batch's own arrays: the chains-first slots do as well as any
         I.d_x_src = D.p.x; I.d_st_src = D.p.st; I.d_x0 = D.x0;
-        I.pa = G.cov_pa.data(); I.pb = G.cov_pb.data(); I.P = (int)G.cov_pa.size();
+        I.pa = G.plan_pa.data(); I.pb = G.plan_pb.data(); I.P = (int)G.plan_pa.size();
+        if (!any_candidates) continue;
+        PoGateInput& Q = gin[(size_t)a];
+        Q.num = (int)G.gate_pa.size(); Q.pair_off = (int)G.cov_pa.size(); Q.cons = G.gate_cons.data();
+        Q.rmeas = G.gate_r.empty() ? nullptr : G.gate_r.data(); Q.sigma2 = G.gate_sigma2;
       }
       PoCovPlan plan;
-      const size_t bytes = po_cov_layout(in, b->huber, PoCarve(), nullptr, nullptr, &plan);
+      PoGatePlan gplan;
+      PoCarve gcarve;
+      gcarve.off = po_cov_layout(in, b->huber, PoCarve(), nullptr, nullptr, &plan);
+      const size_t bytes = any_candidates ? po_gate_layout(gin, gcarve, nullptr, nullptr, &gplan) : gcarve.off;
       HIP_TRY(hipStreamSynchronize(s));     // (an earlier covariance call may still read the plan that is about to be replaced)
       if (bytes > b->cov_dev_bytes) {
         if (b->cov_dev) (void)hipFree(b->cov_dev);
@@ -582,20 +614,91 @@ extern "C" int slslam_po_batch_covariance(slslam_po_batch* b, void* stream) {
         HIP_TRY(hipHostMalloc((void**)&b->cov_h_down, plan.down_bytes, hipHostMallocDefault));
         b->cov_down_cap = plan.down_bytes; ++b->cov_allocs;
       }
-      std::vector<char> img;
+      if (gplan.down_bytes > b->gate_down_cap) {
+        if (b->gate_h_down) (void)hipHostFree(b->gate_h_down);
+        b->gate_h_down = nullptr; b->gate_down_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&b->gate_h_down, gplan.down_bytes, hipHostMallocDefault));
+        b->gate_down_cap = gplan.down_bytes; ++b->cov_allocs;
+      }
+      std::vector<char> img, gimg;
       po_cov_layout(in, b->huber, PoCarve(), b->cov_dev, &img, &plan);
+      if (any_candidates) po_gate_layout(gin, gcarve, b->cov_dev, &gimg, &gplan);
       HIP_TRY(hipMemcpyAsync(b->cov_dev + plan.img_off, img.data(), plan.img_bytes, hipMemcpyHostToDevice, s));
+      if (any_candidates) HIP_TRY(hipMemcpyAsync(b->cov_dev + gplan.img_off, gimg.data(), gplan.img_bytes, hipMemcpyHostToDevice, s));
       HIP_TRY(hipStreamSynchronize(s));     // (img leaves scope)
       HIP_TRY(po_cov_lds_attribute());
       b->cov_plan = std::move(plan);
+      b->gate_plan = std::move(gplan);
       b->cov_dirty = false;
     } catch (const std::bad_alloc&) {
       return SLSLAM_ERR_NO_MEMORY;
     }
   }
-  const int rc = po_cov_enqueue(b->cov_plan, s);
+  int rc = po_cov_enqueue(b->cov_plan, s);
+  if (rc == SLSLAM_OK && gate) rc = po_gate_enqueue(b->cov_plan, b->gate_plan, s);
   if (rc == SLSLAM_OK) b->cov_pending = true;
   return rc;
+}
+}  // namespace
+
+extern "C" int slslam_po_batch_covariance(slslam_po_batch* b, void* stream) { return po_batch_covariance_call(b, stream, false); }
+
+// ---- the gate (po_gate.h): candidates per graph, judged behind a covariance call of the batch
+extern "C" int slslam_po_batch_set_candidates(slslam_po_batch* b, int index, const slslam_po_candidates* c) {
+  if (!b || index < 0 || index >= (int)b->graphs.size()) return SLSLAM_ERR_INVALID_ARGUMENT;
+  slslam_po_batch::Graph& G = b->graphs[(size_t)index];
+  if (!po_candidates_ok(G.N, c)) return SLSLAM_ERR_INVALID_ARGUMENT;
+  try {
+    const size_t m = (size_t)c->num;
+    std::vector<int> pa(c->pose_a, c->pose_a + m), pb(c->pose_b, c->pose_b + m);
+    std::vector<double> cons(c->constraints, c->constraints + 6 * m), r;
+    if (c->cov_meas && m) r.assign(c->cov_meas, c->cov_meas + 36 * m);
+    G.gate_pa.swap(pa); G.gate_pb.swap(pb); G.gate_cons.swap(cons); G.gate_r.swap(r);
+    G.gate_sigma2 = c->sigma2;
+  } catch (const std::bad_alloc&) {
+    return SLSLAM_ERR_NO_MEMORY;
+  }
+  b->cov_dirty = true;
+  b->cov_pending = b->cov_valid = false;    // (results of a call made with the previous list no longer match the list)
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_po_batch_gate(slslam_po_batch* b, void* stream) {
+  const int rc = po_batch_covariance_call(b, stream, true);
+  if (rc != SLSLAM_OK) return rc;
+  // a graph without edges is not on the device (no free pose: every Sigma block is zero, S = R): its candidates go through the primitive
+  for (auto& G : b->graphs) {
+    const int m = (int)G.gate_pa.size();
+    if (G.active >= 0 || m == 0) continue;
+    try {
+      std::vector<double> xa((size_t)6 * m), xb((size_t)6 * m);
+      for (int k = 0; k < m; ++k) {
+        std::memcpy(&xa[(size_t)6 * k], &G.x0[(size_t)6 * G.gate_pa[(size_t)k]], sizeof(double) * 6);
+        std::memcpy(&xb[(size_t)6 * k], &G.x0[(size_t)6 * G.gate_pb[(size_t)k]], sizeof(double) * 6);
+      }
+      G.gate_status.resize((size_t)m); G.gate_err.resize((size_t)6 * m); G.gate_cov.resize((size_t)36 * m); G.gate_W.resize((size_t)36 * m); G.gate_m2.resize((size_t)m);
+      slslam_po_edge_items it = { m, xa.data(), xb.data(), G.gate_cons.data(), nullptr, nullptr, nullptr, G.gate_r.empty() ? nullptr : G.gate_r.data(), G.gate_sigma2 };
+      const int re = slslam_po_edge_statistics(&it, G.gate_status.data(), G.gate_err.data(), G.gate_cov.data(), G.gate_W.data(), G.gate_m2.data());
+      if (re != SLSLAM_OK) return re;
+    } catch (const std::bad_alloc&) {
+      return SLSLAM_ERR_NO_MEMORY;
+    }
+  }
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_po_batch_get_gate(const slslam_po_batch* b, int index, int* status, double* error, double* cov, double* sqrt_information,
+                                        double* mahalanobis2) {
+  if (!b || index < 0 || index >= (int)b->graphs.size() || !b->cov_valid || !b->gate_call) return SLSLAM_ERR_INVALID_ARGUMENT;
+  const slslam_po_batch::Graph& G = b->graphs[(size_t)index];
+  const size_t m = G.gate_pa.size();
+  if (m == 0) return SLSLAM_OK;
+  if (status) std::memcpy(status, G.gate_status.data(), sizeof(int) * m);
+  if (error) std::memcpy(error, G.gate_err.data(), sizeof(double) * 6 * m);
+  if (cov) std::memcpy(cov, G.gate_cov.data(), sizeof(double) * 36 * m);
+  if (sqrt_information) std::memcpy(sqrt_information, G.gate_W.data(), sizeof(double) * 36 * m);
+  if (mahalanobis2) std::memcpy(mahalanobis2, G.gate_m2.data(), sizeof(double) * m);
+  return SLSLAM_OK;
 }
 
 extern "C" int slslam_po_batch_get_covariance(const slslam_po_batch* b, int index, int* status, double* cov_poses, double* cov_pairs) {

@@ -15,6 +15,8 @@
 #include "ceres/ceres.h"
 #include "ceres/rotation.h"
 
+struct slslam_po_candidates;   // include/slslam_hip.h
+
 // The SE(3) helpers of the reference header (src/po_problem.h:27-64), poses as [angle-axis (3) | translation (3)], kept so that
 // code written against that header finds the same three templates.  On the GPU the same algebra runs on dual numbers
 // (slslam_amd/csrc/po_kernels.h); these host forms are for callers and for the tests (tests/test_host_cxx.py compares them with
@@ -84,6 +86,12 @@ class POProblem {
   inline void set_robustify(bool r)       { robustify = r;       }
   bool robust() const { return robustify; }
   int num_poses() const;
+  // An extension the reference does not have (consistency_broken(), src/slam.cpp:1215-1232, tests two fixed thresholds): candidate
+  // edges against this graph at parameters(), under its posterior covariance (slslam_po_gate, include/slslam_hip.h - which defines
+  // slslam_po_candidates and the outputs, [candidates.num] items each, any may be null).  Forwards the problem's own arrays, robust()
+  // (HuberLoss(0.001)) and sqrt_information(); returns the C ABI's status.
+  int gate(const slslam_po_candidates& candidates, int* cov_status, int* status, double* error, double* cov, double* sqrt_information,
+           double* mahalanobis2) const;
 
   void build(Problem* problem);
   void set_options(Solver::Options* options);

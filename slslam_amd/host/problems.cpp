@@ -77,6 +77,16 @@ int POProblem::num_poses() const {
 
 void POProblem::build(Problem* problem) { problem->BindPO(this); }
 
+int POProblem::gate(const slslam_po_candidates& candidates, int* cov_status, int* status, double* error, double* cov, double* sqrt_information,
+                    double* mahalanobis2) const {
+  slslam_po_graph g = {};
+  g.num_poses = num_poses(); g.num_edges = size_;
+  g.pose_index_1 = pose_index_1_; g.pose_index_2 = pose_index_2_;
+  g.constraints = constraints_; g.parameters = parameters_;
+  g.sqrt_information = sqrt_information_;
+  return slslam_po_gate(&g, robustify ? 0.001 : 0.0, &candidates, cov_status, status, error, cov, sqrt_information, mahalanobis2);
+}
+
 void POProblem::set_options(Solver::Options* options) {
   options->linear_solver_type = SPARSE_NORMAL_CHOLESKY;
   options->num_linear_solver_threads = num_threads;
