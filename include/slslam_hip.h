@@ -690,6 +690,47 @@ int  slslam_pose_estimator_stats(const slslam_pose_estimator* est, long long* ca
 int  slslam_pose_estimator_window(const slslam_pose_estimator* est, int frame, unsigned int* index_words, double* observations,
                                   double* parameters, double* solved_camera, int* num_lines);
 
+/* ------------------------------------------------------------------ structure-only refinement: every camera constant, every line free
+ * The mirror image of the motion-only window (multi-view line triangulation): with the cameras fixed every line is its own 4-unknown
+ * Levenberg-Marquardt problem with its own trust region.  Where it is used: a landmark made from one stereo pair (initialize_lm,
+ * reference src/slam.cpp:161-219) has a poor depth until two free keyframes see it; the lines seen from a frame whose pose
+ * slslam_pose_estimator_run has just fixed; the lines of keyframes a pose-graph solve has moved.  One launch solves every line of every
+ * window of a call, lane <-> line (csrc/lba_refine_lines.h); a line's result does not depend on the other lines or windows of the call. */
+typedef struct slslam_line_refiner slslam_line_refiner;
+enum { SLSLAM_LINE_REFINED = 0, SLSLAM_LINE_CONSTANT = 1, SLSLAM_LINE_NO_OBSERVATIONS = 2, SLSLAM_LINE_INVALID = 3 };
+typedef struct slslam_line_result {       /* one per line of a window */
+  int    status;                  /* SLSLAM_LINE_*; anything but REFINED: the line's four doubles are untouched, the fields below 0  */
+  int    termination_type;        /* as slslam_summary.termination_type                                                             */
+  int    num_successful_steps, num_unsuccessful_steps;
+  int    num_observations;        /* observations that name the line (every status)                                                 */
+  double initial_cost, final_cost;
+} slslam_line_result;
+
+/* device < 0 selects the current HIP device.  opt (NULL = slslam_default_options): max_num_iterations (0: the costs only), huber_delta,
+ * baseline, the trust-region constants and jacobi_scaling are used, everything else is ignored.  max_lines / max_observations: what the
+ * device and page-locked buffers are made for at the first run - lines in whole waves of 64 per window, observations with each wave's
+ * lines padded to its longest (at most 126 x a window's longest line); a run that needs more makes larger ones, a run that does not
+ * allocates nothing.  Touches no device: a machine without one fails at run. */
+int  slslam_line_refiner_create(int device, const slslam_solver_options* opt, long long max_lines, long long max_observations,
+                                slslam_line_refiner** out);
+void slslam_line_refiner_destroy(slslam_line_refiner* refiner);
+/* windows[n]: fixed_index[2i] (camera) is ignored - every camera is constant; fixed_index[2i+1] keeps the solve's meaning - one flagged
+ * observation makes the line constant (SLSLAM_LINE_CONSTANT).  A line nobody observes: SLSLAM_LINE_NO_OBSERVATIONS.  A line with a
+ * non-finite parameter or observation, or seen from a camera with a non-finite parameter: SLSLAM_LINE_INVALID; the other lines are
+ * unaffected.  windows[i].parameters: the refined lines in place (a line that ends in SLSLAM_NUMERICAL_FAILURE keeps its values), the
+ * camera part is read and never written.  results (may be NULL; results[i] may be NULL): windows[i].num_lines records; totals (may be
+ * NULL): per window the sums over its refined lines (steps, costs, 4 parameters and the observations of each; termination_type:
+ * NUMERICAL_FAILURE if a line failed, else NO_CONVERGENCE if a line stopped at the iteration cap, else the largest of the lines').
+ * An index out of range, a negative count or a missing array: SLSLAM_ERR_INVALID_ARGUMENT for the call, nothing written.  More than
+ * 630 cameras in a window: SLSLAM_ERR_UNSUPPORTED.  Synchronous; host pointers; one upload, one launch, one download per call. */
+int  slslam_line_refiner_run(slslam_line_refiner* refiner, int n, const slslam_lba_window* windows,
+                             slslam_line_result* const* results, slslam_summary* totals);
+/* Since create: runs, device / page-locked buffer allocations.  Either pointer may be NULL. */
+int  slslam_line_refiner_stats(const slslam_line_refiner* refiner, long long* calls, long long* allocations);
+/* One window, one call (its own buffers, made and freed). */
+int  slslam_lba_refine_lines(const slslam_lba_window* window, const slslam_solver_options* opt,
+                             slslam_line_result* results, slslam_summary* total);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */

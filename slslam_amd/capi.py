@@ -78,6 +78,14 @@ class PoseEstimate(C.Structure):
                 ("num_inliers", C.c_int), ("inlier_bits", C.POINTER(C.c_ulonglong))]
 
 
+class LineResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("termination_type", C.c_int), ("num_successful_steps", C.c_int),
+                ("num_unsuccessful_steps", C.c_int), ("num_observations", C.c_int), ("initial_cost", C.c_double),
+                ("final_cost", C.c_double)]
+
+
+LINE_REFINED, LINE_CONSTANT, LINE_NO_OBSERVATIONS, LINE_INVALID = 0, 1, 2, 3
+LINE_STATUS = {0: "REFINED", 1: "CONSTANT", 2: "NO_OBSERVATIONS", 3: "INVALID"}
 POSE_STATUS = {0: "OK", 1: "TOO_FEW_FEATURES", 2: "RANSAC_FAILED"}
 COV_OK, COV_SINGULAR = 0, 1
 
@@ -112,7 +120,7 @@ EXPORTS = [
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
-    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -219,6 +227,12 @@ def lib():
                                             C.POINTER(PoseEstimate)]
     L.slslam_pose_estimator_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 4
     L.slslam_pose_estimator_window.argtypes = [vp, C.c_int, C.POINTER(C.c_uint), dp, dp, dp, ip]
+    L.slslam_line_refiner_create.argtypes = [C.c_int, C.POINTER(SolverOptions), C.c_longlong, C.c_longlong, C.POINTER(vp)]
+    L.slslam_line_refiner_destroy.argtypes = [vp]
+    L.slslam_line_refiner_destroy.restype = None
+    L.slslam_line_refiner_run.argtypes = [vp, C.c_int, C.POINTER(LBAWindow), C.POINTER(C.POINTER(LineResult)), C.POINTER(Summary)]
+    L.slslam_line_refiner_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+    L.slslam_lba_refine_lines.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), C.POINTER(LineResult), C.POINTER(Summary)]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -364,6 +378,61 @@ def lba_solve(w, params=None, trace_cap=64, **opt):
     n = C.c_int(0)
     _check(lib().slslam_lba_solve(C.byref(arr.c), C.byref(o), C.byref(s), tr, trace_cap, C.byref(n)), "slslam_lba_solve")
     return arr.params, _summary_dict(s), _trace_list(tr, min(n.value, trace_cap))
+
+
+def _line_results(num_lines):
+    """A numpy structured array laid out as slslam_line_result[num_lines]."""
+    return np.zeros(max(int(num_lines), 0), dtype=np.dtype(LineResult))
+
+
+def lba_refine_lines(w, params=None, **opt):
+    """Every line of one window refined against its cameras, all held constant (slslam_lba_refine_lines).
+    Returns (parameters with the refined lines, per-line results as a structured array, totals dict)."""
+    arr = _WindowArrays(w, params)
+    o = default_options(**opt)
+    res = _line_results(w["num_lines"])
+    tot = Summary()
+    _check(lib().slslam_lba_refine_lines(C.byref(arr.c), C.byref(o), res.ctypes.data_as(C.POINTER(LineResult)), C.byref(tot)),
+           "slslam_lba_refine_lines")
+    return arr.params, res, _summary_dict(tot)
+
+
+class LineRefiner:
+    """slslam_line_refiner: every line of every window of a run refined in one launch, buffers reused between runs."""
+
+    def __init__(self, max_lines, max_observations, device=-1, **opt):
+        self.h = C.c_void_p()
+        o = default_options(**opt)
+        _check(lib().slslam_line_refiner_create(device, C.byref(o), int(max_lines), int(max_observations), C.byref(self.h)),
+               "slslam_line_refiner_create")
+
+    def close(self):
+        if self.h:
+            lib().slslam_line_refiner_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, windows, params=None):
+        """windows: dicts as for lba_solve (params: their start vectors, else each window's own).
+        Returns (list of parameter vectors, list of per-line structured arrays, list of totals dicts)."""
+        arrs = [_WindowArrays(w, None if params is None else params[i]) for i, w in enumerate(windows)]
+        n = len(arrs)
+        cw = (LBAWindow * max(n, 1))(*[a.c for a in arrs])
+        res = [_line_results(w["num_lines"]) for w in windows]
+        rp = (C.POINTER(LineResult) * max(n, 1))(*[r.ctypes.data_as(C.POINTER(LineResult)) for r in res])
+        tot = (Summary * max(n, 1))()
+        _check(lib().slslam_line_refiner_run(self.h, n, cw, rp, tot), "slslam_line_refiner_run")
+        return [a.params for a in arrs], res, [_summary_dict(tot[i]) for i in range(n)]
+
+    def stats(self):
+        c, a = C.c_longlong(0), C.c_longlong(0)
+        _check(lib().slslam_line_refiner_stats(self.h, C.byref(c), C.byref(a)), "slslam_line_refiner_stats")
+        return {"calls": c.value, "allocations": a.value}
 
 
 class LBABatch:

@@ -2955,3 +2955,6 @@ extern "C" int slslam_lba_stream_stats(const slslam_lba_stream* st, double* ms_s
   if (host_threads) *host_threads = st->pool ? st->pool->threads() : 1;
   return SLSLAM_OK;
 }
+
+// ---- structure-only refinement: every camera constant, every line its own LM problem (csrc/lba_refine_lines.h)
+#include "lba_refine_api.h"

@@ -2061,8 +2061,12 @@ __global__ __launch_bounds__(64) void k_lm_init(BatchPtrs p, Policy pol) {
 
 // One trust-region step's bookkeeping (Ceres 1.7 TrustRegionMinimizer; policy table in DESIGN.md section 5): given the cost at the
 // candidate point and the step statistics, accept or reject, move the radius, record the iteration, test the stopping rules.
-__device__ __forceinline__ void lm_step(BatchPtrs& p, const Policy& pol, int w, LMState* st, double new_cost, double model,
-                                        double dn2, double xn2) {
+// The policy alone: `record(rec)` is called with every recorded iteration, `step_counted()` once it is counted, `still_running()` when
+// the solve goes on - what a caller does with them (trace, counters) is its own; k_refine_lines (lba_refine_lines.h) keeps one LMState
+// per lane and does nothing in them.
+template <typename Record, typename StepCounted, typename StillRunning>
+__device__ __forceinline__ void lm_step_policy(const Policy& pol, LMState* st, double new_cost, double model, double dn2, double xn2,
+                                               Record&& record, StepCounted&& step_counted, StillRunning&& still_running) {
   IterRec rec;
   rec.pad = 0;
   const double cost = st->cost;
@@ -2108,12 +2112,19 @@ __device__ __forceinline__ void lm_step(BatchPtrs& p, const Policy& pol, int w, 
   rec.cost = st->cost + st->fixed_cost;
   rec.trust_region_radius = st->radius;
   if (rec.cost < st->min_cost) st->min_cost = rec.cost;
-  push_trace(p, w, st, rec);
+  record(rec);
   st->iter = rec.iteration;
-  atomicAdd(p.iter_counter, 1ULL);   // one trust-region step (successful or not), as slam.cpp:949-950 counts
+  step_counted();
   if (st->radius < pol.min_radius) { st->status = 5; return; }
   if (st->iter >= pol.max_num_iterations) { st->status = 0; return; }
-  atomicAdd(p.active_counter, 1u);    // still running: lets the host stop enqueueing long solves early
+  still_running();
+}
+__device__ __forceinline__ void lm_step(BatchPtrs& p, const Policy& pol, int w, LMState* st, double new_cost, double model,
+                                        double dn2, double xn2) {
+  lm_step_policy(pol, st, new_cost, model, dn2, xn2,
+                 [&](const IterRec& rec) { push_trace(p, w, st, rec); },
+                 [&]() { atomicAdd(p.iter_counter, 1ULL); },    // one trust-region step (successful or not), as slam.cpp:949-950 counts
+                 [&]() { atomicAdd(p.active_counter, 1u); });   // still running: lets the host stop enqueueing long solves early
 }
 
 // Small batches (a window cut into ~50 chunks, this kernel on the latency path of every iteration): one wave per window,
