@@ -872,12 +872,7 @@ int plan_capacities(slslam_lba_batch* b, LayoutPlan& plan) {
   b->cap_maxC = plan.maxC; b->cap_maxn = plan.maxn;
 
   // ---- initial LM state (Ceres: LevenbergMarquardtStrategy ctor)
-  b->h_state0.assign(B, LMState());
-  for (int wi = 0; wi < B; ++wi) {
-    LMState& st = b->h_state0[wi];
-    std::memset(&st, 0, sizeof(st));
-    st.radius = b->pol.initial_radius; st.decrease_factor = 2.0; st.status = kRunning; st.fresh = 1;
-  }
+  b->h_state0.assign(B, lm_initial_state(b->pol));
   return SLSLAM_OK;
 }
 

@@ -3,7 +3,7 @@
 // (src/main.cpp:22 ba_window_size) and its study runs W = 40 (80 keyframes, 40 free: BASELINE.md section 1), where the
 // reduced camera system (240^2) no longer fits one wave's LDS partial or one workgroup's Cholesky.
 //
-// Same algorithm, same LM bookkeeping (lm_step, k_lm_update), same per-observation arithmetic (lba_math.h); what changes is
+// Same algorithm, same LM bookkeeping (lm_policy.h through lm_step), same per-observation arithmetic (lba_math.h); what changes is
 // where the sums live: Jacobians and F blocks are kept per observation in HBM / L2, and every sum - a line's 4x4 block, a
 // camera's record, a camera pair's block, the costs - is formed by one thread group walking a host-built list in a fixed
 // order (gather, not scatter: no atomics, results bitwise reproducible; round 2 scattered with fp64 global atomics and
@@ -451,29 +451,9 @@ __global__ __launch_bounds__(256) void k_big_prepare(BatchPtrs p, BigPtrs bg, Po
     gm_c = block_max_256(gm_c, red4);
     xs_c = block_sum_256(xs_c, red4);
     if (tid == 0) {
-      const double cost = cost_sum, fixed = fixed_sum, xn2 = xn2_line + xs_c, gmax = fmax(gmax_line, gm_c);
-      st->cost = cost; st->fixed_cost = fixed; st->initial_cost = cost + fixed; st->min_cost = cost + fixed;
-      st->x_norm = sqrt(xn2);
-      st->grad_max = gmax;
-      st->abs_grad_tol = pol.gradient_tolerance * (gmax > 1e-12 ? gmax : 1e-12);
-      st->need_grad_check = 0;
-      st->fresh = 0;
       bg.scal[(long long)w * kBgScal + kBgWasFresh] = 1.0;      // the kept camera Jacobians are still unscaled: k_big_rescale_cameras
-      int status = kRunning;
-      if (wd.nfree_params == 0) status = 2;
-      else if (!isfinite(cost)) status = 4;
-      else if (gmax <= st->abs_grad_tol) status = 1;
-      if (status == kRunning) {
-        IterRec rec;
-        rec.pad = 0;
-        rec.iteration = 0; rec.step_is_valid = 0; rec.step_is_successful = 0;
-        rec.cost = cost + fixed; rec.cost_change = 0; rec.gradient_max_norm = gmax; rec.step_norm = 0;
-        rec.relative_decrease = 0; rec.trust_region_radius = st->radius; rec.model_cost_change = 0;
-        push_trace(p, w, st, rec);
-        if (pol.max_num_iterations <= 0) status = 0;
-      }
-      st->status = status;
-      red[1] = (double)status;
+      red[1] = (double)lm_initial_evaluation(pol, st, cost_sum, fixed_sum, fmax(gmax_line, gm_c), xn2_line + xs_c, wd.nfree_params,
+                                             [&](const IterRec& rec) { push_trace(p, w, st, rec); });
     }
     __syncthreads();
     if (red[1] != (double)kRunning) return;
@@ -505,10 +485,7 @@ __global__ __launch_bounds__(256) void k_big_prepare(BatchPtrs p, BigPtrs bg, Po
     __syncthreads();
     if (tid == 0) {
       gm = fmax(fmax(fmax(red[2], red[3]), fmax(red[4], red[5])), gmax_line);
-      st->grad_max = gm;
-      st->need_grad_check = 0;
-      if (st->ntrace > 0 && st->ntrace <= kMaxTrace) p.trace[(long long)w * kMaxTrace + st->ntrace - 1].gradient_max_norm = gm;
-      if (gm <= abs_tol) st->status = 1;
+      lm_gradient_check(st, gm, [&](double v) { patch_trace(p, w, st, v); });
       red[0] = gm;
     }
     __syncthreads();
@@ -692,7 +669,7 @@ __global__ __launch_bounds__(256) void k_big_reduce(BatchPtrs p, BigPtrs bg, Pol
     m += la[kBlModel]; d += la[kBlDn2]; x += la[kBlXn2New];
   }
   cs = block_sum_256(cs, red4); m = block_sum_256(m, red4); d = block_sum_256(d, red4); x = block_sum_256(x, red4);
-  // ... and the trust-region bookkeeping of the step (what k_lm_update does for the tiled path)
+  // ... and the trust-region bookkeeping of the step (lm_policy.h through lm_step, as k_lm_update for the tiled path)
   if (tid == 0) {
     LMState* st = p.state + w;
     lm_step(p, pol, w, st, cs, st->cam_model + m, st->cam_dn2 + d, st->cam_xn2 + x);

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include "lba_math.h"
 #include "lba_types.h"
+#include "lm_policy.h"
 #include "dense_tile.h"
 #include "lba_eliminate_mfma_maps.h"
 
@@ -922,6 +923,10 @@ __device__ __forceinline__ void push_trace(BatchPtrs& p, int w, LMState* st, con
   if (st->ntrace < kMaxTrace) p.trace[(long long)w * kMaxTrace + st->ntrace] = r;
   st->ntrace++;
 }
+// the gradient max-norm at the point a recorded step led to (lm_gradient_check)
+__device__ __forceinline__ void patch_trace(BatchPtrs& p, int w, const LMState* st, double gm) {
+  if (st->ntrace > 0 && st->ntrace <= kMaxTrace) p.trace[(long long)w * kMaxTrace + st->ntrace - 1].gradient_max_norm = gm;
+}
 
 __host__ __device__ inline int solve_pad(int n) { return ((n + 15) / 16) * 16; }
 __host__ __device__ inline int solve_stride(int n) { return ((solve_pad(n) + 30) / 32) * 32 + 1; }  // == 1 (mod 32) doubles
@@ -1062,7 +1067,7 @@ __global__ __launch_bounds__(256, RESIDENT) void k_reduced_solve(BatchPtrs p, Po
   const int cur = st->cur;
   const double radius = st->radius;
   const int need_grad_check = st->need_grad_check;
-  const double abs_grad_tol = st->abs_grad_tol;
+  const double grad_tol = st->abs_grad_tol;
   const int fresh = st->fresh;            // read before the barriers below: wave 0 clears it in step 1b
   const bool timing = (pol.debug_flags & 512) && p.dbg_cycles;
   unsigned long long tlast_ = timing ? solve_clock() : 0ull;
@@ -1327,28 +1332,9 @@ __global__ __launch_bounds__(256, RESIDENT) void k_reduced_solve(BatchPtrs p, Po
         p.cam_scale[(long long)(wd.cam_off + c) * 6 + a] = sc;
       }
       cost = wave_sum(cost); fixed = wave_sum(fixed); xn2 = wave_sum(xn2); gmax = wave_max(gmax);
-      if (lane == 0) {
-        st->cost = cost; st->fixed_cost = fixed; st->initial_cost = cost + fixed; st->min_cost = cost + fixed;
-        st->x_norm = sqrt(xn2);
-        st->grad_max = gmax;
-        st->abs_grad_tol = pol.gradient_tolerance * (gmax > 1e-12 ? gmax : 1e-12);
-        st->need_grad_check = 0;
-        st->fresh = 0;
-        int status = kRunning;
-        if (wd.nfree_params == 0) status = 2;                    // FUNCTION_TOLERANCE: no free blocks
-        else if (!isfinite(cost)) status = 4;
-        else if (gmax <= st->abs_grad_tol) status = 1;
-        if (status == kRunning) {
-          IterRec rec;
-          rec.pad = 0;
-          rec.iteration = 0; rec.step_is_valid = 0; rec.step_is_successful = 0;
-          rec.cost = cost + fixed; rec.cost_change = 0; rec.gradient_max_norm = gmax; rec.step_norm = 0;
-          rec.relative_decrease = 0; rec.trust_region_radius = st->radius; rec.model_cost_change = 0;
-          push_trace(p, w, st, rec);
-        }
-        st->status = status;
-        red[1] = (double)status;
-      }
+      if (lane == 0)
+        red[1] = (double)lm_initial_evaluation(pol, st, cost, fixed, gmax, xn2, wd.nfree_params,
+                                               [&](const IterRec& rec) { push_trace(p, w, st, rec); });
     }
     __syncthreads();
     if (red[1] != (double)kRunning) return;
@@ -1377,15 +1363,11 @@ __global__ __launch_bounds__(256, RESIDENT) void k_reduced_solve(BatchPtrs p, Po
       gm = fmax(wave_max(gm), gmax_line);
       if (lane == 0) {
         red[0] = gm;
-        st->grad_max = gm;
-        st->need_grad_check = 0;
-        if (st->ntrace > 0 && st->ntrace <= kMaxTrace)
-          p.trace[(long long)w * kMaxTrace + st->ntrace - 1].gradient_max_norm = gm;
-        if (gm <= abs_grad_tol) st->status = 1 /* SLSLAM_GRADIENT_TOLERANCE */;
+        lm_gradient_check(st, gm, [&](double v) { patch_trace(p, w, st, v); });
       }
     }
     __syncthreads();
-    if (red[0] <= abs_grad_tol) return;
+    if (red[0] <= grad_tol) return;
   }
 
   SLS_SOLVE_STAMP(1);
@@ -2040,85 +2022,10 @@ __global__ __launch_bounds__(64) void k_lm_init(BatchPtrs p, Policy pol) {
   }
   cost = wave_sum(cost); fixed = wave_sum(fixed); xn2 = wave_sum(xn2); gmax = wave_max(gmax);
   if (lane != 0) return;
-  st->cost = cost; st->fixed_cost = fixed; st->initial_cost = cost + fixed; st->min_cost = cost + fixed;
-  st->x_norm = sqrt(xn2);
-  st->grad_max = gmax;
-  const double g0 = gmax > 1e-12 ? gmax : 1e-12;
-  st->abs_grad_tol = pol.gradient_tolerance * g0;
-  st->need_grad_check = 0;
-  st->fresh = 0;
-  if (wd.nfree_params == 0) { st->status = 2 /* FUNCTION_TOLERANCE: no free blocks */; return; }
-  if (!isfinite(cost)) { st->status = 4; return; }
-  if (gmax <= st->abs_grad_tol) { st->status = 1; return; }
-  IterRec rec;
-  rec.pad = 0;
-  rec.iteration = 0; rec.step_is_valid = 0; rec.step_is_successful = 0;
-  rec.cost = cost + fixed; rec.cost_change = 0; rec.gradient_max_norm = gmax; rec.step_norm = 0;
-  rec.relative_decrease = 0; rec.trust_region_radius = st->radius; rec.model_cost_change = 0;
-  push_trace(p, w, st, rec);
-  if (st->iter >= pol.max_num_iterations) st->status = 0;
+  lm_initial_evaluation(pol, st, cost, fixed, gmax, xn2, wd.nfree_params, [&](const IterRec& rec) { push_trace(p, w, st, rec); });
 }
 
-// One trust-region step's bookkeeping (Ceres 1.7 TrustRegionMinimizer; policy table in DESIGN.md section 5): given the cost at the
-// candidate point and the step statistics, accept or reject, move the radius, record the iteration, test the stopping rules.
-// The policy alone: `record(rec)` is called with every recorded iteration, `step_counted()` once it is counted, `still_running()` when
-// the solve goes on - what a caller does with them (trace, counters) is its own; k_refine_lines (lba_refine_lines.h) keeps one LMState
-// per lane and does nothing in them.
-template <typename Record, typename StepCounted, typename StillRunning>
-__device__ __forceinline__ void lm_step_policy(const Policy& pol, LMState* st, double new_cost, double model, double dn2, double xn2,
-                                               Record&& record, StepCounted&& step_counted, StillRunning&& still_running) {
-  IterRec rec;
-  rec.pad = 0;
-  const double cost = st->cost;
-  rec.iteration = st->iter + 1;
-  rec.step_is_valid = 0; rec.step_is_successful = 0;
-  rec.model_cost_change = model;
-  rec.cost_change = 0; rec.step_norm = 0; rec.relative_decrease = 0;
-  rec.gradient_max_norm = st->grad_max;
-  bool valid = !st->solve_failed && !(model < 0.0);
-  if (!isfinite(new_cost)) new_cost = 1.7976931348623157e308;
-  if (!valid) {
-    if (++st->n_invalid >= pol.max_invalid) { st->status = 4; return; }
-  } else {
-    st->n_invalid = 0;
-    rec.step_is_valid = 1;
-    rec.step_norm = sqrt(dn2);
-    if (rec.step_norm <= pol.parameter_tolerance * (st->x_norm + pol.parameter_tolerance)) { st->status = 3; return; }
-    rec.cost_change = cost - new_cost;
-    if (fabs(rec.cost_change) < pol.function_tolerance * cost) { st->status = 2; return; }
-    rec.relative_decrease = rec.cost_change / model;
-    rec.step_is_successful = rec.relative_decrease > pol.min_relative_decrease;
-  }
-  if (rec.step_is_successful) {
-    st->n_success++;
-    const double q = 2.0 * rec.relative_decrease - 1.0;
-    double f = 1.0 - q * q * q;
-    if (f < 1.0 / 3.0) f = 1.0 / 3.0;
-    st->radius = fmin(st->radius / f, pol.max_radius);
-    st->decrease_factor = 2.0;
-    st->cur = 1 - st->cur;
-    st->cost = new_cost;
-    st->x_norm = sqrt(xn2);
-    st->need_grad_check = 1;      // the next linearisation supplies the gradient at the new point
-    st->same_point = 0;
-  } else {
-    // only the radius changes: gradient and column norms of the cameras stay valid - except after the very first
-    // sweep of a solve, whose camera entries are in unscaled coordinates (it doubled as the initial evaluation)
-    st->same_point = st->iter > 0 ? 1 : 0;
-    st->n_unsuccess++;
-    if (rec.step_is_valid) { st->radius = st->radius / st->decrease_factor; st->decrease_factor *= 2.0; }
-    else st->radius *= 0.5;
-  }
-  rec.cost = st->cost + st->fixed_cost;
-  rec.trust_region_radius = st->radius;
-  if (rec.cost < st->min_cost) st->min_cost = rec.cost;
-  record(rec);
-  st->iter = rec.iteration;
-  step_counted();
-  if (st->radius < pol.min_radius) { st->status = 5; return; }
-  if (st->iter >= pol.max_num_iterations) { st->status = 0; return; }
-  still_running();
-}
+// One trust-region step of a window (lm_policy.h) with the books of the batch: the trace record, the step and the window counted.
 __device__ __forceinline__ void lm_step(BatchPtrs& p, const Policy& pol, int w, LMState* st, double new_cost, double model,
                                         double dn2, double xn2) {
   lm_step_policy(pol, st, new_cost, model, dn2, xn2,
@@ -2235,13 +2142,7 @@ __global__ __launch_bounds__(256) void k_reset(BatchPtrs p, Policy pol) {
     const double v = p.cam_x0[q];
     p.cam_x[c * 2 * kCamRec + (q - 6 * c)] = v; p.cam_x[c * 2 * kCamRec + kCamRec + (q - 6 * c)] = v;
   } else if (i < nlp + ncp + p.nwin) {
-    LMState* st = p.state + (i - nlp - ncp);
-    LMState z;
-    z.radius = pol.initial_radius; z.decrease_factor = 2.0; z.cost = 0; z.x_norm = 0; z.fixed_cost = 0;
-    z.initial_cost = 0; z.min_cost = 0; z.abs_grad_tol = 0; z.grad_max = 0; z.cam_model = 0; z.cam_dn2 = 0; z.cam_xn2 = 0;
-    z.status = kRunning; z.cur = 0; z.iter = 0; z.n_success = 0; z.n_unsuccess = 0; z.n_invalid = 0;
-    z.solve_failed = 0; z.need_grad_check = 0; z.ntrace = 0; z.same_point = 0; z.fresh = 1; z.pad = 0;
-    *st = z;
+    p.state[i - nlp - ncp] = lm_initial_state(pol);
   }
 }
 

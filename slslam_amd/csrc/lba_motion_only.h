@@ -5,7 +5,7 @@
 // back-substituted.  The general path still costs 4 dependent launches per iteration; here a wave keeps the system in
 // registers and loops: sweep the observations (same lane <-> observation tiles, same linearisation routines as the
 // elimination kernel), wave-reduce J^T J / J^T r, damp, 6 x 6 Cholesky in registers (every lane, redundantly), candidate
-// pose, sweep for the candidate cost, lm_step().  Same trust-region policy, same trace records as the general path.
+// pose, sweep for the candidate cost, lm_step().  The trust-region policy is lm_policy.h, as on every path; same trace records as the general path.
 #ifndef SLSLAM_LBA_MOTION_ONLY_H_
 #define SLSLAM_LBA_MOTION_ONLY_H_
 
@@ -140,26 +140,7 @@ __global__ __launch_bounds__(64) void k_motion_only(BatchPtrs p, Policy pol) {
         }
         __syncthreads();
         if (lane == 0) {
-          st->cost = cost; st->fixed_cost = fixed; st->initial_cost = cost + fixed; st->min_cost = cost + fixed;
-          st->x_norm = sqrt(xn2);
-          st->grad_max = gmax;
-          st->abs_grad_tol = pol.gradient_tolerance * (gmax > 1e-12 ? gmax : 1e-12);
-          st->need_grad_check = 0;
-          st->fresh = 0;
-          int status = kRunning;
-          if (wd.nfree_params == 0) status = 2;
-          else if (!isfinite(cost)) status = 4;
-          else if (gmax <= st->abs_grad_tol) status = 1;
-          if (status == kRunning) {
-            IterRec rec;
-            rec.pad = 0;
-            rec.iteration = 0; rec.step_is_valid = 0; rec.step_is_successful = 0;
-            rec.cost = cost + fixed; rec.cost_change = 0; rec.gradient_max_norm = gmax; rec.step_norm = 0;
-            rec.relative_decrease = 0; rec.trust_region_radius = st->radius; rec.model_cost_change = 0;
-            push_trace(p, w, st, rec);
-            if (st->iter >= pol.max_num_iterations) status = 0;
-          }
-          st->status = status;
+          lm_initial_evaluation(pol, st, cost, fixed, gmax, xn2, wd.nfree_params, [&](const IterRec& rec) { push_trace(p, w, st, rec); });
 #pragma unroll
           for (int a = 0; a < 6; ++a) camscale[a] = sc[a];
         }
@@ -177,12 +158,7 @@ __global__ __launch_bounds__(64) void k_motion_only(BatchPtrs p, Policy pol) {
 #pragma unroll
         for (int a = 0; a < 6; ++a) gm = fmax(gm, fabs(g[a] / sc[a]));
         __syncthreads();
-        if (lane == 0) {
-          st->grad_max = gm;
-          st->need_grad_check = 0;
-          if (st->ntrace > 0 && st->ntrace <= kMaxTrace) p.trace[(long long)w * kMaxTrace + st->ntrace - 1].gradient_max_norm = gm;
-          if (gm <= st->abs_grad_tol) st->status = 1;
-        }
+        if (lane == 0) lm_gradient_check(st, gm, [&](double v) { patch_trace(p, w, st, v); });
         __syncthreads();
       }
       if (st->status != kRunning) break;

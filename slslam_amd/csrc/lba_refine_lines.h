@@ -7,8 +7,8 @@
 // window's camera table (R, t per camera: the cameras never move, no J_L) in LDS once; then every lane loops
 //   linearise its observations at the accepted point (lba_math.h, Huber corrector folded in) -> J^T J (10 values), J^T r (4) in registers
 //   | Jacobi scale from the first linearisation | D^2 = clamp(diag) / radius | 4 x 4 Cholesky (chol4_inverse, as the sweeps) | candidate
-//   line | second pass over the observations for the candidate cost | lm_step_policy() - the policy the other paths run, one LMState
-//   per lane in registers.
+//   line | second pass over the observations for the candidate cost | lm_step_policy() - lm_policy.h, the policy every path runs, one
+//   LMState per lane in registers.
 // The row loops are wave-uniform (a group's rows), the lanes predicated: a lane whose line has stopped idles, a lane whose step was
 // rejected skips the linearisation pass (the point has not moved), the wave leaves when all its lanes have stopped.  fp64 throughout,
 // no atomics, nothing shared between lanes but the read-only camera table: a line's bytes cannot depend on its company.
@@ -65,11 +65,7 @@ __global__ __launch_bounds__(64) void k_refine_lines(RefinePtrs p, Policy pol) {
   double u[4], sc[4];
 #pragma unroll
   for (int a = 0; a < 4; ++a) { u[a] = p.u[slot * 4 + a]; sc[a] = 1.0; }
-  LMState st;
-  st.radius = pol.initial_radius; st.decrease_factor = 2.0; st.cost = 0; st.x_norm = 0; st.fixed_cost = 0;
-  st.initial_cost = 0; st.min_cost = 0; st.abs_grad_tol = 0; st.grad_max = 0; st.cam_model = 0; st.cam_dn2 = 0; st.cam_xn2 = 0;
-  st.status = kRunning; st.cur = 0; st.iter = 0; st.n_success = 0; st.n_unsuccess = 0; st.n_invalid = 0;
-  st.solve_failed = 0; st.need_grad_check = 0; st.ntrace = 0; st.same_point = 0; st.fresh = 1; st.pad = 0;
+  LMState st = lm_initial_state(pol);
 
   // observation j of this lane and its camera's table entry
   auto load_obs = [&](int j, double (&ob)[8], double (&R)[9], double (&t)[3]) {
@@ -133,15 +129,7 @@ __global__ __launch_bounds__(64) void k_refine_lines(RefinePtrs p, Policy pol) {
             xn2 += u[a] * u[a];
             sc[a] = pol.jacobi_scaling ? 1.0 / (1.0 + sqrt(H[tri_index(a, a)])) : 1.0;
           }
-          st.cost = cost; st.fixed_cost = 0.0; st.initial_cost = cost; st.min_cost = cost;
-          st.x_norm = sqrt(xn2);
-          st.grad_max = gmax;
-          st.abs_grad_tol = pol.gradient_tolerance * (gmax > 1e-12 ? gmax : 1e-12);
-          st.need_grad_check = 0;
-          st.fresh = 0;
-          if (!isfinite(cost)) st.status = kNumericalFailure;
-          else if (gmax <= st.abs_grad_tol) st.status = 1;
-          else if (st.iter >= pol.max_num_iterations) st.status = 0;
+          lm_initial_evaluation(pol, &st, cost, 0.0, gmax, xn2, 4 /* a lane with a line has its four unknowns */, [](const IterRec&) {});
           // the system to scaled coordinates (a congruence with diag(scale)), as the other paths do
 #pragma unroll
           for (int a = 0; a < 4; ++a) {
@@ -154,9 +142,7 @@ __global__ __launch_bounds__(64) void k_refine_lines(RefinePtrs p, Policy pol) {
           double gm = 0.0;
 #pragma unroll
           for (int a = 0; a < 4; ++a) gm = fmax(gm, fabs(g[a] / sc[a]));
-          st.grad_max = gm;
-          st.need_grad_check = 0;
-          if (gm <= st.abs_grad_tol) st.status = 1;
+          lm_gradient_check(&st, gm, [](double) {});
         }
         running = st.status == kRunning;
       }

@@ -228,13 +228,6 @@ long long po_zero_blocks(const PoSymbolic& S, int E) {
   return (zero_items + 255) / 256;
 }
 
-LMState po_initial_state(const Policy& pol) {
-  LMState st;
-  std::memset(&st, 0, sizeof(st));
-  st.radius = pol.initial_radius; st.decrease_factor = 2.0; st.status = kRunning;
-  return st;
-}
-
 // st == nullptr: nothing was solved (no edges, or no non-constant parameter block).
 int po_termination(const LMState* st) {
   if (!st) return SLSLAM_FUNCTION_TOLERANCE;
@@ -461,7 +454,7 @@ int po_solve_upload(PoSolve& c) {
   }
   char* stage = c.stage = hs->p;
   std::memset(stage, 0, c.up_bytes);
-  c.hst = po_initial_state(c.pol);
+  c.hst = lm_initial_state(c.pol);
   std::memcpy(stage + o_st, &c.hst, sizeof(c.hst));
   std::memcpy(stage + o_x, g->parameters, sizeof(double) * 6 * N);
   std::memcpy(stage + o_x + sizeof(double) * 6 * N, g->parameters, sizeof(double) * 6 * N);

@@ -267,7 +267,7 @@ void po_batch_layout(slslam_po_batch* b, char* arena, size_t* up_bytes, size_t* 
   // per graph: the inputs, then (after every graph's inputs) the work arrays
   std::vector<PoBatchGraph> desc((size_t)A);
   std::vector<size_t> o_in((size_t)A * 10);    // (the ninth and tenth: the poses as added and the edges' weights, behind what reset restores)
-  const LMState st = po_initial_state(b->pol);
+  const LMState st = lm_initial_state(b->pol);
   for (int a = 0; a < A; ++a) {
     const auto& G = b->graphs[(size_t)b->active[(size_t)a]];
     const PoSymbolic& S = G.sym;

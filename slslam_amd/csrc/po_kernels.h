@@ -17,13 +17,14 @@
 //                    real matrix contraction on this path
 //   k_po_trisolve    forward / backward substitution
 //   k_po_candidate   x+ = x - scale*y and the step statistics;  k_po_cost  cost at x+
-//   k_po_update      trust-region bookkeeping (same policy as the LBA path)
+//   k_po_update      trust-region bookkeeping (lm_policy.h, the policy every LM loop runs)
 //   k_po_edge_report per-edge |Te|^2 and Huber weight at the solution (slslam_po_edge_report)
 #ifndef SLSLAM_PO_KERNELS_H_
 #define SLSLAM_PO_KERNELS_H_
 
 #include <hip/hip_runtime.h>
 #include "lba_types.h"
+#include "lm_policy.h"
 #include "dense_tile.h"
 
 namespace slslam {
@@ -150,6 +151,10 @@ struct PoPtrs {
   const double* winfo;               // [36E] row-major square-root information W_e of every edge, or null: identity (kWeighted = false)
 };
 enum { kPoCost = 0, kPoCandCost = 1, kPoModel = 2, kPoDn2 = 3, kPoXn2 = 4, kPoFixed = 5 };
+__device__ __forceinline__ void po_push_trace(const PoPtrs& p, LMState* st, const IterRec& r) {
+  if (st->ntrace < kMaxTrace) p.trace[st->ntrace] = r;
+  st->ntrace++;
+}
 
 #ifndef SLSLAM_PO_FACTOR_ONLY    // (lba_api.hip includes this header for the blocked Cholesky kernels only: lba_big.h)
 // ceres::HuberLoss(a) on one edge - the switch the reference has and ships off (robustify ? new HuberLoss(0.001) : NULL, reference
@@ -387,25 +392,13 @@ __device__ __forceinline__ void po_prepare_body(const PoPtrs& p, const Policy& p
       for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
     }
     if (tid == 0) {
-      const double xn2 = red[0];
-      st->cost = p.scal[kPoCost]; st->fixed_cost = p.scal[kPoFixed];
-      st->initial_cost = st->cost + st->fixed_cost; st->min_cost = st->initial_cost;
-      st->x_norm = sqrt(xn2); st->grad_max = gm;
-      st->abs_grad_tol = pol.gradient_tolerance * (gm > 1e-12 ? gm : 1e-12);
-      IterRec rec;
-      rec.iteration = 0; rec.step_is_valid = 0; rec.step_is_successful = 0; rec.pad = 0;
-      rec.cost = st->initial_cost; rec.cost_change = 0; rec.gradient_max_norm = gm; rec.step_norm = 0;
-      rec.relative_decrease = 0; rec.trust_region_radius = st->radius; rec.model_cost_change = 0;
-      if (!isfinite(st->cost)) st->status = 4;
-      else if (gm <= st->abs_grad_tol) st->status = 1;
-      else { p.trace[st->ntrace++] = rec; if (pol.max_num_iterations <= 0) st->status = 0; }
+      // (a graph that reaches the device has free poses: the count only has to be positive)
+      lm_initial_evaluation(pol, st, p.scal[kPoCost], p.scal[kPoFixed], gm, red[0], 1, [&](const IterRec& rec) { po_push_trace(p, st, rec); });
     }
     return;
   } else if (ngc) {
     if (tid == 0) {
-      st->grad_max = gm; st->need_grad_check = 0;
-      if (st->ntrace > 0 && st->ntrace <= kMaxTrace) p.trace[st->ntrace - 1].gradient_max_norm = gm;
-      if (gm <= st->abs_grad_tol) st->status = 1;
+      lm_gradient_check(st, gm, [&](double v) { if (st->ntrace > 0 && st->ntrace <= kMaxTrace) p.trace[st->ntrace - 1].gradient_max_norm = v; });
     }
     __syncthreads();
     if (st->status != kRunning) return;
@@ -1143,54 +1136,12 @@ __device__ __forceinline__ void po_candidate_body(const PoPtrs& p) {
 }
 __global__ __launch_bounds__(256) void k_po_candidate(PoPtrs p) { po_candidate_body(p); }
 
-// trust-region bookkeeping (one thread); same policy as k_lm_update.
+// trust-region bookkeeping (one thread): the step policy of lm_policy.h, the record into the graph's trace
 __device__ __forceinline__ void po_update_body(const PoPtrs& p, const Policy& pol) {
   LMState* st = p.st;
   if (st->status != kRunning || threadIdx.x != 0) return;
-  double new_cost = p.scal[kPoCandCost];
-  const double model = p.scal[kPoModel], cost = st->cost;
-  IterRec rec;
-  rec.pad = 0; rec.iteration = st->iter + 1; rec.step_is_valid = 0; rec.step_is_successful = 0;
-  rec.model_cost_change = model; rec.cost_change = 0; rec.step_norm = 0; rec.relative_decrease = 0;
-  rec.gradient_max_norm = st->grad_max;
-  const bool valid = !st->solve_failed && !(model < 0.0);
-  if (!isfinite(new_cost)) new_cost = 1.7976931348623157e308;
-  if (!valid) {
-    if (++st->n_invalid >= pol.max_invalid) { st->status = 4; return; }
-  } else {
-    st->n_invalid = 0;
-    rec.step_is_valid = 1;
-    rec.step_norm = sqrt(p.scal[kPoDn2]);
-    if (rec.step_norm <= pol.parameter_tolerance * (st->x_norm + pol.parameter_tolerance)) { st->status = 3; return; }
-    rec.cost_change = cost - new_cost;
-    if (fabs(rec.cost_change) < pol.function_tolerance * cost) { st->status = 2; return; }
-    rec.relative_decrease = rec.cost_change / model;
-    rec.step_is_successful = rec.relative_decrease > pol.min_relative_decrease;
-  }
-  if (rec.step_is_successful) {
-    st->n_success++;
-    const double q = 2.0 * rec.relative_decrease - 1.0;
-    double f = 1.0 - q * q * q;
-    if (f < 1.0 / 3.0) f = 1.0 / 3.0;
-    st->radius = fmin(st->radius / f, pol.max_radius);
-    st->decrease_factor = 2.0;
-    st->cur = 1 - st->cur;
-    st->cost = new_cost;
-    st->x_norm = sqrt(p.scal[kPoXn2]);
-    st->need_grad_check = 1;
-  } else {
-    st->n_unsuccess++;
-    if (rec.step_is_valid) { st->radius = st->radius / st->decrease_factor; st->decrease_factor *= 2.0; }
-    else st->radius *= 0.5;
-  }
-  rec.cost = st->cost + st->fixed_cost;
-  rec.trust_region_radius = st->radius;
-  if (rec.cost < st->min_cost) st->min_cost = rec.cost;
-  if (st->ntrace < kMaxTrace) p.trace[st->ntrace] = rec;
-  st->ntrace++;
-  st->iter = rec.iteration;
-  if (st->radius < pol.min_radius) { st->status = 5; return; }
-  if (st->iter >= pol.max_num_iterations) { st->status = 0; return; }
+  lm_step_policy(pol, st, p.scal[kPoCandCost], p.scal[kPoModel], p.scal[kPoDn2], p.scal[kPoXn2],
+                 [&](const IterRec& rec) { po_push_trace(p, st, rec); }, []() {}, []() {});
 }
 __global__ void k_po_update(PoPtrs p, Policy pol) { if (blockIdx.x == 0) po_update_body(p, pol); }
 
