@@ -739,10 +739,11 @@ int slslam_po_set_profiling(int enable);
 /* Timing of the calling thread's last profiled slslam_po_solve: device time of the whole solve, of its slowest factorisation
  * (iterations enqueued after the solve has converged are no-ops), how many factorisations were enqueued, unknowns of the reduced program and of the junction block (0 with the dense factorisations). */
 int slslam_po_last_timing(double* total_ms, double* factor_ms, int* factor_calls, int* unknowns, int* junction_unknowns);
-/* Timing experiments of the matrix-core elimination sweep / the reduced solve (environment SLSLAM_DEBUG_ABLATE, bits 8 / 9):
- * wave-clock cycles per phase summed over the batch since finalize; out[16].  SLSLAM_ERR_STATE unless the variable was set. */
+/* Timing builds only (a variant library compiled with -DSLSLAM_K1_TIMING=1, -DSLSLAM_K1_WALL=1 or -DSLSLAM_SOLVE_TIMING=1: the elimination
+ * sweeps / the reduced solve and k_big_solve): wave-clock cycles per phase summed over the batch since finalize; out[16].  The product
+ * library has no stamps and no stamp buffer: SLSLAM_ERR_STATE there, from this call and the next. */
 int slslam_debug_phase_cycles(slslam_lba_batch* batch, double* out);
-/* The same buffer raw (timing builds, -DSLSLAM_K1_TIMING=1: 32 words per chunk - the elimination sweep's phase cycles and, in words
+/* The same buffer raw (-DSLSLAM_K1_TIMING=1 / -DSLSLAM_K1_WALL=1: 32 words per chunk - the elimination sweep's phase cycles and, in words
  * 30 / 31, the constant-clock (s_memrealtime, 100 MHz) times at which the chunk's wave started and ended its last sweep: what
  * tools/chunk_timeline.py reads).  Copies min(n, size) words; *size = words the buffer holds. */
 int slslam_debug_read_cycles(slslam_lba_batch* batch, unsigned long long* out, long long n, long long* size);

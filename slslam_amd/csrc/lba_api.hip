@@ -220,6 +220,14 @@ struct DeviceArena : NoCopy {
   }
 };
 
+// The timing builds (variant libraries of tools/k1_phases.py, chunk_timeline.py, solve_phases.py and their kin; never the product library):
+// only they have kernels that stamp BatchPtrs::dbg_cycles, and only they allocate it.
+#if (defined(SLSLAM_K1_TIMING) && SLSLAM_K1_TIMING) || (defined(SLSLAM_K1_WALL) && SLSLAM_K1_WALL) || (defined(SLSLAM_SOLVE_TIMING) && SLSLAM_SOLVE_TIMING)
+constexpr bool kTimingBuild = true;
+#else
+constexpr bool kTimingBuild = false;
+#endif
+
 Policy make_policy(const slslam_solver_options& o) {
   Policy p;
   p.huber_delta = o.huber_delta; p.baseline = o.baseline;
@@ -231,8 +239,6 @@ Policy make_policy(const slslam_solver_options& o) {
   p.max_num_iterations = o.max_num_iterations; p.max_invalid = o.max_num_consecutive_invalid_steps;
   p.jacobi_scaling = o.jacobi_scaling; p.keep_jacobian = 0;      // (set by finalize for the sweep that implements it)
   p.store_f = o.reuse_elimination ? 1 : 0;
-  const char* dbg = std::getenv("SLSLAM_DEBUG_ABLATE");    // timing experiments of the elimination sweep; never set in production
-  p.debug_flags = dbg ? std::atoi(dbg) : 0;
   return p;
 }
 
@@ -339,6 +345,7 @@ struct slslam_lba_batch {
   hipEvent_t part_fork = nullptr, part_join = nullptr;
   DevBuf<double> d_part_out[2];
   int num_windows() const { return part[0] ? (int)route.size() : (int)wins.size(); }
+  size_t dbg_words() const { return std::max((size_t)32 * std::max(1, nchunk), (size_t)16 * std::max<size_t>(1, wins.size())); }   // d_dbg_cycles (timing builds)
   // posterior covariances (lba_covariance.h): buffers made by the first slslam_lba_batch_covariance call and kept
   DevBuf<int> d_cov_hdr; DevBuf<double> d_cov_cam, d_cov_line;
   HostArr<int> h_cov_hdr; HostArr<double> h_cov_cam, h_cov_line;
@@ -1008,7 +1015,7 @@ int reserve_arena(slslam_lba_batch* b, const LayoutPlan& plan, BigLists* big_lis
   // the other paths (reuse_elimination, streamed F, matrix-core sweep) keep building their tables per sweep.  Small batches only:
   // there a chunk is a tile or two and the tables are a tenth of a sweep; in a batch that fills the chip a chunk is ~33 tiles, the
   // tables are nothing, and reading them would add 30 MB to a sweep's traffic
-  b->share_cam_tab = B <= b->num_cus && !b->big_mode && !b->fused_motion_only && b->elim_mode == 0 && !b->opt.reuse_elimination && !b->pol.store_f && b->opt.max_num_iterations > 0 && !(b->pol.debug_flags & 16384);
+  b->share_cam_tab = B <= b->num_cus && !b->big_mode && !b->fused_motion_only && b->elim_mode == 0 && !b->opt.reuse_elimination && !b->pol.store_f && b->opt.max_num_iterations > 0;
   ar.zeroed(b->d_cam_tab, b->share_cam_tab ? std::max<size_t>(1, (size_t)2 * kCamTab * cap_cam) : 1);
   ar.staged(b->d_cam_cf, cap_cam);
   ar.staged(b->d_cam_win, cap_cam);
@@ -1071,7 +1078,7 @@ int reserve_arena(slslam_lba_batch* b, const LayoutPlan& plan, BigLists* big_lis
     if (rc != SLSLAM_OK) return rc;
   }
   ar.zeroed(b->d_iter_counter, 1);
-  ar.zeroed(b->d_dbg_cycles, b->pol.debug_flags ? std::max((size_t)32 * std::max(1, b->nchunk), (size_t)16 * std::max(1, B)) : 1);
+  if (kTimingBuild) ar.zeroed(b->d_dbg_cycles, b->dbg_words());
   ar.zeroed(b->d_active, 1);
   return ar.layout();
 }
@@ -1132,8 +1139,7 @@ int set_lds_limits(slslam_lba_batch* b, int maxC, int maxn) {
                         (const void*)k_linearise_schur<false, 1> }, b->lds_lin));
   if (b->elim_mode == 1 && b->lds_elim > 48 * 1024) {
     if (b->lds_elim > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
-    HIP_TRY(allow_lds({ (const void*)k_eliminate_mfma<1, false>, (const void*)k_eliminate_mfma<2, false>, (const void*)k_eliminate_mfma<1, true>,
-                        (const void*)k_eliminate_mfma<2, true>, (const void*)k_eliminate_grouped<false>, (const void*)k_eliminate_grouped<true>,
+    HIP_TRY(allow_lds({ (const void*)k_eliminate_mfma<1>, (const void*)k_eliminate_mfma<2>, (const void*)k_eliminate_grouped<false>, (const void*)k_eliminate_grouped<true>,
                         (const void*)k_eliminate_grouped<false, true>, (const void*)k_eliminate_grouped<false, false, true> }, b->lds_elim));
   }
   if (b->lds_solve > 48 * 1024 && !b->big_mode)
@@ -1206,7 +1212,7 @@ struct Launcher {
 // windows beyond the tiled sweeps whose reduced systems all fit k_big_solve (lba_big_solve.h): no memsets, no per-window launch
 // loop - the solve is a fixed sequence of launches like the tiled path's, and can be captured
 bool big_one_launch(const slslam_lba_batch* b) {
-  if (!b->big_mode || (b->pol.debug_flags & 2048)) return false;
+  if (!b->big_mode) return false;
   for (const WinDesc& wd : b->h_wins) if (wd.n > kBsvMaxN) return false;
   return true;
 }
@@ -1335,11 +1341,8 @@ int enqueue_solve(slslam_lba_batch* b, hipStream_t s, bool prof, bool capturing 
       else if (b->elim_grouped && b->elim_mixed) LAUNCH(FAM_LIN, hipLaunchKernelGGL((k_eliminate_grouped<false, false, true>), g_chunk, blk64, b->lds_elim, s, p, pol));
       else if (b->elim_grouped && pol.keep_jacobian) LAUNCH(FAM_LIN, hipLaunchKernelGGL((k_eliminate_grouped<false, true>), g_chunk, blk64, b->lds_elim, s, p, pol));
       else if (b->elim_grouped) LAUNCH(FAM_LIN, hipLaunchKernelGGL(k_eliminate_grouped<false>, g_chunk, blk64, b->lds_elim, s, p, pol));
-      else if (b->elim_mode == 1 && pol.debug_flags) {          // timing experiments (SLSLAM_DEBUG_ABLATE)
-        if (b->elim_waves == 2) LAUNCH(FAM_LIN, hipLaunchKernelGGL((k_eliminate_mfma<2, true>), g_chunk, dim3(128), b->lds_elim, s, p, pol));
-        else LAUNCH(FAM_LIN, hipLaunchKernelGGL((k_eliminate_mfma<1, true>), g_chunk, blk64, b->lds_elim, s, p, pol));
-      } else if (b->elim_mode == 1 && b->elim_waves == 2) LAUNCH(FAM_LIN, hipLaunchKernelGGL((k_eliminate_mfma<2, false>), g_chunk, dim3(128), b->lds_elim, s, p, pol));
-      else if (b->elim_mode == 1) LAUNCH(FAM_LIN, hipLaunchKernelGGL((k_eliminate_mfma<1, false>), g_chunk, blk64, b->lds_elim, s, p, pol));
+      else if (b->elim_mode == 1 && b->elim_waves == 2) LAUNCH(FAM_LIN, hipLaunchKernelGGL(k_eliminate_mfma<2>, g_chunk, dim3(128), b->lds_elim, s, p, pol));
+      else if (b->elim_mode == 1) LAUNCH(FAM_LIN, hipLaunchKernelGGL(k_eliminate_mfma<1>, g_chunk, blk64, b->lds_elim, s, p, pol));
       // the first sweep of a solve doubles as Ceres' initial evaluation (every window fresh) unless the separate pass above ran
       else if (it == 0 && !(pol.max_num_iterations <= 0 || pol.store_f)) LAUNCH(FAM_LIN, hipLaunchKernelGGL((k_linearise_schur<false, 1>), g_chunk, blk64, b->lds_lin, s, p, pol));
       else LAUNCH(FAM_LIN, hipLaunchKernelGGL((k_linearise_schur<false, 0>), g_chunk, blk64, b->lds_lin, s, p, pol));
@@ -2317,13 +2320,13 @@ extern "C" int slslam_lba_batch_window_chunks(const slslam_lba_batch* b, int ind
   return SLSLAM_OK;
 }
 
-// Timing experiments only (SLSLAM_DEBUG_ABLATE bit 8; not part of include/slslam_hip.h): per-phase wave cycles of the last
-// matrix-core sweep, summed over all waves; out[16].
+// Timing builds only (kTimingBuild; SLSLAM_ERR_STATE in the product build): the stamps of BatchPtrs::dbg_cycles summed per phase
+// slot (word % 16) over all chunks / windows; out[16].
 extern "C" int slslam_debug_phase_cycles(slslam_lba_batch* b, double* out) {
   if (!b || !out || !b->finalized) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (b->part[0]) return slslam_debug_phase_cycles(b->part[0], out);
-  const size_t n = std::max((size_t)32 * std::max(1, b->nchunk), (size_t)16 * std::max<size_t>(1, b->wins.size()));
-  if (!b->pol.debug_flags) return SLSLAM_ERR_STATE;
+  if (!kTimingBuild) return SLSLAM_ERR_STATE;
+  const size_t n = b->dbg_words();
   std::vector<unsigned long long> h(n);
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipDeviceSynchronize());
@@ -2336,8 +2339,8 @@ extern "C" int slslam_debug_phase_cycles(slslam_lba_batch* b, double* out) {
 extern "C" int slslam_debug_read_cycles(slslam_lba_batch* b, unsigned long long* out, long long n, long long* size) {
   if (!b || !b->finalized || !size) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (b->part[0]) return slslam_debug_read_cycles(b->part[0], out, n, size);
-  if (!b->pol.debug_flags) return SLSLAM_ERR_STATE;
-  const long long words = (long long)std::max((size_t)32 * std::max(1, b->nchunk), (size_t)16 * std::max<size_t>(1, b->wins.size()));
+  if (!kTimingBuild) return SLSLAM_ERR_STATE;
+  const long long words = (long long)b->dbg_words();
   *size = words;
   if (!out || n <= 0) return SLSLAM_OK;
   HIP_TRY(hipSetDevice(b->device));

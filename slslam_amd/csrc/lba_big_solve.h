@@ -57,8 +57,7 @@ __global__ __launch_bounds__(64 * kBsvWaves) void k_big_solve(BatchPtrs p, BigPt
   const int n = wd.n, ld = big_ld(n), NB = (n + 15) >> 4;
   const double* S = bg.sys + bg.sys_off[w];
   double* yvec = bg.sys + bg.sys_off[w] + (long long)n * ld + 3LL * n;
-  const bool timing = (pol.debug_flags & 512) && p.dbg_cycles;      // phase timing (timing experiments only, tools/solve_phases.py)
-  unsigned long long tlast_ = timing ? solve_clock() : 0ull;
+  SLS_SOLVE_STAMP_INIT;                                // phase timing (-DSLSLAM_SOLVE_TIMING=1 only, tools/big_solve_phases.py)
   const int am = lane & 15, ak = lane >> 4;            // MFMA operand coordinates (row / k) and result column; result rows ak + 4 q
   // (LDS set up before the loads of S are issued: the first diagonal tile is factored while the rest of them are in flight)
   // the first sweep of a solve built S in unscaled camera coordinates: the congruence with the Jacobi scale k_big_prepare derived
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(64 * kBsvWaves) void k_big_solve(BatchPtrs p, BigPt
   // the diagonal tile (k, k) - already carrying the updates of block columns < k - factored by the wave that holds it, with
   // y_k = X_kk b_k of the forward substitution (lower triangular: lane = (row am, columns 4 ak ..))
   auto factor_diag = [&](const int k, const v4f64 d) {
-    const unsigned long long tf0 = timing ? solve_clock() : 0ull;
+    SLS_SOLVE_SPAN_BEGIN;
 #pragma unroll
     for (int q = 0; q < 4; ++q) Dt[(ak + 4 * q) * kBsvLd + am] = d[q];
     int fail = 0;
@@ -123,7 +122,7 @@ __global__ __launch_bounds__(64 * kBsvWaves) void k_big_solve(BatchPtrs p, BigPt
     t += __shfl_xor(t, 16);
     t += __shfl_xor(t, 32);
     if (ak == 0) yv[16 * k + am] = t;
-    if (timing && lane == 0) p.dbg_cycles[(long long)w * 16 + 5] += solve_clock() - tf0;
+    SLS_SOLVE_SPAN_END(5);
   };
   SLS_SOLVE_STAMP(0);
 

@@ -61,11 +61,10 @@ __device__ __forceinline__ unsigned sources_from_mask(int lane, unsigned d) {
 // the sources of the round after (requested behind those) are in flight: two LDS round trips hide behind ~2.2 MFMAs per
 // line and wave.  The descriptor's tile bits say which accumulators a line updates.
 // tab: the sources come from the tile's gather table (else from the line masks).
-// flags (timing experiments only): bit 1 = fetch the operands but issue no MFMA.
 enum { kMfmaBatch = 2 };
 template <int NW, int W>
 __device__ __forceinline__ void mfma_panel(const double* panel, const unsigned* gtab, bool tab, unsigned descv, int nlines,
-                                           const int (&off)[4], int lane, solve_acc_t (&acc)[ptile_slots(NW)], int flags) {
+                                           const int (&off)[4], int lane, solve_acc_t (&acc)[ptile_slots(NW)]) {
   if (nlines <= 0) return;
   const int r16 = lane & 15;
   auto sources = [&](int s) -> unsigned {
@@ -93,7 +92,6 @@ __device__ __forceinline__ void mfma_panel(const double* panel, const unsigned* 
 #pragma unroll
       for (int i = 0; i < kMfmaBatch; ++i) srcn[i] = sources(s0 + 2 * kMfmaBatch + i);
     }
-    if (flags & 2) continue;
 #pragma unroll
     for (int i = 0; i < kMfmaBatch; ++i) {
       if ((d[i] >> 16) == 0u) continue;
@@ -107,27 +105,9 @@ __device__ __forceinline__ void mfma_panel(const double* panel, const unsigned* 
   }
 }
 
-// Phase timing of the sweep (debug_flags bit 8, timing experiments only): wave-level cycle stamps at the phase boundaries,
-// summed per wave into BatchPtrs::dbg_cycles[(chunk * NW + wave) * 16 + phase].
-__device__ __forceinline__ unsigned long long wave_clock() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  return t;
-}
-#define SLS_STAMP(i)                                                        \
-  do {                                                                      \
-    if (DBG && (dbg & 256)) {                                                   \
-      __builtin_amdgcn_sched_barrier(0);                                    \
-      const unsigned long long now_ = wave_clock();                         \
-      tacc[i] += now_ - tlast; tlast = now_;                                \
-      __builtin_amdgcn_sched_barrier(0);                                    \
-    }                                                                       \
-  } while (0)
-
 enum { kCamTabG = 13 };            // doubles per camera in LDS: R[9] t[3] + pad (odd stride: conflict-free ds_read_b64)
 
-// DBG: the instantiation the timing experiments launch (debug_flags != 0); the production instantiation carries none of it.
-template <int NW, bool DBG>
+template <int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)))
 void k_eliminate_mfma(BatchPtrs p, Policy pol) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -136,7 +116,7 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
   if (ck.win < 0) return;                              // an unused entry of a refillable batch's chunk array (lba_types.h)
   const WinDesc wd = p.wins[ck.win];
   const LMState* st = p.state + ck.win;
-  if (st->status != kRunning && !(DBG && pol.debug_flags)) return;     // (timing experiments keep sweeping windows whose garbage results ended them)
+  if (st->status != kRunning) return;
   const int cur = st->cur;
   const double inv_radius = 1.0 / st->radius;
   const bool need_grad = st->need_grad_check != 0;
@@ -164,7 +144,6 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
   for (int q = tid; q < NW * 64; q += 64 * NW)                 // the 16-double pad of every plane stays zero: what absent rows read
     panels[(q >> 6) * kPanelDoubles + ((q >> 4) & 3) * kPanelPlane + 384 + (q & 15)] = 0.0;
   __syncthreads();
-  const int dbg = DBG ? pol.debug_flags : 0;       // timing experiments only (SLSLAM_DEBUG_ABLATE)
 
   solve_acc_t acc[ptile_slots(NW)];
 #pragma unroll
@@ -175,8 +154,6 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
 
   double acc_cost = 0.0, acc_fixed = 0.0, acc_gmax = 0.0, acc_xn2 = 0.0;
   int fail = 0;
-  unsigned long long tacc[DBG ? 10 : 1] = { 0 }, tlast = 0;
-  if (DBG && (dbg & 256)) tlast = wave_clock();
   TileCtx nxt = fetch_tile(p, ck.tile_begin + wave, ck.tile_end, lane);
   ObsPref pfn;
   prefetch_obs<false, false>(p, nxt, cur, wd.obs_off, pfn, lane);
@@ -221,10 +198,9 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) Q[q] = -pf.trig[6] * e2[q];
       }
-      SLS_STAMP(0);
       // ---- camera side: J_c'^T J_c' and J_c'^T r in raw coordinates (the reduced solve applies JL and the column scale);
       // after a rejected step both are unchanged and the slab keeps them
-      if (cam_free && !same_point && !(dbg & 4)) {
+      if (cam_free && !same_point) {
         double D[21], gc[6];
         gram_camera_block<double>(W, Q, dc, D);
         apply_mc<double>(Q, dc, w, gc);
@@ -234,28 +210,20 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) lds_add(&rec[kDiagG + q], gc[q]);
       }
-      SLS_STAMP(1);
       // ---- line side: Y = W Ml^T, the line's 4x4 block and gradient summed over its run of lanes
       double Y[24], v[14];
       {
         double sl[4], Ml[24];
 #pragma unroll
         for (int a = 0; a < 4; ++a) sl[a] = fresh ? 1.0 : pf.lsc[a];
-        if (!(dbg & 16)) {
-          line_rows<double>(dc, e2, zc, pf.trig[6], pf.trig[1], pf.trig[0], sl, Ml);
-          gram_line<double>(W, w, Ml, Y, v, v + 10);
-        } else {
-          for (int q = 0; q < 24; ++q) Y[q] = W[q % 21];
-          for (int q = 0; q < 14; ++q) v[q] = w[q % 6] + (q == 0 || q == 2 || q == 5 || q == 9 ? 1.0 : 0.0);
-        }
+        line_rows<double>(dc, e2, zc, pf.trig[6], pf.trig[1], pf.trig[0], sl, Ml);
+        gram_line<double>(W, w, Ml, Y, v, v + 10);
         if (!line_free) {
 #pragma unroll
           for (int q = 0; q < 14; ++q) v[q] = 0.0;
         }
       }
-      SLS_STAMP(2);
-      if (!(dbg & 8)) seg_sum_n<14>(v, sg);
-      SLS_STAMP(3);
+      seg_sum_n<14>(v, sg);
       double* H = v;
       double* g = v + 10;
       if (fresh) {
@@ -287,8 +255,7 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
       double D2[4], K[10], u[4] = { 0, 0, 0, 0 };
       lm_diag4(H, pol, inv_radius, D2);
       bool okc = true;
-      if (line_active && !(dbg & 32)) okc = chol4_inverse(H, D2, K);
-      else if (line_active) { for (int q = 0; q < 10; ++q) K[q] = H[q]; }
+      if (line_active) okc = chol4_inverse(H, D2, K);
       else { for (int q = 0; q < 10; ++q) K[q] = 0.0; }
       if (!okc) fail = 1;
       if (line_active) {
@@ -301,7 +268,6 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
         }
         if (j == 0) store_line_elim(line_elim_rec(p, ls), K, D2, g);      // the line's factor, for the back-substitution of this iteration
       }
-      SLS_STAMP(4);
       // ---- Z = Y K^T in place (column m = sum_{b <= m} K[m][b] Y_b), F' = Mc Z to the panel, b' = Mc (w - Z u)
       // the tile's gather table: for every line and every row of the stacked system, the lane that holds the row's camera
       // (64: none).  Cleared by all lanes, then every coupled observation enters its six rows.
@@ -313,7 +279,7 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
           for (int a = 0; a < 6; ++a) { const int r = 6 * cf + a; tbytes[(r & 15) * 4 + (r >> 4)] = (unsigned char)lane; }
         }
       }
-      if (cam_free && !(dbg & 64)) {
+      if (cam_free) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
           const double y0 = Y[q], y1 = Y[6 + q], y2 = Y[12 + q], y3 = Y[18 + q];
@@ -339,16 +305,13 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) lds_add(&rec[kDiagB + q], bq[q]);
       }
-      SLS_STAMP(5);
       // the next tile's loads go out here: their latency overlaps the matrix-core phase
       nxt = resolve_tile(rq);
       prefetch_obs<false, false>(p, nxt, cur, wd.obs_off, pfn, lane);
     } else {
       if (lane == 0) nlin[wave] = 0;
     }
-    SLS_STAMP(6);
     __syncthreads();
-    SLS_STAMP(7);
     // ---- every wave: rank-4 updates of all panels' lines into the tiles it owns
     {
       int l2 = lane;
@@ -359,26 +322,21 @@ void k_eliminate_mfma(BatchPtrs p, Policy pol) {
       for (int I = 0; I < 4; ++I) { const int r = 16 * I + (l2 & 15); off[I] = (l2 >> 4) * kPanelPlane + (r - 6 * (r / 6)); }
 #pragma unroll
       for (int w2 = 0; w2 < NW; ++w2) {
-        const int nl = (dbg & 1) ? 0 : __builtin_amdgcn_readfirstlane(nlin[w2]);
+        const int nl = __builtin_amdgcn_readfirstlane(nlin[w2]);
         const unsigned dv = ldesc[w2 * 64 + lane];
         const double* pn = panels + w2 * kPanelDoubles;
         const unsigned* gt = gtabs + w2 * kGatherLines * 16;
         const bool tab = nl <= kGatherLines;
         if constexpr (NW == 1) {
-          mfma_panel<1, 0>(pn, gt, tab, dv, nl, off, l2, acc, dbg);
+          mfma_panel<1, 0>(pn, gt, tab, dv, nl, off, l2, acc);
         } else {
-          if (wave == 0) mfma_panel<2, 0>(pn, gt, tab, dv, nl, off, l2, acc, dbg);
-          else mfma_panel<2, 1>(pn, gt, tab, dv, nl, off, l2, acc, dbg);
+          if (wave == 0) mfma_panel<2, 0>(pn, gt, tab, dv, nl, off, l2, acc);
+          else mfma_panel<2, 1>(pn, gt, tab, dv, nl, off, l2, acc);
         }
       }
       __builtin_amdgcn_s_setprio(0);
     }
-    SLS_STAMP(8);
     __syncthreads();
-    SLS_STAMP(9);
-  }
-  if (DBG && (dbg & 256) && lane == 0 && p.dbg_cycles) {
-    for (int i = 0; i < (DBG ? 10 : 1); ++i) p.dbg_cycles[((long long)ck.id * NW + wave) * 16 + i] = tacc[i];
   }
 
   // ---- write-out: accumulator tiles (coalesced 512-byte rows), camera records, scalars

@@ -612,7 +612,7 @@ __host__ __device__ inline int lds_doubles_linearise(int C, int n) {
 // (k_reset / finalize precede it), and none is afterwards - lm_step ends a window at max_num_iterations, so a later solve() on the same state finds
 // no kRunning window.  A 'continue solving' entry point would have to launch the FRESH = -1 instantiation (k_reduced_solve, k_backsub and the camera-table
 // mode still read LMState.fresh / cur from memory and would disagree with a hard-coded sweep).
-// Timing experiment (build with -DSLSLAM_K1_TIMING=1 and run with SLSLAM_DEBUG_ABLATE != 0: tools/k1_phases.py): shader-clock stamps
+// Timing experiment (a variant library built with -DSLSLAM_K1_TIMING=1: tools/k1_phases.py): shader-clock stamps
 // of one chunk's sweep, summed over chunks into dbg_cycles[chunk * 32 + i]
 #if defined(SLSLAM_K1_TIMING) && SLSLAM_K1_TIMING
 #define SLS_K1_STAMP(i) do { unsigned long long now_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) :: "memory"); \
@@ -622,7 +622,7 @@ __host__ __device__ inline int lds_doubles_linearise(int C, int n) {
 #define SLS_K1_STAMP(i) do { } while (0)
 #define SLS_K1_STAMP_INIT do { } while (0)
 #endif
-// -DSLSLAM_K1_WALL=1 (with SLSLAM_DEBUG_ABLATE != 0): constant-clock time (s_memrealtime, 100 MHz) at which a chunk's wave starts
+// -DSLSLAM_K1_WALL=1: constant-clock time (s_memrealtime, 100 MHz) at which a chunk's wave starts
 // (word 30) / ends (word 31) its elimination sweep - the timeline of a launch, tools/chunk_timeline.py; no other stamp, so the sweep runs undisturbed
 #if defined(SLSLAM_K1_WALL) && SLSLAM_K1_WALL
 #define SLS_K1_WALL(slot) do { unsigned long long now_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) :: "memory"); \
@@ -967,18 +967,26 @@ __host__ __device__ inline int lds_doubles_solve(int n) {
 }
 typedef double solve_acc_t __attribute__((ext_vector_type(4)));
 
-// Phase timing of the reduced solve (debug_flags bit 9, timing experiments only): wave 0 stamps the shader clock at the phase
-// boundaries, dbg_cycles[win * 16 + phase] accumulates (slslam_debug_phase_cycles reads it).
+// Phase timing of the reduced solve and of k_big_solve (a variant library built with -DSLSLAM_SOLVE_TIMING=1: tools/solve_phases.py):
+// wave 0 stamps the shader clock at the phase boundaries, dbg_cycles[win * 16 + phase] accumulates (slslam_debug_phase_cycles reads it).
+#if defined(SLSLAM_SOLVE_TIMING) && SLSLAM_SOLVE_TIMING
 __device__ __forceinline__ unsigned long long solve_clock() {
   unsigned long long t;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
   return t;
 }
-#define SLS_SOLVE_STAMP(i)                                                                   \
-  do {                                                                                       \
-    if (timing) { const unsigned long long now_ = solve_clock(); if (tid == 0) p.dbg_cycles[(long long)w * 16 + (i)] += now_ - tlast_; tlast_ = now_; } \
-  } while (0)
-
+#define SLS_SOLVE_STAMP_INIT unsigned long long tlast_ = solve_clock()
+#define SLS_SOLVE_STAMP(i) do { const unsigned long long now_ = solve_clock(); \
+    if (tid == 0 && p.dbg_cycles) p.dbg_cycles[(long long)w * 16 + (i)] += now_ - tlast_; tlast_ = now_; } while (0)
+// (a span inside a phase, any wave: the diagonal tiles of k_big_solve)
+#define SLS_SOLVE_SPAN_BEGIN const unsigned long long tf0_ = solve_clock()
+#define SLS_SOLVE_SPAN_END(i) do { if (lane == 0 && p.dbg_cycles) p.dbg_cycles[(long long)w * 16 + (i)] += solve_clock() - tf0_; } while (0)
+#else
+#define SLS_SOLVE_STAMP_INIT do { } while (0)
+#define SLS_SOLVE_STAMP(i) do { } while (0)
+#define SLS_SOLVE_SPAN_BEGIN do { } while (0)
+#define SLS_SOLVE_SPAN_END(i) do { } while (0)
+#endif
 
 // Sum of a window's chunk partials, spread over the chip: launched ahead of k_reduced_solve when a window has many chunks
 // (a single window is cut into ~50 so that its sweeps fill the CUs; one workgroup reading all of them is bound by the
@@ -1069,8 +1077,7 @@ __global__ __launch_bounds__(256, RESIDENT) void k_reduced_solve(BatchPtrs p, Po
   const int need_grad_check = st->need_grad_check;
   const double grad_tol = st->abs_grad_tol;
   const int fresh = st->fresh;            // read before the barriers below: wave 0 clears it in step 1b
-  const bool timing = (pol.debug_flags & 512) && p.dbg_cycles;
-  unsigned long long tlast_ = timing ? solve_clock() : 0ull;
+  SLS_SOLVE_STAMP_INIT;
   // The latency form (RESIDENT == 1: at most one window per CU) asks NOW for what its last phase needs of the window's cameras -
   // pose, Jacobi scale, free index: known before the solve, read after it as a chain of dependent round trips otherwise
   // (index, then per component the pose entry behind the store of the previous one: ~3 k of the launch's 50 k cycles).
@@ -1646,9 +1653,7 @@ __global__ __launch_bounds__(128) void k_backsub(BatchPtrs p, Policy pol) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   SLS_K1_STAMP_INIT;
-  // (experiment SLSLAM_DEBUG_ABLATE bit 15: the back-substitution walks the chunk array from its END - it then starts on the data the elimination
-  // sweep touched last, which the memory-side cache still holds)
-  const Chunk ck = p.chunks[(pol.debug_flags & 32768) ? gridDim.x - 1 - blockIdx.x : blockIdx.x];
+  const Chunk ck = p.chunks[blockIdx.x];
   if (ck.win < 0) return;                              // an unused entry of a refillable batch's chunk array (lba_types.h)
   SLS_K1_WALL(28);
   const WinDesc wd = p.wins[ck.win];

@@ -107,8 +107,6 @@ struct Policy {             // numeric policy, by value into every kernel that n
   int keep_jacobian;           // 1: the grouped elimination sweep leaves J_c^T J_l of every observation (BatchPtrs.fstore) and the line blocks
                                // (BatchPtrs.line_h) in memory and the sweep after a rejected step starts from them instead of linearising again
   int store_f;                 // 1: spill F blocks for the streaming back-substitution (variant B)
-  int debug_flags;             // timing experiments only (environment SLSLAM_DEBUG_ABLATE; results are wrong when set): bit 0 skip the
-                               // matrix-core phase, bit 1 fetch operands without MFMA, bit 2 skip the camera-record atomics
 };
 
 // Everything the kernels need, passed by value.
@@ -159,7 +157,8 @@ struct BatchPtrs {
   const double* cam_x0;       // [ncam][6] initial camera poses (reset)
   const double* line_u0;      // [nline][4] initial line parameters (reset)
   int nwin, nchunk, nline, ncam;
-  unsigned long long* dbg_cycles;   // [nchunk * 2][16] phase timing of the matrix-core sweep (debug_flags bit 8), else unused
+  unsigned long long* dbg_cycles;   // [max(32 nchunk, 16 nwin)] stamps of the timing builds (-DSLSLAM_K1_TIMING=1, -DSLSLAM_K1_WALL=1, -DSLSLAM_SOLVE_TIMING=1);
+                                    // nullptr in the product build, which allocates nothing for it and has no code that reads the field
   int elim_mode;              // 0: per-wave LDS partial fed by ds_add_f64 (lba_kernels.h); 1: matrix-core elimination
                               // (lba_eliminate_mfma.h), slab layout sys_doubles_mfma()
   int elim_waves;             // waves per chunk workgroup of the sweeps (1 or 2)

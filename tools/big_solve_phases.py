@@ -1,8 +1,9 @@
-"""Where the time of k_big_solve goes for a house-sized W = 40 window (timing experiment, SLSLAM_DEBUG_ABLATE=512):
+"""Where the time of k_big_solve goes for a house-sized W = 40 window (timing experiment: variant library built with -DSLSLAM_SOLVE_TIMING=1):
 s_memtime ticks (100 MHz) per launch, by phase."""
 import os, sys, ctypes, json
-os.environ["SLSLAM_DEBUG_ABLATE"] = "512"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from slslam_amd import build
+os.environ["SLSLAM_HIP_LIBRARY"] = build.build_variant("solve_timing", ["-DSLSLAM_SOLVE_TIMING=1"])   # a library of its own: the product library has no stamps
 import numpy as np
 from slslam_amd import capi, synth
 names = ["load", "-", "panels", "trailing + look-ahead factor", "backward", "(diagonal tiles, inside)"]

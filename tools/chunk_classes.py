@@ -1,8 +1,9 @@
 """Chunk durations of one elimination (or back-substitution) launch by dispatch class and by position inside the window (wall-stamp build,
 see tools/chunk_timeline.py): are the chunks of a class equal in TIME?   python tools/chunk_classes.py [windows] [sweep] [elimination|backsub]"""
 import os, sys, ctypes, json
-os.environ["SLSLAM_DEBUG_ABLATE"] = "8192"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from slslam_amd import build
+os.environ["SLSLAM_HIP_LIBRARY"] = build.build_variant("k1_wall", ["-DSLSLAM_K1_WALL=1"])   # a library of its own: the product library has no stamps
 import numpy as np
 from slslam_amd import capi, synth
 nwin = int(sys.argv[1]) if len(sys.argv) > 1 else 1024

@@ -1,9 +1,10 @@
-"""Timeline of one elimination launch: when did every chunk's wave start and end (library built with -DSLSLAM_K1_WALL=1, SLSLAM_DEBUG_ABLATE set so
-that the stamp buffer exists)?  Prints the launch's makespan, the mean chunk duration, how busy the 2048 wave slots were and the spread of the
+"""Timeline of one elimination launch: when did every chunk's wave start and end (runs on its own variant of the library, built with
+-DSLSLAM_K1_WALL=1)?  Prints the launch's makespan, the mean chunk duration, how busy the 2048 wave slots were and the spread of the
 finishing times.   python tools/chunk_timeline.py [windows] [iteration to look at, 1-based, default 6] [chunks per window] [lba_elimination] [elimination | backsub]"""
 import os, sys, ctypes, json
-os.environ["SLSLAM_DEBUG_ABLATE"] = "8192"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from slslam_amd import build
+os.environ["SLSLAM_HIP_LIBRARY"] = build.build_variant("k1_wall", ["-DSLSLAM_K1_WALL=1"])   # a library of its own: the product library has no stamps
 import numpy as np
 from slslam_amd import capi, synth
 nwin = int(sys.argv[1]) if len(sys.argv) > 1 else 1024

@@ -1,9 +1,10 @@
-"""Where the cycles of the grouped matrix-core elimination sweep go (timing experiment: library built with -DSLSLAM_K1_TIMING=1 through
-SLSLAM_EXTRA_FLAGS, SLSLAM_DEBUG_ABLATE set so that the stamp buffer exists).  Stamps wait for the wave's LDS operations, so the
+"""Where the cycles of the grouped matrix-core elimination sweep go (timing experiment: runs on its own variant of the library, built
+with -DSLSLAM_K1_TIMING=1).  Stamps wait for the wave's LDS operations, so the
 phases are what a wave spends in them with its queues drained.   python tools/grouped_phases.py [windows] [elim]"""
 import os, sys, ctypes, json
-os.environ["SLSLAM_DEBUG_ABLATE"] = "8192"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from slslam_amd import build
+os.environ["SLSLAM_HIP_LIBRARY"] = build.build_variant("k1_timing", ["-DSLSLAM_K1_TIMING=1"])   # a library of its own: the product library has no stamps
 import numpy as np
 from slslam_amd import capi, synth
 nwin = int(sys.argv[1]) if len(sys.argv) > 1 else 256

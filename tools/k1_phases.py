@@ -1,8 +1,9 @@
-"""Where the time of the elimination sweep goes when a chunk is ONE tile (a window alone on the chip).  Timing experiment: needs the
-library built with -DSLSLAM_K1_TIMING=1 (SLSLAM_EXTRA_FLAGS) and SLSLAM_DEBUG_ABLATE set (the stamp buffer is allocated then)."""
+"""Where the time of the elimination sweep goes when a chunk is ONE tile (a window alone on the chip).  Timing experiment: runs on
+its own variant of the library, built with -DSLSLAM_K1_TIMING=1 (slslam_amd.build.build_variant)."""
 import os, sys, ctypes, json
-os.environ["SLSLAM_DEBUG_ABLATE"] = "8192"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from slslam_amd import build
+os.environ["SLSLAM_HIP_LIBRARY"] = build.build_variant("k1_timing", ["-DSLSLAM_K1_TIMING=1"])   # a library of its own: the product library has no stamps
 import numpy as np
 from slslam_amd import capi, synth
 names = ["start: chunk, window, state, camera table, zero S", "first tile: descriptor, observations, lines (waited for)", "tiles", "partial: LDS -> memory", "partial: wave sums of the scalars", "partial: scalar stores", "(start: chunk, window, state loads)", "(start: camera table)",

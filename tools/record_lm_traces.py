@@ -1,6 +1,7 @@
 """Records what every device LM loop computes on one tiny problem each: tests/golden/lm_traces_parent.npz.
 
     python tools/record_lm_traces.py [--out tests/golden/lm_traces_parent.npz]
+    python tools/record_lm_traces.py --sweeps [--out tests/golden/lm_traces_sweeps_parent.npz]
 
 Run on the GPU at the commit whose behaviour is to be kept; tests/test_gpu_lm_policy_parity.py replays the recorded inputs and
 demands equal integers and bit-equal doubles (the pose graphs, whose sums go through fp64 atomics, to the oracle-parity tolerances).
@@ -9,6 +10,10 @@ iteration trace (refine-lines: the per-line results - that loop keeps no trace).
 
 The start values of every case are perturbed (Gaussian, the smallest scale of SCALES that does it) until the trace of every loop has
 at least one accepted and one rejected step; the tool refuses to write the file otherwise.
+
+--sweeps records SWEEP_CASES instead: the LBA kernels CASES does not reach (the matrix-core sweeps, the slab reduction of a window cut
+into many chunks, the reduced solve of a batch with more windows than CUs, the wider k_big_solve), replayed by
+tests/test_gpu_sweep_parity.py.
 """
 import argparse
 import os
@@ -44,6 +49,21 @@ CASES = {
     "po_single": ("po", None, {}),
     "po_batch": ("po_batch", None, {}),
 }
+
+# case -> (kind, expected path, solver options); an lba_elimination among the options is also what elimination() must report.  Inputs
+# with "copies" are solved as a batch of that many copies of the window, and the windows listed in "record" are kept (keys "<field>_<i>")
+SWEEP_CASES = {
+    "elim2": ("lba", PATH_TILED, {"lba_elimination": 2}),          # k_eliminate_mfma<1>
+    "elim3": ("lba", PATH_TILED, {"lba_elimination": 3}),          # k_eliminate_mfma<2>, k_backsub with two waves
+    "elim4": ("lba", PATH_TILED, {"lba_elimination": 4}),          # k_eliminate_grouped
+    "elim4_keep": ("lba", PATH_TILED, {"lba_elimination": 4, "lba_keep_jacobian": 1}),
+    "elim4_mixed": ("lba", PATH_TILED, {"lba_elimination": 4, "lba_precision": 1}),
+    "two_chunks": ("lba", PATH_TILED, {"chunks_per_window": 2}),   # the 70-line window in two chunks (no slab reduction: that takes more than 8)
+    "many_chunks": ("lba", PATH_TILED, {"chunks_per_window": 64}),  # one tile per chunk, more than 8 of them: k_slab_reduce, k_lm_update_wave
+    "batch257": ("lba", PATH_TILED, {}),                           # more windows than CUs: k_reduced_solve<4>
+    "big_wide": ("lba", PATH_GLOBAL_MEMORY, {}),                   # 42 free cameras, 252 reduced unknowns: k_big_solve<kBsvSlots>
+}
+MANY_CHUNKS = 9      # what "many_chunks" must be cut into at least (k_slab_reduce runs for windows of more than 8 chunks)
 
 
 def _window(w, params=None):
@@ -102,12 +122,24 @@ def solve(kind, path, opts, inp):
         w = as_window(inp)
         b = capi.LBABatch()
         try:
-            b.add(w)
+            for _ in range(int(inp["copies"]) if "copies" in inp else 1):
+                b.add(w)
             b.finalize(**opts)
             b.solve(); b.download()
             assert b.path() == path, (b.path(), path)
-            out = _pack(b.summary(0), b.trace(0))
-            out["parameters"] = b.parameters(0).copy()
+            if "lba_elimination" in opts:
+                assert b.elimination() == opts["lba_elimination"], (b.elimination(), opts)
+            if opts.get("chunks_per_window", 0) > 8:
+                assert b.window_chunks(0) >= MANY_CHUNKS, b.window_chunks(0)
+            if "copies" in inp:
+                out = {}
+                for i in inp["record"]:
+                    for k, v in _pack(b.summary(int(i)), b.trace(int(i))).items():
+                        out["%s_%d" % (k, i)] = v
+                    out["parameters_%d" % i] = b.parameters(int(i)).copy()
+            else:
+                out = _pack(b.summary(0), b.trace(0))
+                out["parameters"] = b.parameters(0).copy()
         finally:
             b.close()
         return out
@@ -151,12 +183,13 @@ def perturbed(x, scale, seed, first=0):
     return x
 
 
-def search(names, make_inputs):
+def search(names, make_inputs, cases=None):
     """The inputs at the smallest perturbation at which every case of `names` walks both branches, and the outputs."""
+    cases = CASES if cases is None else cases
     for scale in SCALES:
         for seed in SEEDS:
             inputs = make_inputs(scale, seed)
-            outs = {n: solve(*CASES[n], inputs[n]) for n in names}
+            outs = {n: solve(*cases[n], inputs[n]) for n in names}
             if all(walks_both(o) for o in outs.values()):
                 print("%s: start perturbation %g (seed %d)" % (", ".join(names), scale, seed))
                 return {n: (inputs[n], outs[n]) for n in names}
@@ -189,6 +222,33 @@ def record():
                 d["%s_%d" % (k, i)] = v
         return {"po_batch": d}
     done.update(search(["po_batch"], batch_inputs))
+    return _flat(done)
+
+
+def wide_window():
+    """42 free cameras of 44 (252 reduced unknowns, beyond the 240 of k_big_solve<15>), few lines on long tracks."""
+    return oversize(synth.make_window(12, num_lines=60, num_kf=44, num_free=42, mean_track=10.0))
+
+
+def record_sweeps():
+    w = synth.make_window(3, num_lines=12, num_kf=3, num_free=2, mean_track=3.0)
+    w70 = synth.make_window(7, num_lines=70, num_kf=3, num_free=2, mean_track=3.0)
+    w240 = synth.make_window(9, num_lines=240, num_kf=3, num_free=2, mean_track=3.0)
+    wide = wide_window()
+    done = {}
+    for name, base in (("elim2", w), ("elim3", w), ("elim4", w), ("elim4_keep", w), ("elim4_mixed", w), ("two_chunks", w70), ("many_chunks", w240),
+                       ("big_wide", wide)):
+        done.update(search([name], lambda scale, seed: {name: _window(base, perturbed(base["parameters"], scale, seed))}, SWEEP_CASES))
+
+    def copies(scale, seed):
+        d = _window(w, perturbed(w["parameters"], scale, seed))
+        d["copies"], d["record"] = np.array(257, dtype=np.int64), np.array([0, 256], dtype=np.int64)
+        return {"batch257": d}
+    done.update(search(["batch257"], copies, SWEEP_CASES))
+    return _flat(done)
+
+
+def _flat(done):
     flat = {}
     for name, (inp, out) in done.items():
         for k, v in inp.items():
@@ -210,9 +270,11 @@ def load(path):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "lm_traces_parent.npz"))
+    ap.add_argument("--sweeps", action="store_true", help="record SWEEP_CASES (tests/golden/lm_traces_sweeps_parent.npz) instead of CASES")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    flat = record()
+    a.out = a.out or os.path.join(ROOT, "tests", "golden", "lm_traces_sweeps_parent.npz" if a.sweeps else "lm_traces_parent.npz")
+    flat = record_sweeps() if a.sweeps else record()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.savez_compressed(a.out, **flat)
     print("wrote %s: %d arrays, %d bytes" % (a.out, len(flat), os.path.getsize(a.out)))

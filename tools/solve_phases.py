@@ -1,7 +1,8 @@
-"""Where the latency of the reduced camera solve goes for ONE window (timing experiment, SLSLAM_DEBUG_ABLATE=512)."""
+"""Where the latency of the reduced camera solve goes for ONE window (timing experiment: variant library built with -DSLSLAM_SOLVE_TIMING=1)."""
 import os, sys, ctypes, json
-os.environ["SLSLAM_DEBUG_ABLATE"] = "512"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from slslam_amd import build
+os.environ["SLSLAM_HIP_LIBRARY"] = build.build_variant("solve_timing", ["-DSLSLAM_SOLVE_TIMING=1"])   # a library of its own: the product library has no stamps
 import numpy as np
 from slslam_amd import capi, synth
 names = ["zero+reduce+scalars", "initial/grad checks", "damping", "diag tile", "panel", "forward(start)", "forward", "backward", "candidate poses", "trailing"]

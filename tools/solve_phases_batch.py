@@ -1,8 +1,9 @@
-"""Phase cycles of the reduced solve in a chip-filling batch (four workgroups per CU; SLSLAM_DEBUG_ABLATE=512), per window and launch:
+"""Phase cycles of the reduced solve in a chip-filling batch (four workgroups per CU; variant library built with -DSLSLAM_SOLVE_TIMING=1), per window and launch:
    python tools/solve_phases_batch.py [windows] [elim]"""
 import os, sys, ctypes, json
-os.environ["SLSLAM_DEBUG_ABLATE"] = "512"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from slslam_amd import build
+os.environ["SLSLAM_HIP_LIBRARY"] = build.build_variant("solve_timing", ["-DSLSLAM_SOLVE_TIMING=1"])   # a library of its own: the product library has no stamps
 import numpy as np
 from slslam_amd import capi, synth
 nwin = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
