@@ -540,7 +540,7 @@ typedef struct slslam_po_edge_items {
   const double* cov_aa;        /* [36 n] or NULL = zeros (a constant pose) */
   const double* cov_bb;        /* [36 n] or NULL */
   const double* cov_ab;        /* [36 n] or NULL */
-  const double* cov_meas;      /* [36 n] R, or NULL = zeros */
+  const double* cov_meas;      /* [36 n] R, or NULL = zeros (slslam_po_constraint_covariance makes it) */
   double sigma2;
 } slslam_po_edge_items;
 /* n independent items, host pointers, synchronous: one upload, one launch, one download.  Any output may be NULL.
@@ -556,7 +556,7 @@ typedef struct slslam_po_candidates {
   const int* pose_a;           /* [num] pose indices of the graph, a != b */
   const int* pose_b;           /* [num] */
   const double* constraints;   /* [6 num] */
-  const double* cov_meas;      /* [36 num] or NULL */
+  const double* cov_meas;      /* [36 num] or NULL (slslam_po_constraint_covariance makes it) */
   double sigma2;
 } slslam_po_candidates;
 /* One graph at graph->parameters, no solve, synchronous: the launch sequence of slslam_po_covariance (weights and po_huber_delta
@@ -581,6 +581,26 @@ int  slslam_po_batch_gate(slslam_po_batch* b, void* stream);
  * or a replaced pair or candidate list came after it. */
 int  slslam_po_batch_get_gate(const slslam_po_batch* b, int index, int* status, double* error, double* cov, double* sqrt_information,
                               double* mahalanobis2);
+
+/* ---- the covariance of a constraint in the coordinates of its edge's error (csrc/po_constraint_cov.h): the R above.
+ * A loop-closure edge of the reference is the output of pose_estimation on the matched lines (src/slam.cpp:1146-1155: edge_t e(best_motion)
+ * between lc_kf_id and the current keyframe); here that is slslam_pose_estimator_run, whose covariance
+ * (slslam_pose_estimator_get_covariance) is over the constraint's own six parameters (w_C, t_C).  Per item, with Te the edge error above
+ * and J_C = dTe/dC (6 x 6; not the identity: a rotation by R_a, the lever arm t_a, and T_b^-1 in front of both):
+ *   error[6] = Te,  jacobian[36] = J_C row-major,  cov_meas[36] = sigma2 J_C Sigma_C J_C^T, exactly symmetric.
+ * cov_meas is what slslam_po_edge_items.cov_meas and slslam_po_candidates.cov_meas take. */
+typedef struct slslam_po_constraint_items {
+  int n;
+  const double* pose_a;          /* [6 n]  */
+  const double* pose_b;          /* [6 n]  */
+  const double* constraints;     /* [6 n]  */
+  const double* cov_constraint;  /* [36 n] covariance of (w_C, t_C); the lower triangle is read; NULL = zeros */
+  double sigma2;                 /* finite, > 0: multiplies cov_constraint */
+} slslam_po_constraint_items;
+/* n independent items, host pointers, synchronous: one upload, one launch, one download.  Any output may be NULL.
+ * SLSLAM_ERR_INVALID_ARGUMENT - found before an output is written or a device is needed -: items NULL, n < 0, sigma2 not finite or <= 0,
+ * a NULL pose or constraint array with n > 0, a non-finite input.  n == 0 succeeds and does nothing. */
+int  slslam_po_constraint_covariance(const slslam_po_constraint_items* items, double* error, double* jacobian, double* cov_meas);
 
 /* ------------------------------------------------------------------ RANSAC hypothesis scoring
  * (the per-frame cost centre next to the hot path.)
@@ -681,7 +701,8 @@ void slslam_pose_estimator_destroy(slslam_pose_estimator* est);
  * Synchronous; host pointers. */
 int  slslam_pose_estimator_run(slslam_pose_estimator* est, int num_frames, const slslam_ransac_trials* frames, const double* const* lines,
                                double baseline, double error_thr, double prob_free_outliers, int max_trials, slslam_pose_estimate* out);
-/* Since create: runs, device / page-locked buffer allocations of the estimator, batches finalized, batch refills.  Any pointer may be NULL. */
+/* Since create: runs, device / page-locked buffer allocations of the estimator (with covariance enabled: those of
+ * slslam_lba_batch_covariance in its batch included), batches finalized, batch refills.  Any pointer may be NULL. */
 int  slslam_pose_estimator_stats(const slslam_pose_estimator* est, long long* calls, long long* allocations, long long* finalizes,
                                  long long* refills);
 /* Test hook: the motion-only window the last run packed on the device for `frame` (status OK only, else SLSLAM_ERR_STATE) -
@@ -689,6 +710,28 @@ int  slslam_pose_estimator_stats(const slslam_pose_estimator* est, long long* ca
  * the solved (angle-axis, t) of camera 0.  Any array may be NULL. */
 int  slslam_pose_estimator_window(const slslam_pose_estimator* est, int frame, unsigned int* index_words, double* observations,
                                   double* parameters, double* solved_camera, int* num_lines);
+
+/* The covariance of every solved frame's motion, opt-in (default 0).  Host only; takes effect at the next slslam_pose_estimator_run.
+ * With enable == 0 a run is the run it was: the same launches, the same allocations, the same bytes out.  With it, the run enqueues
+ * slslam_lba_batch_covariance (cameras only) on its motion-only batch behind the solve and one launch that gathers the blocks into the
+ * result block of the run's one download; slslam_pose_estimate does not change. */
+int  slslam_pose_estimator_set_covariance(slslam_pose_estimator* est, int enable);
+/* After a run that had covariance enabled, for a frame whose status is SLSLAM_POSE_OK:
+ *   constraint[6]  the solved camera 0 (angle-axis, t) - the six doubles slslam_pose_estimator_window returns as solved_camera: the C of an
+ *                  edge previous frame -> current frame (T_{b<-a}), in the parameters cov is over;
+ *   cov[36]        row-major, exactly symmetric: the camera block slslam_lba_covariance defines for the frame's motion-only window at its
+ *                  solved parameters under the estimator's options (H = sum J_cam^T J_cam over the kept residual blocks after the Huber
+ *                  corrector, no Jacobi scaling, no damping; cov = H^-1), in unit-variance units;
+ *   *status        SLSLAM_COV_* by the pivot rule of slslam_lba_batch_covariance; SLSLAM_COV_SINGULAR: zeros in cov, the rest still written;
+ *   *dof           4 num_residual_blocks - 6 (>= 14: a solved frame has >= 5 inliers);
+ *   *sigma2        2 (summary.final_cost - summary.fixed_cost) / dof: the summary's final_cost includes fixed_cost (the cost of the
+ *                  blocks between the constant camera and the constant lines), so this is the cost of the kept blocks alone at the
+ *                  solved pose.  sigma2 cov is the covariance of constraint.
+ * Any output pointer may be NULL.  SLSLAM_ERR_INVALID_ARGUMENT: a NULL estimator or a negative frame; then SLSLAM_ERR_STATE: no run has
+ * been made, or the last one had covariance disabled or failed; then SLSLAM_ERR_INVALID_ARGUMENT: frame beyond the last run's frames;
+ * then SLSLAM_ERR_STATE: the frame is not SLSLAM_POSE_OK.  Nothing is written in any of these cases. */
+int  slslam_pose_estimator_get_covariance(const slslam_pose_estimator* est, int frame, int* status, double constraint[6], double cov[36],
+                                          double* sigma2, int* dof);
 
 /* ------------------------------------------------------------------ structure-only refinement: every camera constant, every line free
  * The mirror image of the motion-only window (multi-view line triangulation): with the cameras fixed every line is its own 4-unknown

@@ -108,6 +108,11 @@ class POCandidates(C.Structure):
                 ("cov_meas", C.POINTER(C.c_double)), ("sigma2", C.c_double)]
 
 
+class POConstraintItems(C.Structure):
+    _fields_ = [("n", C.c_int), ("pose_a", C.POINTER(C.c_double)), ("pose_b", C.POINTER(C.c_double)), ("constraints", C.POINTER(C.c_double)),
+                ("cov_constraint", C.POINTER(C.c_double)), ("sigma2", C.c_double)]
+
+
 # every symbol include/slslam_hip.h declares (checked by the CPU test-suite)
 EXPORTS = [
     "slslam_default_options", "slslam_lba_solve", "slslam_lba_batch_create", "slslam_lba_batch_destroy",
@@ -120,7 +125,7 @@ EXPORTS = [
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
-    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -213,6 +218,10 @@ def lib():
         L.slslam_po_batch_set_candidates.argtypes = [vp, C.c_int, C.POINTER(POCandidates)]
         L.slslam_po_batch_gate.argtypes = [vp, vp]
         L.slslam_po_batch_get_gate.argtypes = [vp, C.c_int, ip, dp, dp, dp, dp]
+    if hasattr(L, "slslam_po_constraint_covariance"):      # (likewise: a library built before the motion covariances existed)
+        L.slslam_po_constraint_covariance.argtypes = [C.POINTER(POConstraintItems), dp, dp, dp]
+        L.slslam_pose_estimator_set_covariance.argtypes = [vp, C.c_int]
+        L.slslam_pose_estimator_get_covariance.argtypes = [vp, C.c_int, ip, dp, dp, dp, ip]
     L.slslam_ransac_score.argtypes = [C.POINTER(RansacFrame), C.c_double, C.c_double, ip, C.POINTER(C.c_ulonglong)]
     L.slslam_po_structure.argtypes = [C.POINTER(POGraph), ip, C.c_int, ip, ip, ip, ip, ip, ip, ip]
     L.slslam_ransac_generate.argtypes = [C.POINTER(RansacTrials), C.c_double, dp, ip]
@@ -880,6 +889,41 @@ def po_gate(g, candidates, po_huber_delta=0.0, params=None):
     return st.value, _edge_dict(*out)
 
 
+def po_constraint_covariance(pose_a, pose_b, constraints, cov_constraint=None, sigma2=1.0):
+    """The covariance of n constraints in the coordinates of their edges' errors (slslam_po_constraint_covariance): dict(error[n, 6] = Te,
+    jacobian[n, 6, 6] = J_C = dTe/dC, cov_meas[n, 6, 6] = sigma2 J_C cov_constraint J_C^T) - cov_meas is the R po_edge_statistics,
+    po_gate and POBatch.set_candidates take.  cov_constraint [n, 6, 6] over (w_C, t_C), e.g. PoseEstimator's; None: zeros."""
+    xa = np.ascontiguousarray(pose_a, dtype=np.float64).reshape(-1)
+    xb = np.ascontiguousarray(pose_b, dtype=np.float64).reshape(-1)
+    cc = np.ascontiguousarray(constraints, dtype=np.float64).reshape(-1)
+    n = len(xa) // 6
+    if len(xa) != 6 * n or len(xb) != 6 * n or len(cc) != 6 * n:
+        raise ValueError("inconsistent constraint arrays")
+    sc = _opt36(cov_constraint, n)
+    it = POConstraintItems(n, _dp(xa), _dp(xb), _dp(cc), None if sc is None else _dp(sc), float(sigma2))
+    err, jac, cov = np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6, 6))
+    _check(lib().slslam_po_constraint_covariance(C.byref(it), _dp(err), _dp(jac), _dp(cov)), "slslam_po_constraint_covariance")
+    return dict(error=err, jacobian=jac, cov_meas=cov)
+
+
+def motion_candidates(estimates, pose_a, pose_b, x):
+    """Loop-closure candidates from motion estimates: (candidates, skipped).  estimates: the dicts PoseEstimator(covariance=True).run
+    returns, estimate k the motion from graph pose pose_a[k] to pose_b[k]; x: the graph's [N, 6] poses.  candidates is the dict po_gate /
+    POBatch.set_candidates take - constraints = the estimates' `constraint`, cov_meas = J_C (sigma2 covariance) J_C^T by
+    po_constraint_covariance - with the candidates' own sigma2 left out (the default 1): set it to the graph's noise variance.
+    Estimates that are not OK, or whose covariance is singular, are left out; skipped lists their indices."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 6)
+    pa, pb = np.asarray(pose_a, dtype=np.int32).reshape(-1), np.asarray(pose_b, dtype=np.int32).reshape(-1)
+    if len(pa) != len(estimates) or len(pb) != len(estimates):
+        raise ValueError("one pose pair per estimate")
+    keep = [k for k, e in enumerate(estimates) if e.get("status") == "OK" and e.get("cov_status") == COV_OK]
+    skipped = [k for k in range(len(estimates)) if k not in keep]
+    cons = np.array([estimates[k]["constraint"] for k in keep], dtype=np.float64).reshape(-1, 6)
+    sig = np.array([estimates[k]["sigma2"] * np.asarray(estimates[k]["covariance"], dtype=np.float64) for k in keep]).reshape(-1, 6, 6)
+    r = po_constraint_covariance(x[pa[keep]], x[pb[keep]], cons, sig, 1.0)
+    return dict(pose_a=pa[keep], pose_b=pb[keep], constraints=cons, cov_meas=r["cov_meas"]), skipped
+
+
 def se3_inverse(p):
     """P^-1 of a pose [angle-axis | translation] (the reference's gc_T_inv)."""
     p = np.asarray(p, dtype=np.float64)
@@ -1204,11 +1248,28 @@ class PoseEstimator:
     """SLAM::pose_estimation for many frames per call (slslam_pose_estimator_*): RANSAC, motion-only BA on its inliers, final inliers.
     Keeps its device buffers and its refillable motion-only batch between calls."""
 
-    def __init__(self, max_frames=16, max_lines=512, device=-1, **opt):
+    def __init__(self, max_frames=16, max_lines=512, device=-1, covariance=False, **opt):
         self._h = C.c_void_p()
         o = default_options(**opt)
         _check(lib().slslam_pose_estimator_create(int(device), C.byref(o), int(max_frames), int(max_lines), C.byref(self._h)),
                "slslam_pose_estimator_create")
+        self._covariance = bool(covariance)
+        if self._covariance:
+            self.set_covariance(True)
+
+    def set_covariance(self, enable):
+        """From the next run on, OK frames carry the covariance of their motion (slslam_pose_estimator_set_covariance)."""
+        _check(lib().slslam_pose_estimator_set_covariance(self._h, int(bool(enable))), "slslam_pose_estimator_set_covariance")
+        self._covariance = bool(enable)
+
+    def get_covariance(self, frame):
+        """dict(constraint [6], covariance [6, 6], cov_status, sigma2, dof) of an OK frame of the last run
+        (slslam_pose_estimator_get_covariance)."""
+        st, dof, s2 = C.c_int(-1), C.c_int(0), C.c_double(0.0)
+        cons, cov = np.zeros(6), np.zeros((6, 6))
+        _check(lib().slslam_pose_estimator_get_covariance(self._h, int(frame), C.byref(st), _dp(cons), _dp(cov), C.byref(s2), C.byref(dof)),
+               "slslam_pose_estimator_get_covariance")
+        return {"constraint": cons, "covariance": cov, "cov_status": st.value, "sigma2": s2.value, "dof": dof.value}
 
     def close(self):
         if self._h:
@@ -1224,7 +1285,8 @@ class PoseEstimator:
     def run(self, frames, baseline=0.12, error_thr=5.0 / 406.05, prob_free_outliers=0.999, max_trials=1000):
         """frames = list of dicts with obs0, obs1, lines, samples (as make_ransac_pair returns).  Returns one dict per frame:
         status, trial_cnt, ransac_score, ransac_pose [12], ransac_mask [K], summary, pose [12], num_inliers, mask [K]
-        (the RANSAC fields in the shape ransac_motion_batch returns them)."""
+        (the RANSAC fields in the shape ransac_motion_batch returns them) - and, with covariance enabled, for every OK frame
+        constraint [6], covariance [6, 6], cov_status, sigma2, dof (get_covariance)."""
         n = len(frames)
         keep, trs, lns = [], (RansacTrials * max(n, 1))(), (C.POINTER(C.c_double) * max(n, 1))()
         outs = (PoseEstimate * max(n, 1))()
@@ -1249,6 +1311,8 @@ class PoseEstimator:
                         "ransac_pose": np.array(o.ransac_pose[:]), "ransac_mask": _bits_to_mask(bitbufs[i][0], k),
                         "summary": _summary_dict(o.summary), "pose": np.array(o.pose[:]), "num_inliers": o.num_inliers,
                         "mask": _bits_to_mask(bitbufs[i][1], k)})
+            if self._covariance and o.status == 0:
+                res[-1].update(self.get_covariance(i))
         return res
 
     def stats(self):

@@ -7,6 +7,9 @@
 //   solve       the estimator's refillable fused motion-only LBA batch, refilled from those device windows (lba_resident.h)
 //   finish      k_frame_finish: gc_wt_to_Rt of the solved camera (:668-674) and the final inlier set under it (:305-312), with the
 //               refined pose, the summaries and the RANSAC winners gathered into one result block - one download
+//   covariance  (slslam_pose_estimator_set_covariance, off by default) behind the solve: slslam_lba_batch_covariance of the batch, cameras
+//               only, and k_frame_covariance: one wave per slot gathers the 6 x 6 block, its status, the residual variance and the
+//               solved parameters into a third part of the result block - the same one download
 // Two host round trips per call, whatever the number of frames.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
@@ -48,6 +51,14 @@ struct FrameOut {
   double pose[12];
   double initial_cost, final_cost, fixed_cost;
   int n_success, n_unsuccess, termination, nfree, nkept, num_inliers, built, pad;
+};
+
+// Per frame, with covariance enabled: the third part of the result block (zeros for a frame without a slot)
+struct FrameCov {
+  double constraint[6];
+  double cov[36];
+  double sigma2;
+  int status, dof;
 };
 
 // Window slot i lies at a fixed stride in the window buffers: words [2 Lcap], observations [16 Lcap], parameters [12 + 4 Lcap]
@@ -136,6 +147,30 @@ __global__ __launch_bounds__(64) void k_frame_finish(const FrameDesc* __restrict
   }
 }
 
+// One wave per slot: the slot's covariance block (k_lba_covariance: row-major 6 x 6 at the front of the window's slot, zeros when
+// singular) and status, the residual variance 2 (final cost - fixed cost) / dof of the kept blocks with dof = 4 nkept - 6, and the solved
+// camera 0 from the export, into the frame's FrameCov.  A placeholder slot writes nothing.
+__global__ __launch_bounds__(64) void k_frame_covariance(const SlotDesc* __restrict__ slots, int nslots, const int* __restrict__ cov_hdr,
+                                                         int hdr_ints, const double* __restrict__ cov_cam, long long cam_stride,
+                                                         const double* __restrict__ exported, const slslam::LMState* __restrict__ state,
+                                                         const slslam::WinDesc* __restrict__ wins, FrameCov* out) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= nslots) return;
+  const SlotDesc sd = slots[i];
+  if (sd.frame < 0) return;
+  FrameCov& o = out[sd.frame];
+  const int status = cov_hdr[(long long)i * hdr_ints] == SLSLAM_COV_OK && cov_hdr[(long long)i * hdr_ints + 1] == 1 ? SLSLAM_COV_OK : SLSLAM_COV_SINGULAR;
+  if (lane < 36) o.cov[lane] = status == SLSLAM_COV_OK ? cov_cam[(long long)i * cam_stride + lane] : 0.0;
+  else if (lane < 42) o.constraint[lane - 36] = exported[sd.exp_off + (lane - 36)];
+  else if (lane == 42) {
+    const slslam::LMState st = state[i];
+    const int dof = 4 * wins[i].nkept - 6;
+    const double final_cost = st.min_cost < st.initial_cost ? st.min_cost : st.initial_cost;      // (as k_frame_finish: the summary's)
+    o.sigma2 = 2.0 * (final_cost - st.fixed_cost) / (double)dof;
+    o.status = status; o.dof = dof;
+  }
+}
+
 }  // namespace
 
 struct slslam_pose_estimator {
@@ -147,6 +182,8 @@ struct slslam_pose_estimator {
   GrowBuf d_win{Mem::kDevice}, d_export{Mem::kDevice}, d_small{Mem::kDevice}, d_out{Mem::kDevice};
   GrowBuf h_small{Mem::kPinned}, h_out{Mem::kPinned};
   long long calls = 0, finalizes = 0, refills = 0;
+  bool want_cov = false, last_cov = false;         // slslam_pose_estimator_set_covariance; whether the last run gathered covariances ...
+  size_t off_cov = 0;                              // ... and where its FrameCov[F] lie in h_out
   // the last call, for slslam_pose_estimator_window
   std::vector<int> slot_of_frame, n_of_frame;
   std::vector<long long> exp_off_of_frame;
@@ -238,6 +275,8 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
   if (!e->ws.stream) HIP_TRY(hipStreamCreateWithFlags(&e->ws.stream, hipStreamNonBlocking));
   hipStream_t s = e->ws.stream;
   ++e->calls;
+  e->last_cov = false;
+  const bool with_cov = e->want_cov;
   e->slot_of_frame.assign((size_t)F, -1); e->n_of_frame.assign((size_t)F, 0); e->exp_off_of_frame.assign((size_t)F, 0);
 
   // ---- RANSAC of every frame (best_score = -1, slam.cpp:283); a frame with fewer than 5 common lines runs nothing (:275)
@@ -281,7 +320,9 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
   }
   // ---- the small tables (plans, slots) up, the result block [FrameOut F | bits] zeroed
   const size_t off_slots = align256(sizeof(FramePlan) * (size_t)F), small_bytes = off_slots + sizeof(SlotDesc) * (size_t)B;
-  const size_t off_bits = align256(sizeof(FrameOut) * (size_t)F), out_bytes = off_bits + 8 * (size_t)nob;
+  // (with covariance: [FrameOut F | bits | FrameCov F])
+  const size_t off_bits = align256(sizeof(FrameOut) * (size_t)F), off_cov = align256(off_bits + 8 * (size_t)nob);
+  const size_t out_bytes = with_cov ? off_cov + sizeof(FrameCov) * (size_t)F : off_bits + 8 * (size_t)nob;
   HIP_TRY(e->h_small.need(small_bytes, &e->ws.allocations));
   HIP_TRY(e->d_small.need(small_bytes, &e->ws.allocations));
   HIP_TRY(e->h_out.need(out_bytes, &e->ws.allocations));
@@ -322,6 +363,22 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
     if ((rc = slslam_lba_batch_solve(e->batch, s)) != SLSLAM_OK) return rc;
     if ((rc = slslam_lba_batch_export_device(e->batch, e->d_export.at<double>(0), s)) != SLSLAM_OK) return rc;
     if ((rc = slslam::lba_device_results(e->batch, &d_state, &d_wins)) != SLSLAM_OK) return rc;
+    if (with_cov) {
+      const int* d_hdr = nullptr;
+      const double* d_cov = nullptr;
+      int hdr_ints = 0;
+      long long cam_stride = 0;
+      long long cov_allocs[2] = { 0, 0 };
+      (void)slslam_lba_batch_covariance_stats(e->batch, nullptr, &cov_allocs[0]);
+      if ((rc = slslam_lba_batch_covariance(e->batch, s, /*with_lines=*/0)) != SLSLAM_OK) return rc;
+      (void)slslam_lba_batch_covariance_stats(e->batch, nullptr, &cov_allocs[1]);
+      e->ws.allocations += cov_allocs[1] - cov_allocs[0];             // (the batch's covariance buffers count as the estimator's)
+      if ((rc = slslam::lba_device_covariance(e->batch, &d_hdr, &hdr_ints, &d_cov, &cam_stride)) != SLSLAM_OK) return rc;
+      if (cam_stride < 36) return SLSLAM_ERR_UNSUPPORTED;
+      hipLaunchKernelGGL(k_frame_covariance, dim3((unsigned)S), dim3(64), 0, s, d_slot, S, d_hdr, hdr_ints, d_cov, cam_stride,
+                         e->d_export.at<const double>(0), d_state, d_wins, e->d_out.at<FrameCov>(off_cov));
+      HIP_TRY(hipGetLastError());
+    }
   }
 
   // ---- finish every frame in one launch, one download
@@ -363,6 +420,28 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
     if (r.inlier_bits)
       for (int w = 0; w < words_k; ++w) r.inlier_bits[w] = r.status == SLSLAM_POSE_OK ? ob[d.words + w] : 0ull;
   }
+  e->last_cov = with_cov; e->off_cov = off_cov;
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_pose_estimator_set_covariance(slslam_pose_estimator* e, int enable) {
+  if (!e) return SLSLAM_ERR_INVALID_ARGUMENT;
+  e->want_cov = enable != 0;
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_pose_estimator_get_covariance(const slslam_pose_estimator* e, int frame, int* status, double constraint[6], double cov[36],
+                                                    double* sigma2, int* dof) {
+  if (!e || frame < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!e->last_cov) return SLSLAM_ERR_STATE;                                    // (no run yet, or the last one had covariance disabled or failed)
+  if (frame >= (int)e->slot_of_frame.size()) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (e->slot_of_frame[(size_t)frame] < 0) return SLSLAM_ERR_STATE;
+  const FrameCov& c = e->h_out.at<FrameCov>(e->off_cov)[frame];
+  if (status) *status = c.status;
+  if (constraint) std::memcpy(constraint, c.constraint, sizeof(c.constraint));
+  if (cov) std::memcpy(cov, c.cov, sizeof(c.cov));
+  if (sigma2) *sigma2 = c.sigma2;
+  if (dof) *dof = c.dof;
   return SLSLAM_OK;
 }
 

@@ -2126,6 +2126,13 @@ int slslam::lba_device_results(const slslam_lba_batch* b, const LMState** state,
   return SLSLAM_OK;
 }
 
+int slslam::lba_device_covariance(const slslam_lba_batch* b, const int** hdr, int* hdr_ints, const double** cov_cam, long long* cam_stride) {
+  if (!b || !hdr || !hdr_ints || !cov_cam || !cam_stride) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized || b->part[0] || b->cov_state != slslam_lba_batch::COV_ENQUEUED || !b->d_cov_hdr.p) return SLSLAM_ERR_STATE;
+  *hdr = b->d_cov_hdr.p; *hdr_ints = kCovHdr; *cov_cam = b->d_cov_cam.p; *cam_stride = b->cov_cam_stride;
+  return SLSLAM_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // A batch for a stream of windows: every window replaced, nothing allocated, nothing captured again (include/slslam_hip.h).
 extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_window* windows, int n, void* stream) {

@@ -21,6 +21,11 @@ int lba_refill_resident(slslam_lba_batch* b, const slslam_lba_window* windows, c
 // The batch's LM states and window descriptors on the device ([window count] each; a window the device build could not take has C == 0).
 int lba_device_results(const slslam_lba_batch* b, const LMState** state, const WinDesc** wins);
 
+// Where the slslam_lba_batch_covariance call enqueued last left its results on the device: hdr [window count][hdr_ints] (status | free
+// cameras | ...), cov_cam [window count][cam_stride] with the window's row-major (6F)^2 block at the front of its slot.
+// SLSLAM_ERR_STATE: no such call is enqueued (none was made, or a download or a refill came after it).
+int lba_device_covariance(const slslam_lba_batch* b, const int** hdr, int* hdr_ints, const double** cov_cam, long long* cam_stride);
+
 }  // namespace slslam
 
 #endif  // SLSLAM_LBA_RESIDENT_H_

@@ -724,5 +724,7 @@ extern "C" int slslam_po_structure(const slslam_po_graph* g, int* slot_out, int 
 #include "po_covariance.h"
 // edge statistics under those covariances: slslam_po_edge_statistics, slslam_po_gate and the gate's plan
 #include "po_gate.h"
+// a constraint's covariance in the edge error's coordinates (the gate's R): slslam_po_constraint_covariance
+#include "po_constraint_cov.h"
 // many graphs per call: slslam_po_batch_* (the same kernels' bodies, the same symbolic analysis)
 #include "po_batch.h"
