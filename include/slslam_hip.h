@@ -321,6 +321,59 @@ int  slslam_lba_batch_covariance_stats(const slslam_lba_batch* b, long long* cal
 int  slslam_lba_covariance(const slslam_lba_window* window, const slslam_solver_options* opt, int* status, int* num_free_cameras,
                            int* free_camera, double* cov_cameras, double* cov_lines);
 
+/* ---- which observations are outliers, which line is degenerate (csrc/lba_report.h).
+ * The LBA counterpart of slslam_po_edge_report; the Ceres counterpart is ceres::Problem::Evaluate with per-block residuals.  For a
+ * window at its CURRENT device parameters (the point slslam_lba_batch_linearise and slslam_lba_batch_covariance evaluate), with
+ * a = huber_delta (a <= 0: no loss):
+ *   per observation i, in the caller's order, for EVERY observation of the window - those Ceres' preprocessing drops because both
+ *   their camera and their line are constant included:
+ *     sq_norm[i] = s_i = |r_i|^2 of the four raw residuals, before the corrector;
+ *     weight[i]  = rho'(s_i): 1 if s_i <= a^2 or the loss is off, else a / sqrt(s_i) (the semantics of slslam_po_edge_report);
+ *   per line, at the caller's line index: status (SLSLAM_LBA_LINE_*: CONSTANT = some observation flags it), num_observations,
+ *     num_downweighted (observations with weight < 1), sq_norm_sum = sum s_i, cost = sum rho(s_i) / 2, and - FREE lines only, 0 otherwise -
+ *     min_pivot: H_ll = sum J_l^T J_l over the line's observations (J_l after the corrector: the covariance's H_ll) is scaled to unit
+ *     diagonal and Cholesky-factored; min_pivot is the smallest value under the square roots, up to and including the first non-positive
+ *     one (a non-positive diagonal entry gives that entry).  This is the number slslam_lba_batch_covariance tests against 1e-10:
+ *     min_pivot <= 1e-10 names the line that makes its window SLSLAM_COV_SINGULAR;
+ *   per camera, at the caller's camera index: status (SLSLAM_LBA_CAMERA_*), num_observations, num_downweighted, sq_norm_sum, cost.
+ * The sum of the lines' (or the cameras') cost is the window's cost, the fixed part included. */
+enum { SLSLAM_LBA_LINE_FREE = 0, SLSLAM_LBA_LINE_CONSTANT = 1, SLSLAM_LBA_LINE_NO_OBSERVATIONS = 2 };
+enum { SLSLAM_LBA_CAMERA_FREE = 0, SLSLAM_LBA_CAMERA_CONSTANT = 1, SLSLAM_LBA_CAMERA_NO_OBSERVATIONS = 2 };
+typedef struct slslam_lba_line_report {
+  int    status;                  /* SLSLAM_LBA_LINE_* */
+  int    num_observations;
+  int    num_downweighted;
+  int    reserved;
+  double sq_norm_sum;
+  double cost;
+  double min_pivot;
+} slslam_lba_line_report;
+typedef struct slslam_lba_camera_report {
+  int    status;                  /* SLSLAM_LBA_CAMERA_* */
+  int    num_observations;
+  int    num_downweighted;
+  int    reserved;
+  double sq_norm_sum;
+  double cost;
+} slslam_lba_camera_report;
+/* The report on every window of the batch: enqueues at most two launches on `stream` and returns.  No host round trip; changes nothing
+ * the solve or the covariance reads or writes.  The result buffers are allocated by the first call and kept: a batch that never asks
+ * pays nothing.  Every path reports - SLSLAM_PATH_GLOBAL_MEMORY and SLSLAM_PATH_MIXED too, which the covariance refuses -, refilled
+ * batches and, through slslam_lba_stream_batch, a stream's.  A report and a covariance may both be enqueued before one download. */
+int  slslam_lba_batch_report(slslam_lba_batch* b, void* stream);
+/* After slslam_lba_batch_download / _wait (which bring the report enqueued since the last download back with the other results):
+ * sq_norm[M], weight[M], lines[L], cameras[C] of window `index`.  Any output pointer may be NULL.
+ * SLSLAM_ERR_INVALID_ARGUMENT: the last slslam_lba_batch_report call has not been downloaded - none was made, a newer one is still
+ * on the device, or a refill has replaced the windows since; a window a device-built refill flagged returns that window's error. */
+int  slslam_lba_batch_get_report(const slslam_lba_batch* b, int index, double* sq_norm, double* weight,
+                                 slslam_lba_line_report* lines, slslam_lba_camera_report* cameras);
+/* Since create: slslam_lba_batch_report calls, and the device / host buffers they allocated.  Any pointer may be NULL. */
+int  slslam_lba_batch_report_stats(const slslam_lba_batch* b, long long* calls, long long* allocations);
+/* The report for ONE window, no solve: at window->parameters (validates as slslam_lba_solve does, then needs a device).
+ * opt: huber_delta and baseline are what matters (NULL = slslam_default_options). */
+int  slslam_lba_report(const slslam_lba_window* window, const slslam_solver_options* opt, double* sq_norm, double* weight,
+                       slslam_lba_line_report* lines, slslam_lba_camera_report* cameras);
+
 /* Test hook: evaluate residuals / Jacobians (after the Huber corrector, before Jacobi scaling)
  * of window `index` at its CURRENT device parameters, returned in the caller's observation order:
  * residuals[4M], j_cam[24M] (row-major 4x6), j_line[16M] (row-major 4x4), cost[1]. */

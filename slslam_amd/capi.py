@@ -125,6 +125,7 @@ EXPORTS = [
     "slslam_lba_batch_get_trace", "slslam_lba_batch_export_device", "slslam_lba_batch_counts", "slslam_lba_batch_window_chunks", "slslam_lba_batch_path", "slslam_lba_batch_elimination",
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
+    "slslam_lba_batch_report", "slslam_lba_batch_get_report", "slslam_lba_batch_report_stats", "slslam_lba_report",
     "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -191,6 +192,10 @@ def lib():
     L.slslam_lba_batch_get_covariance.argtypes = [vp, C.c_int, ip, ip, ip, dp, dp]
     L.slslam_lba_batch_covariance_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
     L.slslam_lba_covariance.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), ip, ip, ip, dp, dp]
+    L.slslam_lba_batch_report.argtypes = [vp, vp]
+    L.slslam_lba_batch_get_report.argtypes = [vp, C.c_int, dp, dp, vp, vp]
+    L.slslam_lba_batch_report_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+    L.slslam_lba_report.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), dp, dp, vp, vp]
     L.slslam_po_solve.argtypes = [C.POINTER(POGraph), C.POINTER(SolverOptions), C.POINTER(Summary),
                                   C.POINTER(Iteration), C.c_int, ip]
     L.slslam_po_batch_create.argtypes = [C.c_int, C.POINTER(vp)]
@@ -377,6 +382,31 @@ def lba_covariance(w, params=None, with_lines=True, **opt):
                        int(w["num_cameras"]), int(w["num_lines"]), with_lines)
 
 
+# slslam_lba_line_report / slslam_lba_camera_report as numpy structured dtypes (include/slslam_hip.h)
+LINE_REPORT_DTYPE = np.dtype([("status", np.int32), ("num_observations", np.int32), ("num_downweighted", np.int32), ("reserved", np.int32),
+                              ("sq_norm_sum", np.float64), ("cost", np.float64), ("min_pivot", np.float64)])
+CAMERA_REPORT_DTYPE = np.dtype([("status", np.int32), ("num_observations", np.int32), ("num_downweighted", np.int32), ("reserved", np.int32),
+                                ("sq_norm_sum", np.float64), ("cost", np.float64)])
+LBA_LINE_FREE, LBA_LINE_CONSTANT, LBA_LINE_NO_OBSERVATIONS = 0, 1, 2
+
+
+def _report_result(fn, where, num_cameras, num_lines, num_observations):
+    """Calls fn(sq_norm, weight, lines, cameras): dict(sq_norm[M], weight[M], lines[L], cameras[C]), the last two structured arrays."""
+    sq, wt = np.zeros(num_observations), np.zeros(num_observations)
+    ln, cm = np.zeros(num_lines, dtype=LINE_REPORT_DTYPE), np.zeros(num_cameras, dtype=CAMERA_REPORT_DTYPE)
+    _check(fn(_dp(sq), _dp(wt), ln.ctypes.data_as(C.c_void_p), cm.ctypes.data_as(C.c_void_p)), where)
+    return {"sq_norm": sq, "weight": wt, "lines": ln, "cameras": cm}
+
+
+def lba_report(w, params=None, **opt):
+    """Per-observation |r|^2 and Huber weights, per-line and per-camera sums and the lines' smallest scaled pivot of one window at its
+    parameters, no solve (slslam_lba_report; Ceres: ceres::Problem::Evaluate).  Returns the dict LBABatch.get_report returns."""
+    arr = _WindowArrays(w, params)
+    o = default_options(**opt)
+    return _report_result(lambda *a: lib().slslam_lba_report(C.byref(arr.c), C.byref(o), *a), "slslam_lba_report",
+                          int(w["num_cameras"]), int(w["num_lines"]), len(arr.cam))
+
+
 def lba_solve(w, params=None, trace_cap=64, **opt):
     """One window through slslam_lba_solve (LBAProblem::build + set_options + ceres::Solve).
     Returns (solved parameters, summary dict, trace list)."""
@@ -451,6 +481,7 @@ class LBABatch:
         self._h = C.c_void_p()
         _check(lib().slslam_lba_batch_create(int(device), C.byref(self._h)), "slslam_lba_batch_create")
         self.sizes = []          # (num_cameras, num_lines) per window
+        self.num_obs = []        # observations per window
         self.finalized = False
 
     def close(self):
@@ -469,6 +500,7 @@ class LBABatch:
         idx = C.c_int(-1)
         _check(lib().slslam_lba_batch_add(self._h, C.byref(arr.c), C.byref(idx)), "slslam_lba_batch_add")
         self.sizes.append((int(w["num_cameras"]), int(w["num_lines"])))
+        self.num_obs.append(len(arr.cam))
         return idx.value
 
     def finalize(self, **opt):
@@ -497,6 +529,7 @@ class LBABatch:
         ws = windows if isinstance(windows, WindowSet) else WindowSet(windows)
         _check(lib().slslam_lba_batch_refill(self._h, ws.c, len(ws), C.c_void_p(stream or 0)), "slslam_lba_batch_refill")
         self.sizes = list(ws.sizes)
+        self.num_obs = list(ws.num_obs)
 
     def export_device(self, device_ptr, stream=None):
         _check(lib().slslam_lba_batch_export_device(self._h, C.c_void_p(device_ptr), C.c_void_p(stream or 0)),
@@ -575,6 +608,21 @@ class LBABatch:
         _check(lib().slslam_lba_batch_covariance_stats(self._h, *[C.byref(x) for x in v]), "slslam_lba_batch_covariance_stats")
         return dict(zip(["calls", "allocations"], [x.value for x in v]))
 
+    def report(self, stream=None):
+        """Enqueues the report on every window at its current device parameters (slslam_lba_batch_report); download() brings it back."""
+        _check(lib().slslam_lba_batch_report(self._h, C.c_void_p(stream or 0)), "slslam_lba_batch_report")
+
+    def get_report(self, i):
+        """dict(sq_norm[M], weight[M], lines[L] (LINE_REPORT_DTYPE), cameras[C] (CAMERA_REPORT_DTYPE)) of window i, after download()."""
+        c, l = self.sizes[i]
+        return _report_result(lambda *a: lib().slslam_lba_batch_get_report(self._h, int(i), *a), "slslam_lba_batch_get_report",
+                              c, l, self.num_obs[i])
+
+    def report_stats(self):
+        v = [C.c_longlong(0) for _ in range(2)]
+        _check(lib().slslam_lba_batch_report_stats(self._h, *[C.byref(x) for x in v]), "slslam_lba_batch_report_stats")
+        return dict(zip(["calls", "allocations"], [x.value for x in v]))
+
     def linearise(self, i, num_observations):
         m = int(num_observations)
         r, jc, jl, c = np.zeros((m, 4)), np.zeros((m, 4, 6)), np.zeros((m, 4, 4)), np.zeros(1)
@@ -616,6 +664,7 @@ class WindowSet:
             self.packed = (C.POINTER(C.c_uint) * max(len(self.arrays), 1))(*[p_.ctypes.data_as(C.POINTER(C.c_uint)) for p_ in self.packed_arrays])
         self.c = (LBAWindow * max(len(self.arrays), 1))(*[a.c for a in self.arrays])
         self.sizes = [(int(w["num_cameras"]), int(w["num_lines"])) for w in windows]
+        self.num_obs = [int(a.c.num_observations) for a in self.arrays]
 
     def __len__(self):
         return len(self.arrays)
@@ -644,6 +693,7 @@ class WindowSet:
             out.arrays.append(a)
         out.c = (LBAWindow * max(len(out.arrays), 1))(*[a.c for a in out.arrays])
         out.sizes = [self.sizes[j] for j in order]
+        out.num_obs = [self.num_obs[j] for j in order]
         out._base = self                      # (the shared arrays live in the base set's block)
         return out
 
@@ -658,9 +708,10 @@ class WindowSet:
 class _BatchView(LBABatch):
     """A batch owned by somebody else (a stream's slot): the getters of LBABatch, no destroy."""
 
-    def __init__(self, handle, sizes):
+    def __init__(self, handle, sizes, num_obs=()):
         self._h = handle
         self.sizes = list(sizes)
+        self.num_obs = list(num_obs)
         self.finalized = True
 
     def close(self):
@@ -735,7 +786,7 @@ class LBAStream:
         """The batch that served `ticket` (its traces, chunk cuts, sweep): valid until the slot is submitted to again."""
         h = C.c_void_p()
         _check(lib().slslam_lba_stream_batch(self._h, int(ticket), C.byref(h)), "slslam_lba_stream_batch")
-        return _BatchView(h, ws.sizes)
+        return _BatchView(h, ws.sizes, ws.num_obs)
 
     def build_stats(self):
         q = [C.c_longlong(0) for _ in range(3)]

@@ -22,6 +22,7 @@
 #include "device_cache.h"
 #include "lba_motion_only.h"
 #include "lba_covariance.h"
+#include "lba_report.h"
 #include "lba_pack.h"
 #include "lba_device_build.h"
 #include "lba_resident.h"
@@ -355,6 +356,13 @@ struct slslam_lba_batch {
   CovState cov_state = COV_NONE;
   bool cov_lines = false;                                // ... and whether that call asked for the lines' blocks
   long long cov_calls = 0, cov_allocations = 0;
+  // the report on observations, lines and cameras (lba_report.h): the covariance's protocol - buffers made by the first
+  // slslam_lba_batch_report call and kept, the result of the LAST call enqueued / being copied / on the host
+  DevBuf<double> d_rep_obs, d_rep_cam_part; DevBuf<RepLine> d_rep_line; DevBuf<RepCam> d_rep_cam;
+  HostArr<double> h_rep_obs; HostArr<RepLine> h_rep_line; HostArr<RepCam> h_rep_cam;
+  size_t rep_cap_obs = 0;                                // d_rep_obs = sq_norm [rep_cap_obs] | weight [rep_cap_obs]
+  CovState rep_state = COV_NONE;
+  long long rep_calls = 0, rep_allocations = 0;
   // profiling
   bool profiling = false;
   double fam_ms[FAM_N] = { 0 };
@@ -1540,6 +1548,13 @@ int download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
       HIP_TRY(hipMemcpyAsync(b->h_cov_line.data(), b->d_cov_line.p, b->h_cov_line.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     b->cov_state = slslam_lba_batch::COV_COPYING;
   }
+  if (b->rep_state == slslam_lba_batch::COV_ENQUEUED) {
+    // ... and so does the report
+    HIP_TRY(hipMemcpyAsync(b->h_rep_obs.data(), b->d_rep_obs.p, b->h_rep_obs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_rep_line.data(), b->d_rep_line.p, b->h_rep_line.size() * sizeof(RepLine), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_rep_cam.data(), b->d_rep_cam.p, b->h_rep_cam.size() * sizeof(RepCam), hipMemcpyDeviceToHost, s));
+    b->rep_state = slslam_lba_batch::COV_COPYING;
+  }
   if (!b->ev_results) HIP_TRY(hipEventCreateWithFlags(&b->ev_results, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_results, s));
   b->results_pending = true;
@@ -1569,6 +1584,7 @@ int finish_download(slslam_lba_batch* b) {
   if (b->profiling) b->harvest_events();
   adopt_device_build(b);
   if (b->cov_state == slslam_lba_batch::COV_COPYING) b->cov_state = slslam_lba_batch::COV_READY;
+  if (b->rep_state == slslam_lba_batch::COV_COPYING) b->rep_state = slslam_lba_batch::COV_READY;
   b->downloaded = true;
   return SLSLAM_OK;
 }
@@ -1938,7 +1954,7 @@ void refill_commit(slslam_lba_batch* b, const slslam_lba_window* windows, int B,
   b->total_params = z.nparams; b->nobs = z.nobs;
   b->used_ncam = z.ncam; b->used_nline = z.nline; b->used_nobs = z.nobs; b->used_tiles = (long long)b->d_tiles.n; b->used_items = (long long)(b->d_items.n / 2);
   b->device_built = true; b->inplace_export = z.params_pinned; b->results_inplace = false;
-  b->cov_state = slslam_lba_batch::COV_NONE;
+  b->cov_state = slslam_lba_batch::COV_NONE; b->rep_state = slslam_lba_batch::COV_NONE;
   b->src_windows.assign(windows, windows + B);
   b->build_status.assign((size_t)B, SLSLAM_OK);
   b->downloaded = false;
@@ -2206,7 +2222,7 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   b->wins.swap(wins);
   b->downloaded = false;
   b->device_built = false; b->inplace_export = false; b->results_inplace = false; b->src_windows.clear(); b->build_status.clear();
-  b->cov_state = slslam_lba_batch::COV_NONE;
+  b->cov_state = slslam_lba_batch::COV_NONE; b->rep_state = slslam_lba_batch::COV_NONE;
   auto fill_one = [&](int wi) { fill_window(b, plan, b->wins, wi, img, /*copy_observations=*/false); };
   (void)run_all(pool, B, fill_one);                      // (fill_window copies into the image: it allocates nothing)
   fill_tail(b, plan, img);
@@ -2491,6 +2507,113 @@ extern "C" int slslam_lba_covariance(const slslam_lba_window* w, const slslam_so
       (rc = slslam_lba_batch_covariance(b, nullptr, cov_lines ? 1 : 0)) == SLSLAM_OK &&
       (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
     rc = slslam_lba_batch_get_covariance(b, 0, status, num_free_cameras, free_camera, cov_cameras, cov_lines);
+  slslam_lba_batch_destroy(b);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// Which observations are down-weighted, which line is degenerate: the report on every window at its current device parameters (lba_report.h)
+static_assert(sizeof(RepLine) == sizeof(slslam_lba_line_report) && sizeof(RepCam) == sizeof(slslam_lba_camera_report), "the device writes the caller's structs");
+static_assert((int)kRepLineFree == SLSLAM_LBA_LINE_FREE && (int)kRepLineConstant == SLSLAM_LBA_LINE_CONSTANT && (int)kRepLineNoObs == SLSLAM_LBA_LINE_NO_OBSERVATIONS, "");
+
+extern "C" int slslam_lba_batch_report(slslam_lba_batch* b, void* stream) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized) return SLSLAM_ERR_STATE;
+  if (b->part[0]) {                                     // a mixed batch: both parts, one after the other on the caller's stream
+    ++b->rep_calls;
+    const int rc0 = slslam_lba_batch_report(b->part[0], stream);
+    return rc0 != SLSLAM_OK ? rc0 : slslam_lba_batch_report(b->part[1], stream);
+  }
+  const size_t B = b->wins.size();
+  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
+  const size_t lds = b->big_mode ? lds_bytes_report_lines(maxC, maxn) : lds_bytes_report_tiles(maxC, maxn);
+  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  ++b->rep_calls;
+  int rc;
+  if (!b->d_rep_line.p) {
+    const size_t cap_obs = std::max<size_t>(1, b->d_ob_orig.n), cap_line = std::max<size_t>(1, b->d_line_flags.n), cap_cam = std::max<size_t>(1, b->d_cam_cf.n);
+    const size_t cap_part = b->big_mode ? 1 : (size_t)std::max(1, b->nchunk) * kRepCamAcc * (size_t)maxC;
+    if ((rc = b->d_rep_obs.alloc(2 * cap_obs)) || (rc = b->d_rep_line.alloc(cap_line)) || (rc = b->d_rep_cam.alloc(cap_cam)) ||
+        (rc = b->d_rep_cam_part.alloc(cap_part)) || (rc = b->h_rep_obs.alloc(2 * cap_obs, b->refillable)) ||
+        (rc = b->h_rep_line.alloc(cap_line, b->refillable)) || (rc = b->h_rep_cam.alloc(cap_cam, b->refillable))) {
+      b->d_rep_line.release();
+      return rc;
+    }
+    b->rep_cap_obs = cap_obs;
+    b->rep_allocations += 7;
+    // (a window the launches skip - none today - reads as zeros: status FREE without observations never comes from the kernels)
+    HIP_TRY(hipMemsetAsync(b->d_rep_obs.p, 0, 2 * cap_obs * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(b->d_rep_line.p, 0, cap_line * sizeof(RepLine), s));
+    HIP_TRY(hipMemsetAsync(b->d_rep_cam.p, 0, cap_cam * sizeof(RepCam), s));
+    HIP_TRY(hipMemsetAsync(b->d_rep_cam_part.p, 0, cap_part * sizeof(double), s));
+    if (lds > 48 * 1024) HIP_TRY(allow_lds({ (const void*)k_lba_report_tiles, (const void*)k_lba_report_lines }, 160 * 1024));
+  }
+  ReportPtrs rp;
+  rp.ob_orig = b->d_ob_orig.p; rp.line_orig = b->d_line_orig.p;
+  rp.sq_norm = b->d_rep_obs.p; rp.weight = b->d_rep_obs.p + b->rep_cap_obs;
+  rp.lines = b->d_rep_line.p; rp.cams = b->d_rep_cam.p;
+  rp.cam_part = b->d_rep_cam_part.p; rp.cam_stride = (long long)kRepCamAcc * maxC;
+  if (B > 0) {
+    if (b->big_mode) {
+      hipLaunchKernelGGL(k_lba_report_lines, dim3((unsigned)B), dim3(kRepLinesThreads), lds, s, b->ptrs, b->pol, rp, maxC, maxn);
+    } else {
+      if (b->nchunk > 0) hipLaunchKernelGGL(k_lba_report_tiles, dim3((unsigned)b->nchunk), dim3(64), lds, s, b->ptrs, b->pol, rp, maxC, maxn);
+      hipLaunchKernelGGL(k_lba_report_cameras, dim3((unsigned)B), dim3(64), 0, s, b->ptrs, rp);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  b->rep_state = slslam_lba_batch::COV_ENQUEUED;
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_lba_batch_report_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  long long a = b->rep_allocations;
+  for (int h = 0; h < 2; ++h) if (b->part[h]) a += b->part[h]->rep_allocations;
+  if (calls) *calls = b->rep_calls;
+  if (allocations) *allocations = a;
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_lba_batch_get_report(const slslam_lba_batch* b, int index, double* sq_norm, double* weight,
+                                           slslam_lba_line_report* lines, slslam_lba_camera_report* cameras) {
+  if (!b || index < 0 || index >= b->num_windows()) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (b->part[0]) return slslam_lba_batch_get_report(b->part[b->route[(size_t)index].first], b->route[(size_t)index].second, sq_norm, weight, lines, cameras);
+  if (b->rep_state != slslam_lba_batch::COV_READY) return SLSLAM_ERR_INVALID_ARGUMENT;      // the last report call (if any) has not been downloaded
+  if (b->device_built && b->build_status[(size_t)index] != SLSLAM_OK) return b->build_status[(size_t)index];
+  const WinDesc& wd = b->h_wins[(size_t)index];
+  if (sq_norm && wd.M > 0) std::memcpy(sq_norm, b->h_rep_obs.data() + (size_t)wd.obs_off, (size_t)wd.M * sizeof(double));
+  if (weight && wd.M > 0) std::memcpy(weight, b->h_rep_obs.data() + b->rep_cap_obs + (size_t)wd.obs_off, (size_t)wd.M * sizeof(double));
+  if (lines && wd.L > 0) std::memcpy(lines, b->h_rep_line.data() + (size_t)wd.line_off, (size_t)wd.L * sizeof(RepLine));
+  if (cameras && wd.C > 0) std::memcpy(cameras, b->h_rep_cam.data() + (size_t)wd.cam_off, (size_t)wd.C * sizeof(RepCam));
+  return SLSLAM_OK;
+}
+
+// One window, no solve: the report at window->parameters
+extern "C" int slslam_lba_report(const slslam_lba_window* w, const slslam_solver_options* opt, double* sq_norm, double* weight,
+                                 slslam_lba_line_report* lines, slslam_lba_camera_report* cameras) {
+  if (!w) return SLSLAM_ERR_INVALID_ARGUMENT;
+  slslam_solver_options o;
+  if (opt) o = *opt; else slslam_default_options(&o);
+  if (o.max_num_iterations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
+  PackedWindow pw;   // malformed input is reported as such on any machine, before the device is looked for
+  {
+    const int prc = pack_window(w, &pw);
+    if (prc != SLSLAM_OK) return prc;
+  }
+  slslam_lba_batch* b = nullptr;
+  int rc = slslam_lba_batch_create(-1, &b);
+  if (rc) return rc;
+  o.use_graph = 0;
+  o.refill_headroom_percent = 0;
+  b->wins.push_back(std::move(pw));
+  b->arena.cached = true;
+  if ((rc = slslam_lba_batch_finalize(b, &o)) == SLSLAM_OK &&
+      (rc = slslam_lba_batch_report(b, nullptr)) == SLSLAM_OK &&
+      (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
+    rc = slslam_lba_batch_get_report(b, 0, sq_norm, weight, lines, cameras);
   slslam_lba_batch_destroy(b);
   return rc;
 }

@@ -342,7 +342,7 @@ template <bool SCALED>
 __device__ __forceinline__ void lane_linearise(const BatchPtrs& p, const Policy& pol, const double* camtab,
                                                const double* camscale, const signed char* camcf, int ls, int j, int k, int o0, bool line_ok,
                                                int lflags, int cur, int safe_obs, LaneLin& L, double (&ob)[8],
-                                               const ObsPref* pf = nullptr, bool unit_line = false) {
+                                               const ObsPref* pf = nullptr, bool unit_line = false, double* sq_norm = nullptr) {
   L.valid = line_ok && j < k;
   const int lsafe = line_ok ? ls : 0;
   double trig[7];
@@ -379,6 +379,7 @@ __device__ __forceinline__ void lane_linearise(const BatchPtrs& p, const Policy&
   obs_linearise<double>(R, JL, t, cp, dv, dcp, ddv, ob, pol.baseline, r, L.Jc, L.Jl);
   const double s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3];
   const double sr = huber_scale<double>(s, pol.huber_delta, &L.cost);
+  if (sq_norm) *sq_norm = s;            // (the report: |r|^2 before the corrector)
 #pragma unroll
   for (int q = 0; q < 4; ++q) L.rs[q] = r[q] * sr;
   if (SCALED) {
