@@ -374,6 +374,56 @@ int  slslam_lba_batch_report_stats(const slslam_lba_batch* b, long long* calls, 
 int  slslam_lba_report(const slslam_lba_window* window, const slslam_solver_options* opt, double* sq_norm, double* weight,
                        slslam_lba_line_report* lines, slslam_lba_camera_report* cameras);
 
+/* ---- the 3-D segment of every line landmark (csrc/lba_segments.h).
+ * The solve returns infinite lines; a map, a viewer or a data association needs their extent.  This is the reference's
+ * SLAM::extend_end_points (src/slam.cpp:979-1084) per observation, for a window at its CURRENT device parameters (the point
+ * slslam_lba_batch_report and _covariance evaluate), for EVERY line of the window, constant ones included.  A line u = (a, b, g, t) is
+ * cp + s dv, cp its point closest to the origin and dv its unit direction as in the residual; a segment is an interval of s.
+ *   per observation i of line l from camera c (R, t_c world to camera), LEFT image only (observations[8 i + 0..3] = x0 y0 x1 y1), in the
+ *   caller's order:
+ *     1. pc = R cp + t_c, dc = R dv; p1 = (x0, y0, 1), p2 = (x1, y1, 1); ln = (p1 x p2)[0:2] / its norm sqrt(lx^2 + ly^2).  A zero norm or a
+ *        non-finite input: DEGENERATE.
+ *     2. per endpoint p: the plane through the camera centre, p and p + (ln, 0) - normal m = p x (ln, 0) - cuts the line at
+ *        s = -(m . pc) / (m . dc) (the reference's Lc * pi).  |m . dc| <= 1e-6 |m| for either endpoint: DEGENERATE.
+ *     3. (pc + s dc).z < 0 for either endpoint: BEHIND.
+ *     4. only with max_range > 0 (the reference: extension_length = 5.0): q = pc . dc, p0 = pc - q dc the line's point closest to the
+ *        camera centre.  |p0| > max_range: OUT_OF_RANGE.  Else e = sqrt(max_range^2 - |p0|^2) and an endpoint with |s + q| > e moves to
+ *        s = sign(s + q) e - q; the observation is then USED_CLAMPED.
+ *     5. lo = min(s_1, s_2), hi = max(s_1, s_2); lo == hi: COLLAPSED, else USED / USED_CLAMPED.
+ *     obs_status[i] = SLSLAM_SEGMENT_OBS_*; obs_range[2 i] = lo, hi - zeros unless USED / USED_CLAMPED;
+ *   per line, at the caller's line index: status (OK; NO_OBSERVATIONS; NONE = observed, but no observation was used), num_observations,
+ *     num_used, num_clamped, t_min = min lo and t_max = max hi over the used observations, p_min = cp + t_min dv and p_max = cp + t_max dv in
+ *     the window's world frame.  All doubles are 0 unless the status is OK.
+ * The union over a line's observations is what the reference's keyframe-by-keyframe update (slam.cpp:1065-1074) arrives at for a line
+ * that does not move.  The reference's reset of tt when the direction pvn turns is map bookkeeping and stays with the caller. */
+enum { SLSLAM_SEGMENT_OK = 0, SLSLAM_SEGMENT_NO_OBSERVATIONS = 1, SLSLAM_SEGMENT_NONE = 2 };
+enum { SLSLAM_SEGMENT_OBS_USED = 0, SLSLAM_SEGMENT_OBS_USED_CLAMPED = 1, SLSLAM_SEGMENT_OBS_DEGENERATE = 2, SLSLAM_SEGMENT_OBS_BEHIND = 3,
+       SLSLAM_SEGMENT_OBS_OUT_OF_RANGE = 4, SLSLAM_SEGMENT_OBS_COLLAPSED = 5 };
+typedef struct slslam_lba_line_segment {
+  int    status;                  /* SLSLAM_SEGMENT_* */
+  int    num_observations;
+  int    num_used;                /* USED + USED_CLAMPED */
+  int    num_clamped;             /* USED_CLAMPED */
+  double t_min, t_max;
+  double p_min[3], p_max[3];
+} slslam_lba_line_segment;
+/* The segments of every window of the batch: enqueues one launch on `stream` and returns.  No host round trip; changes nothing the
+ * solve, the covariance or the report reads or writes.  The result buffers are allocated by the first call and kept.  Every path
+ * answers (SLSLAM_PATH_GLOBAL_MEMORY and SLSLAM_PATH_MIXED too), refilled batches and, through slslam_lba_stream_batch, a stream's.
+ * Segments, a report and a covariance may all be enqueued before one download.  max_range <= 0: no clamp, nothing out of range; a
+ * non-finite max_range: SLSLAM_ERR_INVALID_ARGUMENT. */
+int  slslam_lba_batch_segments(slslam_lba_batch* b, void* stream, double max_range);
+/* After slslam_lba_batch_download / _wait: obs_status[M], obs_range[2 M], lines[L] of window `index`.  Any output pointer may be NULL.
+ * SLSLAM_ERR_INVALID_ARGUMENT: the last slslam_lba_batch_segments call has not been downloaded - none was made, a newer one is still
+ * on the device, or a refill has replaced the windows since; a window a device-built refill flagged returns that window's error. */
+int  slslam_lba_batch_get_segments(const slslam_lba_batch* b, int index, int* obs_status, double* obs_range, slslam_lba_line_segment* lines);
+/* Since create: slslam_lba_batch_segments calls, and the device / host buffers they allocated.  Any pointer may be NULL. */
+int  slslam_lba_batch_segments_stats(const slslam_lba_batch* b, long long* calls, long long* allocations);
+/* The segments of ONE window, no solve: at window->parameters (validates as slslam_lba_report does, then needs a device).
+ * opt: NULL = slslam_default_options. */
+int  slslam_lba_segments(const slslam_lba_window* window, const slslam_solver_options* opt, double max_range, int* obs_status,
+                         double* obs_range, slslam_lba_line_segment* lines);
+
 /* Test hook: evaluate residuals / Jacobians (after the Huber corrector, before Jacobi scaling)
  * of window `index` at its CURRENT device parameters, returned in the caller's observation order:
  * residuals[4M], j_cam[24M] (row-major 4x6), j_line[16M] (row-major 4x4), cost[1]. */

@@ -126,6 +126,7 @@ EXPORTS = [
     "slslam_lba_batch_iterations", "slslam_lba_batch_set_profiling", "slslam_lba_batch_kernel_times", "slslam_lba_batch_linearise",
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
     "slslam_lba_batch_report", "slslam_lba_batch_get_report", "slslam_lba_batch_report_stats", "slslam_lba_report",
+    "slslam_lba_batch_segments", "slslam_lba_batch_get_segments", "slslam_lba_batch_segments_stats", "slslam_lba_segments",
     "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -196,6 +197,10 @@ def lib():
     L.slslam_lba_batch_get_report.argtypes = [vp, C.c_int, dp, dp, vp, vp]
     L.slslam_lba_batch_report_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
     L.slslam_lba_report.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), dp, dp, vp, vp]
+    L.slslam_lba_batch_segments.argtypes = [vp, vp, C.c_double]
+    L.slslam_lba_batch_get_segments.argtypes = [vp, C.c_int, ip, dp, vp]
+    L.slslam_lba_batch_segments_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+    L.slslam_lba_segments.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), C.c_double, ip, dp, vp]
     L.slslam_po_solve.argtypes = [C.POINTER(POGraph), C.POINTER(SolverOptions), C.POINTER(Summary),
                                   C.POINTER(Iteration), C.c_int, ip]
     L.slslam_po_batch_create.argtypes = [C.c_int, C.POINTER(vp)]
@@ -405,6 +410,33 @@ def lba_report(w, params=None, **opt):
     o = default_options(**opt)
     return _report_result(lambda *a: lib().slslam_lba_report(C.byref(arr.c), C.byref(o), *a), "slslam_lba_report",
                           int(w["num_cameras"]), int(w["num_lines"]), len(arr.cam))
+
+
+# slslam_lba_line_segment as a numpy structured dtype (include/slslam_hip.h)
+LINE_SEGMENT_DTYPE = np.dtype([("status", np.int32), ("num_observations", np.int32), ("num_used", np.int32), ("num_clamped", np.int32),
+                               ("t_min", np.float64), ("t_max", np.float64), ("p_min", np.float64, (3,)), ("p_max", np.float64, (3,))])
+SEGMENT_OK, SEGMENT_NO_OBSERVATIONS, SEGMENT_NONE = 0, 1, 2
+(SEGMENT_OBS_USED, SEGMENT_OBS_USED_CLAMPED, SEGMENT_OBS_DEGENERATE, SEGMENT_OBS_BEHIND, SEGMENT_OBS_OUT_OF_RANGE,
+ SEGMENT_OBS_COLLAPSED) = range(6)
+
+
+def _segments_result(fn, where, num_lines, num_observations):
+    """Calls fn(obs_status, obs_range, lines): dict(obs_status[M], obs_range[M, 2], and the fields of slslam_lba_line_segment as arrays [L])."""
+    st, rg = np.zeros(num_observations, dtype=np.int32), np.zeros((num_observations, 2))
+    ln = np.zeros(num_lines, dtype=LINE_SEGMENT_DTYPE)
+    _check(fn(_ip(st), _dp(rg), ln.ctypes.data_as(C.c_void_p)), where)
+    out = {"obs_status": st, "obs_range": rg}
+    out.update({k: np.ascontiguousarray(ln[k]) for k in LINE_SEGMENT_DTYPE.names})
+    return out
+
+
+def lba_segments(w, max_range=0.0, params=None, **opt):
+    """The 3-D segments of the lines of one window at its parameters, no solve (slslam_lba_segments; the reference's
+    SLAM::extend_end_points per observation).  max_range <= 0: no range clamp.  Returns the dict LBABatch.get_segments returns."""
+    arr = _WindowArrays(w, params)
+    o = default_options(**opt)
+    return _segments_result(lambda *a: lib().slslam_lba_segments(C.byref(arr.c), C.byref(o), float(max_range), *a), "slslam_lba_segments",
+                            int(w["num_lines"]), len(arr.cam))
 
 
 def lba_solve(w, params=None, trace_cap=64, **opt):
@@ -621,6 +653,22 @@ class LBABatch:
     def report_stats(self):
         v = [C.c_longlong(0) for _ in range(2)]
         _check(lib().slslam_lba_batch_report_stats(self._h, *[C.byref(x) for x in v]), "slslam_lba_batch_report_stats")
+        return dict(zip(["calls", "allocations"], [x.value for x in v]))
+
+    def segments(self, max_range=0.0, stream=None):
+        """Enqueues the 3-D segments of the lines of every window at its current device parameters (slslam_lba_batch_segments);
+        download() brings them back, get_segments(i) reads window i.  max_range <= 0: no range clamp."""
+        _check(lib().slslam_lba_batch_segments(self._h, C.c_void_p(stream or 0), float(max_range)), "slslam_lba_batch_segments")
+
+    def get_segments(self, i):
+        """dict(obs_status[M], obs_range[M, 2], status[L], num_observations[L], num_used[L], num_clamped[L], t_min[L], t_max[L],
+        p_min[L, 3], p_max[L, 3]) of window i, after download()."""
+        return _segments_result(lambda *a: lib().slslam_lba_batch_get_segments(self._h, int(i), *a), "slslam_lba_batch_get_segments",
+                                self.sizes[i][1], self.num_obs[i])
+
+    def segments_stats(self):
+        v = [C.c_longlong(0) for _ in range(2)]
+        _check(lib().slslam_lba_batch_segments_stats(self._h, *[C.byref(x) for x in v]), "slslam_lba_batch_segments_stats")
         return dict(zip(["calls", "allocations"], [x.value for x in v]))
 
     def linearise(self, i, num_observations):

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +24,7 @@
 #include "lba_motion_only.h"
 #include "lba_covariance.h"
 #include "lba_report.h"
+#include "lba_segments.h"
 #include "lba_pack.h"
 #include "lba_device_build.h"
 #include "lba_resident.h"
@@ -363,6 +365,11 @@ struct slslam_lba_batch {
   size_t rep_cap_obs = 0;                                // d_rep_obs = sq_norm [rep_cap_obs] | weight [rep_cap_obs]
   CovState rep_state = COV_NONE;
   long long rep_calls = 0, rep_allocations = 0;
+  // the 3-D segments of the lines (lba_segments.h): the same protocol
+  DevBuf<int> d_seg_status; DevBuf<double> d_seg_range; DevBuf<SegLine> d_seg_line;
+  HostArr<int> h_seg_status; HostArr<double> h_seg_range; HostArr<SegLine> h_seg_line;
+  CovState seg_state = COV_NONE;
+  long long seg_calls = 0, seg_allocations = 0;
   // profiling
   bool profiling = false;
   double fam_ms[FAM_N] = { 0 };
@@ -1555,6 +1562,13 @@ int download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
     HIP_TRY(hipMemcpyAsync(b->h_rep_cam.data(), b->d_rep_cam.p, b->h_rep_cam.size() * sizeof(RepCam), hipMemcpyDeviceToHost, s));
     b->rep_state = slslam_lba_batch::COV_COPYING;
   }
+  if (b->seg_state == slslam_lba_batch::COV_ENQUEUED) {
+    // ... and the segments
+    HIP_TRY(hipMemcpyAsync(b->h_seg_status.data(), b->d_seg_status.p, b->h_seg_status.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_seg_range.data(), b->d_seg_range.p, b->h_seg_range.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_seg_line.data(), b->d_seg_line.p, b->h_seg_line.size() * sizeof(SegLine), hipMemcpyDeviceToHost, s));
+    b->seg_state = slslam_lba_batch::COV_COPYING;
+  }
   if (!b->ev_results) HIP_TRY(hipEventCreateWithFlags(&b->ev_results, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_results, s));
   b->results_pending = true;
@@ -1585,6 +1599,7 @@ int finish_download(slslam_lba_batch* b) {
   adopt_device_build(b);
   if (b->cov_state == slslam_lba_batch::COV_COPYING) b->cov_state = slslam_lba_batch::COV_READY;
   if (b->rep_state == slslam_lba_batch::COV_COPYING) b->rep_state = slslam_lba_batch::COV_READY;
+  if (b->seg_state == slslam_lba_batch::COV_COPYING) b->seg_state = slslam_lba_batch::COV_READY;
   b->downloaded = true;
   return SLSLAM_OK;
 }
@@ -1954,7 +1969,7 @@ void refill_commit(slslam_lba_batch* b, const slslam_lba_window* windows, int B,
   b->total_params = z.nparams; b->nobs = z.nobs;
   b->used_ncam = z.ncam; b->used_nline = z.nline; b->used_nobs = z.nobs; b->used_tiles = (long long)b->d_tiles.n; b->used_items = (long long)(b->d_items.n / 2);
   b->device_built = true; b->inplace_export = z.params_pinned; b->results_inplace = false;
-  b->cov_state = slslam_lba_batch::COV_NONE; b->rep_state = slslam_lba_batch::COV_NONE;
+  b->cov_state = slslam_lba_batch::COV_NONE; b->rep_state = slslam_lba_batch::COV_NONE; b->seg_state = slslam_lba_batch::COV_NONE;
   b->src_windows.assign(windows, windows + B);
   b->build_status.assign((size_t)B, SLSLAM_OK);
   b->downloaded = false;
@@ -2222,7 +2237,7 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   b->wins.swap(wins);
   b->downloaded = false;
   b->device_built = false; b->inplace_export = false; b->results_inplace = false; b->src_windows.clear(); b->build_status.clear();
-  b->cov_state = slslam_lba_batch::COV_NONE; b->rep_state = slslam_lba_batch::COV_NONE;
+  b->cov_state = slslam_lba_batch::COV_NONE; b->rep_state = slslam_lba_batch::COV_NONE; b->seg_state = slslam_lba_batch::COV_NONE;
   auto fill_one = [&](int wi) { fill_window(b, plan, b->wins, wi, img, /*copy_observations=*/false); };
   (void)run_all(pool, B, fill_one);                      // (fill_window copies into the image: it allocates nothing)
   fill_tail(b, plan, img);
@@ -2614,6 +2629,106 @@ extern "C" int slslam_lba_report(const slslam_lba_window* w, const slslam_solver
       (rc = slslam_lba_batch_report(b, nullptr)) == SLSLAM_OK &&
       (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
     rc = slslam_lba_batch_get_report(b, 0, sq_norm, weight, lines, cameras);
+  slslam_lba_batch_destroy(b);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// The 3-D segments of the lines of every window at its current device parameters (lba_segments.h)
+static_assert(sizeof(SegLine) == sizeof(slslam_lba_line_segment), "the device writes the caller's struct");
+static_assert((int)kSegOk == SLSLAM_SEGMENT_OK && (int)kSegNoObs == SLSLAM_SEGMENT_NO_OBSERVATIONS && (int)kSegNone == SLSLAM_SEGMENT_NONE, "");
+static_assert((int)kSegObsUsed == SLSLAM_SEGMENT_OBS_USED && (int)kSegObsUsedClamped == SLSLAM_SEGMENT_OBS_USED_CLAMPED &&
+              (int)kSegObsDegenerate == SLSLAM_SEGMENT_OBS_DEGENERATE && (int)kSegObsBehind == SLSLAM_SEGMENT_OBS_BEHIND &&
+              (int)kSegObsOutOfRange == SLSLAM_SEGMENT_OBS_OUT_OF_RANGE && (int)kSegObsCollapsed == SLSLAM_SEGMENT_OBS_COLLAPSED, "");
+
+extern "C" int slslam_lba_batch_segments(slslam_lba_batch* b, void* stream, double max_range) {
+  if (!b || !std::isfinite(max_range)) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized) return SLSLAM_ERR_STATE;
+  if (b->part[0]) {                                     // a mixed batch: both parts, one after the other on the caller's stream
+    ++b->seg_calls;
+    const int rc0 = slslam_lba_batch_segments(b->part[0], stream, max_range);
+    return rc0 != SLSLAM_OK ? rc0 : slslam_lba_batch_segments(b->part[1], stream, max_range);
+  }
+  const size_t B = b->wins.size();
+  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
+  const size_t lds = lds_bytes_segments(maxC, maxn);
+  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  ++b->seg_calls;
+  int rc;
+  if (!b->d_seg_line.p) {
+    const size_t cap_obs = std::max<size_t>(1, b->d_ob_orig.n), cap_line = std::max<size_t>(1, b->d_line_flags.n);
+    if ((rc = b->d_seg_status.alloc(cap_obs)) || (rc = b->d_seg_range.alloc(2 * cap_obs)) || (rc = b->d_seg_line.alloc(cap_line)) ||
+        (rc = b->h_seg_status.alloc(cap_obs, b->refillable)) || (rc = b->h_seg_range.alloc(2 * cap_obs, b->refillable)) ||
+        (rc = b->h_seg_line.alloc(cap_line, b->refillable))) {
+      b->d_seg_line.release();
+      return rc;
+    }
+    b->seg_allocations += 6;
+    // (a window the launch skips - none today - reads as zeros)
+    HIP_TRY(hipMemsetAsync(b->d_seg_status.p, 0, cap_obs * sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(b->d_seg_range.p, 0, 2 * cap_obs * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(b->d_seg_line.p, 0, cap_line * sizeof(SegLine), s));
+    if (lds > 48 * 1024) HIP_TRY(allow_lds({ (const void*)k_lba_segments_tiles, (const void*)k_lba_segments_lines }, 160 * 1024));
+  }
+  SegmentPtrs sp;
+  sp.ob_orig = b->d_ob_orig.p; sp.line_orig = b->d_line_orig.p;
+  sp.obs_status = b->d_seg_status.p; sp.obs_range = b->d_seg_range.p; sp.lines = b->d_seg_line.p;
+  sp.max_range = max_range;
+  if (B > 0) {
+    if (b->big_mode) hipLaunchKernelGGL(k_lba_segments_lines, dim3((unsigned)B), dim3(kSegLinesThreads), lds, s, b->ptrs, sp, maxC, maxn);
+    else if (b->nchunk > 0) hipLaunchKernelGGL(k_lba_segments_tiles, dim3((unsigned)b->nchunk), dim3(64), lds, s, b->ptrs, sp, maxC, maxn);
+  }
+  HIP_TRY(hipGetLastError());
+  b->seg_state = slslam_lba_batch::COV_ENQUEUED;
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_lba_batch_segments_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  long long a = b->seg_allocations;
+  for (int h = 0; h < 2; ++h) if (b->part[h]) a += b->part[h]->seg_allocations;
+  if (calls) *calls = b->seg_calls;
+  if (allocations) *allocations = a;
+  return SLSLAM_OK;
+}
+
+extern "C" int slslam_lba_batch_get_segments(const slslam_lba_batch* b, int index, int* obs_status, double* obs_range, slslam_lba_line_segment* lines) {
+  if (!b || index < 0 || index >= b->num_windows()) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (b->part[0]) return slslam_lba_batch_get_segments(b->part[b->route[(size_t)index].first], b->route[(size_t)index].second, obs_status, obs_range, lines);
+  if (b->seg_state != slslam_lba_batch::COV_READY) return SLSLAM_ERR_INVALID_ARGUMENT;      // the last segments call (if any) has not been downloaded
+  if (b->device_built && b->build_status[(size_t)index] != SLSLAM_OK) return b->build_status[(size_t)index];
+  const WinDesc& wd = b->h_wins[(size_t)index];
+  if (obs_status && wd.M > 0) std::memcpy(obs_status, b->h_seg_status.data() + (size_t)wd.obs_off, (size_t)wd.M * sizeof(int));
+  if (obs_range && wd.M > 0) std::memcpy(obs_range, b->h_seg_range.data() + 2 * (size_t)wd.obs_off, 2 * (size_t)wd.M * sizeof(double));
+  if (lines && wd.L > 0) std::memcpy(lines, b->h_seg_line.data() + (size_t)wd.line_off, (size_t)wd.L * sizeof(SegLine));
+  return SLSLAM_OK;
+}
+
+// One window, no solve: the segments at window->parameters
+extern "C" int slslam_lba_segments(const slslam_lba_window* w, const slslam_solver_options* opt, double max_range, int* obs_status,
+                                   double* obs_range, slslam_lba_line_segment* lines) {
+  if (!w || !std::isfinite(max_range)) return SLSLAM_ERR_INVALID_ARGUMENT;
+  slslam_solver_options o;
+  if (opt) o = *opt; else slslam_default_options(&o);
+  if (o.max_num_iterations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
+  PackedWindow pw;   // malformed input is reported as such on any machine, before the device is looked for
+  {
+    const int prc = pack_window(w, &pw);
+    if (prc != SLSLAM_OK) return prc;
+  }
+  slslam_lba_batch* b = nullptr;
+  int rc = slslam_lba_batch_create(-1, &b);
+  if (rc) return rc;
+  o.use_graph = 0;
+  o.refill_headroom_percent = 0;
+  b->wins.push_back(std::move(pw));
+  b->arena.cached = true;
+  if ((rc = slslam_lba_batch_finalize(b, &o)) == SLSLAM_OK &&
+      (rc = slslam_lba_batch_segments(b, nullptr, max_range)) == SLSLAM_OK &&
+      (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
+    rc = slslam_lba_batch_get_segments(b, 0, obs_status, obs_range, lines);
   slslam_lba_batch_destroy(b);
   return rc;
 }

@@ -61,7 +61,11 @@ int slslam_write_trajectory(const char* path, const slslam_pose* T, int n);
 /* save_landmark: the two 3-D endpoints of every landmark in the root frame: the point of the line closest to the
  * origin of its initial keyframe, moved tt[0] / tt[1] along the unit direction, taken to the world with the
  * initial keyframe's pose; line i = "z1 \t -y1 \t x1 \t z2 \t -y2 \t x2".
- * lines[6 n] = (point, direction) in the initial keyframe's frame, tt[2 n], T_init[n]. */
+ * lines[6 n] = (point, direction) in the initial keyframe's frame, tt[2 n], T_init[n].
+ * Where tt comes from: SLAM::extend_end_points in the reference; here slslam_lba_batch_segments / slslam_lba_segments
+ * (include/slslam_hip.h) give t_min, t_max of every line of a solved window - along the line's unit direction from its point closest
+ * to the WINDOW's origin, and the end points p_min, p_max in the window's frame: a caller whose landmark lives in its initial
+ * keyframe's frame moves the two end points there (or re-bases t by the shift of the closest point) before this call. */
 int slslam_landmark_endpoints(const double line[6], const double tt[2], const slslam_pose* T_init, double endpoints[6]);
 int slslam_write_landmarks(const char* path, const double* lines, const double* tt, const slslam_pose* T_init, int n);
 
