@@ -836,6 +836,63 @@ int  slslam_pose_estimator_set_covariance(slslam_pose_estimator* est, int enable
 int  slslam_pose_estimator_get_covariance(const slslam_pose_estimator* est, int frame, int* status, double constraint[6], double cov[36],
                                           double* sigma2, int* dof);
 
+/* ------------------------------------------------------------------ line matching: which observation of a frame sees which map line
+ * The link in front of the pose estimator (csrc/line_match.h).  The reference pairs observations by landmark id
+ * (SLAM::pose_estimation, src/slam.cpp:250-272) or takes the pairs of its place recogniser, which is commented out; a caller who has a
+ * predicted pose, a frame of stereo line observations and a map of solved lines - loop closure, relocalisation, landmarks whose track
+ * was lost - has no correspondences.  Every observation k of a frame is tried against every map line l:
+ *   e(k, l)     the float SLAM::reprojection_error(obs_k, pose, line_l) returns (src/slam.cpp:691-726), with the arithmetic of
+ *               slslam_ransac_score: the bits are the same;
+ *   admissible  e is finite and (double)e < error_thr and, when the frame gives extents, the 3-D interval [lo, hi] that the
+ *               observation's LEFT segment cuts out of line l (the per-observation steps of slslam_lba_batch_segments with max_range 0;
+ *               pc, dc under the frame's pose) is SLSLAM_SEGMENT_OBS_USED and meets [t_min - margin, t_max + margin]:
+ *               hi >= t_min - margin and lo <= t_max + margin.  Any other segment status (a line behind the camera, a segment of zero
+ *               length, ...) makes the pair inadmissible; so does a NaN extent.  A line without a segment: pass t_min > t_max.
+ *   per k       best_line = the admissible l of the smallest e, the lowest l on ties (-1: none); best_error = that e, second_error = the
+ *               smallest admissible e over l != best_line (+inf each when absent); num_admissible = admissible l;
+ *   per l       best_observation = the admissible k of the smallest e, the lowest k on ties (-1: none);
+ *   match[k]    best_line[k] when best_line[k] >= 0, best_observation[best_line[k]] == k (mutual) and
+ *               (double)best_error[k] * ratio <= (double)second_error[k] (unambiguous; ratio <= 1 switches this test off), else -1.
+ * Minima and counts only: a frame's results do not depend on the other frames of the call or on the order of evaluation. */
+typedef struct slslam_match_frame {
+  int num_observations;          /* K >= 0 */
+  int num_lines;                 /* L >= 0 */
+  const double* pose;            /* [12] predicted pose_t of the frame, R row-major | t, as in slslam_ransac_frame */
+  const double* observations;    /* [8 K] */
+  const double* lines;           /* [6 L] (closest point, direction), world frame, as in slslam_ransac_frame */
+  const double* extents;         /* [2 L] t_min, t_max of each line along its direction (slslam_lba_line_segment), or NULL */
+} slslam_match_frame;
+enum { SLSLAM_MATCH_OK = 0, SLSLAM_MATCH_EMPTY = 1, SLSLAM_MATCH_INVALID_POSE = 2 };
+typedef struct slslam_match_result {
+  int    status;                 /* SLSLAM_MATCH_*: EMPTY when K = 0 or L = 0 (the pose is not read), else INVALID_POSE when one of the    */
+                                 /* pose's 12 doubles is not finite; either way nothing is admissible and the arrays say so               */
+  int    num_matched;            /* match[k] >= 0                                                                                         */
+  int*   match;                  /* in: caller-owned arrays, any of them may be NULL; out: as above.  [K]                                 */
+  int*   best_line;              /* [K] */
+  float* best_error;             /* [K] */
+  float* second_error;           /* [K] */
+  int*   num_admissible;         /* [K] */
+  int*   best_observation;       /* [L] */
+} slslam_match_result;
+typedef struct slslam_line_matcher slslam_line_matcher;
+
+/* device < 0 selects the current HIP device.  max_observations / max_lines (>= 1): the most a frame of a run may hold; max_frames (>= 1)
+ * with them: what the matcher's one device block and one page-locked block are made for at the first run.  A run of more frames makes
+ * larger ones; a run that fits allocates nothing.  Touches no device: a machine without one fails at run. */
+int  slslam_line_matcher_create(int device, int max_frames, int max_observations, int max_lines, slslam_line_matcher** out);
+void slslam_line_matcher_destroy(slslam_line_matcher* matcher);
+/* frames[F], out[F].  baseline, error_thr as slslam_ransac_score; ratio, margin as above (none of the four may be NaN, margin >= 0).
+ * Every argument is validated before an output is written or the device is asked - a negative count, a missing array of a non-zero
+ * count, K or L beyond the matcher's maximum: SLSLAM_ERR_INVALID_ARGUMENT, outputs untouched.  Synchronous; host pointers; one upload,
+ * three launches (per line, per pair, finish) and one download per call whatever the number of frames. */
+int  slslam_line_matcher_run(slslam_line_matcher* matcher, int num_frames, const slslam_match_frame* frames, double baseline,
+                             double error_thr, double ratio, double margin, slslam_match_result* out);
+/* Since create: runs, and how often the matcher's blocks were made or made larger.  Either pointer may be NULL. */
+int  slslam_line_matcher_stats(const slslam_line_matcher* matcher, long long* calls, long long* allocations);
+/* One frame, one call (its own buffers, made and freed). */
+int  slslam_match_lines(const slslam_match_frame* frame, double baseline, double error_thr, double ratio, double margin,
+                        slslam_match_result* out);
+
 /* ------------------------------------------------------------------ structure-only refinement: every camera constant, every line free
  * The mirror image of the motion-only window (multi-view line triangulation): with the cameras fixed every line is its own 4-unknown
  * Levenberg-Marquardt problem with its own trust region.  Where it is used: a landmark made from one stereo pair (initialize_lm,

@@ -78,6 +78,17 @@ class PoseEstimate(C.Structure):
                 ("num_inliers", C.c_int), ("inlier_bits", C.POINTER(C.c_ulonglong))]
 
 
+class MatchFrame(C.Structure):
+    _fields_ = [("num_observations", C.c_int), ("num_lines", C.c_int), ("pose", C.POINTER(C.c_double)),
+                ("observations", C.POINTER(C.c_double)), ("lines", C.POINTER(C.c_double)), ("extents", C.POINTER(C.c_double))]
+
+
+class MatchResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("num_matched", C.c_int), ("match", C.POINTER(C.c_int)), ("best_line", C.POINTER(C.c_int)),
+                ("best_error", C.POINTER(C.c_float)), ("second_error", C.POINTER(C.c_float)), ("num_admissible", C.POINTER(C.c_int)),
+                ("best_observation", C.POINTER(C.c_int))]
+
+
 class LineResult(C.Structure):
     _fields_ = [("status", C.c_int), ("termination_type", C.c_int), ("num_successful_steps", C.c_int),
                 ("num_unsuccessful_steps", C.c_int), ("num_observations", C.c_int), ("initial_cost", C.c_double),
@@ -87,6 +98,7 @@ class LineResult(C.Structure):
 LINE_REFINED, LINE_CONSTANT, LINE_NO_OBSERVATIONS, LINE_INVALID = 0, 1, 2, 3
 LINE_STATUS = {0: "REFINED", 1: "CONSTANT", 2: "NO_OBSERVATIONS", 3: "INVALID"}
 POSE_STATUS = {0: "OK", 1: "TOO_FEW_FEATURES", 2: "RANSAC_FAILED"}
+MATCH_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_POSE"}
 COV_OK, COV_SINGULAR = 0, 1
 
 
@@ -127,7 +139,7 @@ EXPORTS = [
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
     "slslam_lba_batch_report", "slslam_lba_batch_get_report", "slslam_lba_batch_report_stats", "slslam_lba_report",
     "slslam_lba_batch_segments", "slslam_lba_batch_get_segments", "slslam_lba_batch_segments_stats", "slslam_lba_segments",
-    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_matcher_create", "slslam_line_matcher_destroy", "slslam_line_matcher_run", "slslam_line_matcher_stats", "slslam_match_lines", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -246,6 +258,14 @@ def lib():
                                             C.POINTER(PoseEstimate)]
     L.slslam_pose_estimator_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 4
     L.slslam_pose_estimator_window.argtypes = [vp, C.c_int, C.POINTER(C.c_uint), dp, dp, dp, ip]
+    if hasattr(L, "slslam_match_lines"):         # (likewise: a library built before the line matcher existed)
+        L.slslam_line_matcher_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.slslam_line_matcher_destroy.argtypes = [vp]
+        L.slslam_line_matcher_destroy.restype = None
+        L.slslam_line_matcher_run.argtypes = [vp, C.c_int, C.POINTER(MatchFrame), C.c_double, C.c_double, C.c_double, C.c_double,
+                                              C.POINTER(MatchResult)]
+        L.slslam_line_matcher_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+        L.slslam_match_lines.argtypes = [C.POINTER(MatchFrame), C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(MatchResult)]
     L.slslam_line_refiner_create.argtypes = [C.c_int, C.POINTER(SolverOptions), C.c_longlong, C.c_longlong, C.POINTER(vp)]
     L.slslam_line_refiner_destroy.argtypes = [vp]
     L.slslam_line_refiner_destroy.restype = None
@@ -1432,3 +1452,107 @@ class PoseEstimator:
         _check(lib().slslam_pose_estimator_window(self._h, int(frame), words.ctypes.data_as(C.POINTER(C.c_uint)), _dp(obs), _dp(par), _dp(cam),
                                                   C.byref(nl)), "slslam_pose_estimator_window")
         return {"index_words": words[:2 * n], "observations": obs[:16 * n].reshape(-1, 8), "parameters": par, "solved_camera": cam}
+
+
+# ----------------------------------------------------------------------------- line matching (slslam_line_matcher_*)
+def _match_frame(fr):
+    """frame dict (pose [12], observations [K, 8], lines [L, 6], optionally extents [L, 2]) -> (MatchFrame, the arrays it points to)"""
+    pose = np.ascontiguousarray(fr["pose"], dtype=np.float64).reshape(-1)
+    obs = np.ascontiguousarray(fr["observations"], dtype=np.float64).reshape(-1, 8)
+    ln = np.ascontiguousarray(fr["lines"], dtype=np.float64).reshape(-1, 6)
+    ext = fr.get("extents")
+    if ext is not None:
+        ext = np.ascontiguousarray(ext, dtype=np.float64).reshape(-1, 2)
+        if len(ext) != len(ln):
+            raise ValueError("extents and lines must have the same length")
+    if len(pose) != 12:
+        raise ValueError("pose must hold 12 doubles (R row-major | t)")
+    return MatchFrame(len(obs), len(ln), _dp(pose), _dp(obs), _dp(ln), _dp(ext) if ext is not None else None), (pose, obs, ln, ext)
+
+
+def _match_buffers(k, l):
+    b = {"match": np.full(max(k, 1), -2, dtype=np.int32), "best_line": np.full(max(k, 1), -2, dtype=np.int32),
+         "best_error": np.zeros(max(k, 1), dtype=np.float32), "second_error": np.zeros(max(k, 1), dtype=np.float32),
+         "num_admissible": np.zeros(max(k, 1), dtype=np.int32), "best_observation": np.full(max(l, 1), -2, dtype=np.int32)}
+    fp = C.POINTER(C.c_float)
+    r = MatchResult(-1, 0, _ip(b["match"]), _ip(b["best_line"]), b["best_error"].ctypes.data_as(fp), b["second_error"].ctypes.data_as(fp),
+                    _ip(b["num_admissible"]), _ip(b["best_observation"]))
+    return r, b
+
+
+def _match_dict(r, b, k, l):
+    out = {"status": MATCH_STATUS[r.status], "num_matched": r.num_matched}
+    out.update({key: (a[:l] if key == "best_observation" else a[:k]) for key, a in b.items()})
+    return out
+
+
+def match_lines(frame, baseline=0.12, error_thr=5.0 / 406.05, ratio=1.5, margin=0.0):
+    """One frame's observations against its map lines under its predicted pose (slslam_match_lines).  frame: dict of pose [12],
+    observations [K, 8], lines [L, 6] and optionally extents [L, 2].  Returns dict(status, num_matched, match [K], best_line [K],
+    best_error [K] float32, second_error [K] float32, num_admissible [K], best_observation [L])."""
+    mf, keep = _match_frame(frame)
+    r, b = _match_buffers(mf.num_observations, mf.num_lines)
+    _check(lib().slslam_match_lines(C.byref(mf), float(baseline), float(error_thr), float(ratio), float(margin), C.byref(r)),
+           "slslam_match_lines")
+    return _match_dict(r, b, mf.num_observations, mf.num_lines)
+
+
+class LineMatcher:
+    """slslam_line_matcher: many frames per call, every observation of a frame against every line of its map; buffers kept between runs."""
+
+    def __init__(self, max_frames=16, max_observations=512, max_lines=4096, device=-1):
+        self._h = C.c_void_p()
+        _check(lib().slslam_line_matcher_create(int(device), int(max_frames), int(max_observations), int(max_lines), C.byref(self._h)),
+               "slslam_line_matcher_create")
+
+    def close(self):
+        if self._h:
+            lib().slslam_line_matcher_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, frames, baseline=0.12, error_thr=5.0 / 406.05, ratio=1.5, margin=0.0):
+        """frames: dicts as match_lines takes.  Returns one dict per frame, as match_lines returns."""
+        n = len(frames)
+        mfs, outs, keep, bufs = (MatchFrame * max(n, 1))(), (MatchResult * max(n, 1))(), [], []
+        for i, fr in enumerate(frames):
+            mfs[i], k = _match_frame(fr)
+            outs[i], b = _match_buffers(mfs[i].num_observations, mfs[i].num_lines)
+            keep.append(k)
+            bufs.append(b)
+        _check(lib().slslam_line_matcher_run(self._h, n, mfs, float(baseline), float(error_thr), float(ratio), float(margin), outs),
+               "slslam_line_matcher_run")
+        return [_match_dict(outs[i], bufs[i], mfs[i].num_observations, mfs[i].num_lines) for i in range(n)]
+
+    def stats(self):
+        c, a = C.c_longlong(0), C.c_longlong(0)
+        _check(lib().slslam_line_matcher_stats(self._h, C.byref(c), C.byref(a)), "slslam_line_matcher_stats")
+        return {"calls": c.value, "allocations": a.value}
+
+
+def matched_trials(frame, result, map_observations, num_trials=1001, sample_size=5, seed=0):
+    """From a match result to the inputs of PoseEstimator.run / ransac_motion: the matched observations of the frame in ascending order,
+    each aligned with its map line and with that landmark's earlier observation.  map_observations [L, 8]: the observation of every map
+    line in the frame the lines are expressed in (obs0).  Returns dict(obs0, obs1, lines, samples [num_trials, sample_size] - distinct
+    indices per trial, drawn from `seed` -, observation_index, line_index)."""
+    obs = np.ascontiguousarray(frame["observations"], dtype=np.float64).reshape(-1, 8)
+    ln = np.ascontiguousarray(frame["lines"], dtype=np.float64).reshape(-1, 6)
+    mo = np.ascontiguousarray(map_observations, dtype=np.float64).reshape(-1, 8)
+    if len(mo) != len(ln):
+        raise ValueError("map_observations and lines must have the same length")
+    match = np.asarray(result["match"])
+    k = np.nonzero(match >= 0)[0]
+    l = match[k]
+    n = len(k)
+    rng = np.random.default_rng(np.random.SeedSequence([11, int(seed)]))
+    if n >= sample_size:
+        samples = np.stack([rng.choice(n, size=sample_size, replace=False) for _ in range(num_trials)]).astype(np.int32)
+    else:                # (too few for a sample: the estimator reports TOO_FEW_FEATURES; the indices only have to be in range)
+        samples = (np.arange(num_trials * sample_size, dtype=np.int32).reshape(num_trials, sample_size) % max(n, 1)).astype(np.int32)
+    return {"obs0": mo[l], "obs1": obs[k], "lines": ln[l], "samples": samples, "observation_index": k.astype(np.int32),
+            "line_index": l.astype(np.int32)}

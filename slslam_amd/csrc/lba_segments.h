@@ -33,10 +33,10 @@
 #define SLSLAM_LBA_SEGMENTS_H_
 
 #include "lba_kernels.h"
+#include "segment_eval.h"      // segment_eval: steps 1-5 of the contract for one observation
 
 namespace slslam {
 
-enum { kSegObsUsed = 0, kSegObsUsedClamped = 1, kSegObsDegenerate = 2, kSegObsBehind = 3, kSegObsOutOfRange = 4, kSegObsCollapsed = 5 };   // = SLSLAM_SEGMENT_OBS_*
 enum { kSegOk = 0, kSegNoObs = 1, kSegNone = 2 };                                                                                     // = SLSLAM_SEGMENT_*
 enum { kSegLinesThreads = 256, kSegLinesWaves = 4 };
 
@@ -52,57 +52,6 @@ struct SegmentPtrs {
 };
 
 __host__ __device__ inline size_t lds_bytes_segments(int C, int n) { return sizeof(double) * (size_t)lds_doubles_cost(C, n); }
-
-// Steps 1-5 of the contract for one observation; e = x0 y0 x1 y1 of the left image.  lo, hi: zeros unless USED / USED_CLAMPED.
-__device__ __forceinline__ int segment_eval(const double (&R)[9], const double (&t)[3], const double (&cp)[3], const double (&dv)[3],
-                                            const double (&e)[4], double max_range, double& lo, double& hi) {
-  lo = 0.0; hi = 0.0;
-  double pc[3], dc[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    pc[i] = R[3 * i] * cp[0] + R[3 * i + 1] * cp[1] + R[3 * i + 2] * cp[2] + t[i];
-    dc[i] = R[3 * i] * dv[0] + R[3 * i + 1] * dv[1] + R[3 * i + 2] * dv[2];
-  }
-  bool fin = true;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) fin = fin && isfinite(pc[i]) && isfinite(dc[i]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) fin = fin && isfinite(e[i]);
-  double lx = e[1] - e[3], ly = e[2] - e[0];                 // (p1 x p2)[0:2]
-  const double nrm = sqrt(lx * lx + ly * ly);
-  if (!fin || !(nrm > 0.0)) return kSegObsDegenerate;
-  lx /= nrm; ly /= nrm;
-  double s[2];
-  bool degenerate = false;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const double m2 = e[2 * k] * ly - e[2 * k + 1] * lx;     // m = p x (ln, 0) = (-ly, lx, px ly - py lx)
-    const double mn = sqrt(ly * ly + lx * lx + m2 * m2);
-    const double den = -ly * dc[0] + lx * dc[1] + m2 * dc[2];
-    const double num = -ly * pc[0] + lx * pc[1] + m2 * pc[2];
-    degenerate = degenerate || !(fabs(den) > 1e-6 * mn);
-    s[k] = -num / den;
-  }
-  if (degenerate) return kSegObsDegenerate;
-  if (pc[2] + s[0] * dc[2] < 0.0 || pc[2] + s[1] * dc[2] < 0.0) return kSegObsBehind;
-  bool clamped = false;
-  if (max_range > 0.0) {
-    const double q = pc[0] * dc[0] + pc[1] * dc[1] + pc[2] * dc[2];
-    const double p0[3] = { pc[0] - q * dc[0], pc[1] - q * dc[1], pc[2] - q * dc[2] };
-    const double d2 = p0[0] * p0[0] + p0[1] * p0[1] + p0[2] * p0[2];
-    if (sqrt(d2) > max_range) return kSegObsOutOfRange;
-    const double ext = sqrt(fmax(max_range * max_range - d2, 0.0));
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const double tau = s[k] + q;
-      if (fabs(tau) > ext) { s[k] = copysign(ext, tau) - q; clamped = true; }
-    }
-  }
-  const double a = fmin(s[0], s[1]), b = fmax(s[0], s[1]);
-  if (a == b) return kSegObsCollapsed;
-  lo = a; hi = b;
-  return clamped ? kSegObsUsedClamped : kSegObsUsed;
-}
 
 // Min over the lanes of a line's run, result in every lane of the run: seg_sum_n's twin.  Inclusive prefix along the 16-lane row
 // restricted to the lane's own run (row_shr by 1, 2, 4, 8; the source is in the same run AND the same row iff the lane's position in

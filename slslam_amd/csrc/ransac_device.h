@@ -1,5 +1,6 @@
 // slslam_amd/csrc/ransac_device.h — the bodies of RANSAC hypothesis scoring and generation: called by the one kernel pair of
-// ransac_api.hip (every frame of a call in one launch) and, for the final inlier set, by frame_api.hip's k_frame_finish.
+// ransac_api.hip (every frame of a call in one launch), for the final inlier set by frame_api.hip's k_frame_finish, and - the error in
+// its two parts - by the line matcher (line_match.h).
 //
 // Scoring: SLAM::reprojection_error (reference src/slam.cpp:691-726) of one line under one pose.  The reference mixes float
 // and double (float `sql = nc.head(2).norm()`, `float error`); the same conversions are applied in the same places so that
@@ -22,32 +23,58 @@ __device__ __forceinline__ bool pose_skipped(const double* T) {
   return sqrt(t0 * t0 + t1 * t1 + t2 * t2) > 1.0;
 }
 
-// reprojection_error(ft, T, line) < thr for one common line: ft = its observation [8], ln = (closest point, direction) [6]
-__device__ __forceinline__ bool line_inlier(const double* T, const double* __restrict__ ft, const double* __restrict__ ln, double baseline,
-                                            double thr) {
+// reprojection_error in two parts, so that a caller with many observations per line (line_match.h) evaluates the first once per line;
+// the operations and their order are the reference's, so splitting them changes no rounding.
+// Part 1, pose and line ln = (closest point, direction) [6]: per stereo camera i the image line's normal n[i] = nc / (float)sql; pc, dc =
+// the line's point and direction in the left camera (gc_point_to_pose, T.R * dv)
+__device__ __forceinline__ void line_normals(const double* T, const double* __restrict__ ln, double baseline, double (&n)[2][3],
+                                             double (&pc)[3], double (&dc)[3]) {
   const double t0 = T[9], t1 = T[10], t2 = T[11];
   const double cp[3] = { ln[0], ln[1], ln[2] }, dv[3] = { ln[3], ln[4], ln[5] };
   double tt0 = t0;
-  float error = 0.f;
   // dvc = T.R * dv is the same for both cameras
   const double d0 = T[0] * dv[0] + T[1] * dv[1] + T[2] * dv[2];
   const double d1 = T[3] * dv[0] + T[4] * dv[1] + T[5] * dv[2];
   const double d2 = T[6] * dv[0] + T[7] * dv[1] + T[8] * dv[2];
+  dc[0] = d0; dc[1] = d1; dc[2] = d2;
+#pragma unroll
   for (int i = 0; i < 2; ++i) {
     if (i == 1) tt0 -= baseline;                                   // T.t(0) -= baseline
     const double c0 = T[0] * cp[0] + T[1] * cp[1] + T[2] * cp[2] + tt0;   // gc_point_to_pose
     const double c1 = T[3] * cp[0] + T[4] * cp[1] + T[5] * cp[2] + t1;
     const double c2 = T[6] * cp[0] + T[7] * cp[1] + T[8] * cp[2] + t2;
+    if (i == 0) { pc[0] = c0; pc[1] = c1; pc[2] = c2; }
     double n0 = c1 * d2 - c2 * d1, n1 = c2 * d0 - c0 * d2, n2 = c0 * d1 - c1 * d0;   // cpc.cross(dvc)
     const float sql = (float)sqrt(n0 * n0 + n1 * n1);              // float sql = nc.head(2).norm()
     n0 /= (double)sql; n1 /= (double)sql; n2 /= (double)sql;       // nc /= sql
-    const double e1 = fabs(n0 * ft[4 * i] + n1 * ft[4 * i + 1] + n2);          // nc.dot(p1), p1 = (x, y, 1)
-    const double e2 = fabs(n0 * ft[4 * i + 2] + n1 * ft[4 * i + 3] + n2);
+    n[i][0] = n0; n[i][1] = n1; n[i][2] = n2;
+  }
+}
+
+// Part 2, the normals and one observation ft [8]: the float reprojection_error returns
+__device__ __forceinline__ float normals_error(const double (&n)[2][3], const double* __restrict__ ft) {
+  float error = 0.f;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const double e1 = fabs(n[i][0] * ft[4 * i] + n[i][1] * ft[4 * i + 1] + n[i][2]);          // nc.dot(p1), p1 = (x, y, 1)
+    const double e2 = fabs(n[i][0] * ft[4 * i + 2] + n[i][1] * ft[4 * i + 3] + n[i][2]);
     error = (float)((double)error + e1);                           // float error += double
     error = (float)((double)error + e2);
   }
-  const float ret = (float)((double)error / 4.0);                  // return error / 4.0  (float function)
-  return (double)ret < thr;                                        // error < error_thr (double)
+  return (float)((double)error / 4.0);                             // return error / 4.0  (float function)
+}
+
+// reprojection_error(ft, T, line) of one common line: ft = its observation [8], ln = (closest point, direction) [6]
+__device__ __forceinline__ float line_error(const double* T, const double* __restrict__ ft, const double* __restrict__ ln, double baseline) {
+  double n[2][3], pc[3], dc[3];
+  line_normals(T, ln, baseline, n, pc, dc);
+  return normals_error(n, ft);
+}
+
+// reprojection_error(ft, T, line) < thr
+__device__ __forceinline__ bool line_inlier(const double* T, const double* __restrict__ ft, const double* __restrict__ ln, double baseline,
+                                            double thr) {
+  return (double)line_error(T, ft, ln, baseline) < thr;            // error < error_thr (double)
 }
 
 // ---------------------------------------------------------------------------------------------
