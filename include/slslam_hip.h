@@ -934,6 +934,73 @@ int  slslam_line_refiner_stats(const slslam_line_refiner* refiner, long long* ca
 int  slslam_lba_refine_lines(const slslam_lba_window* window, const slslam_solver_options* opt,
                              slslam_line_result* results, slslam_summary* total);
 
+/* ------------------------------------------------------------------ line triangulation: making a landmark from all its observations
+ * Replaces: SLAM::add_lms -> SLAM::initialize_lm (reference src/slam.cpp:161-219), which makes a line from the first stereo pair that
+ * sees it and never revisits that start, and the gc_line_from_pose + gc_av_to_orth that put it into a window (src/slam.cpp:884-888).
+ * Fills the line part of slslam_lba_window.parameters from the window's cameras and observations (csrc/lba_triangulate.h):
+ *   stereo-first  initialize_lm of the line's first observation in the caller's order, in its operation order - gc_ppp_pi of the left and
+ *                 right segments, gc_pipi_plk, gc_plucker_origin, the |cp| < 0.1 || > 10 clamp to cp / |cp| / inverse_depth, the cp.z < 0
+ *                 flip - then gc_line_from_pose under that observation's camera;
+ *   multi-view    (method 1) the two back-projected planes of EVERY observation of the line, in the world, scaled to a unit normal (a
+ *                 plane whose normal has no length - a segment of zero length - is skipped); their symmetric 4 x 4 Gram matrix, summed in
+ *                 the caller's order; the line of the two eigenvectors of its two largest eigenvalues (gc_pipi_plk, gc_plucker_origin),
+ *                 its direction signed like the stereo-first one.  Neither the clamp nor the flip applies to it;
+ *   choice        with the eigenvalues l1 >= l2 >= l3 >= l4: the multi-view line when the line has >= 2 observations, every number of it
+ *                 is finite and l2 >= min_parallax l1, else the stereo-first line.  l2 / l1 is a parallax measure.
+ * Where it is used: the unmatched observations slslam_line_matcher_run leaves, once slslam_pose_estimator_run has fixed their frame;
+ * the lines of a window rebuilt after a pose-graph solve; in front of slslam_line_refiner_run or the window solve.  One launch handles
+ * every line of every window of a call, lane <-> line; a line's bytes do not depend on the other lines or windows of the call. */
+typedef struct slslam_line_triangulator slslam_line_triangulator;
+enum { SLSLAM_TRI_MULTIVIEW = 0, SLSLAM_TRI_STEREO = 1, SLSLAM_TRI_CONSTANT = 2, SLSLAM_TRI_NO_OBSERVATIONS = 3, SLSLAM_TRI_INVALID = 4 };
+typedef struct slslam_triangulated_line {  /* one per line of a window */
+  int    status;                  /* SLSLAM_TRI_*; anything but MULTIVIEW / STEREO: the line's four doubles are untouched               */
+  int    num_observations;        /* observations that name the line (every status)                                                   */
+  int    num_planes;              /* planes that entered the Gram matrix: 2 per observation less the skipped ones; 0 for method 0     */
+                                  /* and for a line that is not MULTIVIEW / STEREO                                                    */
+  int    first_camera;            /* camera of the line's first observation (every status; -1: nobody observes the line)              */
+  double eigenvalues[4];          /* descending; zeros for method 0 and for every line that is not MULTIVIEW: read as "no parallax"   */
+  int    clamped;                 /* the stereo-first line was taken and its depth clamp fired                                        */
+  int    reserved;
+} slslam_triangulated_line;
+
+/* device < 0 selects the current HIP device.  opt (NULL = slslam_default_options): baseline is used, everything else is ignored.
+ * max_lines / max_observations: as for slslam_line_refiner_create.  Touches no device: a machine without one fails at run. */
+int  slslam_line_triangulator_create(int device, const slslam_solver_options* opt, long long max_lines, long long max_observations,
+                                     slslam_line_triangulator** out);
+void slslam_line_triangulator_destroy(slslam_line_triangulator* triangulator);
+/* windows[n].  method 0: the reference's start (stereo-first) for every line; method 1: as above.  inverse_depth: what the clamp puts a
+ * line at (the reference's value is 0.1, src/parameter.h:55).  min_parallax: 0 never falls back on parallax.
+ * fixed_index[2i] (camera) is ignored; one flagged fixed_index[2i+1] makes the line SLSLAM_TRI_CONSTANT, as in the refiner.  A line
+ * nobody observes: SLSLAM_TRI_NO_OBSERVATIONS.  SLSLAM_TRI_INVALID: a non-finite observation of the line or a non-finite parameter of
+ * a camera that sees it, or a stereo-first line with v = 0 (the two planes of the first observation are parallel or coincide, or one
+ * of its segments has no length) or with a non-finite number.  The four doubles of such lines are untouched and the other lines
+ * unaffected; the current values of the line parameters are never read.  windows[i].parameters: the lines in place (slslam_gc
+ * av_to_orth of the chosen line); the camera part is read and never written.  results (may be NULL; results[i] may be NULL):
+ * windows[i].num_lines records.  lines_av (may be NULL; lines_av[i] may be NULL): [6 num_lines] (closest point, direction) of the chosen
+ * line in the world; the six doubles of a line that is not MULTIVIEW / STEREO are untouched.
+ * Every argument is validated before an output is written or the device is asked - an index out of range, a negative count, a missing
+ * array of a non-zero count, a method outside {0, 1}, a NaN or negative min_parallax, an inverse_depth that is not finite or <= 0:
+ * SLSLAM_ERR_INVALID_ARGUMENT, outputs untouched.  More than 630 cameras in a window: SLSLAM_ERR_UNSUPPORTED.  Synchronous; host
+ * pointers; one upload, one launch, one download per call. */
+int  slslam_line_triangulator_run(slslam_line_triangulator* triangulator, int n, const slslam_lba_window* windows, int method,
+                                  double inverse_depth, double min_parallax, slslam_triangulated_line* const* results,
+                                  double* const* lines_av);
+/* Since create: runs, device / page-locked buffer allocations.  Either pointer may be NULL. */
+int  slslam_line_triangulator_stats(const slslam_line_triangulator* triangulator, long long* calls, long long* allocations);
+/* Host wall-clock milliseconds of the last successful run, ms[5]: validation + layout + upload image, upload, kernel, download, scatter
+ * of the results (tools/lba_triangulate_bench.py). */
+int  slslam_line_triangulator_timing(const slslam_line_triangulator* triangulator, double* ms);
+/* One window, one call (its own buffers, made and freed). */
+int  slslam_lba_triangulate_lines(const slslam_lba_window* window, const slslam_solver_options* opt, int method, double inverse_depth,
+                                  double min_parallax, slslam_triangulated_line* results, double* lines_av);
+/* Test hook: ONE line through the same header functions on the host, in the kernel's order.  observations[8 n] in the caller's order,
+ * cameras[6 n]: the (w, t) of each observation's camera.  line_av[6] (written unless *status is SLSLAM_TRI_INVALID), eigenvalues[4],
+ * *status, *num_planes, *clamped as the device reports them; *offdiagonal: the off-diagonal norm the Jacobi sweeps left (method 1).
+ * Any output may be NULL.  Needs no device. */
+int  slslam_debug_triangulate_host(int num_observations, const double* observations, const double* cameras, double baseline, int method,
+                                   double inverse_depth, double min_parallax, double* line_av, double* eigenvalues, int* status,
+                                   int* num_planes, int* clamped, double* offdiagonal);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */

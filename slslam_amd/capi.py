@@ -95,6 +95,13 @@ class LineResult(C.Structure):
                 ("final_cost", C.c_double)]
 
 
+class TriangulatedLine(C.Structure):
+    _fields_ = [("status", C.c_int), ("num_observations", C.c_int), ("num_planes", C.c_int), ("first_camera", C.c_int),
+                ("eigenvalues", C.c_double * 4), ("clamped", C.c_int), ("reserved", C.c_int)]
+
+
+TRI_MULTIVIEW, TRI_STEREO, TRI_CONSTANT, TRI_NO_OBSERVATIONS, TRI_INVALID = 0, 1, 2, 3, 4
+TRI_STATUS = {0: "MULTIVIEW", 1: "STEREO", 2: "CONSTANT", 3: "NO_OBSERVATIONS", 4: "INVALID"}
 LINE_REFINED, LINE_CONSTANT, LINE_NO_OBSERVATIONS, LINE_INVALID = 0, 1, 2, 3
 LINE_STATUS = {0: "REFINED", 1: "CONSTANT", 2: "NO_OBSERVATIONS", 3: "INVALID"}
 POSE_STATUS = {0: "OK", 1: "TOO_FEW_FEATURES", 2: "RANSAC_FAILED"}
@@ -139,7 +146,7 @@ EXPORTS = [
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
     "slslam_lba_batch_report", "slslam_lba_batch_get_report", "slslam_lba_batch_report_stats", "slslam_lba_report",
     "slslam_lba_batch_segments", "slslam_lba_batch_get_segments", "slslam_lba_batch_segments_stats", "slslam_lba_segments",
-    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_matcher_create", "slslam_line_matcher_destroy", "slslam_line_matcher_run", "slslam_line_matcher_stats", "slslam_match_lines", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_matcher_create", "slslam_line_matcher_destroy", "slslam_line_matcher_run", "slslam_line_matcher_stats", "slslam_match_lines", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_line_triangulator_create", "slslam_line_triangulator_destroy", "slslam_line_triangulator_run", "slslam_line_triangulator_stats", "slslam_line_triangulator_timing", "slslam_lba_triangulate_lines", "slslam_debug_triangulate_host", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -272,6 +279,16 @@ def lib():
     L.slslam_line_refiner_run.argtypes = [vp, C.c_int, C.POINTER(LBAWindow), C.POINTER(C.POINTER(LineResult)), C.POINTER(Summary)]
     L.slslam_line_refiner_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
     L.slslam_lba_refine_lines.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), C.POINTER(LineResult), C.POINTER(Summary)]
+    L.slslam_line_triangulator_create.argtypes = [C.c_int, C.POINTER(SolverOptions), C.c_longlong, C.c_longlong, C.POINTER(vp)]
+    L.slslam_line_triangulator_destroy.argtypes = [vp]
+    L.slslam_line_triangulator_destroy.restype = None
+    L.slslam_line_triangulator_run.argtypes = [vp, C.c_int, C.POINTER(LBAWindow), C.c_int, C.c_double, C.c_double,
+                                               C.POINTER(C.POINTER(TriangulatedLine)), C.POINTER(dp)]
+    L.slslam_line_triangulator_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+    L.slslam_line_triangulator_timing.argtypes = [vp, dp]
+    L.slslam_lba_triangulate_lines.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), C.c_int, C.c_double, C.c_double,
+                                               C.POINTER(TriangulatedLine), dp]
+    L.slslam_debug_triangulate_host.argtypes = [C.c_int, dp, dp, C.c_double, C.c_int, C.c_double, C.c_double, dp, dp, ip, ip, ip, dp]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -524,6 +541,80 @@ class LineRefiner:
         c, a = C.c_longlong(0), C.c_longlong(0)
         _check(lib().slslam_line_refiner_stats(self.h, C.byref(c), C.byref(a)), "slslam_line_refiner_stats")
         return {"calls": c.value, "allocations": a.value}
+
+
+def lba_triangulate_lines(w, method=1, inverse_depth=0.1, min_parallax=0.0, **opt):
+    """Every line of one window made from its observations under the window's cameras (slslam_lba_triangulate_lines): method 0 the
+    reference's stereo-first start, method 1 the multi-view line where it has parallax.  Returns (parameters with the new lines,
+    per-line records as a structured array, lines_av[L, 6] - rows of lines that were not made are NaN)."""
+    arr = _WindowArrays(w)
+    o = default_options(**opt)
+    res = np.zeros(max(int(w["num_lines"]), 0), dtype=np.dtype(TriangulatedLine))
+    av = np.full((max(int(w["num_lines"]), 0), 6), np.nan)
+    _check(lib().slslam_lba_triangulate_lines(C.byref(arr.c), C.byref(o), int(method), float(inverse_depth), float(min_parallax),
+                                              res.ctypes.data_as(C.POINTER(TriangulatedLine)), _dp(av)), "slslam_lba_triangulate_lines")
+    return arr.params, res, av
+
+
+class LineTriangulator:
+    """slslam_line_triangulator: every line of every window of a run made in one launch, buffers reused between runs."""
+
+    def __init__(self, max_lines, max_observations, device=-1, **opt):
+        self.h = C.c_void_p()
+        o = default_options(**opt)
+        _check(lib().slslam_line_triangulator_create(device, C.byref(o), int(max_lines), int(max_observations), C.byref(self.h)),
+               "slslam_line_triangulator_create")
+
+    def close(self):
+        if self.h:
+            lib().slslam_line_triangulator_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, windows, method=1, inverse_depth=0.1, min_parallax=0.0):
+        """windows: dicts as for lba_solve.  Returns (list of parameter vectors, list of per-line structured arrays, list of lines_av)."""
+        arrs = [_WindowArrays(w) for w in windows]
+        n = len(arrs)
+        cw = (LBAWindow * max(n, 1))(*[a.c for a in arrs])
+        res = [np.zeros(max(int(w["num_lines"]), 0), dtype=np.dtype(TriangulatedLine)) for w in windows]
+        avs = [np.full((max(int(w["num_lines"]), 0), 6), np.nan) for w in windows]
+        rp = (C.POINTER(TriangulatedLine) * max(n, 1))(*[r.ctypes.data_as(C.POINTER(TriangulatedLine)) for r in res])
+        ap = (C.POINTER(C.c_double) * max(n, 1))(*[_dp(a) for a in avs])
+        _check(lib().slslam_line_triangulator_run(self.h, n, cw, int(method), float(inverse_depth), float(min_parallax), rp, ap),
+               "slslam_line_triangulator_run")
+        return [a.params for a in arrs], res, avs
+
+    def stats(self):
+        c, a = C.c_longlong(0), C.c_longlong(0)
+        _check(lib().slslam_line_triangulator_stats(self.h, C.byref(c), C.byref(a)), "slslam_line_triangulator_stats")
+        return {"calls": c.value, "allocations": a.value}
+
+    def timing(self):
+        """Host wall-clock milliseconds of the last run: dict(layout, upload, kernel, download, scatter)."""
+        ms = np.zeros(5)
+        _check(lib().slslam_line_triangulator_timing(self.h, _dp(ms)), "slslam_line_triangulator_timing")
+        return dict(zip(("layout", "upload", "kernel", "download", "scatter"), ms.tolist()))
+
+
+def triangulate_host(observations, cameras, baseline=0.12, method=1, inverse_depth=0.1, min_parallax=0.0):
+    """One line through the device's header functions on the host (slslam_debug_triangulate_host): observations[n, 8] in the caller's
+    order, cameras[n, 6] the (w, t) of each observation's camera.  Returns dict(status, num_planes, clamped, eigenvalues[4], av[6],
+    offdiagonal)."""
+    ob = np.ascontiguousarray(observations, dtype=np.float64).reshape(-1, 8)
+    cm = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 6)
+    if len(ob) != len(cm):
+        raise ValueError("one camera per observation")
+    av, eig, off = np.full(6, np.nan), np.zeros(4), C.c_double(0.0)
+    st, pl, cl = C.c_int(-1), C.c_int(0), C.c_int(0)
+    _check(lib().slslam_debug_triangulate_host(len(ob), _dp(ob), _dp(cm), float(baseline), int(method), float(inverse_depth),
+                                               float(min_parallax), _dp(av), _dp(eig), C.byref(st), C.byref(pl), C.byref(cl), C.byref(off)),
+           "slslam_debug_triangulate_host")
+    return {"status": st.value, "num_planes": pl.value, "clamped": cl.value, "eigenvalues": eig, "av": av, "offdiagonal": off.value}
 
 
 class LBABatch:

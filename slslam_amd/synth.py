@@ -163,6 +163,41 @@ def _initialize_lm(obs):
     return np.concatenate([cp, v], -1)
 
 
+def _camera_planes(ob):
+    """The back-projected planes of the left and right segments of one observation, in its camera (gc_ppp_pi, gc.cpp:100-105)."""
+    p1, p2 = np.array([ob[0], ob[1], 1.0]), np.array([ob[2], ob[3], 1.0])
+    p3, p4 = np.array([ob[4] + BASELINE, ob[5], 1.0]), np.array([ob[6] + BASELINE, ob[7], 1.0])
+    c = np.array([BASELINE, 0.0, 0.0])
+    return (np.concatenate([np.cross(p1, p2), [0.0]]),
+            np.concatenate([np.cross(p3 - c, p4 - c), [-np.dot(c, np.cross(p3, p4))]]))
+
+
+def _multiview_lm(obs, Rs, ts, cp0, v0):
+    """The linear multi-view start of one line (the algorithm of tests/lba_triangulate_reference.py with
+    min_parallax = 0): the best-fitting pencil of the back-projected planes of all its observations obs[n, 8] under their cameras
+    (Rs[n], ts[n]) - the two leading eigenvectors of the Gram matrix of the unit-normal world planes -, direction signed like the
+    stereo-first line (cp0, v0), which a line with one observation or a non-finite fit keeps."""
+    G = np.zeros((4, 4))
+    for ob, R, t in zip(obs, Rs, ts):
+        for pi in _camera_planes(ob):
+            nw = R.T @ pi[:3]
+            nn = np.sqrt(np.dot(nw, nw))
+            if nn > 0.0:
+                pw = np.concatenate([nw, [np.dot(pi[:3], t) + pi[3]]]) / nn
+                G += np.outer(pw, pw)
+    lam, vec = np.linalg.eigh(G)
+    dp = np.outer(vec[:, 3], vec[:, 2]) - np.outer(vec[:, 2], vec[:, 3])     # gc_pipi_plk, gc.cpp:107-113
+    n = np.array([dp[0, 3], dp[1, 3], dp[2, 3]])
+    v = np.array([-dp[1, 2], dp[0, 2], -dp[0, 1]])
+    with np.errstate(all="ignore"):
+        cp = np.cross(v, n) / np.dot(v, v)                                    # gc_plucker_origin
+    if np.dot(v, v0) < 0:
+        v = -v
+    if len(obs) < 2 or not (np.isfinite(cp).all() and np.isfinite(v).all() and np.isfinite(lam).all()):
+        return cp0, v0
+    return cp, v
+
+
 def make_window(seed, num_lines=2000, num_kf=20, num_free=10, noise_px=0.5,
                 pose_sigma_t=0.01, pose_sigma_r_deg=0.3, all_free=False,
                 line_init="perturb", line_sigma_rel=0.01, line_sigma_dir_deg=0.5, mean_track=9.0):
@@ -178,7 +213,9 @@ def make_window(seed, num_lines=2000, num_kf=20, num_free=10, noise_px=0.5,
     "perturb" = landmarks already refined by earlier windows (truth + small error; the
     reference's windows start within a few % of their optimum cost, BASELINE.md section 1);
     "triangulate" = every landmark freshly initialised from its first stereo observation
-    (SLAM::initialize_lm) - the hard, far-from-optimum case.
+    (SLAM::initialize_lm) - the hard, far-from-optimum case;
+    "multiview" = every landmark from all its observations under the window's (perturbed) cameras: the linear start the line
+    triangulator makes (slslam_line_triangulator_run, method 1, min_parallax 0).
     """
     if (num_kf if all_free else min(num_free, num_kf)) < 2:
         raise ValueError("a window line must be seen by >= 2 free keyframes (slam.cpp:839-840): num_free >= 2; "
@@ -281,6 +318,11 @@ def make_window(seed, num_lines=2000, num_kf=20, num_free=10, noise_px=0.5,
         dv_p /= np.linalg.norm(dv_p, axis=1, keepdims=True)
         cp_p = cp_p - np.sum(cp_p * dv_p, 1, keepdims=True) * dv_p
         init_lines = av_to_orth(np.concatenate([cp_p, dv_p], 1))
+    elif line_init == "multiview":
+        starts = np.nonzero(first)[0].tolist() + [M]
+        mv = [_multiview_lm(obs[a:b], init_R[ki[a:b]], init_t[ki[a:b]], cp_w[l], dv_w[l])
+              for l, (a, b) in enumerate(zip(starts[:-1], starts[1:]))]
+        init_lines = av_to_orth(np.array([np.concatenate(m) for m in mv]))
     elif line_init != "triangulate":
         raise ValueError(line_init)
 
