@@ -734,6 +734,12 @@ class LBABatch:
         _check(lib().slslam_lba_batch_kernel_times(self._h, _dp(ms), _ip(n)), "slslam_lba_batch_kernel_times")
         return {KERNEL_FAMILIES[i]: (float(ms[i]), int(n[i])) for i in range(8)}
 
+    def _derived_stats(self, symbol):
+        """{"calls", "allocations"} of one derived result (covariance, report, segments: they share a protocol and the shape of this call)."""
+        v = [C.c_longlong(0) for _ in range(2)]
+        _check(getattr(lib(), symbol)(self._h, *[C.byref(x) for x in v]), symbol)
+        return dict(zip(["calls", "allocations"], [x.value for x in v]))
+
     def covariance(self, stream=None, with_lines=True):
         """Enqueues the posterior covariances of every window at its current device parameters (slslam_lba_batch_covariance);
         download() brings them back."""
@@ -747,9 +753,7 @@ class LBABatch:
                            c, l, getattr(self, "_cov_lines", False))
 
     def covariance_stats(self):
-        v = [C.c_longlong(0) for _ in range(2)]
-        _check(lib().slslam_lba_batch_covariance_stats(self._h, *[C.byref(x) for x in v]), "slslam_lba_batch_covariance_stats")
-        return dict(zip(["calls", "allocations"], [x.value for x in v]))
+        return self._derived_stats("slslam_lba_batch_covariance_stats")
 
     def report(self, stream=None):
         """Enqueues the report on every window at its current device parameters (slslam_lba_batch_report); download() brings it back."""
@@ -762,9 +766,7 @@ class LBABatch:
                               c, l, self.num_obs[i])
 
     def report_stats(self):
-        v = [C.c_longlong(0) for _ in range(2)]
-        _check(lib().slslam_lba_batch_report_stats(self._h, *[C.byref(x) for x in v]), "slslam_lba_batch_report_stats")
-        return dict(zip(["calls", "allocations"], [x.value for x in v]))
+        return self._derived_stats("slslam_lba_batch_report_stats")
 
     def segments(self, max_range=0.0, stream=None):
         """Enqueues the 3-D segments of the lines of every window at its current device parameters (slslam_lba_batch_segments);
@@ -778,9 +780,7 @@ class LBABatch:
                                 self.sizes[i][1], self.num_obs[i])
 
     def segments_stats(self):
-        v = [C.c_longlong(0) for _ in range(2)]
-        _check(lib().slslam_lba_batch_segments_stats(self._h, *[C.byref(x) for x in v]), "slslam_lba_batch_segments_stats")
-        return dict(zip(["calls", "allocations"], [x.value for x in v]))
+        return self._derived_stats("slslam_lba_batch_segments_stats")
 
     def linearise(self, i, num_observations):
         m = int(num_observations)

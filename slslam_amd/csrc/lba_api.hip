@@ -145,6 +145,58 @@ struct HostArr : NoCopy {
   const T& operator[](size_t i) const { return p[i]; }
 };
 
+// A derived result of a resident batch (its posterior covariances, its report, its segments): device arrays that kernels of its own
+// fill at the batch's current parameters, and their copies on the host.  ONE protocol: the first call makes the buffers and they are
+// kept; a call leaves its result ENQUEUED on the device, the next download copies it with the other results (COPYING), its arrival
+// makes it READY for the getter; a refill replaces the windows and with them the result (NONE).
+struct DerivedResult : NoCopy {
+  enum State { NONE, ENQUEUED, COPYING, READY };
+  struct Mirror {                    // bytes on the device and, where the host reads them, as many on the host
+    DevBuf<char> d; HostArr<char> h;
+    bool active = true;              // part of the last call's result: a download copies it
+    template <typename T> T* dev() const { return reinterpret_cast<T*>(d.p); }
+    template <typename T> const T* host() const { return reinterpret_cast<const T*>(h.p); }
+  };
+  struct Shape { size_t bytes; bool zeroed, mirrored; };
+  Mirror m[4];
+  State state = NONE;                // where the result of the LAST call is
+  long long calls = 0, allocations = 0;
+  bool allocated(int first = 0) const { return m[first].d.p != nullptr; }
+  // Makes m[first ...] (the host side pinned when the downloads are asynchronous copies) and zeroes on `s` what is to read as zeros where
+  // no launch writes.  A failure leaves them unallocated: the next call tries again.
+  int allocate(int first, std::initializer_list<Shape> shapes, bool pin, hipStream_t s) {
+    int rc = SLSLAM_OK, k = first;
+    long long made = 0;
+    for (const Shape& sh : shapes) {
+      Mirror& x = m[k++];
+      if ((rc = x.d.alloc(sh.bytes)) || (sh.mirrored && (rc = x.h.alloc(sh.bytes, pin)))) break;
+      made += sh.mirrored ? 2 : 1;
+    }
+    if (rc != SLSLAM_OK) {
+      for (int q = first; q < k; ++q) { m[q].d.release(); m[q].h.release(); }
+      return rc;
+    }
+    allocations += made;
+    k = first;
+    for (const Shape& sh : shapes) {
+      if (sh.zeroed) HIP_TRY(hipMemsetAsync(m[k].d.p, 0, sh.bytes, s));
+      ++k;
+    }
+    return SLSLAM_OK;
+  }
+  int launched() { HIP_TRY(hipGetLastError()); state = ENQUEUED; return SLSLAM_OK; }      // behind a call's launches
+  // what was enqueued since the last download comes back with it
+  int download(hipStream_t s) {
+    if (state != ENQUEUED) return SLSLAM_OK;
+    for (Mirror& x : m)
+      if (x.active && x.h.size() > 0) HIP_TRY(hipMemcpyAsync(x.h.data(), x.d.p, x.h.size(), hipMemcpyDeviceToHost, s));
+    state = COPYING;
+    return SLSLAM_OK;
+  }
+  void arrive() { if (state == COPYING) state = READY; }
+  void invalidate() { state = NONE; }
+};
+
 // All device arrays of a batch in ONE allocation, everything the host fills in ONE host-to-device copy: the build of
 // a single window (slslam_lba_solve, the per-keyframe call of the reference) is dominated by per-call driver overheads
 // otherwise (~35 hipMalloc + ~20 synchronous hipMemcpy).
@@ -246,6 +298,12 @@ Policy make_policy(const slslam_solver_options& o) {
 }
 
 enum { FAM_LIN = 0, FAM_SOLVE = 1, FAM_BACKSUB = 2, FAM_TRIG = 3, FAM_COST = 4, FAM_UPDATE = 5, FAM_INIT = 6, FAM_N = 8 };
+
+// The mirrors (DerivedResult::m) of a batch's derived results
+enum { COV_M_HDR, COV_M_CAMS, COV_M_LINES };                  // posterior covariances (lba_covariance.h): int [B][kCovHdr], double [B][stride], and -
+                                                              // made by the first call that asks for them, active when the last one did - the lines' blocks, double [lines][16]
+enum { REP_M_OBS, REP_M_LINES, REP_M_CAMS, REP_M_CAM_PART };  // the report (lba_report.h): double [2 obs], RepLine [lines], RepCam [cams]; double, device only
+enum { SEG_M_STATUS, SEG_M_RANGE, SEG_M_LINES };              // the 3-D segments (lba_segments.h): int [obs], double [2 obs], SegLine [lines]
 
 }  // namespace
 
@@ -349,27 +407,11 @@ struct slslam_lba_batch {
   DevBuf<double> d_part_out[2];
   int num_windows() const { return part[0] ? (int)route.size() : (int)wins.size(); }
   size_t dbg_words() const { return std::max((size_t)32 * std::max(1, nchunk), (size_t)16 * std::max<size_t>(1, wins.size())); }   // d_dbg_cycles (timing builds)
-  // posterior covariances (lba_covariance.h): buffers made by the first slslam_lba_batch_covariance call and kept
-  DevBuf<int> d_cov_hdr; DevBuf<double> d_cov_cam, d_cov_line;
-  HostArr<int> h_cov_hdr; HostArr<double> h_cov_cam, h_cov_line;
-  long long cov_cam_stride = 0;
-  // where the result of the LAST slslam_lba_batch_covariance call is: enqueued on the device, part of the download under way, on the host
-  enum CovState { COV_NONE, COV_ENQUEUED, COV_COPYING, COV_READY };
-  CovState cov_state = COV_NONE;
-  bool cov_lines = false;                                // ... and whether that call asked for the lines' blocks
-  long long cov_calls = 0, cov_allocations = 0;
-  // the report on observations, lines and cameras (lba_report.h): the covariance's protocol - buffers made by the first
-  // slslam_lba_batch_report call and kept, the result of the LAST call enqueued / being copied / on the host
-  DevBuf<double> d_rep_obs, d_rep_cam_part; DevBuf<RepLine> d_rep_line; DevBuf<RepCam> d_rep_cam;
-  HostArr<double> h_rep_obs; HostArr<RepLine> h_rep_line; HostArr<RepCam> h_rep_cam;
-  size_t rep_cap_obs = 0;                                // d_rep_obs = sq_norm [rep_cap_obs] | weight [rep_cap_obs]
-  CovState rep_state = COV_NONE;
-  long long rep_calls = 0, rep_allocations = 0;
-  // the 3-D segments of the lines (lba_segments.h): the same protocol
-  DevBuf<int> d_seg_status; DevBuf<double> d_seg_range; DevBuf<SegLine> d_seg_line;
-  HostArr<int> h_seg_status; HostArr<double> h_seg_range; HostArr<SegLine> h_seg_line;
-  CovState seg_state = COV_NONE;
-  long long seg_calls = 0, seg_allocations = 0;
+  // the derived results (DerivedResult) and their mirrors.  A new one: a member, a place in `derived`, its enqueue function and its getter
+  DerivedResult cov, rep, seg;
+  DerivedResult* const derived[3] = { &cov, &rep, &seg };      // what downloads and refills go through
+  long long cov_cam_stride = 0;                               // cov.m[COV_M_CAMS] = double [B][cov_cam_stride]
+  size_t rep_cap_obs = 0;                                     // rep.m[REP_M_OBS] = double sq_norm [rep_cap_obs] | weight [rep_cap_obs]
   // profiling
   bool profiling = false;
   double fam_ms[FAM_N] = { 0 };
@@ -1546,28 +1588,9 @@ int download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
     HIP_TRY(hipMemcpyAsync(b->h_buildwin.data(), b->d_buildwin.p, b->wins.size() * sizeof(BuildWin), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(b->h_totals.data(), b->d_totals.p, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
   }
-  if (b->cov_state == slslam_lba_batch::COV_ENQUEUED) {
-    // the covariances enqueued since the last download come back with it
-    const size_t B = b->wins.size();
-    HIP_TRY(hipMemcpyAsync(b->h_cov_hdr.data(), b->d_cov_hdr.p, B * kCovHdr * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_cov_cam.data(), b->d_cov_cam.p, B * (size_t)b->cov_cam_stride * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (b->cov_lines && b->h_cov_line.size() > 0)
-      HIP_TRY(hipMemcpyAsync(b->h_cov_line.data(), b->d_cov_line.p, b->h_cov_line.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    b->cov_state = slslam_lba_batch::COV_COPYING;
-  }
-  if (b->rep_state == slslam_lba_batch::COV_ENQUEUED) {
-    // ... and so does the report
-    HIP_TRY(hipMemcpyAsync(b->h_rep_obs.data(), b->d_rep_obs.p, b->h_rep_obs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_rep_line.data(), b->d_rep_line.p, b->h_rep_line.size() * sizeof(RepLine), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_rep_cam.data(), b->d_rep_cam.p, b->h_rep_cam.size() * sizeof(RepCam), hipMemcpyDeviceToHost, s));
-    b->rep_state = slslam_lba_batch::COV_COPYING;
-  }
-  if (b->seg_state == slslam_lba_batch::COV_ENQUEUED) {
-    // ... and the segments
-    HIP_TRY(hipMemcpyAsync(b->h_seg_status.data(), b->d_seg_status.p, b->h_seg_status.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_seg_range.data(), b->d_seg_range.p, b->h_seg_range.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_seg_line.data(), b->d_seg_line.p, b->h_seg_line.size() * sizeof(SegLine), hipMemcpyDeviceToHost, s));
-    b->seg_state = slslam_lba_batch::COV_COPYING;
+  for (DerivedResult* r : b->derived) {
+    const int rc = r->download(s);
+    if (rc != SLSLAM_OK) return rc;
   }
   if (!b->ev_results) HIP_TRY(hipEventCreateWithFlags(&b->ev_results, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_results, s));
@@ -1597,9 +1620,7 @@ int finish_download(slslam_lba_batch* b) {
   b->results_pending = false;
   if (b->profiling) b->harvest_events();
   adopt_device_build(b);
-  if (b->cov_state == slslam_lba_batch::COV_COPYING) b->cov_state = slslam_lba_batch::COV_READY;
-  if (b->rep_state == slslam_lba_batch::COV_COPYING) b->rep_state = slslam_lba_batch::COV_READY;
-  if (b->seg_state == slslam_lba_batch::COV_COPYING) b->seg_state = slslam_lba_batch::COV_READY;
+  for (DerivedResult* r : b->derived) r->arrive();
   b->downloaded = true;
   return SLSLAM_OK;
 }
@@ -1969,7 +1990,7 @@ void refill_commit(slslam_lba_batch* b, const slslam_lba_window* windows, int B,
   b->total_params = z.nparams; b->nobs = z.nobs;
   b->used_ncam = z.ncam; b->used_nline = z.nline; b->used_nobs = z.nobs; b->used_tiles = (long long)b->d_tiles.n; b->used_items = (long long)(b->d_items.n / 2);
   b->device_built = true; b->inplace_export = z.params_pinned; b->results_inplace = false;
-  b->cov_state = slslam_lba_batch::COV_NONE; b->rep_state = slslam_lba_batch::COV_NONE; b->seg_state = slslam_lba_batch::COV_NONE;
+  for (DerivedResult* r : b->derived) r->invalidate();
   b->src_windows.assign(windows, windows + B);
   b->build_status.assign((size_t)B, SLSLAM_OK);
   b->downloaded = false;
@@ -2159,8 +2180,9 @@ int slslam::lba_device_results(const slslam_lba_batch* b, const LMState** state,
 
 int slslam::lba_device_covariance(const slslam_lba_batch* b, const int** hdr, int* hdr_ints, const double** cov_cam, long long* cam_stride) {
   if (!b || !hdr || !hdr_ints || !cov_cam || !cam_stride) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (!b->finalized || b->part[0] || b->cov_state != slslam_lba_batch::COV_ENQUEUED || !b->d_cov_hdr.p) return SLSLAM_ERR_STATE;
-  *hdr = b->d_cov_hdr.p; *hdr_ints = kCovHdr; *cov_cam = b->d_cov_cam.p; *cam_stride = b->cov_cam_stride;
+  if (!b->finalized || b->part[0] || b->cov.state != DerivedResult::ENQUEUED || !b->cov.allocated()) return SLSLAM_ERR_STATE;
+  *hdr = b->cov.m[COV_M_HDR].dev<int>(); *hdr_ints = kCovHdr;
+  *cov_cam = b->cov.m[COV_M_CAMS].dev<double>(); *cam_stride = b->cov_cam_stride;
   return SLSLAM_OK;
 }
 
@@ -2237,7 +2259,7 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   b->wins.swap(wins);
   b->downloaded = false;
   b->device_built = false; b->inplace_export = false; b->results_inplace = false; b->src_windows.clear(); b->build_status.clear();
-  b->cov_state = slslam_lba_batch::COV_NONE; b->rep_state = slslam_lba_batch::COV_NONE; b->seg_state = slslam_lba_batch::COV_NONE;
+  for (DerivedResult* r : b->derived) r->invalidate();
   auto fill_one = [&](int wi) { fill_window(b, plan, b->wins, wi, img, /*copy_observations=*/false); };
   (void)run_all(pool, B, fill_one);                      // (fill_window copies into the image: it allocates nothing)
   fill_tail(b, plan, img);
@@ -2433,310 +2455,50 @@ extern "C" int slslam_lba_batch_linearise(slslam_lba_batch* b, int index, double
 }
 
 // ------------------------------------------------------------------------------------------
-// Posterior covariances of the windows at their current device parameters (lba_covariance.h)
-extern "C" int slslam_lba_batch_covariance(slslam_lba_batch* b, void* stream, int with_lines) {
+// What the derived results (DerivedResult) share beyond the object: the steps of their enqueue functions, getters and one-window calls
+namespace {
+
+// A mixed batch: both parts, one after the other on the CALLER's stream; the call is counted on the batch the caller holds
+template <typename Fn>
+int derived_on_parts(slslam_lba_batch* b, DerivedResult& r, Fn fn) {
+  ++r.calls;
+  const int rc0 = fn(b->part[0]);
+  return rc0 != SLSLAM_OK ? rc0 : fn(b->part[1]);
+}
+
+int derived_stats(const slslam_lba_batch* b, DerivedResult slslam_lba_batch::* r, long long* calls, long long* allocations) {
   if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (!b->finalized) return SLSLAM_ERR_STATE;
-  if (b->part[0] || b->big_mode) return SLSLAM_ERR_UNSUPPORTED;      // (a 240 x 240 reduced system does not fit LDS)
-  const size_t B = b->wins.size();
-  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
-  if (maxC > kMaxCams || maxn > 6 * kMaxFreeCams) return SLSLAM_ERR_UNSUPPORTED;
-  const size_t lds = lds_bytes_covariance(maxC, maxn);
-  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
-  HIP_TRY(hipSetDevice(b->device));
-  hipStream_t s = (hipStream_t)stream;
-  ++b->cov_calls;
-  int rc;
-  if (!b->d_cov_hdr.p) {
-    b->cov_cam_stride = std::max<long long>(1, (long long)maxn * maxn);
-    if ((rc = b->d_cov_hdr.alloc(std::max<size_t>(1, B) * kCovHdr)) || (rc = b->d_cov_cam.alloc(std::max<size_t>(1, B) * (size_t)b->cov_cam_stride)) ||
-        (rc = b->h_cov_hdr.alloc(std::max<size_t>(1, B) * kCovHdr, b->refillable)) ||
-        (rc = b->h_cov_cam.alloc(std::max<size_t>(1, B) * (size_t)b->cov_cam_stride, b->refillable))) {
-      b->d_cov_hdr.release();
-      return rc;
-    }
-    b->cov_allocations += 4;
-    // (the kernel's limit is a property of the process, not of this batch: always the ceiling, so that no batch lowers it for another)
-    HIP_TRY(allow_lds({ (const void*)k_lba_covariance }, 160 * 1024));
-  }
-  if (with_lines && !b->d_cov_line.p) {
-    const size_t cap_line = std::max<size_t>(1, b->d_line_flags.n);
-    if ((rc = b->d_cov_line.alloc(16 * cap_line)) || (rc = b->h_cov_line.alloc(16 * cap_line, b->refillable))) { b->d_cov_line.release(); return rc; }
-    b->cov_allocations += 2;
-  }
-  if (B > 0)
-    hipLaunchKernelGGL(k_lba_covariance, dim3((unsigned)B), dim3(kCovThreads), lds, s, b->ptrs, b->pol, (const int*)b->d_line_orig.p, b->d_cov_hdr.p,
-                       b->d_cov_cam.p, b->cov_cam_stride, with_lines ? b->d_cov_line.p : (double*)nullptr, maxC, maxn);
-  HIP_TRY(hipGetLastError());
-  b->cov_state = slslam_lba_batch::COV_ENQUEUED; b->cov_lines = with_lines != 0;
-  return SLSLAM_OK;
-}
-
-extern "C" int slslam_lba_batch_covariance_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
-  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (calls) *calls = b->cov_calls;
-  if (allocations) *allocations = b->cov_allocations;
-  return SLSLAM_OK;
-}
-
-extern "C" int slslam_lba_batch_get_covariance(const slslam_lba_batch* b, int index, int* status, int* num_free_cameras, int* free_camera,
-                                               double* cov_cameras, double* cov_lines) {
-  if (!b || index < 0 || index >= b->num_windows()) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (b->part[0] || b->cov_state != slslam_lba_batch::COV_READY) return SLSLAM_ERR_INVALID_ARGUMENT;      // the last covariance call (if any) has not been downloaded
-  if (b->device_built && b->build_status[(size_t)index] != SLSLAM_OK) return b->build_status[(size_t)index];
-  if (cov_lines && !b->cov_lines) return SLSLAM_ERR_STATE;            // (the call that was downloaded skipped the lines)
-  const WinDesc& wd = b->h_wins[(size_t)index];
-  const int* hdr = b->h_cov_hdr.data() + (size_t)index * kCovHdr;
-  const int F = std::min(std::max(hdr[1], 0), (int)kMaxFreeCams);
-  if (status) *status = hdr[0];
-  if (num_free_cameras) *num_free_cameras = F;
-  if (free_camera) {
-    for (int c = 0; c < wd.C; ++c) free_camera[c] = -1;
-    for (int f = 0; f < F && f < wd.C; ++f) free_camera[f] = hdr[2 + f];
-  }
-  if (cov_cameras && F > 0) std::memcpy(cov_cameras, b->h_cov_cam.data() + (size_t)index * (size_t)b->cov_cam_stride, (size_t)(6 * F) * (6 * F) * sizeof(double));
-  if (cov_lines && wd.L > 0) std::memcpy(cov_lines, b->h_cov_line.data() + 16 * (size_t)wd.line_off, 16 * (size_t)wd.L * sizeof(double));
-  return SLSLAM_OK;
-}
-
-// One window, no solve: the covariance at window->parameters
-extern "C" int slslam_lba_covariance(const slslam_lba_window* w, const slslam_solver_options* opt, int* status, int* num_free_cameras,
-                                     int* free_camera, double* cov_cameras, double* cov_lines) {
-  if (!w) return SLSLAM_ERR_INVALID_ARGUMENT;
-  slslam_solver_options o;
-  if (opt) o = *opt; else slslam_default_options(&o);
-  if (o.max_num_iterations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-  PackedWindow pw;   // malformed input is reported as such on any machine, before the device is looked for
-  {
-    const int prc = pack_window(w, &pw);
-    if (prc != SLSLAM_OK) return prc;
-  }
-  slslam_lba_batch* b = nullptr;
-  int rc = slslam_lba_batch_create(-1, &b);
-  if (rc) return rc;
-  o.use_graph = 0;
-  o.refill_headroom_percent = 0;
-  b->wins.push_back(std::move(pw));
-  b->arena.cached = true;
-  if ((rc = slslam_lba_batch_finalize(b, &o)) == SLSLAM_OK &&
-      (rc = slslam_lba_batch_covariance(b, nullptr, cov_lines ? 1 : 0)) == SLSLAM_OK &&
-      (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
-    rc = slslam_lba_batch_get_covariance(b, 0, status, num_free_cameras, free_camera, cov_cameras, cov_lines);
-  slslam_lba_batch_destroy(b);
-  return rc;
-}
-
-// ------------------------------------------------------------------------------------------
-// Which observations are down-weighted, which line is degenerate: the report on every window at its current device parameters (lba_report.h)
-static_assert(sizeof(RepLine) == sizeof(slslam_lba_line_report) && sizeof(RepCam) == sizeof(slslam_lba_camera_report), "the device writes the caller's structs");
-static_assert((int)kRepLineFree == SLSLAM_LBA_LINE_FREE && (int)kRepLineConstant == SLSLAM_LBA_LINE_CONSTANT && (int)kRepLineNoObs == SLSLAM_LBA_LINE_NO_OBSERVATIONS, "");
-
-extern "C" int slslam_lba_batch_report(slslam_lba_batch* b, void* stream) {
-  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (!b->finalized) return SLSLAM_ERR_STATE;
-  if (b->part[0]) {                                     // a mixed batch: both parts, one after the other on the caller's stream
-    ++b->rep_calls;
-    const int rc0 = slslam_lba_batch_report(b->part[0], stream);
-    return rc0 != SLSLAM_OK ? rc0 : slslam_lba_batch_report(b->part[1], stream);
-  }
-  const size_t B = b->wins.size();
-  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
-  const size_t lds = b->big_mode ? lds_bytes_report_lines(maxC, maxn) : lds_bytes_report_tiles(maxC, maxn);
-  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
-  HIP_TRY(hipSetDevice(b->device));
-  hipStream_t s = (hipStream_t)stream;
-  ++b->rep_calls;
-  int rc;
-  if (!b->d_rep_line.p) {
-    const size_t cap_obs = std::max<size_t>(1, b->d_ob_orig.n), cap_line = std::max<size_t>(1, b->d_line_flags.n), cap_cam = std::max<size_t>(1, b->d_cam_cf.n);
-    const size_t cap_part = b->big_mode ? 1 : (size_t)std::max(1, b->nchunk) * kRepCamAcc * (size_t)maxC;
-    if ((rc = b->d_rep_obs.alloc(2 * cap_obs)) || (rc = b->d_rep_line.alloc(cap_line)) || (rc = b->d_rep_cam.alloc(cap_cam)) ||
-        (rc = b->d_rep_cam_part.alloc(cap_part)) || (rc = b->h_rep_obs.alloc(2 * cap_obs, b->refillable)) ||
-        (rc = b->h_rep_line.alloc(cap_line, b->refillable)) || (rc = b->h_rep_cam.alloc(cap_cam, b->refillable))) {
-      b->d_rep_line.release();
-      return rc;
-    }
-    b->rep_cap_obs = cap_obs;
-    b->rep_allocations += 7;
-    // (a window the launches skip - none today - reads as zeros: status FREE without observations never comes from the kernels)
-    HIP_TRY(hipMemsetAsync(b->d_rep_obs.p, 0, 2 * cap_obs * sizeof(double), s));
-    HIP_TRY(hipMemsetAsync(b->d_rep_line.p, 0, cap_line * sizeof(RepLine), s));
-    HIP_TRY(hipMemsetAsync(b->d_rep_cam.p, 0, cap_cam * sizeof(RepCam), s));
-    HIP_TRY(hipMemsetAsync(b->d_rep_cam_part.p, 0, cap_part * sizeof(double), s));
-    if (lds > 48 * 1024) HIP_TRY(allow_lds({ (const void*)k_lba_report_tiles, (const void*)k_lba_report_lines }, 160 * 1024));
-  }
-  ReportPtrs rp;
-  rp.ob_orig = b->d_ob_orig.p; rp.line_orig = b->d_line_orig.p;
-  rp.sq_norm = b->d_rep_obs.p; rp.weight = b->d_rep_obs.p + b->rep_cap_obs;
-  rp.lines = b->d_rep_line.p; rp.cams = b->d_rep_cam.p;
-  rp.cam_part = b->d_rep_cam_part.p; rp.cam_stride = (long long)kRepCamAcc * maxC;
-  if (B > 0) {
-    if (b->big_mode) {
-      hipLaunchKernelGGL(k_lba_report_lines, dim3((unsigned)B), dim3(kRepLinesThreads), lds, s, b->ptrs, b->pol, rp, maxC, maxn);
-    } else {
-      if (b->nchunk > 0) hipLaunchKernelGGL(k_lba_report_tiles, dim3((unsigned)b->nchunk), dim3(64), lds, s, b->ptrs, b->pol, rp, maxC, maxn);
-      hipLaunchKernelGGL(k_lba_report_cameras, dim3((unsigned)B), dim3(64), 0, s, b->ptrs, rp);
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  b->rep_state = slslam_lba_batch::COV_ENQUEUED;
-  return SLSLAM_OK;
-}
-
-extern "C" int slslam_lba_batch_report_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
-  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
-  long long a = b->rep_allocations;
-  for (int h = 0; h < 2; ++h) if (b->part[h]) a += b->part[h]->rep_allocations;
-  if (calls) *calls = b->rep_calls;
+  long long a = (b->*r).allocations;
+  for (int h = 0; h < 2; ++h) if (b->part[h]) a += (b->part[h]->*r).allocations;
+  if (calls) *calls = (b->*r).calls;
   if (allocations) *allocations = a;
   return SLSLAM_OK;
 }
 
-extern "C" int slslam_lba_batch_get_report(const slslam_lba_batch* b, int index, double* sq_norm, double* weight,
-                                           slslam_lba_line_report* lines, slslam_lba_camera_report* cameras) {
-  if (!b || index < 0 || index >= b->num_windows()) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (b->part[0]) return slslam_lba_batch_get_report(b->part[b->route[(size_t)index].first], b->route[(size_t)index].second, sq_norm, weight, lines, cameras);
-  if (b->rep_state != slslam_lba_batch::COV_READY) return SLSLAM_ERR_INVALID_ARGUMENT;      // the last report call (if any) has not been downloaded
-  if (b->device_built && b->build_status[(size_t)index] != SLSLAM_OK) return b->build_status[(size_t)index];
-  const WinDesc& wd = b->h_wins[(size_t)index];
-  if (sq_norm && wd.M > 0) std::memcpy(sq_norm, b->h_rep_obs.data() + (size_t)wd.obs_off, (size_t)wd.M * sizeof(double));
-  if (weight && wd.M > 0) std::memcpy(weight, b->h_rep_obs.data() + b->rep_cap_obs + (size_t)wd.obs_off, (size_t)wd.M * sizeof(double));
-  if (lines && wd.L > 0) std::memcpy(lines, b->h_rep_line.data() + (size_t)wd.line_off, (size_t)wd.L * sizeof(RepLine));
-  if (cameras && wd.C > 0) std::memcpy(cameras, b->h_rep_cam.data() + (size_t)wd.cam_off, (size_t)wd.C * sizeof(RepCam));
+// What every getter begins with.  Window *index of the caller's batch becomes window *index of the batch *b that holds its result: of a
+// mixed batch a part (route_mixed), or INVALID_ARGUMENT where the result is not made for one.  INVALID_ARGUMENT too when the last call
+// (if any) has not been downloaded; a window the device build flagged is reported with its status.
+int derived_window(const slslam_lba_batch** b, int* index, DerivedResult slslam_lba_batch::* r, bool route_mixed) {
+  const slslam_lba_batch* p = *b;
+  if (!p || *index < 0 || *index >= p->num_windows()) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (p->part[0]) {
+    if (!route_mixed) return SLSLAM_ERR_INVALID_ARGUMENT;
+    const std::pair<int, int> to = p->route[(size_t)*index];
+    p = p->part[to.first]; *index = to.second;
+  }
+  if ((p->*r).state != DerivedResult::READY) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (p->device_built && p->build_status[(size_t)*index] != SLSLAM_OK) return p->build_status[(size_t)*index];
+  *b = p;
   return SLSLAM_OK;
 }
 
-// One window, no solve: the report at window->parameters
-extern "C" int slslam_lba_report(const slslam_lba_window* w, const slslam_solver_options* opt, double* sq_norm, double* weight,
-                                 slslam_lba_line_report* lines, slslam_lba_camera_report* cameras) {
-  if (!w) return SLSLAM_ERR_INVALID_ARGUMENT;
-  slslam_solver_options o;
-  if (opt) o = *opt; else slslam_default_options(&o);
-  if (o.max_num_iterations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-  PackedWindow pw;   // malformed input is reported as such on any machine, before the device is looked for
-  {
-    const int prc = pack_window(w, &pw);
-    if (prc != SLSLAM_OK) return prc;
-  }
-  slslam_lba_batch* b = nullptr;
-  int rc = slslam_lba_batch_create(-1, &b);
-  if (rc) return rc;
-  o.use_graph = 0;
-  o.refill_headroom_percent = 0;
-  b->wins.push_back(std::move(pw));
-  b->arena.cached = true;
-  if ((rc = slslam_lba_batch_finalize(b, &o)) == SLSLAM_OK &&
-      (rc = slslam_lba_batch_report(b, nullptr)) == SLSLAM_OK &&
-      (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
-    rc = slslam_lba_batch_get_report(b, 0, sq_norm, weight, lines, cameras);
-  slslam_lba_batch_destroy(b);
-  return rc;
-}
-
-// ------------------------------------------------------------------------------------------
-// The 3-D segments of the lines of every window at its current device parameters (lba_segments.h)
-static_assert(sizeof(SegLine) == sizeof(slslam_lba_line_segment), "the device writes the caller's struct");
-static_assert((int)kSegOk == SLSLAM_SEGMENT_OK && (int)kSegNoObs == SLSLAM_SEGMENT_NO_OBSERVATIONS && (int)kSegNone == SLSLAM_SEGMENT_NONE, "");
-static_assert((int)kSegObsUsed == SLSLAM_SEGMENT_OBS_USED && (int)kSegObsUsedClamped == SLSLAM_SEGMENT_OBS_USED_CLAMPED &&
-              (int)kSegObsDegenerate == SLSLAM_SEGMENT_OBS_DEGENERATE && (int)kSegObsBehind == SLSLAM_SEGMENT_OBS_BEHIND &&
-              (int)kSegObsOutOfRange == SLSLAM_SEGMENT_OBS_OUT_OF_RANGE && (int)kSegObsCollapsed == SLSLAM_SEGMENT_OBS_COLLAPSED, "");
-
-extern "C" int slslam_lba_batch_segments(slslam_lba_batch* b, void* stream, double max_range) {
-  if (!b || !std::isfinite(max_range)) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (!b->finalized) return SLSLAM_ERR_STATE;
-  if (b->part[0]) {                                     // a mixed batch: both parts, one after the other on the caller's stream
-    ++b->seg_calls;
-    const int rc0 = slslam_lba_batch_segments(b->part[0], stream, max_range);
-    return rc0 != SLSLAM_OK ? rc0 : slslam_lba_batch_segments(b->part[1], stream, max_range);
-  }
-  const size_t B = b->wins.size();
-  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
-  const size_t lds = lds_bytes_segments(maxC, maxn);
-  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
-  HIP_TRY(hipSetDevice(b->device));
-  hipStream_t s = (hipStream_t)stream;
-  ++b->seg_calls;
-  int rc;
-  if (!b->d_seg_line.p) {
-    const size_t cap_obs = std::max<size_t>(1, b->d_ob_orig.n), cap_line = std::max<size_t>(1, b->d_line_flags.n);
-    if ((rc = b->d_seg_status.alloc(cap_obs)) || (rc = b->d_seg_range.alloc(2 * cap_obs)) || (rc = b->d_seg_line.alloc(cap_line)) ||
-        (rc = b->h_seg_status.alloc(cap_obs, b->refillable)) || (rc = b->h_seg_range.alloc(2 * cap_obs, b->refillable)) ||
-        (rc = b->h_seg_line.alloc(cap_line, b->refillable))) {
-      b->d_seg_line.release();
-      return rc;
-    }
-    b->seg_allocations += 6;
-    // (a window the launch skips - none today - reads as zeros)
-    HIP_TRY(hipMemsetAsync(b->d_seg_status.p, 0, cap_obs * sizeof(int), s));
-    HIP_TRY(hipMemsetAsync(b->d_seg_range.p, 0, 2 * cap_obs * sizeof(double), s));
-    HIP_TRY(hipMemsetAsync(b->d_seg_line.p, 0, cap_line * sizeof(SegLine), s));
-    if (lds > 48 * 1024) HIP_TRY(allow_lds({ (const void*)k_lba_segments_tiles, (const void*)k_lba_segments_lines }, 160 * 1024));
-  }
-  SegmentPtrs sp;
-  sp.ob_orig = b->d_ob_orig.p; sp.line_orig = b->d_line_orig.p;
-  sp.obs_status = b->d_seg_status.p; sp.obs_range = b->d_seg_range.p; sp.lines = b->d_seg_line.p;
-  sp.max_range = max_range;
-  if (B > 0) {
-    if (b->big_mode) hipLaunchKernelGGL(k_lba_segments_lines, dim3((unsigned)B), dim3(kSegLinesThreads), lds, s, b->ptrs, sp, maxC, maxn);
-    else if (b->nchunk > 0) hipLaunchKernelGGL(k_lba_segments_tiles, dim3((unsigned)b->nchunk), dim3(64), lds, s, b->ptrs, sp, maxC, maxn);
-  }
-  HIP_TRY(hipGetLastError());
-  b->seg_state = slslam_lba_batch::COV_ENQUEUED;
-  return SLSLAM_OK;
-}
-
-extern "C" int slslam_lba_batch_segments_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
-  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
-  long long a = b->seg_allocations;
-  for (int h = 0; h < 2; ++h) if (b->part[h]) a += b->part[h]->seg_allocations;
-  if (calls) *calls = b->seg_calls;
-  if (allocations) *allocations = a;
-  return SLSLAM_OK;
-}
-
-extern "C" int slslam_lba_batch_get_segments(const slslam_lba_batch* b, int index, int* obs_status, double* obs_range, slslam_lba_line_segment* lines) {
-  if (!b || index < 0 || index >= b->num_windows()) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (b->part[0]) return slslam_lba_batch_get_segments(b->part[b->route[(size_t)index].first], b->route[(size_t)index].second, obs_status, obs_range, lines);
-  if (b->seg_state != slslam_lba_batch::COV_READY) return SLSLAM_ERR_INVALID_ARGUMENT;      // the last segments call (if any) has not been downloaded
-  if (b->device_built && b->build_status[(size_t)index] != SLSLAM_OK) return b->build_status[(size_t)index];
-  const WinDesc& wd = b->h_wins[(size_t)index];
-  if (obs_status && wd.M > 0) std::memcpy(obs_status, b->h_seg_status.data() + (size_t)wd.obs_off, (size_t)wd.M * sizeof(int));
-  if (obs_range && wd.M > 0) std::memcpy(obs_range, b->h_seg_range.data() + 2 * (size_t)wd.obs_off, 2 * (size_t)wd.M * sizeof(double));
-  if (lines && wd.L > 0) std::memcpy(lines, b->h_seg_line.data() + (size_t)wd.line_off, (size_t)wd.L * sizeof(SegLine));
-  return SLSLAM_OK;
-}
-
-// One window, no solve: the segments at window->parameters
-extern "C" int slslam_lba_segments(const slslam_lba_window* w, const slslam_solver_options* opt, double max_range, int* obs_status,
-                                   double* obs_range, slslam_lba_line_segment* lines) {
-  if (!w || !std::isfinite(max_range)) return SLSLAM_ERR_INVALID_ARGUMENT;
-  slslam_solver_options o;
-  if (opt) o = *opt; else slslam_default_options(&o);
-  if (o.max_num_iterations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-  PackedWindow pw;   // malformed input is reported as such on any machine, before the device is looked for
-  {
-    const int prc = pack_window(w, &pw);
-    if (prc != SLSLAM_OK) return prc;
-  }
-  slslam_lba_batch* b = nullptr;
-  int rc = slslam_lba_batch_create(-1, &b);
-  if (rc) return rc;
-  o.use_graph = 0;
-  o.refill_headroom_percent = 0;
-  b->wins.push_back(std::move(pw));
-  b->arena.cached = true;
-  if ((rc = slslam_lba_batch_finalize(b, &o)) == SLSLAM_OK &&
-      (rc = slslam_lba_batch_segments(b, nullptr, max_range)) == SLSLAM_OK &&
-      (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
-    rc = slslam_lba_batch_get_segments(b, 0, obs_status, obs_range, lines);
-  slslam_lba_batch_destroy(b);
-  return rc;
-}
-
-// ------------------------------------------------------------------------------------------
-// LBAProblem::build + set_options + ceres::Solve for one window (reference src/slam.cpp:924-944)
-extern "C" int slslam_lba_solve(const slslam_lba_window* w, const slslam_solver_options* opt,
-                                slslam_summary* summary, slslam_iteration* trace, int trace_cap, int* trace_len) {
+// The one-window calls (the per-keyframe calls of the reference): the window as a finalized batch of its own, `enqueue`d, downloaded,
+// read by `get`, destroyed.
+// keep_headroom: only slslam_lba_solve hands options.refill_headroom_percent on to finalize.  A nonzero value makes a refillable batch
+// (room in every array, a pinned host image, the build stage), wasted on a batch that goes after one call: the derived results clear
+// it.  The solve keeps it: the option sets the strides its kernels walk, and what a caller gets under it is not for a helper to change.
+template <typename Enqueue, typename Get>
+int one_window(const slslam_lba_window* w, const slslam_solver_options* opt, bool keep_headroom, Enqueue enqueue, Get get) {
   if (!w) return SLSLAM_ERR_INVALID_ARGUMENT;
   slslam_solver_options o;
   if (opt) o = *opt; else slslam_default_options(&o);
@@ -2750,17 +2512,224 @@ extern "C" int slslam_lba_solve(const slslam_lba_window* w, const slslam_solver_
   int rc = slslam_lba_batch_create(-1, &b);
   if (rc) return rc;
   o.use_graph = 0;   // a single solve is replayed once: capture would only add latency
+  if (!keep_headroom) o.refill_headroom_percent = 0;
   b->wins.push_back(std::move(pw));
   b->arena.cached = true;
-  if ((rc = slslam_lba_batch_finalize(b, &o)) == SLSLAM_OK &&
-      (rc = slslam_lba_batch_solve(b, nullptr)) == SLSLAM_OK &&
-      (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK) {
-    rc = slslam_lba_batch_get_parameters(b, 0, w->parameters);
-    if (summary && rc == SLSLAM_OK) rc = slslam_lba_batch_get_summary(b, 0, summary);
-    if (rc == SLSLAM_OK) rc = slslam_lba_batch_get_trace(b, 0, trace, trace_cap, trace_len);
-  }
+  if ((rc = slslam_lba_batch_finalize(b, &o)) == SLSLAM_OK && (rc = enqueue(b)) == SLSLAM_OK && (rc = slslam_lba_batch_download(b, nullptr)) == SLSLAM_OK)
+    rc = get(b);
   slslam_lba_batch_destroy(b);
   return rc;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
+// Posterior covariances of the windows at their current device parameters (lba_covariance.h)
+extern "C" int slslam_lba_batch_covariance(slslam_lba_batch* b, void* stream, int with_lines) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized) return SLSLAM_ERR_STATE;
+  if (b->part[0] || b->big_mode) return SLSLAM_ERR_UNSUPPORTED;      // (a 240 x 240 reduced system does not fit LDS)
+  const size_t B = b->wins.size();
+  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
+  if (maxC > kMaxCams || maxn > 6 * kMaxFreeCams) return SLSLAM_ERR_UNSUPPORTED;
+  const size_t lds = lds_bytes_covariance(maxC, maxn);
+  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  DerivedResult& r = b->cov;
+  ++r.calls;
+  int rc;
+  if (!r.allocated()) {
+    const size_t stride = (size_t)std::max<long long>(1, (long long)maxn * maxn), nwin = std::max<size_t>(1, B);
+    if ((rc = r.allocate(COV_M_HDR, { { nwin * kCovHdr * sizeof(int), false, true }, { nwin * stride * sizeof(double), false, true } },
+                         b->refillable, s)) != SLSLAM_OK)
+      return rc;
+    b->cov_cam_stride = (long long)stride;
+    // (a kernel's limit is a property of the process, not of this batch: always the ceiling, so that no batch lowers it for another)
+    HIP_TRY(allow_lds({ (const void*)k_lba_covariance }, 160 * 1024));
+  }
+  if (with_lines && !r.allocated(COV_M_LINES) &&
+      (rc = r.allocate(COV_M_LINES, { { 16 * std::max<size_t>(1, b->d_line_flags.n) * sizeof(double), false, true } }, b->refillable, s)) != SLSLAM_OK)
+    return rc;
+  if (B > 0)
+    hipLaunchKernelGGL(k_lba_covariance, dim3((unsigned)B), dim3(kCovThreads), lds, s, b->ptrs, b->pol, (const int*)b->d_line_orig.p,
+                       r.m[COV_M_HDR].dev<int>(), r.m[COV_M_CAMS].dev<double>(), b->cov_cam_stride,
+                       with_lines ? r.m[COV_M_LINES].dev<double>() : (double*)nullptr, maxC, maxn);
+  if ((rc = r.launched()) == SLSLAM_OK) r.m[COV_M_LINES].active = with_lines != 0;
+  return rc;
+}
+
+extern "C" int slslam_lba_batch_covariance_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
+  return derived_stats(b, &slslam_lba_batch::cov, calls, allocations);
+}
+
+extern "C" int slslam_lba_batch_get_covariance(const slslam_lba_batch* b, int index, int* status, int* num_free_cameras, int* free_camera,
+                                               double* cov_cameras, double* cov_lines) {
+  const int rc = derived_window(&b, &index, &slslam_lba_batch::cov, /*route_mixed=*/false);
+  if (rc != SLSLAM_OK) return rc;
+  const DerivedResult& r = b->cov;
+  if (cov_lines && !r.m[COV_M_LINES].active) return SLSLAM_ERR_STATE;            // (the call that was downloaded skipped the lines)
+  const WinDesc& wd = b->h_wins[(size_t)index];
+  const int* hdr = r.m[COV_M_HDR].host<int>() + (size_t)index * kCovHdr;
+  const int F = std::min(std::max(hdr[1], 0), (int)kMaxFreeCams);
+  if (status) *status = hdr[0];
+  if (num_free_cameras) *num_free_cameras = F;
+  if (free_camera) {
+    for (int c = 0; c < wd.C; ++c) free_camera[c] = -1;
+    for (int f = 0; f < F && f < wd.C; ++f) free_camera[f] = hdr[2 + f];
+  }
+  if (cov_cameras && F > 0)
+    std::memcpy(cov_cameras, r.m[COV_M_CAMS].host<double>() + (size_t)index * (size_t)b->cov_cam_stride, (size_t)(6 * F) * (6 * F) * sizeof(double));
+  if (cov_lines && wd.L > 0) std::memcpy(cov_lines, r.m[COV_M_LINES].host<double>() + 16 * (size_t)wd.line_off, 16 * (size_t)wd.L * sizeof(double));
+  return SLSLAM_OK;
+}
+
+// One window, no solve: the covariance at window->parameters
+extern "C" int slslam_lba_covariance(const slslam_lba_window* w, const slslam_solver_options* opt, int* status, int* num_free_cameras,
+                                     int* free_camera, double* cov_cameras, double* cov_lines) {
+  return one_window(w, opt, /*keep_headroom=*/false, [&](slslam_lba_batch* b) { return slslam_lba_batch_covariance(b, nullptr, cov_lines ? 1 : 0); },
+                    [&](slslam_lba_batch* b) { return slslam_lba_batch_get_covariance(b, 0, status, num_free_cameras, free_camera, cov_cameras, cov_lines); });
+}
+
+// ------------------------------------------------------------------------------------------
+// Which observations are down-weighted, which line is degenerate: the report on every window at its current device parameters (lba_report.h)
+static_assert(sizeof(RepLine) == sizeof(slslam_lba_line_report) && sizeof(RepCam) == sizeof(slslam_lba_camera_report), "the device writes the caller's structs");
+static_assert((int)kRepLineFree == SLSLAM_LBA_LINE_FREE && (int)kRepLineConstant == SLSLAM_LBA_LINE_CONSTANT && (int)kRepLineNoObs == SLSLAM_LBA_LINE_NO_OBSERVATIONS, "");
+
+extern "C" int slslam_lba_batch_report(slslam_lba_batch* b, void* stream) {
+  if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized) return SLSLAM_ERR_STATE;
+  DerivedResult& r = b->rep;
+  if (b->part[0]) return derived_on_parts(b, r, [&](slslam_lba_batch* pb) { return slslam_lba_batch_report(pb, stream); });
+  const size_t B = b->wins.size();
+  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
+  const size_t lds = b->big_mode ? lds_bytes_report_lines(maxC, maxn) : lds_bytes_report_tiles(maxC, maxn);
+  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  ++r.calls;
+  if (!r.allocated()) {
+    const size_t cap_obs = std::max<size_t>(1, b->d_ob_orig.n), cap_line = std::max<size_t>(1, b->d_line_flags.n), cap_cam = std::max<size_t>(1, b->d_cam_cf.n);
+    const size_t cap_part = b->big_mode ? 1 : (size_t)std::max(1, b->nchunk) * kRepCamAcc * (size_t)maxC;
+    // (zeroed: a window the launches skip - none today - reads as zeros: status FREE without observations never comes from the kernels)
+    const int rc = r.allocate(REP_M_OBS, { { 2 * cap_obs * sizeof(double), true, true }, { cap_line * sizeof(RepLine), true, true },
+                                           { cap_cam * sizeof(RepCam), true, true }, { cap_part * sizeof(double), true, false } }, b->refillable, s);
+    if (rc != SLSLAM_OK) return rc;
+    b->rep_cap_obs = cap_obs;
+    HIP_TRY(allow_lds({ (const void*)k_lba_report_tiles, (const void*)k_lba_report_lines }, 160 * 1024));
+  }
+  ReportPtrs rp;
+  rp.ob_orig = b->d_ob_orig.p; rp.line_orig = b->d_line_orig.p;
+  rp.sq_norm = r.m[REP_M_OBS].dev<double>(); rp.weight = rp.sq_norm + b->rep_cap_obs;
+  rp.lines = r.m[REP_M_LINES].dev<RepLine>(); rp.cams = r.m[REP_M_CAMS].dev<RepCam>();
+  rp.cam_part = r.m[REP_M_CAM_PART].dev<double>(); rp.cam_stride = (long long)kRepCamAcc * maxC;
+  if (B > 0) {
+    if (b->big_mode) {
+      hipLaunchKernelGGL(k_lba_report_lines, dim3((unsigned)B), dim3(kRepLinesThreads), lds, s, b->ptrs, b->pol, rp, maxC, maxn);
+    } else {
+      if (b->nchunk > 0) hipLaunchKernelGGL(k_lba_report_tiles, dim3((unsigned)b->nchunk), dim3(64), lds, s, b->ptrs, b->pol, rp, maxC, maxn);
+      hipLaunchKernelGGL(k_lba_report_cameras, dim3((unsigned)B), dim3(64), 0, s, b->ptrs, rp);
+    }
+  }
+  return r.launched();
+}
+
+extern "C" int slslam_lba_batch_report_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
+  return derived_stats(b, &slslam_lba_batch::rep, calls, allocations);
+}
+
+extern "C" int slslam_lba_batch_get_report(const slslam_lba_batch* b, int index, double* sq_norm, double* weight,
+                                           slslam_lba_line_report* lines, slslam_lba_camera_report* cameras) {
+  const int rc = derived_window(&b, &index, &slslam_lba_batch::rep, /*route_mixed=*/true);
+  if (rc != SLSLAM_OK) return rc;
+  const DerivedResult& r = b->rep;
+  const WinDesc& wd = b->h_wins[(size_t)index];
+  if (sq_norm && wd.M > 0) std::memcpy(sq_norm, r.m[REP_M_OBS].host<double>() + (size_t)wd.obs_off, (size_t)wd.M * sizeof(double));
+  if (weight && wd.M > 0) std::memcpy(weight, r.m[REP_M_OBS].host<double>() + b->rep_cap_obs + (size_t)wd.obs_off, (size_t)wd.M * sizeof(double));
+  if (lines && wd.L > 0) std::memcpy(lines, r.m[REP_M_LINES].host<RepLine>() + (size_t)wd.line_off, (size_t)wd.L * sizeof(RepLine));
+  if (cameras && wd.C > 0) std::memcpy(cameras, r.m[REP_M_CAMS].host<RepCam>() + (size_t)wd.cam_off, (size_t)wd.C * sizeof(RepCam));
+  return SLSLAM_OK;
+}
+
+// One window, no solve: the report at window->parameters
+extern "C" int slslam_lba_report(const slslam_lba_window* w, const slslam_solver_options* opt, double* sq_norm, double* weight,
+                                 slslam_lba_line_report* lines, slslam_lba_camera_report* cameras) {
+  return one_window(w, opt, /*keep_headroom=*/false, [](slslam_lba_batch* b) { return slslam_lba_batch_report(b, nullptr); },
+                    [&](slslam_lba_batch* b) { return slslam_lba_batch_get_report(b, 0, sq_norm, weight, lines, cameras); });
+}
+
+// ------------------------------------------------------------------------------------------
+// The 3-D segments of the lines of every window at its current device parameters (lba_segments.h)
+static_assert(sizeof(SegLine) == sizeof(slslam_lba_line_segment), "the device writes the caller's struct");
+static_assert((int)kSegOk == SLSLAM_SEGMENT_OK && (int)kSegNoObs == SLSLAM_SEGMENT_NO_OBSERVATIONS && (int)kSegNone == SLSLAM_SEGMENT_NONE, "");
+static_assert((int)kSegObsUsed == SLSLAM_SEGMENT_OBS_USED && (int)kSegObsUsedClamped == SLSLAM_SEGMENT_OBS_USED_CLAMPED &&
+              (int)kSegObsDegenerate == SLSLAM_SEGMENT_OBS_DEGENERATE && (int)kSegObsBehind == SLSLAM_SEGMENT_OBS_BEHIND &&
+              (int)kSegObsOutOfRange == SLSLAM_SEGMENT_OBS_OUT_OF_RANGE && (int)kSegObsCollapsed == SLSLAM_SEGMENT_OBS_COLLAPSED, "");
+
+extern "C" int slslam_lba_batch_segments(slslam_lba_batch* b, void* stream, double max_range) {
+  if (!b || !std::isfinite(max_range)) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (!b->finalized) return SLSLAM_ERR_STATE;
+  DerivedResult& r = b->seg;
+  if (b->part[0]) return derived_on_parts(b, r, [&](slslam_lba_batch* pb) { return slslam_lba_batch_segments(pb, stream, max_range); });
+  const size_t B = b->wins.size();
+  const int maxC = std::max(1, b->cap_maxC), maxn = b->cap_maxn;
+  const size_t lds = lds_bytes_segments(maxC, maxn);
+  if (lds > 160 * 1024) return SLSLAM_ERR_UNSUPPORTED;
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  ++r.calls;
+  if (!r.allocated()) {
+    const size_t cap_obs = std::max<size_t>(1, b->d_ob_orig.n), cap_line = std::max<size_t>(1, b->d_line_flags.n);
+    // (zeroed: a window the launch skips - none today - reads as zeros)
+    const int rc = r.allocate(SEG_M_STATUS, { { cap_obs * sizeof(int), true, true }, { 2 * cap_obs * sizeof(double), true, true },
+                                              { cap_line * sizeof(SegLine), true, true } }, b->refillable, s);
+    if (rc != SLSLAM_OK) return rc;
+    HIP_TRY(allow_lds({ (const void*)k_lba_segments_tiles, (const void*)k_lba_segments_lines }, 160 * 1024));
+  }
+  SegmentPtrs sp;
+  sp.ob_orig = b->d_ob_orig.p; sp.line_orig = b->d_line_orig.p;
+  sp.obs_status = r.m[SEG_M_STATUS].dev<int>(); sp.obs_range = r.m[SEG_M_RANGE].dev<double>(); sp.lines = r.m[SEG_M_LINES].dev<SegLine>();
+  sp.max_range = max_range;
+  if (B > 0) {
+    if (b->big_mode) hipLaunchKernelGGL(k_lba_segments_lines, dim3((unsigned)B), dim3(kSegLinesThreads), lds, s, b->ptrs, sp, maxC, maxn);
+    else if (b->nchunk > 0) hipLaunchKernelGGL(k_lba_segments_tiles, dim3((unsigned)b->nchunk), dim3(64), lds, s, b->ptrs, sp, maxC, maxn);
+  }
+  return r.launched();
+}
+
+extern "C" int slslam_lba_batch_segments_stats(const slslam_lba_batch* b, long long* calls, long long* allocations) {
+  return derived_stats(b, &slslam_lba_batch::seg, calls, allocations);
+}
+
+extern "C" int slslam_lba_batch_get_segments(const slslam_lba_batch* b, int index, int* obs_status, double* obs_range, slslam_lba_line_segment* lines) {
+  const int rc = derived_window(&b, &index, &slslam_lba_batch::seg, /*route_mixed=*/true);
+  if (rc != SLSLAM_OK) return rc;
+  const DerivedResult& r = b->seg;
+  const WinDesc& wd = b->h_wins[(size_t)index];
+  if (obs_status && wd.M > 0) std::memcpy(obs_status, r.m[SEG_M_STATUS].host<int>() + (size_t)wd.obs_off, (size_t)wd.M * sizeof(int));
+  if (obs_range && wd.M > 0) std::memcpy(obs_range, r.m[SEG_M_RANGE].host<double>() + 2 * (size_t)wd.obs_off, 2 * (size_t)wd.M * sizeof(double));
+  if (lines && wd.L > 0) std::memcpy(lines, r.m[SEG_M_LINES].host<SegLine>() + (size_t)wd.line_off, (size_t)wd.L * sizeof(SegLine));
+  return SLSLAM_OK;
+}
+
+// One window, no solve: the segments at window->parameters
+extern "C" int slslam_lba_segments(const slslam_lba_window* w, const slslam_solver_options* opt, double max_range, int* obs_status,
+                                   double* obs_range, slslam_lba_line_segment* lines) {
+  if (!std::isfinite(max_range)) return SLSLAM_ERR_INVALID_ARGUMENT;
+  return one_window(w, opt, /*keep_headroom=*/false, [&](slslam_lba_batch* b) { return slslam_lba_batch_segments(b, nullptr, max_range); },
+                    [&](slslam_lba_batch* b) { return slslam_lba_batch_get_segments(b, 0, obs_status, obs_range, lines); });
+}
+
+// ------------------------------------------------------------------------------------------
+// LBAProblem::build + set_options + ceres::Solve for one window (reference src/slam.cpp:924-944)
+extern "C" int slslam_lba_solve(const slslam_lba_window* w, const slslam_solver_options* opt,
+                                slslam_summary* summary, slslam_iteration* trace, int trace_cap, int* trace_len) {
+  return one_window(w, opt, /*keep_headroom=*/true, [](slslam_lba_batch* b) { return slslam_lba_batch_solve(b, nullptr); }, [&](slslam_lba_batch* b) {
+    int rc = slslam_lba_batch_get_parameters(b, 0, w->parameters);
+    if (summary && rc == SLSLAM_OK) rc = slslam_lba_batch_get_summary(b, 0, summary);
+    if (rc == SLSLAM_OK) rc = slslam_lba_batch_get_trace(b, 0, trace, trace_cap, trace_len);
+    return rc;
+  });
 }
 
 // ------------------------------------------------------------------------------------------
