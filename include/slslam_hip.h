@@ -1001,6 +1001,97 @@ int  slslam_debug_triangulate_host(int num_observations, const double* observati
                                    double inverse_depth, double min_parallax, double* line_av, double* eigenvalues, int* status,
                                    int* num_planes, int* clamped, double* offdiagonal);
 
+/* ------------------------------------------------------------------ place recognition: which old keyframe does this frame look like
+ * The first link of the loop-closure chain (csrc/place_recognition.h, host/place_filter.h), after the reference's
+ * src/voctree_bf.h: a K-ary vocabulary tree of L levels over descriptors of D floats, tf-idf scores against the documents of the visible
+ * keyframes, and a Bayes filter over "which keyframe am I at, or none".  A reported document feeds slslam_line_matcher_run.
+ *   tree      (K^L - 1) / (K - 1) interior nodes of K x D floats, breadth-first, child j of node i at i K + j + 1, raw floats without a
+ *             header: what voctree_t::load reads.  K^L leaves; leaf index = node index - interior nodes.
+ *   word      of a descriptor f (find_leaf): from the root, L times, go to the child c of the smallest distance
+ *             r = 1.0f; for i in 0 .. D-1: r -= c[i] * f[i]  - float, in this order, product and difference rounded separately -, the
+ *             first minimum under a strict < : ties go to the lowest child.  The word of every finite descriptor is the reference's.
+ *   document  of a frame of n descriptors: its distinct words, ascending, each with tf = (float)count / (float)n.
+ *   database  documents in insertion order.  A document becomes visible once more than `recent` documents have been inserted after it
+ *             (the reference's doc_buffer: the front is released while more than `recent` documents are pending behind it): after
+ *             recent + 1 inserts none is visible, after recent + 2 the first.  Visible documents are numbered 0, 1, ... in insertion
+ *             order.  df[word] = visible documents that contain the word.
+ *   virtual   document (the reference's document -1, "no place"): exists exactly when more than num_avg_words words have df > 0; it is
+ *             the num_avg_words words of the largest df, the lower word on ties, each with tf = 1.0f / num_avg_words; while it exists
+ *             it counts as one document in doc_size and in the df of its words.  doc_size = visible documents + (virtual ? 1 : 0).
+ *   states    of a query: -1 (index 0 of every per-state array; scored only while the virtual document exists), then the visible
+ *             documents d at index d + 1.
+ *   score     of a scored state = the float sum, over the words common to the query and the state's document in ascending word
+ *             order, of l = -((|n - m| - n) - m) with n = tf_query * idf, m = tf_document * idf, idf = (float)log10((double)doc_size /
+ *             (double)df[word]) (libm on the host, uploaded): all float, every operation rounded separately.  touched = the state has
+ *             a common word.  An untouched scored state gets score = (float)(sum / (1 + touched states)), sum = the double sum of
+ *             every l: per state in ascending word order, then over the states in ascending order.
+ *   likelihood over the scored states after the fill: mean and sigma = sqrt(E[s^2] - mean^2) in double; (float)((s - 2 sigma) / mean)
+ *             where s > mean + 2 sigma, else 1; all 1 when mean == 0.  An unscored state -1: score 0, touched 0, likelihood 1.
+ * Departures from voctree_bf.h, which the reference never compiled in: its `n *= log10(...)` inside the per-document loop compounds
+ * the idf once per document of a word - here the idf is applied once; a document's weight is count / n, not count float additions of
+ * 1 / n; the L1 term is evaluated in float as written above; its fill loop `for (i = -1; i < doc_size - 1; ...)` assumes the virtual
+ * document always exists - here the scored states are exactly the ones listed; a frame without descriptors is not inserted. */
+enum { SLSLAM_PLACE_MAX_K = 64, SLSLAM_PLACE_MAX_L = 4, SLSLAM_PLACE_MAX_D = 128, SLSLAM_PLACE_MAX_WORDS = 512, SLSLAM_PLACE_MAX_TOP_K = 32 };
+typedef struct slslam_voctree slslam_voctree;
+typedef struct slslam_place_db slslam_place_db;
+typedef struct slslam_place_filter slslam_place_filter;
+/* device < 0 selects the current HIP device.  2 <= K <= 64, 1 <= L <= 4, 1 <= D <= 128, K^L <= 2^24; nodes: the interior nodes as
+ * above (copied).  Touches no device: the nodes are uploaded at the first insert or run of a database. */
+int  slslam_voctree_create(int device, int K, int L, int D, const float* nodes, slslam_voctree** out);
+/* The same from a file of exactly that many floats; a file that cannot be read, is shorter or is longer (it was made for another K, L
+ * or D): SLSLAM_ERR_INVALID_ARGUMENT, *out untouched. */
+int  slslam_voctree_load(const char* path, int device, int K, int L, int D, slslam_voctree** out);
+void slslam_voctree_destroy(slslam_voctree* tree);   /* after the databases that use it */
+
+typedef struct slslam_place_frame {
+  int num_descriptors;           /* n >= 0, at most the database's max_words */
+  const float* descriptors;      /* [n D] row-major */
+} slslam_place_frame;
+enum { SLSLAM_PLACE_OK = 0, SLSLAM_PLACE_EMPTY = 1, SLSLAM_PLACE_INVALID_DESCRIPTOR = 2 };
+typedef struct slslam_place_result {
+  int    status;                 /* SLSLAM_PLACE_*: INVALID_DESCRIPTOR when one of the n D floats is not finite (words all -1), else EMPTY */
+                                 /* when n = 0 or no document is visible; unless OK: score 0, touched 0, likelihood 1, top_id -1    */
+  int    num_states;             /* visible documents + 1: the length of the per-state arrays                                      */
+  int    has_virtual;            /* state -1 was scored                                                                            */
+  int*   words;                  /* in: caller-owned arrays, any of them may be NULL; out: as above.  [n]                          */
+  float* score;                  /* [num_states] */
+  unsigned char* touched;        /* [num_states] */
+  float* likelihood;             /* [num_states] */
+  int*   top_id;                 /* [top_k] the documents (never state -1) of the largest scores, the lower id on ties; -1 beyond   */
+  float* top_score;              /* [top_k] their scores; 0 beyond                                                                  */
+} slslam_place_result;
+
+/* 1 <= max_docs (inserted documents, pending ones included), 1 <= max_words <= 512 (descriptors of a frame), 1 <= max_frames (frames of
+ * a run: what the blocks are made for), recent >= 0, num_avg_words >= 1.  The tree's device.  Touches no device. */
+int  slslam_place_db_create(slslam_voctree* tree, int max_docs, int max_words, int max_frames, int recent, int num_avg_words,
+                            slslam_place_db** out);
+void slslam_place_db_destroy(slslam_place_db* db);
+/* Quantises the frame on the device and appends its document.  *status (may be NULL): SLSLAM_PLACE_OK; EMPTY (n = 0) or
+ * INVALID_DESCRIPTOR: the database is unchanged.  words (may be NULL): [n].  SLSLAM_ERR_STATE: max_docs documents are in. */
+int  slslam_place_db_insert(slslam_place_db* db, const slslam_place_frame* frame, int* status, int* words);
+/* frames[F] (F <= max_frames), out[F], all against the same visible set; 0 <= top_k <= 32.  Every argument is validated before an
+ * output is written or the device is asked: SLSLAM_ERR_INVALID_ARGUMENT, outputs untouched, nothing launched.  Synchronous; host
+ * pointers; one upload, three launches (documents, scores, likelihoods) and one download per call whatever the number of frames; a
+ * frame's bytes do not depend on the other frames of the call. */
+int  slslam_place_db_run(slslam_place_db* db, int num_frames, const slslam_place_frame* frames, int top_k, slslam_place_result* out);
+/* Documents inserted, visible, and doc_size (visible + the virtual one).  Any pointer may be NULL. */
+int  slslam_place_db_size(const slslam_place_db* db, int* inserted, int* visible, int* doc_size);
+/* The virtual document's words, ascending: words[num_avg_words] (may be NULL); *num = num_avg_words, or 0 while it does not exist. */
+int  slslam_place_db_virtual(const slslam_place_db* db, int* words, int* num);
+/* Since create: inserts + runs, and how often the database's blocks were made or made larger.  Either pointer may be NULL. */
+int  slslam_place_db_stats(const slslam_place_db* db, long long* calls, long long* allocations);
+
+/* The Bayes filter and the loop decision (host/place_filter.h has the rule): sigma > 0 of the transition's Gaussian, threshold on the
+ * posterior mass of seq_len + 1 consecutive documents, no decision while fewer than min_docs documents are visible.  The reference's
+ * presets (recent, sigma, threshold, seq_len; min_docs = recent): indoor 40, 1.0, 0.7, 10; outdoor 100, 0.8, 0.8, 15; outdoor
+ * long-loop 300, 0.8, 0.5, 5.  Needs no device. */
+int  slslam_place_filter_create(double sigma, double threshold, int seq_len, int min_docs, slslam_place_filter** out);
+void slslam_place_filter_destroy(slslam_place_filter* filter);
+/* One step: likelihood[num_docs + 1] as slslam_place_db_run returns it (state -1 first); the visible set may have grown since the last
+ * step.  posterior[num_docs + 1], *loop (0 / 1), *keyframe (the reported document, -1 without a loop): any of them may be NULL. */
+int  slslam_place_filter_update(slslam_place_filter* filter, int num_docs, const float* likelihood, float* posterior, int* loop,
+                                int* keyframe);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */

@@ -100,6 +100,17 @@ class TriangulatedLine(C.Structure):
                 ("eigenvalues", C.c_double * 4), ("clamped", C.c_int), ("reserved", C.c_int)]
 
 
+class PlaceFrame(C.Structure):
+    _fields_ = [("num_descriptors", C.c_int), ("descriptors", C.POINTER(C.c_float))]
+
+
+class PlaceResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("num_states", C.c_int), ("has_virtual", C.c_int), ("words", C.POINTER(C.c_int)),
+                ("score", C.POINTER(C.c_float)), ("touched", C.POINTER(C.c_ubyte)), ("likelihood", C.POINTER(C.c_float)),
+                ("top_id", C.POINTER(C.c_int)), ("top_score", C.POINTER(C.c_float))]
+
+
+PLACE_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_DESCRIPTOR"}
 TRI_MULTIVIEW, TRI_STEREO, TRI_CONSTANT, TRI_NO_OBSERVATIONS, TRI_INVALID = 0, 1, 2, 3, 4
 TRI_STATUS = {0: "MULTIVIEW", 1: "STEREO", 2: "CONSTANT", 3: "NO_OBSERVATIONS", 4: "INVALID"}
 LINE_REFINED, LINE_CONSTANT, LINE_NO_OBSERVATIONS, LINE_INVALID = 0, 1, 2, 3
@@ -146,7 +157,10 @@ EXPORTS = [
     "slslam_lba_batch_covariance", "slslam_lba_batch_get_covariance", "slslam_lba_batch_covariance_stats", "slslam_lba_covariance",
     "slslam_lba_batch_report", "slslam_lba_batch_get_report", "slslam_lba_batch_report_stats", "slslam_lba_report",
     "slslam_lba_batch_segments", "slslam_lba_batch_get_segments", "slslam_lba_batch_segments_stats", "slslam_lba_segments",
-    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_matcher_create", "slslam_line_matcher_destroy", "slslam_line_matcher_run", "slslam_line_matcher_stats", "slslam_match_lines", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_line_triangulator_create", "slslam_line_triangulator_destroy", "slslam_line_triangulator_run", "slslam_line_triangulator_stats", "slslam_line_triangulator_timing", "slslam_lba_triangulate_lines", "slslam_debug_triangulate_host", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_matcher_create", "slslam_line_matcher_destroy", "slslam_line_matcher_run", "slslam_line_matcher_stats", "slslam_match_lines", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_line_triangulator_create", "slslam_line_triangulator_destroy", "slslam_line_triangulator_run", "slslam_line_triangulator_stats", "slslam_line_triangulator_timing", "slslam_lba_triangulate_lines", "slslam_debug_triangulate_host",
+    "slslam_voctree_create", "slslam_voctree_load", "slslam_voctree_destroy", "slslam_place_db_create", "slslam_place_db_destroy",
+    "slslam_place_db_insert", "slslam_place_db_run", "slslam_place_db_size", "slslam_place_db_virtual", "slslam_place_db_stats",
+    "slslam_place_filter_create", "slslam_place_filter_destroy", "slslam_place_filter_update", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -289,6 +303,24 @@ def lib():
     L.slslam_lba_triangulate_lines.argtypes = [C.POINTER(LBAWindow), C.POINTER(SolverOptions), C.c_int, C.c_double, C.c_double,
                                                C.POINTER(TriangulatedLine), dp]
     L.slslam_debug_triangulate_host.argtypes = [C.c_int, dp, dp, C.c_double, C.c_int, C.c_double, C.c_double, dp, dp, ip, ip, ip, dp]
+    if hasattr(L, "slslam_place_db_run"):        # (likewise: a library built before the place recogniser existed)
+        fp = C.POINTER(C.c_float)
+        L.slslam_voctree_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, fp, C.POINTER(vp)]
+        L.slslam_voctree_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.slslam_voctree_destroy.argtypes = [vp]
+        L.slslam_voctree_destroy.restype = None
+        L.slslam_place_db_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.slslam_place_db_destroy.argtypes = [vp]
+        L.slslam_place_db_destroy.restype = None
+        L.slslam_place_db_insert.argtypes = [vp, C.POINTER(PlaceFrame), ip, ip]
+        L.slslam_place_db_run.argtypes = [vp, C.c_int, C.POINTER(PlaceFrame), C.c_int, C.POINTER(PlaceResult)]
+        L.slslam_place_db_size.argtypes = [vp, ip, ip, ip]
+        L.slslam_place_db_virtual.argtypes = [vp, ip, ip]
+        L.slslam_place_db_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+        L.slslam_place_filter_create.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
+        L.slslam_place_filter_destroy.argtypes = [vp]
+        L.slslam_place_filter_destroy.restype = None
+        L.slslam_place_filter_update.argtypes = [vp, C.c_int, fp, fp, ip, ip]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -1647,3 +1679,152 @@ def matched_trials(frame, result, map_observations, num_trials=1001, sample_size
         samples = (np.arange(num_trials * sample_size, dtype=np.int32).reshape(num_trials, sample_size) % max(n, 1)).astype(np.int32)
     return {"obs0": mo[l], "obs1": obs[k], "lines": ln[l], "samples": samples, "observation_index": k.astype(np.int32),
             "line_index": l.astype(np.int32)}
+
+
+# ----------------------------------------------------------------------------- place recognition (slslam_voctree_*, slslam_place_*)
+def _fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+class VocTree:
+    """slslam_voctree: K children per node, L levels, descriptors of D floats.  nodes: the interior nodes [(K^L - 1) / (K - 1), K, D]
+    breadth-first (any shape of that many floats), or path: a file of exactly those floats."""
+
+    def __init__(self, K, L, D, nodes=None, path=None, device=-1):
+        self.K, self.L, self.D = int(K), int(L), int(D)
+        self.num_leaves = self.K ** self.L
+        self._h = C.c_void_p()
+        if (nodes is None) == (path is None):
+            raise ValueError("give nodes or path")
+        if path is not None:
+            _check(lib().slslam_voctree_load(os.fsencode(path), int(device), self.K, self.L, self.D, C.byref(self._h)), "slslam_voctree_load")
+            return
+        nodes = np.ascontiguousarray(nodes, dtype=np.float32).reshape(-1)
+        if 2 <= self.K and 1 <= self.L <= 8 and nodes.size != (self.K ** self.L - 1) // (self.K - 1) * self.K * self.D:
+            raise ValueError("nodes must hold (K^L - 1) / (K - 1) * K * D floats")
+        _check(lib().slslam_voctree_create(int(device), self.K, self.L, self.D, _fp(nodes), C.byref(self._h)), "slslam_voctree_create")
+
+    def close(self):
+        if self._h:
+            lib().slslam_voctree_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _place_frame(tree, fr):
+    d = np.ascontiguousarray(fr, dtype=np.float32).reshape(-1, tree.D)
+    return PlaceFrame(len(d), _fp(d)), d
+
+
+class PlaceDB:
+    """slslam_place_db: the documents of the inserted keyframes and queries against the visible ones; buffers kept between calls.
+    A frame is its descriptors [n, D] float32."""
+
+    def __init__(self, tree, max_docs=4096, max_words=512, max_frames=64, recent=40, num_avg_words=100):
+        self.tree = tree                                           # (the database uses the tree: keep it alive)
+        self._h = C.c_void_p()
+        _check(lib().slslam_place_db_create(tree._h, int(max_docs), int(max_words), int(max_frames), int(recent), int(num_avg_words),
+                                            C.byref(self._h)), "slslam_place_db_create")
+
+    def close(self):
+        if self._h:
+            lib().slslam_place_db_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def insert(self, frame):
+        """Returns dict(status, words [n])."""
+        pf, keep = _place_frame(self.tree, frame)
+        st, words = C.c_int(-1), np.full(max(pf.num_descriptors, 1), -2, dtype=np.int32)
+        _check(lib().slslam_place_db_insert(self._h, C.byref(pf), C.byref(st), _ip(words)), "slslam_place_db_insert")
+        return {"status": PLACE_STATUS[st.value], "words": words[:pf.num_descriptors]}
+
+    def run(self, frames, top_k=0):
+        """Returns one dict per frame: status, has_virtual, words [n], score / touched / likelihood [visible + 1] (index 0: state -1,
+        index d + 1: visible document d), top_id / top_score [top_k]."""
+        n, s = len(frames), self.size()["visible"] + 1
+        pfs, outs, keep, bufs = (PlaceFrame * max(n, 1))(), (PlaceResult * max(n, 1))(), [], []
+        for i, fr in enumerate(frames):
+            pfs[i], k = _place_frame(self.tree, fr)
+            b = {"words": np.full(max(pfs[i].num_descriptors, 1), -2, dtype=np.int32), "score": np.zeros(s, dtype=np.float32),
+                 "touched": np.zeros(s, dtype=np.uint8), "likelihood": np.zeros(s, dtype=np.float32),
+                 "top_id": np.full(max(top_k, 1), -2, dtype=np.int32), "top_score": np.zeros(max(top_k, 1), dtype=np.float32)}
+            outs[i] = PlaceResult(-1, 0, 0, _ip(b["words"]), _fp(b["score"]), b["touched"].ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                  _fp(b["likelihood"]), _ip(b["top_id"]), _fp(b["top_score"]))
+            keep.append(k)
+            bufs.append(b)
+        _check(lib().slslam_place_db_run(self._h, n, pfs, int(top_k), outs), "slslam_place_db_run")
+        res = []
+        for i in range(n):
+            b = bufs[i]
+            res.append({"status": PLACE_STATUS[outs[i].status], "has_virtual": bool(outs[i].has_virtual),
+                        "words": b["words"][:pfs[i].num_descriptors], "score": b["score"], "touched": b["touched"],
+                        "likelihood": b["likelihood"], "top_id": b["top_id"][:top_k], "top_score": b["top_score"][:top_k]})
+        return res
+
+    def size(self):
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().slslam_place_db_size(self._h, C.byref(a), C.byref(b), C.byref(c)), "slslam_place_db_size")
+        return {"inserted": a.value, "visible": b.value, "doc_size": c.value}
+
+    def virtual_words(self):
+        n = C.c_int(0)
+        _check(lib().slslam_place_db_virtual(self._h, None, C.byref(n)), "slslam_place_db_virtual")
+        w = np.zeros(max(n.value, 1), dtype=np.int32)
+        _check(lib().slslam_place_db_virtual(self._h, _ip(w), None), "slslam_place_db_virtual")
+        return w[:n.value]
+
+    def stats(self):
+        c, a = C.c_longlong(0), C.c_longlong(0)
+        _check(lib().slslam_place_db_stats(self._h, C.byref(c), C.byref(a)), "slslam_place_db_stats")
+        return {"calls": c.value, "allocations": a.value}
+
+
+class PlaceFilter:
+    """slslam_place_filter: the Bayes filter over (no place, visible documents) and the loop decision.  Defaults: the reference's indoor
+    preset (with recent = min_docs = 40).  Needs no device."""
+
+    def __init__(self, sigma=1.0, threshold=0.7, seq_len=10, min_docs=40):
+        self._h = C.c_void_p()
+        _check(lib().slslam_place_filter_create(float(sigma), float(threshold), int(seq_len), int(min_docs), C.byref(self._h)),
+               "slslam_place_filter_create")
+
+    def close(self):
+        if self._h:
+            lib().slslam_place_filter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, likelihood):
+        """likelihood [N + 1] as PlaceDB.run returns it.  Returns (loop, keyframe, posterior [N + 1])."""
+        lik = np.ascontiguousarray(likelihood, dtype=np.float32).reshape(-1)
+        if len(lik) < 1:
+            raise ValueError("likelihood holds state -1 and the visible documents")
+        post, loop, kf = np.zeros(len(lik), dtype=np.float32), C.c_int(0), C.c_int(-1)
+        _check(lib().slslam_place_filter_update(self._h, len(lik) - 1, _fp(lik), _fp(post), C.byref(loop), C.byref(kf)),
+               "slslam_place_filter_update")
+        return bool(loop.value), kf.value, post
+
+
+def place_candidates(db, filt, frame):
+    """One keyframe through the recogniser: insert it, query it against the visible documents, one filter step.  Returns
+    (loop, keyframe, posterior): keyframe is the visible document a closed loop reports (-1 without one).  A frame the database does not
+    take (no descriptors, a non-finite one) is neither inserted nor filtered: (False, -1, None)."""
+    if db.insert(frame)["status"] != "OK":
+        return False, -1, None
+    return filt.update(db.run([frame])[0]["likelihood"])

@@ -493,3 +493,27 @@ def make_ransac_pair(seed, num_lines=150, noise_px=0.5, outlier_frac=0.2, num_tr
     samples = np.stack([rng.choice(num_lines, size=sample_size, replace=False) for _ in range(num_trials)]).astype(np.int32)
     return dict(obs0=obs0, obs1=obs1, lines=lines, samples=samples, true_pose=np.concatenate([R.reshape(-1), tv]),
                 outliers=bad)
+
+
+def make_voctree(seed, K, L, D):
+    """A seeded random vocabulary tree: the interior nodes [(K^L - 1) / (K - 1), K, D] float32 (breadth-first, as slslam_voctree_create
+    takes them), every centre of unit norm.  Stands in for the tree file the reference does not ship."""
+    rng = np.random.default_rng(np.random.SeedSequence([12, int(seed)]))
+    c = rng.standard_normal(((K ** L - 1) // (K - 1), K, D))
+    return (c / np.linalg.norm(c, axis=2, keepdims=True)).astype(np.float32)
+
+
+def make_place_sequence(seed, places=60, words_per_place=40, noise=0.05, revisit=(10, 25), dim=16):
+    """Descriptors of a walk that passes `places` distinct places, one keyframe each, and then revisits places revisit[0] ..
+    revisit[1] - 1 in the same order.  A place is words_per_place random unit vectors of `dim` floats; a visit sees each of them with
+    Gaussian noise of that standard deviation per component, renormalised.  Returns dict(frames: list of [words_per_place, dim] float32,
+    place: the place of every keyframe, first_pass: places)."""
+    rng = np.random.default_rng(np.random.SeedSequence([13, int(seed)]))
+    base = rng.standard_normal((places, words_per_place, dim))
+    base /= np.linalg.norm(base, axis=2, keepdims=True)
+    order = list(range(places)) + list(range(int(revisit[0]), int(revisit[1])))
+    frames = []
+    for p in order:
+        d = base[p] + noise * rng.standard_normal((words_per_place, dim))
+        frames.append((d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32))
+    return {"frames": frames, "place": np.array(order, dtype=np.int32), "first_pass": places}
