@@ -1092,6 +1092,70 @@ void slslam_place_filter_destroy(slslam_place_filter* filter);
 int  slslam_place_filter_update(slslam_place_filter* filter, int num_docs, const float* likelihood, float* posterior, int* loop,
                                 int* keyframe);
 
+/* ------------------------------------------------------------------ training a vocabulary tree: hierarchical spherical k-means
+ * Makes the nodes slslam_voctree_create takes from the caller's own descriptors (csrc/voctree_train.h, host/voctree_host.h, DESIGN.md
+ * 6.5); the reference has no trainer and ships no tree.  The distance is the recogniser's (`word` above, slslam_place::nearest_child),
+ * so the training descriptors' words equal find_leaf on the finished tree.  Every sum that decides a centre is an int64 sum of
+ * fixed-point values and so independent of its order: nodes, words and counts are a function of the arguments alone, bit for bit.
+ *   inputs    n descriptors [n D] float, 1 <= n <= 2^24, every value finite and |f| <= 16; K, L, D within slslam_voctree_create's
+ *             limits and K^L D <= 2^27 (the last level's accumulators); 0 <= max_iterations <= 1000; a 64-bit seed.
+ *   q(f)      = llrint((double)f * 2^30): round to nearest even, the product is exact.  Sums of q are int64: |sum| <= 2^58.
+ *   centre(acc, prev), on the host: s_i = (double)acc_i; n2 = the sum over i ascending of s_i * s_i, each operation rounded on its own;
+ *             n2 == 0: the centre stays prev; otherwise c_i = (float)(s_i / sqrt(n2)).
+ *   key(m)    = splitmix64(seed ^ splitmix64(m)), splitmix64(x): x += 0x9E3779B97F4A7C15; z = x; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *             z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31 - all mod 2^64.
+ *   levels    l = 0 .. L-1, one after the other; every descriptor is in exactly one node of its level, all start at the root; all nodes
+ *             of a level iterate together.
+ *   initial   centres of a node with n members: every centre starts at 0; child j < min(n, K) is centre(q(member), 0) of the member of
+ *             the j-th smallest (key, m); children n .. K-1 are copies of child 0 (they never win under the strict <).  A node without
+ *             members gets K copies of the centre its parent holds for it.
+ *   loop      assign every descriptor to the nearest child of its node; changed = labels that differ from the previous assignment
+ *             (the first assignment changes all n).  Stop when max_iterations updates are done, or when at least one is done and
+ *             changed == 0.  Otherwise acc[node][child] += q(f), every centre of the level becomes centre(acc, its previous value) - an
+ *             empty child keeps its centre - and the loop goes round again.  It always ends on an assignment under the final centres:
+ *             those labels are the descriptors' nodes of the next level and, after the last level, their words.
+ *   report    per level: iterations = updates done; changed = of the last assignment; empty_children = children (of all K^l nodes)
+ *             without a member after the last assignment; distortion = the double mean of the winning r - the one field whose
+ *             summation order is free (here: fixed per call shape, so two calls give the same bits).  The *_ms fields are wall-clock
+ *             times of the call's phases, for tools/voctree_train_bench.py. */
+typedef struct slslam_voctree_train_options {
+  int K, L, D;
+  int max_iterations;
+  unsigned long long seed;
+} slslam_voctree_train_options;
+typedef struct slslam_voctree_train_report {
+  int       levels;                                    /* L */
+  int       iterations[SLSLAM_PLACE_MAX_L];
+  long long changed[SLSLAM_PLACE_MAX_L];
+  long long empty_children[SLSLAM_PLACE_MAX_L];
+  double    distortion[SLSLAM_PLACE_MAX_L];
+  double    setup_ms[SLSLAM_PLACE_MAX_L];              /* host: partition by node, initial centres; their upload                       */
+  double    kernel_ms[SLSLAM_PLACE_MAX_L];             /* every assign-and-accumulate launch of the level, to the arrival of `changed` */
+  double    download_ms[SLSLAM_PLACE_MAX_L];           /* the accumulators of every update; labels and counts at the level's end       */
+  double    centre_ms[SLSLAM_PLACE_MAX_L];             /* host: centre() over the level's rows, every update                           */
+  double    upload_ms[SLSLAM_PLACE_MAX_L];             /* the level's centres, every update                                            */
+  double    total_ms;                                  /* the call, validation and the descriptors' upload included                    */
+} slslam_voctree_train_report;
+/* nodes: [(K^L - 1) / (K - 1)][K][D], breadth-first as slslam_voctree_create takes them; words (may be NULL): [n]; report (may be
+ * NULL).  Shape errors (NULL options / descriptors / nodes, n, K, L, D, max_iterations outside the limits above) return
+ * SLSLAM_ERR_INVALID_ARGUMENT before any device call, value errors (a non-finite value, |f| > 16) the same status; a failed
+ * allocation, on the host or on the device, returns SLSLAM_ERR_NO_MEMORY.  On every error no output is written.  Synchronous; host
+ * pointers; the descriptors are uploaded once and stay on the device for the call.  device < 0 selects the current HIP device. */
+int  slslam_voctree_train(int device, const slslam_voctree_train_options* options, long long n, const float* descriptors, float* nodes,
+                          int* words, slslam_voctree_train_report* report);
+/* Writes the file slslam_voctree_load reads (raw floats, no header).  Needs no device.  A shape outside slslam_voctree_create's limits
+ * or a file that cannot be written: SLSLAM_ERR_INVALID_ARGUMENT. */
+int  slslam_voctree_save(const char* path, int K, int L, int D, const float* nodes);
+/* The host half of the trainer, exported so that it can be pinned without a device: centre(acc, prev) of `rows` rows of D values
+ * (out may be prev), and key(m). */
+int  slslam_voctree_centres(long long rows, int D, const long long* acc, const float* prev, float* out);
+unsigned long long slslam_voctree_key(unsigned long long seed, unsigned long long m);
+/* Test hook: ONE assignment plus accumulation through the kernel slslam_voctree_train uses, after the same partition by node, for an
+ * arbitrary unsorted node[n] (0 <= node < num_nodes): centres [num_nodes][K][D]; label [n], acc [num_nodes K][D] and count
+ * [num_nodes K] come back.  Inputs as for slslam_voctree_train, and num_nodes K D <= 2^27. */
+int  slslam_debug_voctree_step(int device, int K, int D, long long num_nodes, const float* centres, long long n, const float* descriptors,
+                               const int* node, int* label, long long* acc, long long* count);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */

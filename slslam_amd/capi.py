@@ -110,6 +110,16 @@ class PlaceResult(C.Structure):
                 ("top_id", C.POINTER(C.c_int)), ("top_score", C.POINTER(C.c_float))]
 
 
+class VocTreeTrainOptions(C.Structure):
+    _fields_ = [("K", C.c_int), ("L", C.c_int), ("D", C.c_int), ("max_iterations", C.c_int), ("seed", C.c_ulonglong)]
+
+
+class VocTreeTrainReport(C.Structure):
+    _fields_ = [("levels", C.c_int), ("iterations", C.c_int * 4), ("changed", C.c_longlong * 4), ("empty_children", C.c_longlong * 4),
+                ("distortion", C.c_double * 4), ("setup_ms", C.c_double * 4), ("kernel_ms", C.c_double * 4), ("download_ms", C.c_double * 4),
+                ("centre_ms", C.c_double * 4), ("upload_ms", C.c_double * 4), ("total_ms", C.c_double)]
+
+
 PLACE_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_DESCRIPTOR"}
 TRI_MULTIVIEW, TRI_STEREO, TRI_CONSTANT, TRI_NO_OBSERVATIONS, TRI_INVALID = 0, 1, 2, 3, 4
 TRI_STATUS = {0: "MULTIVIEW", 1: "STEREO", 2: "CONSTANT", 3: "NO_OBSERVATIONS", 4: "INVALID"}
@@ -160,7 +170,8 @@ EXPORTS = [
     "slslam_po_solve", "slslam_po_edge_report", "slslam_po_batch_get_edge_report", "slslam_po_structure", "slslam_po_structure_level1", "slslam_po_batch_create", "slslam_po_batch_destroy", "slslam_po_batch_add", "slslam_po_batch_finalize", "slslam_po_batch_solve", "slslam_po_batch_reset", "slslam_po_batch_download", "slslam_po_batch_get_parameters", "slslam_po_batch_get_summary", "slslam_po_batch_get_trace", "slslam_po_covariance", "slslam_po_sqrt_information", "slslam_po_batch_set_covariance_pairs", "slslam_po_batch_covariance", "slslam_po_batch_get_covariance", "slslam_po_batch_covariance_stats", "slslam_po_edge_statistics", "slslam_po_gate", "slslam_po_batch_set_candidates", "slslam_po_batch_gate", "slslam_po_batch_get_gate", "slslam_po_constraint_covariance", "slslam_po_set_profiling", "slslam_po_last_timing", "slslam_debug_phase_cycles", "slslam_debug_read_cycles", "slslam_ransac_score", "slslam_ransac_generate", "slslam_ransac_motion", "slslam_ransac_motion_batch", "slslam_pose_estimator_create", "slslam_pose_estimator_destroy", "slslam_pose_estimator_run", "slslam_pose_estimator_stats", "slslam_pose_estimator_window", "slslam_pose_estimator_set_covariance", "slslam_pose_estimator_get_covariance", "slslam_line_matcher_create", "slslam_line_matcher_destroy", "slslam_line_matcher_run", "slslam_line_matcher_stats", "slslam_match_lines", "slslam_line_refiner_create", "slslam_line_refiner_destroy", "slslam_line_refiner_run", "slslam_line_refiner_stats", "slslam_lba_refine_lines", "slslam_line_triangulator_create", "slslam_line_triangulator_destroy", "slslam_line_triangulator_run", "slslam_line_triangulator_stats", "slslam_line_triangulator_timing", "slslam_lba_triangulate_lines", "slslam_debug_triangulate_host",
     "slslam_voctree_create", "slslam_voctree_load", "slslam_voctree_destroy", "slslam_place_db_create", "slslam_place_db_destroy",
     "slslam_place_db_insert", "slslam_place_db_run", "slslam_place_db_size", "slslam_place_db_virtual", "slslam_place_db_stats",
-    "slslam_place_filter_create", "slslam_place_filter_destroy", "slslam_place_filter_update", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
+    "slslam_place_filter_create", "slslam_place_filter_destroy", "slslam_place_filter_update",
+    "slslam_voctree_train", "slslam_voctree_save", "slslam_voctree_centres", "slslam_voctree_key", "slslam_debug_voctree_step", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
 _lib = None
@@ -321,6 +332,14 @@ def lib():
         L.slslam_place_filter_destroy.argtypes = [vp]
         L.slslam_place_filter_destroy.restype = None
         L.slslam_place_filter_update.argtypes = [vp, C.c_int, fp, fp, ip, ip]
+    if hasattr(L, "slslam_voctree_train"):       # (likewise: a library built before the tree trainer existed)
+        fp, lp = C.POINTER(C.c_float), C.POINTER(C.c_longlong)
+        L.slslam_voctree_train.argtypes = [C.c_int, C.POINTER(VocTreeTrainOptions), C.c_longlong, fp, fp, ip, C.POINTER(VocTreeTrainReport)]
+        L.slslam_voctree_save.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, fp]
+        L.slslam_voctree_centres.argtypes = [C.c_longlong, C.c_int, lp, fp, fp]
+        L.slslam_voctree_key.argtypes = [C.c_ulonglong, C.c_ulonglong]
+        L.slslam_voctree_key.restype = C.c_ulonglong
+        L.slslam_debug_voctree_step.argtypes = [C.c_int, C.c_int, C.c_int, C.c_longlong, fp, C.c_longlong, fp, ip, ip, lp, lp]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -1703,6 +1722,19 @@ class VocTree:
         if 2 <= self.K and 1 <= self.L <= 8 and nodes.size != (self.K ** self.L - 1) // (self.K - 1) * self.K * self.D:
             raise ValueError("nodes must hold (K^L - 1) / (K - 1) * K * D floats")
         _check(lib().slslam_voctree_create(int(device), self.K, self.L, self.D, _fp(nodes), C.byref(self._h)), "slslam_voctree_create")
+        self.nodes = nodes.reshape(-1, self.K, self.D)
+
+    @classmethod
+    def train(cls, descriptors, K, L, max_iterations=10, seed=0, device=-1):
+        """Trains a tree on descriptors [N, D] (train_voctree).  Returns (tree, the dict train_voctree returns)."""
+        rep = train_voctree(descriptors, K, L, max_iterations=max_iterations, seed=seed, device=device)
+        return cls(K, L, rep["nodes"].shape[2], nodes=rep["nodes"], device=device), rep
+
+    def save(self, path):
+        """Writes the file VocTree(path=...) reads.  A tree made from a path has no nodes to write."""
+        if getattr(self, "nodes", None) is None:
+            raise ValueError("this tree was loaded from a file")
+        save_voctree(path, self.nodes)
 
     def close(self):
         if self._h:
@@ -1714,6 +1746,40 @@ class VocTree:
             self.close()
         except Exception:
             pass
+
+
+def train_voctree(descriptors, K, L, max_iterations=10, seed=0, device=-1, timing=False):
+    """slslam_voctree_train: hierarchical spherical k-means over descriptors [N, D] on the device; nodes, words and the counts are a
+    function of the arguments alone, bit for bit.  Returns dict(nodes [(K^L - 1) / (K - 1), K, D], words [N], and per level iterations,
+    changed, empty_children, distortion); timing=True adds the call's wall-clock split (setup_ms, kernel_ms, download_ms, centre_ms,
+    upload_ms per level, total_ms)."""
+    d = np.ascontiguousarray(descriptors, dtype=np.float32)
+    if d.ndim != 2:
+        raise ValueError("descriptors must be [N, D]")
+    K, L = int(K), int(L)
+    n, D = d.shape
+    opt = VocTreeTrainOptions(K, L, D, int(max_iterations), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    num_int = (K ** L - 1) // (K - 1) if K >= 2 and 1 <= L <= 8 else 1
+    nodes = np.zeros((num_int, max(K, 1), max(D, 1)), dtype=np.float32)
+    words, rep = np.zeros(max(n, 1), dtype=np.int32), VocTreeTrainReport()
+    _check(lib().slslam_voctree_train(int(device), C.byref(opt), n, _fp(d), _fp(nodes), _ip(words), C.byref(rep)), "slslam_voctree_train")
+    out = {"nodes": nodes, "words": words[:n], "iterations": list(rep.iterations[:L]), "changed": list(rep.changed[:L]),
+           "empty_children": list(rep.empty_children[:L]), "distortion": list(rep.distortion[:L])}
+    if timing:
+        for k in ("setup_ms", "kernel_ms", "download_ms", "centre_ms", "upload_ms"):
+            out[k] = list(getattr(rep, k)[:L])
+        out["total_ms"] = rep.total_ms
+    return out
+
+
+def save_voctree(path, nodes):
+    """slslam_voctree_save: nodes [(K^L - 1) / (K - 1), K, D] as the file slslam_voctree_load reads."""
+    nodes = np.ascontiguousarray(nodes, dtype=np.float32)
+    if nodes.ndim != 3:
+        raise ValueError("nodes must be [(K^L - 1) / (K - 1), K, D]")
+    num_int, K, D = nodes.shape
+    L = next((l for l in range(1, 9) if K >= 2 and (K ** l - 1) // (K - 1) == num_int), 0)
+    _check(lib().slslam_voctree_save(os.fsencode(path), K, L, D, _fp(nodes)), "slslam_voctree_save")
 
 
 def _place_frame(tree, fr):

@@ -95,10 +95,12 @@ __device__ inline int nearest_child(const float* node, const float* f, int K, in
   return arg;
 }
 
+// The kernels are static: voctree_train.h includes this header for nearest_child, in a second translation unit.
 // grid F, block kDocThreads, dynamic LDS K D floats.  db_slot >= 0 (F = 1, an insert): the document also goes into that column.
-__global__ __launch_bounds__(kDocThreads) void k_place_document(Tree tree, const Frame* __restrict__ frames, const float* __restrict__ desc,
-                                                                int max_words, QueryOut o, int db_slot, long long db_cap,
-                                                                int* __restrict__ db_word, float* __restrict__ db_tf, int* __restrict__ db_n) {
+static __global__ __launch_bounds__(kDocThreads) void k_place_document(Tree tree, const Frame* __restrict__ frames,
+                                                                       const float* __restrict__ desc, int max_words, QueryOut o, int db_slot,
+                                                                       long long db_cap, int* __restrict__ db_word, float* __restrict__ db_tf,
+                                                                       int* __restrict__ db_n) {
   extern __shared__ float s_root[];
   __shared__ int s_w[kDocThreads];
   __shared__ int s_start[kDocThreads + 1];
@@ -166,14 +168,14 @@ __global__ __launch_bounds__(kDocThreads) void k_place_document(Tree tree, const
   if (db_slot >= 0 && t == 0) db_n[db_slot] = runs;
 }
 
-__global__ __launch_bounds__(256) void k_place_scatter(int num, const int* __restrict__ word, const int* __restrict__ value,
-                                                       int* __restrict__ df) {
+static __global__ __launch_bounds__(256) void k_place_scatter(int num, const int* __restrict__ word, const int* __restrict__ value,
+                                                              int* __restrict__ df) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < num) df[word[i]] = value[i];
 }
 
 // grid (ceil(scored states / 64), F), block 64
-__global__ __launch_bounds__(64) void k_place_score(const Frame* __restrict__ frames, Db db, int max_words, QueryOut o) {
+static __global__ __launch_bounds__(64) void k_place_score(const Frame* __restrict__ frames, Db db, int max_words, QueryOut o) {
   __shared__ int s_qw[kMaxWords];
   __shared__ float s_qtf[kMaxWords];
   const int f = blockIdx.y, lane = threadIdx.x;
@@ -221,8 +223,8 @@ __global__ __launch_bounds__(64) void k_place_score(const Frame* __restrict__ fr
 }
 
 // grid F, block kFinishThreads
-__global__ __launch_bounds__(kFinishThreads) void k_place_finish(const Frame* __restrict__ frames, int visible, int has_virtual, int top_k,
-                                                                 QueryOut o) {
+static __global__ __launch_bounds__(kFinishThreads) void k_place_finish(const Frame* __restrict__ frames, int visible, int has_virtual,
+                                                                        int top_k, QueryOut o) {
   __shared__ double s_d[kFillChunk];
   __shared__ double s_r0[kFinishThreads], s_r1[kFinishThreads];
   __shared__ unsigned long long s_key[kFinishThreads];
