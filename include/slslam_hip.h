@@ -1004,7 +1004,7 @@ int  slslam_debug_triangulate_host(int num_observations, const double* observati
 /* ------------------------------------------------------------------ place recognition: which old keyframe does this frame look like
  * The first link of the loop-closure chain (csrc/place_recognition.h, host/place_filter.h), after the reference's
  * src/voctree_bf.h: a K-ary vocabulary tree of L levels over descriptors of D floats, tf-idf scores against the documents of the visible
- * keyframes, and a Bayes filter over "which keyframe am I at, or none".  A reported document feeds slslam_line_matcher_run.
+ * keyframes, and a Bayes filter over "which keyframe am I at, or none".  A reported document feeds slslam_descriptor_matcher_run.
  *   tree      (K^L - 1) / (K - 1) interior nodes of K x D floats, breadth-first, child j of node i at i K + j + 1, raw floats without a
  *             header: what voctree_t::load reads.  K^L leaves; leaf index = node index - interior nodes.
  *   word      of a descriptor f (find_leaf): from the root, L times, go to the child c of the smallest distance
@@ -1091,6 +1091,77 @@ void slslam_place_filter_destroy(slslam_place_filter* filter);
  * step.  posterior[num_docs + 1], *loop (0 / 1), *keyframe (the reported document, -1 without a loop): any of them may be NULL. */
 int  slslam_place_filter_update(slslam_place_filter* filter, int num_docs, const float* likelihood, float* posterior, int* loop,
                                 int* keyframe);
+
+/* ------------------------------------------------------------------ descriptor matching: which feature of a frame is which of a keyframe
+ * The link between the place recogniser and the pose estimator in a loop closure (csrc/descriptor_match.h).
+ * SLAM::loop_closure (src/slam.cpp:1108-1143) starts from match_result, a map from the current frame's features to the loop keyframe's
+ * landmarks, which the commented-out pr.pr_DB_query was to deliver from appearance.  slslam_line_matcher_run scores pairs under a
+ * predicted pose; a loop closes because that pose has drifted, so the pairs have to come from the descriptors that made the recogniser
+ * fire: the nearest neighbours between the query frame and the reported keyframe, by the recogniser's own distance.
+ *   distance    of a query descriptor q and a keyframe descriptor k of D floats each:
+ *               r = 1.0f; for i in 0 .. D-1: r -= q[i] * k[i]  - float, in this order, product and difference rounded separately, no
+ *               contraction: the chain of `word` above (slslam_place::nearest_child).  The fixed order is why this is not a matrix
+ *               product: every decision below is a function of the two frames alone, bit for bit.  r of two equal unit descriptors may
+ *               lie a few ulp below zero.
+ *   admissible  a pair (a, j) of a query frame of n descriptors and a keyframe of m: r is finite and (double)r < max_distance.
+ *   per a       best = the admissible j of the smallest r, the lowest j on ties (-1: none); best_distance = that r, second_distance =
+ *               the smallest admissible r over j != best (+inf each when absent); num_admissible = admissible j;
+ *   per j       best_query = the admissible a of the smallest r, the lowest a on ties (-1: none);
+ *   match[a]    best[a] when best[a] >= 0, best_query[best[a]] == a (mutual) and
+ *               (double)best_distance[a] * ratio <= (double)second_distance[a] (unambiguous; ratio <= 1 switches this test off), else -1.
+ * Minima and counts only: a pair's results do not depend on the other pairs of the call or on the order of evaluation.
+ * The store numbers its keyframes 0, 1, ... in the order of accepted inserts and refuses what slslam_place_db_insert refuses: fed the
+ * same frames, a store id is the database's document id. */
+enum { SLSLAM_DESC_MAX_D = 128, SLSLAM_DESC_MAX_DESCRIPTORS = 512, SLSLAM_DESC_MAX_CANDIDATES = 8 };
+enum { SLSLAM_DESC_OK = 0, SLSLAM_DESC_EMPTY = 1, SLSLAM_DESC_INVALID_DESCRIPTOR = 2 };
+typedef struct slslam_descriptor_query {
+  int num_descriptors;           /* n >= 0, at most the matcher's max_descriptors */
+  const float* descriptors;      /* [n D] row-major */
+  int num_candidates;            /* 0 .. the matcher's max_candidates: the frame's pairs, in this order */
+  const int* candidates;         /* [num_candidates] store ids, each in [-1, inserted); -1 (what top_id holds beyond the last document) */
+                                 /* gives an EMPTY pair                                                                               */
+} slslam_descriptor_query;
+typedef struct slslam_descriptor_result {
+  int    status;                 /* SLSLAM_DESC_*: INVALID_DESCRIPTOR when one of the query's n D floats is not finite, else EMPTY when  */
+                                 /* n = 0 or the candidate is -1; unless OK no pair is evaluated and the arrays say "none"              */
+  int    num_matched;            /* match[a] >= 0                                                                                        */
+  int    num_keyframe_descriptors;   /* m of the candidate (0 for candidate -1): the length of best_query                              */
+  int*   match;                  /* in: caller-owned arrays, any of them may be NULL; out: as above.  [n]                                */
+  int*   best;                   /* [n] */
+  float* best_distance;          /* [n] */
+  float* second_distance;        /* [n] */
+  int*   num_admissible;         /* [n] */
+  int*   best_query;             /* [m]; a caller that does not track m passes max_descriptors entries */
+} slslam_descriptor_result;
+typedef struct slslam_descriptor_matcher slslam_descriptor_matcher;
+
+/* device < 0 selects the current HIP device.  1 <= D <= 128 and 1 <= max_descriptors <= 512 (descriptors of a frame): the place
+ * recogniser's limits; 1 <= max_keyframes: the store's one device block [max_keyframes][max_descriptors][D], made at the first insert;
+ * 1 <= max_frames and 1 <= max_candidates <= 8 (candidates of one frame): what the run's one device block and one page-locked block are
+ * made for at the first run.  A run of more frames makes larger ones; a run that fits allocates nothing.  Touches no device. */
+int  slslam_descriptor_matcher_create(int device, int D, int max_keyframes, int max_descriptors, int max_frames, int max_candidates,
+                                      slslam_descriptor_matcher** out);
+void slslam_descriptor_matcher_destroy(slslam_descriptor_matcher* matcher);
+/* Uploads one keyframe's descriptors [n D].  *status (may be NULL): SLSLAM_DESC_OK; EMPTY (n = 0) or INVALID_DESCRIPTOR (a non-finite
+ * float): the store is unchanged.  *id (may be NULL): the keyframe's id, -1 when refused.  n < 0, n > max_descriptors or a missing
+ * array: SLSLAM_ERR_INVALID_ARGUMENT; SLSLAM_ERR_STATE: max_keyframes keyframes are in. */
+int  slslam_descriptor_matcher_insert(slslam_descriptor_matcher* matcher, int n, const float* descriptors, int* status, int* id);
+/* queries[F]; out[num_pairs], frame-major: the pairs of frame 0 in the order of its candidates, then those of frame 1, ...; num_pairs
+ * must be the sum of num_candidates.  ratio, max_distance as above (neither may be NaN).  Every argument is validated before an output
+ * is written or the device is asked - a negative count, a missing array of a non-zero count, n beyond max_descriptors, more candidates
+ * than max_candidates, a candidate outside [-1, inserted), a wrong num_pairs, a NaN: SLSLAM_ERR_INVALID_ARGUMENT, outputs untouched.
+ * Synchronous; host pointers; one upload, two launches (per pair, finish) and one download per call whatever F; a frame's descriptors
+ * are uploaded once for all its candidates. */
+int  slslam_descriptor_matcher_run(slslam_descriptor_matcher* matcher, int num_frames, const slslam_descriptor_query* queries, double ratio,
+                                   double max_distance, int num_pairs, slslam_descriptor_result* out);
+/* Keyframes inserted.  The pointer may be NULL. */
+int  slslam_descriptor_matcher_size(const slslam_descriptor_matcher* matcher, int* inserted);
+/* Since create: inserts + runs, and how often the store or the run's blocks were made or made larger.  Either pointer may be NULL. */
+int  slslam_descriptor_matcher_stats(const slslam_descriptor_matcher* matcher, long long* calls, long long* allocations);
+/* One query frame [n D] against one keyframe [m D], one call (its own buffers, made and freed); n, m <= 512.  The keyframe goes through
+ * the store's insert: m = 0 gives EMPTY, a non-finite keyframe float INVALID_DESCRIPTOR, num_keyframe_descriptors 0 either way. */
+int  slslam_match_descriptors(int D, int n, const float* query, int m, const float* keyframe, double ratio, double max_distance,
+                              slslam_descriptor_result* out);
 
 /* ------------------------------------------------------------------ training a vocabulary tree: hierarchical spherical k-means
  * Makes the nodes slslam_voctree_create takes from the caller's own descriptors (csrc/voctree_train.h, host/voctree_host.h, DESIGN.md

@@ -110,6 +110,17 @@ class PlaceResult(C.Structure):
                 ("top_id", C.POINTER(C.c_int)), ("top_score", C.POINTER(C.c_float))]
 
 
+class DescriptorQuery(C.Structure):
+    _fields_ = [("num_descriptors", C.c_int), ("descriptors", C.POINTER(C.c_float)), ("num_candidates", C.c_int),
+                ("candidates", C.POINTER(C.c_int))]
+
+
+class DescriptorResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("num_matched", C.c_int), ("num_keyframe_descriptors", C.c_int), ("match", C.POINTER(C.c_int)),
+                ("best", C.POINTER(C.c_int)), ("best_distance", C.POINTER(C.c_float)), ("second_distance", C.POINTER(C.c_float)),
+                ("num_admissible", C.POINTER(C.c_int)), ("best_query", C.POINTER(C.c_int))]
+
+
 class VocTreeTrainOptions(C.Structure):
     _fields_ = [("K", C.c_int), ("L", C.c_int), ("D", C.c_int), ("max_iterations", C.c_int), ("seed", C.c_ulonglong)]
 
@@ -121,6 +132,7 @@ class VocTreeTrainReport(C.Structure):
 
 
 PLACE_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_DESCRIPTOR"}
+DESC_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_DESCRIPTOR"}
 TRI_MULTIVIEW, TRI_STEREO, TRI_CONSTANT, TRI_NO_OBSERVATIONS, TRI_INVALID = 0, 1, 2, 3, 4
 TRI_STATUS = {0: "MULTIVIEW", 1: "STEREO", 2: "CONSTANT", 3: "NO_OBSERVATIONS", 4: "INVALID"}
 LINE_REFINED, LINE_CONSTANT, LINE_NO_OBSERVATIONS, LINE_INVALID = 0, 1, 2, 3
@@ -171,6 +183,8 @@ EXPORTS = [
     "slslam_voctree_create", "slslam_voctree_load", "slslam_voctree_destroy", "slslam_place_db_create", "slslam_place_db_destroy",
     "slslam_place_db_insert", "slslam_place_db_run", "slslam_place_db_size", "slslam_place_db_virtual", "slslam_place_db_stats",
     "slslam_place_filter_create", "slslam_place_filter_destroy", "slslam_place_filter_update",
+    "slslam_descriptor_matcher_create", "slslam_descriptor_matcher_destroy", "slslam_descriptor_matcher_insert",
+    "slslam_descriptor_matcher_run", "slslam_descriptor_matcher_size", "slslam_descriptor_matcher_stats", "slslam_match_descriptors",
     "slslam_voctree_train", "slslam_voctree_save", "slslam_voctree_centres", "slslam_voctree_key", "slslam_debug_voctree_step", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -332,7 +346,18 @@ def lib():
         L.slslam_place_filter_destroy.argtypes = [vp]
         L.slslam_place_filter_destroy.restype = None
         L.slslam_place_filter_update.argtypes = [vp, C.c_int, fp, fp, ip, ip]
-    if hasattr(L, "slslam_voctree_train"):       # (likewise: a library built before the tree trainer existed)
+    if hasattr(L, "slslam_match_descriptors"):   # (likewise: a library built before the descriptor matcher existed)
+        fp = C.POINTER(C.c_float)
+        L.slslam_descriptor_matcher_create.argtypes = [C.c_int] * 6 + [C.POINTER(vp)]
+        L.slslam_descriptor_matcher_destroy.argtypes = [vp]
+        L.slslam_descriptor_matcher_destroy.restype = None
+        L.slslam_descriptor_matcher_insert.argtypes = [vp, C.c_int, fp, ip, ip]
+        L.slslam_descriptor_matcher_run.argtypes = [vp, C.c_int, C.POINTER(DescriptorQuery), C.c_double, C.c_double, C.c_int,
+                                                    C.POINTER(DescriptorResult)]
+        L.slslam_descriptor_matcher_size.argtypes = [vp, ip]
+        L.slslam_descriptor_matcher_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+        L.slslam_match_descriptors.argtypes = [C.c_int, C.c_int, fp, C.c_int, fp, C.c_double, C.c_double, C.POINTER(DescriptorResult)]
+    if hasattr(L, "slslam_voctree_train"):      # (likewise: a library built before the tree trainer existed)
         fp, lp = C.POINTER(C.c_float), C.POINTER(C.c_longlong)
         L.slslam_voctree_train.argtypes = [C.c_int, C.POINTER(VocTreeTrainOptions), C.c_longlong, fp, fp, ip, C.POINTER(VocTreeTrainReport)]
         L.slslam_voctree_save.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, fp]
@@ -1894,3 +1919,113 @@ def place_candidates(db, filt, frame):
     if db.insert(frame)["status"] != "OK":
         return False, -1, None
     return filt.update(db.run([frame])[0]["likelihood"])
+
+
+# ----------------------------------------------------------------------------- descriptor matching (slslam_descriptor_matcher_*)
+def _desc_buffers(n, m):
+    b = {"match": np.full(max(n, 1), -2, dtype=np.int32), "best": np.full(max(n, 1), -2, dtype=np.int32),
+         "best_distance": np.zeros(max(n, 1), dtype=np.float32), "second_distance": np.zeros(max(n, 1), dtype=np.float32),
+         "num_admissible": np.zeros(max(n, 1), dtype=np.int32), "best_query": np.full(max(m, 1), -2, dtype=np.int32)}
+    r = DescriptorResult(-1, 0, 0, _ip(b["match"]), _ip(b["best"]), _fp(b["best_distance"]), _fp(b["second_distance"]),
+                         _ip(b["num_admissible"]), _ip(b["best_query"]))
+    return r, b
+
+
+def _desc_dict(r, b, n, candidate):
+    out = {"status": DESC_STATUS[r.status], "num_matched": r.num_matched, "candidate": candidate}
+    out.update({key: (a[:r.num_keyframe_descriptors] if key == "best_query" else a[:n]) for key, a in b.items()})
+    return out
+
+
+def match_descriptors(query, keyframe, ratio=1.5, max_distance=float("inf")):
+    """One frame's descriptors [n, D] against one keyframe's [m, D] by the place recogniser's distance (slslam_match_descriptors).
+    Returns dict(status, num_matched, candidate (0), match [n], best [n], best_distance [n] float32, second_distance [n] float32,
+    num_admissible [n], best_query [m])."""
+    q = np.ascontiguousarray(query, dtype=np.float32)
+    k = np.ascontiguousarray(keyframe, dtype=np.float32)
+    if q.ndim != 2 or k.ndim != 2 or q.shape[1] != k.shape[1]:
+        raise ValueError("query and keyframe must be [n, D] and [m, D]")
+    r, b = _desc_buffers(len(q), len(k))
+    _check(lib().slslam_match_descriptors(q.shape[1], len(q), _fp(q), len(k), _fp(k), float(ratio), float(max_distance), C.byref(r)),
+           "slslam_match_descriptors")
+    return _desc_dict(r, b, len(q), 0)
+
+
+class DescriptorMatcher:
+    """slslam_descriptor_matcher: the descriptors of the inserted keyframes on the device, and many (frame, candidate keyframe) pairs
+    matched per call; buffers kept between calls.  A frame is its descriptors [n, D] float32.  Fed the frames a PlaceDB is fed, a
+    keyframe's id here is its document id there."""
+
+    def __init__(self, D, max_keyframes=4096, max_descriptors=512, max_frames=64, max_candidates=3, device=-1):
+        self.D = int(D)
+        self._h = C.c_void_p()
+        _check(lib().slslam_descriptor_matcher_create(int(device), self.D, int(max_keyframes), int(max_descriptors), int(max_frames),
+                                                      int(max_candidates), C.byref(self._h)), "slslam_descriptor_matcher_create")
+        self._counts = []                                          # descriptors of every inserted keyframe
+
+    def close(self):
+        if self._h:
+            lib().slslam_descriptor_matcher_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _frame(self, fr):
+        return np.ascontiguousarray(fr, dtype=np.float32).reshape(-1, self.D)
+
+    def insert(self, frame):
+        """Returns dict(status, id): id is the keyframe's number in the store, -1 when the frame is refused."""
+        d = self._frame(frame)
+        st, kid = C.c_int(-1), C.c_int(-1)
+        _check(lib().slslam_descriptor_matcher_insert(self._h, len(d), _fp(d), C.byref(st), C.byref(kid)), "slslam_descriptor_matcher_insert")
+        if kid.value >= 0:
+            self._counts.append(len(d))
+        return {"status": DESC_STATUS[st.value], "id": kid.value}
+
+    def run(self, queries, ratio=1.5, max_distance=float("inf")):
+        """queries: (frame, candidates) per query frame, candidates a sequence of store ids (-1: none).  Returns per query the list of
+        its pairs' results, each a dict as match_descriptors returns with `candidate` the store id."""
+        n = len(queries)
+        qs, keep, bufs, cand = (DescriptorQuery * max(n, 1))(), [], [], []
+        for i, (fr, cs) in enumerate(queries):
+            d, c = self._frame(fr), np.ascontiguousarray(cs, dtype=np.int32).reshape(-1)
+            qs[i] = DescriptorQuery(len(d), _fp(d), len(c), _ip(c))
+            keep.append((d, c))
+            for kid in c.tolist():
+                cand.append((i, len(d), kid))
+        outs = (DescriptorResult * max(len(cand), 1))()
+        for p, (i, nd, kid) in enumerate(cand):
+            outs[p], b = _desc_buffers(nd, self._counts[kid] if 0 <= kid < len(self._counts) else 0)
+            bufs.append(b)
+        _check(lib().slslam_descriptor_matcher_run(self._h, n, qs, float(ratio), float(max_distance), len(cand), outs),
+               "slslam_descriptor_matcher_run")
+        res = [[] for _ in range(n)]
+        for p, (i, nd, kid) in enumerate(cand):
+            res[i].append(_desc_dict(outs[p], bufs[p], nd, kid))
+        return res
+
+    def size(self):
+        a = C.c_int(0)
+        _check(lib().slslam_descriptor_matcher_size(self._h, C.byref(a)), "slslam_descriptor_matcher_size")
+        return a.value
+
+    def stats(self):
+        c, a = C.c_longlong(0), C.c_longlong(0)
+        _check(lib().slslam_descriptor_matcher_stats(self._h, C.byref(c), C.byref(a)), "slslam_descriptor_matcher_stats")
+        return {"calls": c.value, "allocations": a.value}
+
+
+def loop_matches(matcher, frame, candidates, ratio=1.5, max_distance=float("inf")):
+    """The link between place_candidates and matched_trials: one frame against the candidate keyframes a closed loop names (say the
+    reported document and its neighbours).  Returns (candidate, result): the candidate with the most matches, the lowest id on ties,
+    and its result as DescriptorMatcher.run returns it; (-1, None) when no candidate gives an OK pair.  result["match"] is what
+    matched_trials takes, with keyframe descriptor j standing for map line j."""
+    best = None
+    for r in matcher.run([(frame, candidates)], ratio=ratio, max_distance=max_distance)[0]:
+        if r["status"] == "OK" and (best is None or (r["num_matched"], -r["candidate"]) > (best["num_matched"], -best["candidate"])):
+            best = r
+    return (best["candidate"], best) if best is not None else (-1, None)

@@ -517,3 +517,27 @@ def make_place_sequence(seed, places=60, words_per_place=40, noise=0.05, revisit
         d = base[p] + noise * rng.standard_normal((words_per_place, dim))
         frames.append((d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32))
     return {"frames": frames, "place": np.array(order, dtype=np.int32), "first_pass": places}
+
+
+def make_descriptor_pair(seed, n=150, dim=72, noise=0.03, outliers=0):
+    """Two views of the same n random unit descriptors of `dim` floats - a keyframe and a later frame that sees the same features -,
+    each with Gaussian noise of that standard deviation per component, renormalised, each with `outliers` further descriptors the other
+    view does not hold, each in a shuffled order of its own.  Returns dict(query [n + outliers, dim] float32, keyframe likewise,
+    query_id / keyframe_id: the feature (0 .. n-1) a row shows, -1 for an outlier, truth [n + outliers]: the keyframe row that shows
+    the feature of query row a, -1 for an outlier)."""
+    rng = np.random.default_rng(np.random.SeedSequence([14, int(seed)]))
+    n, o = int(n), int(outliers)
+    base = rng.standard_normal((n, dim))
+    base /= np.linalg.norm(base, axis=1, keepdims=True)
+    views, ids = [], []
+    for _ in range(2):
+        d = np.concatenate([base + noise * rng.standard_normal((n, dim)), rng.standard_normal((o, dim))])
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        perm = rng.permutation(n + o)
+        views.append(d[perm].astype(np.float32))
+        ids.append(np.where(perm < n, perm, -1).astype(np.int32))
+    row_of = np.full(n + 1, -1, dtype=np.int32)                 # feature -> keyframe row (the last entry: an outlier's -1)
+    kf_rows = np.nonzero(ids[1] >= 0)[0]
+    row_of[ids[1][kf_rows]] = kf_rows
+    return {"query": views[0], "keyframe": views[1], "query_id": ids[0], "keyframe_id": ids[1],
+            "truth": row_of[ids[0]]}
