@@ -391,6 +391,33 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
+class _Handle:
+    """An object of the library behind a pointer: close() destroys it once, and the end of the Python object closes it.  A class names
+    the library's destroy (_DESTROY) and, where it is not _h, the attribute that holds the pointer (_H)."""
+    _H, _DESTROY = "_h", None
+
+    def close(self):
+        if getattr(self, self._H):
+            getattr(lib(), self._DESTROY)(getattr(self, self._H))
+            setattr(self, self._H, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _CountedHandle(_Handle):
+    """A handle that counts its calls and the times it allocated (_STATS: the library's getter of the two)."""
+    _STATS = None
+
+    def stats(self):
+        c, a = C.c_longlong(0), C.c_longlong(0)
+        _check(getattr(lib(), self._STATS)(getattr(self, self._H), C.byref(c), C.byref(a)), self._STATS)
+        return {"calls": c.value, "allocations": a.value}
+
+
 def default_options(**kw):
     o = SolverOptions()
     lib().slslam_default_options(C.byref(o))
@@ -581,25 +608,15 @@ def lba_refine_lines(w, params=None, **opt):
     return arr.params, res, _summary_dict(tot)
 
 
-class LineRefiner:
+class LineRefiner(_CountedHandle):
     """slslam_line_refiner: every line of every window of a run refined in one launch, buffers reused between runs."""
+    _H, _DESTROY, _STATS = "h", "slslam_line_refiner_destroy", "slslam_line_refiner_stats"
 
     def __init__(self, max_lines, max_observations, device=-1, **opt):
         self.h = C.c_void_p()
         o = default_options(**opt)
         _check(lib().slslam_line_refiner_create(device, C.byref(o), int(max_lines), int(max_observations), C.byref(self.h)),
                "slslam_line_refiner_create")
-
-    def close(self):
-        if self.h:
-            lib().slslam_line_refiner_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, windows, params=None):
         """windows: dicts as for lba_solve (params: their start vectors, else each window's own).
@@ -612,11 +629,6 @@ class LineRefiner:
         tot = (Summary * max(n, 1))()
         _check(lib().slslam_line_refiner_run(self.h, n, cw, rp, tot), "slslam_line_refiner_run")
         return [a.params for a in arrs], res, [_summary_dict(tot[i]) for i in range(n)]
-
-    def stats(self):
-        c, a = C.c_longlong(0), C.c_longlong(0)
-        _check(lib().slslam_line_refiner_stats(self.h, C.byref(c), C.byref(a)), "slslam_line_refiner_stats")
-        return {"calls": c.value, "allocations": a.value}
 
 
 def lba_triangulate_lines(w, method=1, inverse_depth=0.1, min_parallax=0.0, **opt):
@@ -632,25 +644,15 @@ def lba_triangulate_lines(w, method=1, inverse_depth=0.1, min_parallax=0.0, **op
     return arr.params, res, av
 
 
-class LineTriangulator:
+class LineTriangulator(_CountedHandle):
     """slslam_line_triangulator: every line of every window of a run made in one launch, buffers reused between runs."""
+    _H, _DESTROY, _STATS = "h", "slslam_line_triangulator_destroy", "slslam_line_triangulator_stats"
 
     def __init__(self, max_lines, max_observations, device=-1, **opt):
         self.h = C.c_void_p()
         o = default_options(**opt)
         _check(lib().slslam_line_triangulator_create(device, C.byref(o), int(max_lines), int(max_observations), C.byref(self.h)),
                "slslam_line_triangulator_create")
-
-    def close(self):
-        if self.h:
-            lib().slslam_line_triangulator_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, windows, method=1, inverse_depth=0.1, min_parallax=0.0):
         """windows: dicts as for lba_solve.  Returns (list of parameter vectors, list of per-line structured arrays, list of lines_av)."""
@@ -664,11 +666,6 @@ class LineTriangulator:
         _check(lib().slslam_line_triangulator_run(self.h, n, cw, int(method), float(inverse_depth), float(min_parallax), rp, ap),
                "slslam_line_triangulator_run")
         return [a.params for a in arrs], res, avs
-
-    def stats(self):
-        c, a = C.c_longlong(0), C.c_longlong(0)
-        _check(lib().slslam_line_triangulator_stats(self.h, C.byref(c), C.byref(a)), "slslam_line_triangulator_stats")
-        return {"calls": c.value, "allocations": a.value}
 
     def timing(self):
         """Host wall-clock milliseconds of the last run: dict(layout, upload, kernel, download, scatter)."""
@@ -693,8 +690,9 @@ def triangulate_host(observations, cameras, baseline=0.12, method=1, inverse_dep
     return {"status": st.value, "num_planes": pl.value, "clamped": cl.value, "eigenvalues": eig, "av": av, "offdiagonal": off.value}
 
 
-class LBABatch:
+class LBABatch(_Handle):
     """Many independent windows resident in HBM, solved in lock-step (slslam_lba_batch_*)."""
+    _DESTROY = "slslam_lba_batch_destroy"
 
     def __init__(self, device=-1):
         self._h = C.c_void_p()
@@ -702,17 +700,6 @@ class LBABatch:
         self.sizes = []          # (num_cameras, num_lines) per window
         self.num_obs = []        # observations per window
         self.finalized = False
-
-    def close(self):
-        if self._h:
-            lib().slslam_lba_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def add(self, w, params=None):
         arr = _WindowArrays(w, params)
@@ -978,26 +965,16 @@ def debug_device_pack(w, grouping=0, clocks=None):
                           lane_map=lane_map[:64 * int(counts[1])].reshape(-1, 64))
 
 
-class LBAStream:
+class LBAStream(_Handle):
     """slslam_lba_stream_*: `depth` refillable batches in flight; submit(WindowSet) -> ticket, collect(ticket) -> summaries, the solved
     parameters land in the WindowSet's parameter arrays."""
+    _DESTROY = "slslam_lba_stream_destroy"
 
     def __init__(self, device=-1, depth=3, **opt):
         self._h = C.c_void_p()
         o = default_options(**opt)
         _check(lib().slslam_lba_stream_create(int(device), C.byref(o), int(depth), C.byref(self._h)), "slslam_lba_stream_create")
         self._live = {}
-
-    def close(self):
-        if self._h:
-            lib().slslam_lba_stream_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def submit(self, ws):
         t = C.c_int(-1)
@@ -1268,9 +1245,10 @@ def lba_odometry_edges(cov_result, cameras, pairs, sigma2=1.0):
     return cc, po_edge_statistics(xa, xb, cc, saa, sbb, sab, None, sigma2)
 
 
-class POBatch:
+class POBatch(_Handle):
     """Many pose graphs solved together (slslam_po_batch_*): each graph gets what po_solve gives it.  add() copies the graph,
     finalize() uploads (the first call that needs a device), solve() enqueues, download() waits and brings the results back."""
+    _DESTROY = "slslam_po_batch_destroy"
 
     def __init__(self, device=-1):
         self._h = C.c_void_p()
@@ -1365,17 +1343,6 @@ class POBatch:
         n = C.c_int(0)
         _check(lib().slslam_po_batch_get_trace(self._h, int(i), tr, cap, C.byref(n)), "slslam_po_batch_get_trace")
         return _trace_list(tr, min(n.value, cap))
-
-    def close(self):
-        if self._h:
-            lib().slslam_po_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def po_solve_batch(graphs, trace_cap=64, stream=None, **opt):
@@ -1530,9 +1497,10 @@ def _bits_to_mask(bits, k):
     return mask
 
 
-class PoseEstimator:
+class PoseEstimator(_Handle):
     """SLAM::pose_estimation for many frames per call (slslam_pose_estimator_*): RANSAC, motion-only BA on its inliers, final inliers.
     Keeps its device buffers and its refillable motion-only batch between calls."""
+    _DESTROY = "slslam_pose_estimator_destroy"
 
     def __init__(self, max_frames=16, max_lines=512, device=-1, covariance=False, **opt):
         self._h = C.c_void_p()
@@ -1556,17 +1524,6 @@ class PoseEstimator:
         _check(lib().slslam_pose_estimator_get_covariance(self._h, int(frame), C.byref(st), _dp(cons), _dp(cov), C.byref(s2), C.byref(dof)),
                "slslam_pose_estimator_get_covariance")
         return {"constraint": cons, "covariance": cov, "cov_status": st.value, "sigma2": s2.value, "dof": dof.value}
-
-    def close(self):
-        if self._h:
-            lib().slslam_pose_estimator_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, frames, baseline=0.12, error_thr=5.0 / 406.05, prob_free_outliers=0.999, max_trials=1000):
         """frames = list of dicts with obs0, obs1, lines, samples (as make_ransac_pair returns).  Returns one dict per frame:
@@ -1637,20 +1594,28 @@ def _match_frame(fr):
     return MatchFrame(len(obs), len(ln), _dp(pose), _dp(obs), _dp(ln), _dp(ext) if ext is not None else None), (pose, obs, ln, ext)
 
 
-def _match_buffers(k, l):
-    b = {"match": np.full(max(k, 1), -2, dtype=np.int32), "best_line": np.full(max(k, 1), -2, dtype=np.int32),
-         "best_error": np.zeros(max(k, 1), dtype=np.float32), "second_error": np.zeros(max(k, 1), dtype=np.float32),
-         "num_admissible": np.zeros(max(k, 1), dtype=np.int32), "best_observation": np.full(max(l, 1), -2, dtype=np.int32)}
-    fp = C.POINTER(C.c_float)
-    r = MatchResult(-1, 0, _ip(b["match"]), _ip(b["best_line"]), b["best_error"].ctypes.data_as(fp), b["second_error"].ctypes.data_as(fp),
-                    _ip(b["num_admissible"]), _ip(b["best_observation"]))
+def _mutual_buffers(result, keys, n, m):
+    """What the two matchers' results share: the six caller-owned arrays under the result struct's names for them - match, best, best
+    value, second value, number admissible [n] each, the best row of every column [m]; -2 in what holds indices, 0 elsewhere - and
+    the struct pointing at them."""
+    b = {k: np.full(max(m if i == 5 else n, 1), 0 if i in (2, 3, 4) else -2, dtype=np.float32 if i in (2, 3) else np.int32)
+         for i, k in enumerate(keys)}
+    r = result(status=-1, **{k: a.ctypes.data_as(C.POINTER(C.c_float if a.dtype == np.float32 else C.c_int)) for k, a in b.items()})
     return r, b
 
 
-def _match_dict(r, b, k, l):
-    out = {"status": MATCH_STATUS[r.status], "num_matched": r.num_matched}
-    out.update({key: (a[:l] if key == "best_observation" else a[:k]) for key, a in b.items()})
+def _mutual_dict(status, r, b, n, m, **extra):
+    out = dict(status=status[r.status], num_matched=r.num_matched, **extra)
+    out.update({k: a[:m if i == 5 else n] for i, (k, a) in enumerate(b.items())})
     return out
+
+
+def _match_buffers(k, l):
+    return _mutual_buffers(MatchResult, ("match", "best_line", "best_error", "second_error", "num_admissible", "best_observation"), k, l)
+
+
+def _match_dict(r, b, k, l):
+    return _mutual_dict(MATCH_STATUS, r, b, k, l)
 
 
 def match_lines(frame, baseline=0.12, error_thr=5.0 / 406.05, ratio=1.5, margin=0.0):
@@ -1664,24 +1629,14 @@ def match_lines(frame, baseline=0.12, error_thr=5.0 / 406.05, ratio=1.5, margin=
     return _match_dict(r, b, mf.num_observations, mf.num_lines)
 
 
-class LineMatcher:
+class LineMatcher(_CountedHandle):
     """slslam_line_matcher: many frames per call, every observation of a frame against every line of its map; buffers kept between runs."""
+    _DESTROY, _STATS = "slslam_line_matcher_destroy", "slslam_line_matcher_stats"
 
     def __init__(self, max_frames=16, max_observations=512, max_lines=4096, device=-1):
         self._h = C.c_void_p()
         _check(lib().slslam_line_matcher_create(int(device), int(max_frames), int(max_observations), int(max_lines), C.byref(self._h)),
                "slslam_line_matcher_create")
-
-    def close(self):
-        if self._h:
-            lib().slslam_line_matcher_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, frames, baseline=0.12, error_thr=5.0 / 406.05, ratio=1.5, margin=0.0):
         """frames: dicts as match_lines takes.  Returns one dict per frame, as match_lines returns."""
@@ -1695,11 +1650,6 @@ class LineMatcher:
         _check(lib().slslam_line_matcher_run(self._h, n, mfs, float(baseline), float(error_thr), float(ratio), float(margin), outs),
                "slslam_line_matcher_run")
         return [_match_dict(outs[i], bufs[i], mfs[i].num_observations, mfs[i].num_lines) for i in range(n)]
-
-    def stats(self):
-        c, a = C.c_longlong(0), C.c_longlong(0)
-        _check(lib().slslam_line_matcher_stats(self._h, C.byref(c), C.byref(a)), "slslam_line_matcher_stats")
-        return {"calls": c.value, "allocations": a.value}
 
 
 def matched_trials(frame, result, map_observations, num_trials=1001, sample_size=5, seed=0):
@@ -1730,9 +1680,10 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-class VocTree:
+class VocTree(_Handle):
     """slslam_voctree: K children per node, L levels, descriptors of D floats.  nodes: the interior nodes [(K^L - 1) / (K - 1), K, D]
     breadth-first (any shape of that many floats), or path: a file of exactly those floats."""
+    _DESTROY = "slslam_voctree_destroy"
 
     def __init__(self, K, L, D, nodes=None, path=None, device=-1):
         self.K, self.L, self.D = int(K), int(L), int(D)
@@ -1760,17 +1711,6 @@ class VocTree:
         if getattr(self, "nodes", None) is None:
             raise ValueError("this tree was loaded from a file")
         save_voctree(path, self.nodes)
-
-    def close(self):
-        if self._h:
-            lib().slslam_voctree_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def train_voctree(descriptors, K, L, max_iterations=10, seed=0, device=-1, timing=False):
@@ -1812,26 +1752,16 @@ def _place_frame(tree, fr):
     return PlaceFrame(len(d), _fp(d)), d
 
 
-class PlaceDB:
+class PlaceDB(_CountedHandle):
     """slslam_place_db: the documents of the inserted keyframes and queries against the visible ones; buffers kept between calls.
     A frame is its descriptors [n, D] float32."""
+    _DESTROY, _STATS = "slslam_place_db_destroy", "slslam_place_db_stats"
 
     def __init__(self, tree, max_docs=4096, max_words=512, max_frames=64, recent=40, num_avg_words=100):
         self.tree = tree                                           # (the database uses the tree: keep it alive)
         self._h = C.c_void_p()
         _check(lib().slslam_place_db_create(tree._h, int(max_docs), int(max_words), int(max_frames), int(recent), int(num_avg_words),
                                             C.byref(self._h)), "slslam_place_db_create")
-
-    def close(self):
-        if self._h:
-            lib().slslam_place_db_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def insert(self, frame):
         """Returns dict(status, words [n])."""
@@ -1875,31 +1805,16 @@ class PlaceDB:
         _check(lib().slslam_place_db_virtual(self._h, _ip(w), None), "slslam_place_db_virtual")
         return w[:n.value]
 
-    def stats(self):
-        c, a = C.c_longlong(0), C.c_longlong(0)
-        _check(lib().slslam_place_db_stats(self._h, C.byref(c), C.byref(a)), "slslam_place_db_stats")
-        return {"calls": c.value, "allocations": a.value}
 
-
-class PlaceFilter:
+class PlaceFilter(_Handle):
     """slslam_place_filter: the Bayes filter over (no place, visible documents) and the loop decision.  Defaults: the reference's indoor
     preset (with recent = min_docs = 40).  Needs no device."""
+    _DESTROY = "slslam_place_filter_destroy"
 
     def __init__(self, sigma=1.0, threshold=0.7, seq_len=10, min_docs=40):
         self._h = C.c_void_p()
         _check(lib().slslam_place_filter_create(float(sigma), float(threshold), int(seq_len), int(min_docs), C.byref(self._h)),
                "slslam_place_filter_create")
-
-    def close(self):
-        if self._h:
-            lib().slslam_place_filter_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def update(self, likelihood):
         """likelihood [N + 1] as PlaceDB.run returns it.  Returns (loop, keyframe, posterior [N + 1])."""
@@ -1923,18 +1838,11 @@ def place_candidates(db, filt, frame):
 
 # ----------------------------------------------------------------------------- descriptor matching (slslam_descriptor_matcher_*)
 def _desc_buffers(n, m):
-    b = {"match": np.full(max(n, 1), -2, dtype=np.int32), "best": np.full(max(n, 1), -2, dtype=np.int32),
-         "best_distance": np.zeros(max(n, 1), dtype=np.float32), "second_distance": np.zeros(max(n, 1), dtype=np.float32),
-         "num_admissible": np.zeros(max(n, 1), dtype=np.int32), "best_query": np.full(max(m, 1), -2, dtype=np.int32)}
-    r = DescriptorResult(-1, 0, 0, _ip(b["match"]), _ip(b["best"]), _fp(b["best_distance"]), _fp(b["second_distance"]),
-                         _ip(b["num_admissible"]), _ip(b["best_query"]))
-    return r, b
+    return _mutual_buffers(DescriptorResult, ("match", "best", "best_distance", "second_distance", "num_admissible", "best_query"), n, m)
 
 
 def _desc_dict(r, b, n, candidate):
-    out = {"status": DESC_STATUS[r.status], "num_matched": r.num_matched, "candidate": candidate}
-    out.update({key: (a[:r.num_keyframe_descriptors] if key == "best_query" else a[:n]) for key, a in b.items()})
-    return out
+    return _mutual_dict(DESC_STATUS, r, b, n, r.num_keyframe_descriptors, candidate=candidate)
 
 
 def match_descriptors(query, keyframe, ratio=1.5, max_distance=float("inf")):
@@ -1951,10 +1859,11 @@ def match_descriptors(query, keyframe, ratio=1.5, max_distance=float("inf")):
     return _desc_dict(r, b, len(q), 0)
 
 
-class DescriptorMatcher:
+class DescriptorMatcher(_CountedHandle):
     """slslam_descriptor_matcher: the descriptors of the inserted keyframes on the device, and many (frame, candidate keyframe) pairs
     matched per call; buffers kept between calls.  A frame is its descriptors [n, D] float32.  Fed the frames a PlaceDB is fed, a
     keyframe's id here is its document id there."""
+    _DESTROY, _STATS = "slslam_descriptor_matcher_destroy", "slslam_descriptor_matcher_stats"
 
     def __init__(self, D, max_keyframes=4096, max_descriptors=512, max_frames=64, max_candidates=3, device=-1):
         self.D = int(D)
@@ -1962,17 +1871,6 @@ class DescriptorMatcher:
         _check(lib().slslam_descriptor_matcher_create(int(device), self.D, int(max_keyframes), int(max_descriptors), int(max_frames),
                                                       int(max_candidates), C.byref(self._h)), "slslam_descriptor_matcher_create")
         self._counts = []                                          # descriptors of every inserted keyframe
-
-    def close(self):
-        if self._h:
-            lib().slslam_descriptor_matcher_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _frame(self, fr):
         return np.ascontiguousarray(fr, dtype=np.float32).reshape(-1, self.D)
@@ -2012,11 +1910,6 @@ class DescriptorMatcher:
         a = C.c_int(0)
         _check(lib().slslam_descriptor_matcher_size(self._h, C.byref(a)), "slslam_descriptor_matcher_size")
         return a.value
-
-    def stats(self):
-        c, a = C.c_longlong(0), C.c_longlong(0)
-        _check(lib().slslam_descriptor_matcher_stats(self._h, C.byref(c), C.byref(a)), "slslam_descriptor_matcher_stats")
-        return {"calls": c.value, "allocations": a.value}
 
 
 def loop_matches(matcher, frame, candidates, ratio=1.5, max_distance=float("inf")):

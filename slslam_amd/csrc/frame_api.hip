@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "../../include/slslam_hip.h"
-#include "hip_status.h"
+#include "call_block.h"
 #include "ransac_device.h"
 #include "ransac_front.h"
 #include "gc_convert.h"
@@ -268,10 +268,8 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
   for (int f = 0; f < F; ++f)
     if (frames[f].num_lines > 0xfffe) return SLSLAM_ERR_INVALID_ARGUMENT;        // (the windows' index words hold 16-bit line indices)
   if (!trials_valid(F, frames, lines, true)) return SLSLAM_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
-  if (e->device >= 0) HIP_TRY(hipSetDevice(e->device));
-  else HIP_TRY(hipGetDevice(&e->device));
+  int rc = slslam::use_device(e->device);
+  if (rc != SLSLAM_OK) return rc;
   if (!e->ws.stream) HIP_TRY(hipStreamCreateWithFlags(&e->ws.stream, hipStreamNonBlocking));
   hipStream_t s = e->ws.stream;
   ++e->calls;
@@ -284,7 +282,7 @@ extern "C" int slslam_pose_estimator_run(slslam_pose_estimator* e, int num_frame
   for (slslam_ransac_trials& tr : gated)
     if (tr.num_lines < kMaxFeatNum) tr.num_trials = 0;
   Front fr;
-  int rc = front_ransac(e->ws, F, gated.data(), lines, baseline, error_thr, prob_free_outliers, max_trials, nullptr, &fr);
+  rc = front_ransac(e->ws, F, gated.data(), lines, baseline, error_thr, prob_free_outliers, max_trials, nullptr, &fr);
   if (rc != SLSLAM_OK) return rc;
   const std::vector<FrameDesc>& fd = fr.fd;
   const std::vector<TrialLoop>& loop = fr.loop;

@@ -1,5 +1,6 @@
 // slslam_amd/csrc/grow_buf.h — a buffer that only grows (its contents are not kept over a growth), in device, page-locked host or
-// plain host memory; every allocation is counted.  Used by the RANSAC front and the pose estimator.  Internal: not part of the C ABI.
+// plain host memory; every allocation is counted.  Used by every handle that keeps its blocks between calls.  Internal: not part of
+// the C ABI.
 #ifndef SLSLAM_GROW_BUF_H_
 #define SLSLAM_GROW_BUF_H_
 
@@ -7,6 +8,8 @@
 
 #include <algorithm>
 #include <cstdlib>
+
+#include "call_layout.h"
 
 namespace slslam {
 
@@ -42,8 +45,6 @@ struct GrowBuf {
     p = nullptr; n = 0;
   }
 };
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace slslam
 

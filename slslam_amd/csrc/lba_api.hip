@@ -28,7 +28,7 @@
 #include "lba_pack.h"
 #include "lba_device_build.h"
 #include "lba_resident.h"
-#include "hip_status.h"
+#include "call_block.h"
 #include "host_pool.h"
 #include "pinned_registry.h"
 
@@ -448,8 +448,8 @@ struct slslam_lba_batch {
 extern "C" int slslam_lba_batch_create(int device, slslam_lba_batch** out) {
   if (!out) return SLSLAM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  const int ndev = device_count();
+  if (ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
   if (device < 0) { if (hipGetDevice(&device) != hipSuccess) return SLSLAM_ERR_NO_DEVICE; }
   if (device >= ndev) return SLSLAM_ERR_INVALID_ARGUMENT;
   slslam_lba_batch* b = new (std::nothrow) slslam_lba_batch();
@@ -2737,8 +2737,7 @@ extern "C" int slslam_lba_solve(const slslam_lba_window* w, const slslam_solver_
 extern "C" int slslam_pinned_alloc(size_t bytes, void** out) {
   if (!out) return SLSLAM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   HIP_TRY(PinnedRegistry::get().alloc(bytes, out));
   return SLSLAM_OK;
 }
@@ -2748,8 +2747,7 @@ extern "C" int slslam_pinned_free(void* p) {
 }
 extern "C" int slslam_pinned_register(void* p, size_t bytes) {
   if (!p || !bytes) return SLSLAM_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   HIP_TRY(PinnedRegistry::get().register_range(p, bytes));
   return SLSLAM_OK;
 }
@@ -2778,8 +2776,7 @@ extern "C" int slslam_debug_device_pack_timed(const slslam_lba_window* w, int gr
                                               unsigned char* items, int* cam_cf, int max_tiles, int max_items, unsigned short* lane_map, unsigned* line_desc,
                                               int* status_out, unsigned long long* phase_clocks /*[16] or NULL*/) {
   if (!w || !out_counts || !status_out) return SLSLAM_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   const int C = w->num_cameras, L = w->num_lines, M = w->num_observations;
   if (C < 0 || L < 0 || M < 0 || C > kMaxCams || L > 0xfffe || M >= (1 << 24)) return SLSLAM_ERR_UNSUPPORTED;
   size_t lds_tiles = build_tiles_lds_bytes(L, L);
@@ -2926,8 +2923,8 @@ int drop_slot_batch(slslam_lba_stream* st, slslam_lba_stream::Slot& sl) {
 extern "C" int slslam_lba_stream_create(int device, const slslam_solver_options* opt, int depth, slslam_lba_stream** out) {
   if (!out) return SLSLAM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  const int ndev = device_count();
+  if (ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
   if (device < 0) { if (hipGetDevice(&device) != hipSuccess) return SLSLAM_ERR_NO_DEVICE; }
   if (device >= ndev || depth < 1 || depth > 8) return SLSLAM_ERR_INVALID_ARGUMENT;
   slslam_lba_stream* st = new (std::nothrow) slslam_lba_stream();

@@ -7,7 +7,7 @@
 
 #include <cmath>
 
-#include "grow_buf.h"
+#include "call_block.h"
 #include "lba_refine_layout.h"
 #include "lba_refine_lines.h"
 
@@ -48,10 +48,7 @@ extern "C" int slslam_line_refiner_create(int device, const slslam_solver_option
 extern "C" void slslam_line_refiner_destroy(slslam_line_refiner* r) { delete r; }
 
 extern "C" int slslam_line_refiner_stats(const slslam_line_refiner* r, long long* calls, long long* allocations) {
-  if (!r) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (calls) *calls = r->calls;
-  if (allocations) *allocations = r->allocations;
-  return SLSLAM_OK;
+  return handle_stats(r, calls, allocations);
 }
 
 extern "C" int slslam_line_refiner_run(slslam_line_refiner* r, int n, const slslam_lba_window* windows,
@@ -114,10 +111,8 @@ extern "C" int slslam_line_refiner_run(slslam_line_refiner* r, int n, const slsl
     ++r->calls;
 
     if (ngroups > 0) {
-      int ndev = 0;
-      if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
-      if (r->device >= 0) HIP_TRY(hipSetDevice(r->device));
-      else HIP_TRY(hipGetDevice(&r->device));
+      const int rc = use_device(r->device);
+      if (rc != SLSLAM_OK) return rc;
 
       // ---- the upload image: groups | cameras | line parameters | counts | observation cameras | observations (4 planes)
       const size_t o_grp = 0;

@@ -10,18 +10,15 @@
 //                   read by broadcast: every lane reads line j of the tile at the same address.  Per pair the four dot products and the
 //                   float accumulation (normals_error), the compare, for a frame with extents and only for pairs that passed it
 //                   segment_cut and the interval test, then the lane's running (best, second, count).  Lines go by in ascending order and
-//                   only a strictly smaller error replaces the best: the lowest line wins a tie whatever the launch geometry.  The best
-//                   observation of line l is a 64-bit minimum over (float bits of e << 32 | k) - e >= 0, so its bits order as e does, and
-//                   the low word breaks ties towards the lowest k -, taken across the wave by shuffles and once per wave by atomicMin on
-//                   global memory: a minimum does not depend on the order it is taken in.
-//   k_match_finish  lane <-> observation and lane <-> line: the mutual and ratio tests, best_observation out of its key, num_matched by a
-//                   ballot and one integer atomicAdd per wave.
-// No fp atomics, no sums of floating-point values across lanes: a frame's bytes do not depend on its place in the call.
+//                   the lowest line wins a tie (mutual_match.h: take_pair).  The key of line l's best observation (offer_key) carries
+//                   the float bits of e: e >= 0, so its bits order as e does.
+// The mutual and ratio tests are mutual_match.h's k_mutual_finish: observations are its rows, lines its columns.
 #ifndef SLSLAM_LINE_MATCH_H_
 #define SLSLAM_LINE_MATCH_H_
 
 #include <hip/hip_runtime.h>
 
+#include "mutual_match.h"
 #include "ransac_device.h"
 #include "segment_eval.h"
 
@@ -31,33 +28,25 @@
 namespace slslam_match {
 
 enum { kTile = 64, kLineValues = 6, kLineValuesExt = 14 };
-constexpr unsigned long long kNoObservation = ~0ull;
 
 // Per frame, where its inputs lie in the upload and its results in the output arrays
 struct FrameDesc {
   long long pose, obs, lines, ext;      // doubles: [12], [8 K], [6 L], [2 L] (ext < 0: the frame has no extents)
-  long long k0, l0;                     // the frame's first observation / line among those of all frames
-  int K, L;
+  slslam::Span span;                    // observations (a0, n) and lines (j0, m)
   int run, pad;                         // run = 0: EMPTY or INVALID_POSE - no pair is evaluated, the outputs say "nothing admissible"
 };
 
-// Where the results of all frames go: [F], then [Ktot] each, then [Ltot]
-struct Out {
-  int* num_matched;
-  int *match, *best_line, *num_admissible;
-  float *best_error, *second_error;
-  int* best_observation;
-};
+using Out = slslam::MatchOut;         // best = best_line, best_value / second_value = the errors, best_row = best_observation
 
 // blockIdx = (64 lines, frame)
 __global__ __launch_bounds__(64) void k_match_lines(const FrameDesc* __restrict__ fr, const double* __restrict__ dd, double baseline, double margin,
                                                     long long Ltot, double* __restrict__ soa) {
   const FrameDesc fd = fr[blockIdx.y];
   const int l = blockIdx.x * 64 + threadIdx.x;
-  if (!fd.run || l >= fd.L) return;
+  if (!fd.run || l >= fd.span.m) return;
   double n[2][3], pc[3], dc[3];
   slslam_ransac::line_normals(dd + fd.pose, dd + fd.lines + 6 * (long long)l, baseline, n, pc, dc);
-  double* o = soa + fd.l0 + l;
+  double* o = soa + fd.span.j0 + l;
 #pragma unroll
   for (int c = 0; c < 6; ++c) o[c * Ltot] = n[c / 3][c % 3];
   if (fd.ext < 0) return;
@@ -74,20 +63,20 @@ __device__ __forceinline__ void match_sweep(const FrameDesc& fd, const double* _
                                             float& second, int& best_line, int& count) {
   constexpr int NV = EXT ? kLineValuesExt : kLineValues;
   const int lane = threadIdx.x;
-  const double* src = soa + fd.l0;
+  const double* src = soa + fd.span.j0;
   const double el[4] = { ob[0], ob[1], ob[2], ob[3] };
   double nxt[NV];
 #pragma unroll
-  for (int c = 0; c < NV; ++c) nxt[c] = lane < fd.L ? src[c * Ltot + lane] : 0.0;
-  for (int l0 = 0; l0 < fd.L; l0 += kTile) {
+  for (int c = 0; c < NV; ++c) nxt[c] = lane < fd.span.m ? src[c * Ltot + lane] : 0.0;
+  for (int l0 = 0; l0 < fd.span.m; l0 += kTile) {
     __syncthreads();                                             // (the wave is done with the tile before)
 #pragma unroll
     for (int c = 0; c < NV; ++c) tile[NV * lane + c] = nxt[c];
     __syncthreads();
     const int ln = l0 + kTile + lane;
 #pragma unroll
-    for (int c = 0; c < NV; ++c) nxt[c] = ln < fd.L ? src[c * Ltot + ln] : 0.0;
-    const int nl = fd.L - l0 < kTile ? fd.L - l0 : kTile;
+    for (int c = 0; c < NV; ++c) nxt[c] = ln < fd.span.m ? src[c * Ltot + ln] : 0.0;
+    const int nl = fd.span.m - l0 < kTile ? fd.span.m - l0 : kTile;
     for (int j = 0; j < nl; ++j) {
       const double* t = tile + NV * j;
       const double n[2][3] = { { t[0], t[1], t[2] }, { t[3], t[4], t[5] } };
@@ -101,19 +90,8 @@ __device__ __forceinline__ void match_sweep(const FrameDesc& fd, const double* _
           adm = st == slslam::kSegObsUsed && hi >= t[12] && lo <= t[13];
         }
       }
-      if (__ballot(adm) != 0ull) {                                // (wave-uniform)
-        unsigned long long key = adm ? ((unsigned long long)__float_as_uint(e) << 32) | (unsigned)k : kNoObservation;
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long other = __shfl_xor(key, o);
-          key = other < key ? other : key;
-        }
-        if (lane == 0) atomicMin(&lbest[fd.l0 + l0 + j], key);
-      }
-      if (adm) {
-        ++count;
-        if (e < best) { second = best; best = e; best_line = l0 + j; }
-        else if (e < second) second = e;
-      }
+      slslam::offer_key(adm, __float_as_uint(e), k, lbest, fd.span.j0 + l0 + j);
+      slslam::take_pair(adm, e, l0 + j, best, second, best_line, count);
     }
   }
 }
@@ -124,8 +102,8 @@ __global__ __launch_bounds__(64) void k_match_pairs(const FrameDesc* __restrict_
   __shared__ __attribute__((aligned(16))) double tile[kTile * kLineValuesExt];
   const FrameDesc fd = fr[blockIdx.y];
   const int k = blockIdx.x * 64 + threadIdx.x;
-  if ((int)blockIdx.x * 64 >= fd.K) return;                      // (the whole wave)
-  const bool kvalid = k < fd.K;
+  if ((int)blockIdx.x * 64 >= fd.span.n) return;                      // (the whole wave)
+  const bool kvalid = k < fd.span.n;
   double ob[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) ob[q] = kvalid ? dd[fd.obs + 8 * (long long)k + q] : 0.0;
@@ -136,34 +114,8 @@ __global__ __launch_bounds__(64) void k_match_pairs(const FrameDesc* __restrict_
     else match_sweep<false>(fd, soa, Ltot, ob, k, kvalid, thr, tile, lbest, best, second, best_line, count);
   }
   if (!kvalid) return;
-  const long long at = fd.k0 + k;
-  out.best_line[at] = best_line; out.best_error[at] = best; out.second_error[at] = second; out.num_admissible[at] = count;
-}
-
-// blockIdx = (64 observations and 64 lines, frame)
-__global__ __launch_bounds__(64) void k_match_finish(const FrameDesc* __restrict__ fr, const unsigned long long* __restrict__ lbest, double ratio,
-                                                     Out out) {
-  const FrameDesc fd = fr[blockIdx.y];
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if ((int)blockIdx.x * 64 >= fd.K && (int)blockIdx.x * 64 >= fd.L) return;      // (the whole wave)
-  if (i < fd.L) {
-    const unsigned long long key = lbest[fd.l0 + i];
-    out.best_observation[fd.l0 + i] = key == kNoObservation ? -1 : (int)(unsigned)(key & 0xffffffffull);
-  }
-  bool matched = false;
-  if (i < fd.K) {
-    const long long at = fd.k0 + i;
-    const int bl = out.best_line[at];
-    if (bl >= 0) {
-      const unsigned long long key = lbest[fd.l0 + bl];
-      const bool mutual = key != kNoObservation && (int)(unsigned)(key & 0xffffffffull) == i;
-      const bool unambiguous = ratio <= 1.0 || (double)out.best_error[at] * ratio <= (double)out.second_error[at];
-      matched = mutual && unambiguous;
-    }
-    out.match[at] = matched ? bl : -1;
-  }
-  const int n = __popcll(__ballot(matched));
-  if (threadIdx.x == 0 && n > 0) atomicAdd(&out.num_matched[blockIdx.y], n);
+  const long long at = fd.span.a0 + k;
+  out.best[at] = best_line; out.best_value[at] = best; out.second_value[at] = second; out.num_admissible[at] = count;
 }
 
 }  // namespace slslam_match

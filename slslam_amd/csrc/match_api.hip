@@ -4,9 +4,9 @@
 //   lines    k_match_lines: the per-line part of the reprojection error, and of the overlap test, under each frame's pose
 //   pairs    k_match_pairs: every observation against every line of its frame -> per observation (best, second, count), per line the key
 //            of its best observation
-//   finish   k_match_finish: mutual and ratio tests, matches, num_matched
+//   finish   k_mutual_finish (mutual_match.h): mutual and ratio tests, matches, num_matched
 //   download one block [num_matched F | match, best_line, num_admissible, best_error, second_error: Ktot each | best_observation Ltot]
-// The frame index lies in the grid.  The kernels are in line_match.h.  No CPU fallback.
+// The frame index lies in the grid.  The kernels are in line_match.h, the scaffold in call_block.h.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,52 +16,39 @@
 #include <vector>
 
 #include "../../include/slslam_hip.h"
-#include "grow_buf.h"
-#include "hip_status.h"
+#include "call_block.h"
 #include "line_match.h"
 
 using namespace slslam_match;
-using slslam::align256;
-using slslam::GrowBuf;
-using slslam::Mem;
+using slslam::device_present;
 
 namespace {
 
 constexpr int kMaxGrid = 65535;         // what the y dimension of a grid takes: frames go in slices of it
 
 // Where everything of a call lies: the upload (the same offsets on the host and on the device), the device's work arrays behind it,
-// and the result block (the same offsets on the device and on the host)
-struct Layout {
+// and the result block (on the host behind the upload)
+struct CallLayout {
   size_t off_d = 0, in_bytes = 0;                        // upload: FrameDesc[F] at 0, doubles at off_d
-  size_t off_soa = 0, off_lbest = 0, off_out = 0, dev_bytes = 0;
-  size_t o_match = 0, o_line = 0, o_count = 0, o_best = 0, o_second = 0, o_obs = 0, out_bytes = 0;   // in the result block; num_matched[F] at 0
-  size_t host_bytes = 0;                                 // upload, then the result block at align256(in_bytes)
-  long long Ktot = 0, Ltot = 0;
+  size_t off_soa = 0, off_lbest = 0, off_out = 0;
+  slslam::MatchBlock out;
+  slslam::BlockBytes bytes;
 };
 
-Layout make_layout(long long F, long long Ktot, long long Ltot) {
-  Layout y;
-  y.Ktot = Ktot; y.Ltot = Ltot;
-  y.off_d = align256(sizeof(FrameDesc) * (size_t)F);
-  y.in_bytes = y.off_d + 8 * (size_t)(12 * F + 8 * Ktot + 8 * Ltot);
-  y.o_match = align256(4 * (size_t)F);
-  y.o_line = y.o_match + align256(4 * (size_t)Ktot);
-  y.o_count = y.o_line + align256(4 * (size_t)Ktot);
-  y.o_best = y.o_count + align256(4 * (size_t)Ktot);
-  y.o_second = y.o_best + align256(4 * (size_t)Ktot);
-  y.o_obs = y.o_second + align256(4 * (size_t)Ktot);
-  y.out_bytes = y.o_obs + align256(4 * (size_t)Ltot);
-  y.off_soa = align256(y.in_bytes);
-  y.off_lbest = y.off_soa + align256(8 * (size_t)kLineValuesExt * (size_t)Ltot);
-  y.off_out = y.off_lbest + align256(8 * (size_t)Ltot);
-  y.dev_bytes = y.off_out + y.out_bytes;
-  y.host_bytes = align256(y.in_bytes) + y.out_bytes;
+CallLayout call_layout(long long F, long long Ktot, long long Ltot) {
+  CallLayout y;
+  slslam::Carve c;
+  const size_t doubles = 8 * (size_t)(12 * F + 8 * Ktot + 8 * Ltot);
+  c.take(sizeof(FrameDesc) * (size_t)F);
+  y.off_d = c.take(doubles);
+  y.in_bytes = y.off_d + doubles;
+  y.out = slslam::match_block((size_t)F, (size_t)Ktot, (size_t)Ltot);
+  y.bytes.host = c.at + y.out.bytes;
+  y.off_soa = c.take(8 * (size_t)kLineValuesExt * (size_t)Ltot);
+  y.off_lbest = c.take(8 * (size_t)Ltot);
+  y.off_out = c.at;
+  y.bytes.dev = y.off_out + y.out.bytes;
   return y;
-}
-
-bool device_present() {
-  int ndev = 0;
-  return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
 }
 
 // sizes, then pointers of one frame; max_k / max_l < 0: no maximum
@@ -80,15 +67,9 @@ bool thresholds_valid(double baseline, double error_thr, double ratio, double ma
 
 }  // namespace
 
-struct slslam_line_matcher {
-  int device = -1;
+struct slslam_line_matcher : slslam::Handle {
   int max_frames = 0, max_observations = 0, max_lines = 0;
-  GrowBuf d_block{Mem::kDevice}, h_block{Mem::kPinned};
-  hipStream_t stream = nullptr;
-  long long calls = 0, allocations = 0;
-  ~slslam_line_matcher() {
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  slslam::BlockPair block;
 };
 
 extern "C" int slslam_line_matcher_create(int device, int max_frames, int max_observations, int max_lines, slslam_line_matcher** out) {
@@ -104,10 +85,7 @@ extern "C" int slslam_line_matcher_create(int device, int max_frames, int max_ob
 extern "C" void slslam_line_matcher_destroy(slslam_line_matcher* m) { delete m; }
 
 extern "C" int slslam_line_matcher_stats(const slslam_line_matcher* m, long long* calls, long long* allocations) {
-  if (!m) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (calls) *calls = m->calls;
-  if (allocations) *allocations = m->allocations;
-  return SLSLAM_OK;
+  return slslam::handle_stats(m, calls, allocations);
 }
 
 extern "C" int slslam_line_matcher_run(slslam_line_matcher* m, int num_frames, const slslam_match_frame* frames, double baseline,
@@ -118,10 +96,8 @@ extern "C" int slslam_line_matcher_run(slslam_line_matcher* m, int num_frames, c
   const int F = num_frames;
   for (int f = 0; f < F; ++f)
     if (!frame_valid(frames[f], m->max_observations, m->max_lines)) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
-  if (m->device >= 0) HIP_TRY(hipSetDevice(m->device));
-  else HIP_TRY(hipGetDevice(&m->device));
-  if (!m->stream) HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+  int rc = m->ensure();
+  if (rc != SLSLAM_OK) return rc;
   hipStream_t s = m->stream;
   ++m->calls;
   if (F == 0) return SLSLAM_OK;
@@ -134,34 +110,30 @@ extern "C" int slslam_line_matcher_run(slslam_line_matcher* m, int num_frames, c
   for (int f = 0; f < F; ++f) {
     const slslam_match_frame& fr = frames[f];
     FrameDesc& d = fd[(size_t)f];
-    d.K = fr.num_observations; d.L = fr.num_lines; d.pad = 0;
-    int st = d.K == 0 || d.L == 0 ? SLSLAM_MATCH_EMPTY : SLSLAM_MATCH_OK;
+    const int K = fr.num_observations, L = fr.num_lines;
+    d.span.n = K; d.span.m = L; d.pad = 0;
+    int st = K == 0 || L == 0 ? SLSLAM_MATCH_EMPTY : SLSLAM_MATCH_OK;
     for (int q = 0; st == SLSLAM_MATCH_OK && q < 12; ++q)
       if (!std::isfinite(fr.pose[q])) st = SLSLAM_MATCH_INVALID_POSE;
     status[(size_t)f] = st;
     d.run = st == SLSLAM_MATCH_OK ? 1 : 0;
     d.pose = nd; nd += 12;
-    d.obs = nd; nd += 8LL * d.K;
-    d.lines = nd; if (d.run) nd += 6LL * d.L;
-    d.ext = -1; if (d.run && fr.extents) { d.ext = nd; nd += 2LL * d.L; }
-    d.k0 = Ktot; Ktot += d.K;
-    d.l0 = Ltot; Ltot += d.L;
-    maxK = std::max(maxK, d.K); maxL = std::max(maxL, d.L);
+    d.obs = nd; nd += 8LL * K;
+    d.lines = nd; if (d.run) nd += 6LL * L;
+    d.ext = -1; if (d.run && fr.extents) { d.ext = nd; nd += 2LL * L; }
+    d.span.a0 = Ktot; Ktot += K;
+    d.span.j0 = Ltot; Ltot += L;
+    maxK = std::max(maxK, K); maxL = std::max(maxL, L);
   }
   // the blocks: made for the matcher's capacity at the first run, larger only when a call exceeds them
   const long long capF = std::max<long long>(F, m->max_frames);
-  const Layout cap = make_layout(capF, capF * m->max_observations, capF * m->max_lines);
-  const Layout y = make_layout(F, Ktot, Ltot);
-  if (m->d_block.n < y.dev_bytes || m->h_block.n < y.host_bytes || !m->d_block.p || !m->h_block.p) {
-    long long unused = 0;
-    HIP_TRY(m->d_block.need(std::max(cap.dev_bytes, y.dev_bytes), &unused));
-    HIP_TRY(m->h_block.need(std::max(cap.host_bytes, y.host_bytes), &unused));
-    ++m->allocations;
-  }
+  const CallLayout y = call_layout(F, Ktot, Ltot);
+  if ((rc = m->block.fit(call_layout(capF, capF * m->max_observations, capF * m->max_lines).bytes, y.bytes, &m->allocations)) != SLSLAM_OK)
+    return rc;
 
   // ---- one upload
-  char* h = m->h_block.p;
-  char* dv = m->d_block.p;
+  char* h = m->block.host.p;
+  char* dv = m->block.dev.p;
   std::memcpy(h, fd.data(), sizeof(FrameDesc) * (size_t)F);
   double* hd = reinterpret_cast<double*>(h + y.off_d);
   for (int f = 0; f < F; ++f) {
@@ -169,9 +141,9 @@ extern "C" int slslam_line_matcher_run(slslam_line_matcher* m, int num_frames, c
     const FrameDesc& d = fd[(size_t)f];
     if (d.run) std::memcpy(hd + d.pose, fr.pose, 96);
     else std::memset(hd + d.pose, 0, 96);
-    if (d.K > 0) std::memcpy(hd + d.obs, fr.observations, 64 * (size_t)d.K);
-    if (d.run) std::memcpy(hd + d.lines, fr.lines, 48 * (size_t)d.L);
-    if (d.ext >= 0) std::memcpy(hd + d.ext, fr.extents, 16 * (size_t)d.L);
+    if (d.span.n > 0) std::memcpy(hd + d.obs, fr.observations, 64 * (size_t)d.span.n);
+    if (d.run) std::memcpy(hd + d.lines, fr.lines, 48 * (size_t)d.span.m);
+    if (d.ext >= 0) std::memcpy(hd + d.ext, fr.extents, 16 * (size_t)d.span.m);
   }
   const size_t up_bytes = y.off_d + 8 * (size_t)nd;
   HIP_TRY(hipMemcpyAsync(dv, h, up_bytes, hipMemcpyHostToDevice, s));
@@ -180,16 +152,8 @@ extern "C" int slslam_line_matcher_run(slslam_line_matcher* m, int num_frames, c
   double* d_soa = reinterpret_cast<double*>(dv + y.off_soa);
   unsigned long long* d_lbest = reinterpret_cast<unsigned long long*>(dv + y.off_lbest);
   char* d_out = dv + y.off_out;
-  Out o;
-  o.num_matched = reinterpret_cast<int*>(d_out);
-  o.match = reinterpret_cast<int*>(d_out + y.o_match);
-  o.best_line = reinterpret_cast<int*>(d_out + y.o_line);
-  o.num_admissible = reinterpret_cast<int*>(d_out + y.o_count);
-  o.best_error = reinterpret_cast<float*>(d_out + y.o_best);
-  o.second_error = reinterpret_cast<float*>(d_out + y.o_second);
-  o.best_observation = reinterpret_cast<int*>(d_out + y.o_obs);
-  HIP_TRY(hipMemsetAsync(o.num_matched, 0, 4 * (size_t)F, s));
-  if (Ltot > 0) HIP_TRY(hipMemsetAsync(d_lbest, 0xff, 8 * (size_t)Ltot, s));
+  const Out o = slslam::match_bind(d_out, y.out);
+  if ((rc = slslam::match_clear(o, (size_t)F, d_lbest, (size_t)Ltot, s)) != SLSLAM_OK) return rc;
 
   // ---- three launches for all frames
   const unsigned tk = (unsigned)((maxK + 63) / 64), tl = (unsigned)((maxL + 63) / 64);
@@ -202,27 +166,19 @@ extern "C" int slslam_line_matcher_run(slslam_line_matcher* m, int num_frames, c
     if (tk > 0)
       hipLaunchKernelGGL(k_match_pairs, dim3(tk, nf), dim3(64), 0, s, d_fd + f0, d_dd, (const double*)d_soa, Ltot, error_thr, d_lbest, of);
     if (std::max(tk, tl) > 0)
-      hipLaunchKernelGGL(k_match_finish, dim3(std::max(tk, tl), nf), dim3(64), 0, s, d_fd + f0, (const unsigned long long*)d_lbest, ratio, of);
+      hipLaunchKernelGGL(slslam::k_mutual_finish<FrameDesc>, dim3(std::max(tk, tl), nf), dim3(64), 0, s, d_fd + f0,
+                         (const unsigned long long*)d_lbest, ratio, of);
   }
   HIP_TRY(hipGetLastError());
 
   // ---- one download
-  char* h_out = h + align256(y.in_bytes);
-  HIP_TRY(hipMemcpyAsync(h_out, d_out, y.out_bytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int* r_nm = reinterpret_cast<const int*>(h_out);
+  char* h_out = h + slslam::align256(y.in_bytes);
+  if ((rc = slslam::match_download(h_out, d_out, y.out, s)) != SLSLAM_OK) return rc;
   for (int f = 0; f < F; ++f) {
-    const FrameDesc& d = fd[(size_t)f];
     slslam_match_result& r = out[f];
     r.status = status[(size_t)f];
-    r.num_matched = r_nm[f];
-    const size_t kb = 4 * (size_t)d.K, ko = 4 * (size_t)d.k0;
-    if (r.match && d.K > 0) std::memcpy(r.match, h_out + y.o_match + ko, kb);
-    if (r.best_line && d.K > 0) std::memcpy(r.best_line, h_out + y.o_line + ko, kb);
-    if (r.num_admissible && d.K > 0) std::memcpy(r.num_admissible, h_out + y.o_count + ko, kb);
-    if (r.best_error && d.K > 0) std::memcpy(r.best_error, h_out + y.o_best + ko, kb);
-    if (r.second_error && d.K > 0) std::memcpy(r.second_error, h_out + y.o_second + ko, kb);
-    if (r.best_observation && d.L > 0) std::memcpy(r.best_observation, h_out + y.o_obs + 4 * (size_t)d.l0, 4 * (size_t)d.L);
+    r.num_matched = slslam::match_scatter(h_out, y.out, (size_t)f, fd[(size_t)f].span,
+                                          {r.match, r.best_line, r.best_error, r.second_error, r.num_admissible, r.best_observation});
   }
   return SLSLAM_OK;
 }

@@ -18,8 +18,8 @@
 #include <vector>
 
 #include "../../include/slslam_hip.h"
-#include "grow_buf.h"
-#include "hip_status.h"
+#include "call_block.h"
+#include "place_layout.h"
 #include "place_recognition.h"
 
 using namespace slslam_place;
@@ -42,11 +42,6 @@ struct slslam_voctree {
 
 namespace {
 
-bool device_present() {
-  int ndev = 0;
-  return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
-}
-
 // interior nodes and leaves of a (K, L) tree; false outside the limits
 bool tree_shape(int K, int L, int D, size_t* num_int, size_t* num_leaf) {
   if (K < 2 || K > kMaxK || L < 1 || L > kMaxL || D < 1 || D > kMaxD) return false;
@@ -57,59 +52,9 @@ bool tree_shape(int K, int L, int D, size_t* num_int, size_t* num_leaf) {
   return true;
 }
 
-// the persistent device block of a database
-struct DbLayout {
-  size_t o_word = 0, o_tf = 0, o_n = 0, o_df = 0, o_idf = 0, o_vword = 0, o_sw = 0, o_sv = 0, bytes = 0;
-  size_t max_changes = 0;
-};
-
-DbLayout db_layout(size_t cap, size_t mw, size_t num_leaf, size_t navg) {
-  DbLayout y;
-  y.max_changes = mw + 2 * navg;
-  y.o_word = 0;
-  y.o_tf = y.o_word + align256(4 * mw * cap);
-  y.o_n = y.o_tf + align256(4 * mw * cap);
-  y.o_df = y.o_n + align256(4 * cap);
-  y.o_idf = y.o_df + align256(4 * num_leaf);
-  y.o_vword = y.o_idf + align256(4 * (cap + 2));
-  y.o_sw = y.o_vword + align256(4 * navg);
-  y.o_sv = y.o_sw + align256(4 * y.max_changes);
-  y.bytes = y.o_sv + align256(4 * y.max_changes);
-  return y;
-}
-
-// a call: the upload (the same offsets on the host and on the device), the device's work arrays, the result block
-struct CallLayout {
-  size_t off_desc = 0, in_bytes = 0;
-  size_t off_dtf = 0, off_dsum = 0, off_out = 0, dev_bytes = 0;
-  size_t o_words = 0, o_dword = 0, o_topid = 0, o_topscore = 0, o_score = 0, o_lik = 0, o_touched = 0, doc_bytes = 0, out_bytes = 0;
-  size_t host_bytes = 0;
-};
-
-CallLayout call_layout(size_t F, size_t nfloats, size_t mw, size_t S, size_t top_k) {
-  CallLayout y;
-  y.off_desc = align256(sizeof(Frame) * F);
-  y.in_bytes = y.off_desc + 4 * nfloats;
-  y.o_words = align256(4 * F);
-  y.o_dword = y.o_words + align256(4 * F * mw);
-  y.doc_bytes = y.o_dword + align256(4 * F * mw);             // what an insert downloads
-  y.o_topid = y.doc_bytes;
-  y.o_topscore = y.o_topid + align256(4 * F * top_k);
-  y.o_score = y.o_topscore + align256(4 * F * top_k);
-  y.o_lik = y.o_score + align256(4 * F * S);
-  y.o_touched = y.o_lik + align256(4 * F * S);
-  y.out_bytes = y.o_touched + align256(F * S);
-  y.off_dtf = align256(y.in_bytes);
-  y.off_dsum = y.off_dtf + align256(4 * F * mw);
-  y.off_out = y.off_dsum + align256(8 * F * S);
-  y.dev_bytes = y.off_out + y.out_bytes;
-  y.host_bytes = align256(y.in_bytes) + y.out_bytes;
-  return y;
-}
-
 }  // namespace
 
-struct slslam_place_db {
+struct slslam_place_db : slslam::Handle {                // (the device is the tree's)
   slslam_voctree* tree = nullptr;
   int max_docs = 0, max_words = 0, max_frames = 0, recent = 0, navg = 0;
   int inserted = 0, visible = 0;
@@ -120,11 +65,6 @@ struct slslam_place_db {
   std::vector<int> vwords;                     // the virtual document, ascending (empty: none)
   GrowBuf d_db{Mem::kDevice}, d_block{Mem::kDevice}, h_block{Mem::kPinned}, h_rel{Mem::kPinned};
   DbLayout dl;
-  hipStream_t stream = nullptr;
-  long long calls = 0, allocations = 0;
-  ~slslam_place_db() {
-    if (stream) (void)hipStreamDestroy(stream);
-  }
 };
 
 namespace {
@@ -135,11 +75,9 @@ bool frame_valid(const slslam_place_frame& f, int max_words) {
 
 // The device, the stream, the tree's nodes and every block of the database, made once for its capacity
 int ensure_device(slslam_place_db* db) {
-  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   slslam_voctree* t = db->tree;
-  if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
-  else HIP_TRY(hipGetDevice(&t->device));
-  if (!db->stream) HIP_TRY(hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking));
+  const int rc = db->ensure(t->device);
+  if (rc != SLSLAM_OK) return rc;
   if (!t->d_nodes) {
     float* p = nullptr;
     HIP_TRY(hipMalloc((void**)&p, 4 * t->nodes.size()));
@@ -151,11 +89,11 @@ int ensure_device(slslam_place_db* db) {
     long long unused = 0;
     const size_t mw = (size_t)db->max_words, F = (size_t)db->max_frames;
     db->dl = db_layout((size_t)db->max_docs, mw, t->num_leaf, (size_t)db->navg);
-    const CallLayout cap = call_layout(F, F * mw * (size_t)t->D, mw, (size_t)db->max_docs + 1, kMaxTopK);
+    const CallLayout cap = call_layout(sizeof(Frame), F, F * mw * (size_t)t->D, mw, (size_t)db->max_docs + 1, kMaxTopK);
     HIP_TRY(db->d_db.need(db->dl.bytes, &unused));
     HIP_TRY(hipMemsetAsync(db->d_db.p + db->dl.o_n, 0, db->dl.o_idf - db->dl.o_n, db->stream));    // n and df
-    HIP_TRY(db->d_block.need(cap.dev_bytes, &unused));
-    HIP_TRY(db->h_block.need(cap.host_bytes, &unused));
+    HIP_TRY(db->d_block.need(cap.bytes.dev, &unused));
+    HIP_TRY(db->h_block.need(cap.bytes.host, &unused));
     HIP_TRY(db->h_rel.need(8 * db->dl.max_changes + 4 * ((size_t)db->max_docs + 2) + 4 * (size_t)db->navg, &unused));
     ++db->allocations;
   }
@@ -331,10 +269,7 @@ extern "C" int slslam_place_db_virtual(const slslam_place_db* db, int* words, in
 }
 
 extern "C" int slslam_place_db_stats(const slslam_place_db* db, long long* calls, long long* allocations) {
-  if (!db) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (calls) *calls = db->calls;
-  if (allocations) *allocations = db->allocations;
-  return SLSLAM_OK;
+  return slslam::handle_stats(db, calls, allocations);
 }
 
 extern "C" int slslam_place_db_insert(slslam_place_db* db, const slslam_place_frame* frame, int* status, int* words) {
@@ -345,7 +280,7 @@ extern "C" int slslam_place_db_insert(slslam_place_db* db, const slslam_place_fr
   ++db->calls;
   const size_t mw = (size_t)db->max_words;
   const int n = frame->num_descriptors;
-  const CallLayout y = call_layout(1, (size_t)n * (size_t)db->tree->D, mw, 1, 0);
+  const CallLayout y = call_layout(sizeof(Frame), 1, (size_t)n * (size_t)db->tree->D, mw, 1, 0);
   int st = SLSLAM_PLACE_OK;
   stage_frames(db, 1, frame, y, &st);
   if (status) *status = st;
@@ -410,7 +345,7 @@ extern "C" int slslam_place_db_run(slslam_place_db* db, int num_frames, const sl
   const size_t mw = (size_t)db->max_words, S = (size_t)db->visible + 1, tk = (size_t)top_k;
   size_t nfloats = 0;
   for (int f = 0; f < F; ++f) nfloats += (size_t)frames[f].num_descriptors * (size_t)db->tree->D;
-  const CallLayout y = call_layout((size_t)F, nfloats, mw, S, tk);
+  const CallLayout y = call_layout(sizeof(Frame), (size_t)F, nfloats, mw, S, tk);
   std::vector<int> status((size_t)F);
   const size_t staged = stage_frames(db, F, frames, y, status.data());
 

@@ -14,7 +14,7 @@
 #include "../../include/slslam_hip.h"
 #include "po_kernels.h"
 #include "device_cache.h"
-#include "hip_status.h"
+#include "call_block.h"
 
 using namespace slslam;
 
@@ -596,8 +596,7 @@ extern "C" int slslam_po_solve(const slslam_po_graph* g, const slslam_solver_opt
   if (rc != SLSLAM_OK) return rc;
   if (trace_len) *trace_len = 0;
   if (summary) std::memset(summary, 0, sizeof(*summary));
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   if (g->num_edges == 0) { if (summary) summary->termination_type = po_termination(nullptr); return SLSLAM_OK; }
   po_solve_analyse(c);
   if ((rc = po_solve_upload(c)) != SLSLAM_OK) return rc;
@@ -623,8 +622,7 @@ extern "C" int slslam_po_solve(const slslam_po_graph* g, const slslam_solver_opt
 // HuberLoss(po_huber_delta) - the switch of reference src/po_problem.cpp:27,55.  One launch, one lane per edge.
 extern "C" int slslam_po_edge_report(const slslam_po_graph* g, double po_huber_delta, double* sq_norm, double* weight) {
   if (!g || !po_graph_arrays_ok(g, true) || !po_huber_ok(po_huber_delta) || !po_graph_entries_ok(g, true)) return SLSLAM_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   const int N = g->num_poses, E = g->num_edges;
   if (E == 0 || (!sq_norm && !weight)) return SLSLAM_OK;
   PoCarve a;

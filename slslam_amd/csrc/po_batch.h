@@ -338,8 +338,8 @@ extern "C" int slslam_po_batch_finalize(slslam_po_batch* b, const slslam_solver_
   if (!po_policy(opt_in, &opt, &b->pol)) return SLSLAM_ERR_INVALID_ARGUMENT;      // (slslam_po_solve's policy)
   if (opt.po_dense_factor || opt.po_factor_fp32) return SLSLAM_ERR_UNSUPPORTED;      // the structured fp64 factorisation only
   b->huber = opt.po_huber_delta;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  const int ndev = device_count();
+  if (ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
   if (b->device < 0) { if (hipGetDevice(&b->device) != hipSuccess) return SLSLAM_ERR_NO_DEVICE; }
   if (b->device >= ndev) return SLSLAM_ERR_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(b->device));

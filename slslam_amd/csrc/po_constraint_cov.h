@@ -103,8 +103,7 @@ extern "C" int slslam_po_constraint_covariance(const slslam_po_constraint_items*
       !po_all_finite(it->cov_constraint, 36 * n))
     return SLSLAM_ERR_INVALID_ARGUMENT;
   if (n == 0) return SLSLAM_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   try {
     PoCarve a;
     const size_t o_pa = a.take(sizeof(double) * 6 * n), o_pb = a.take(sizeof(double) * 6 * n), o_c = a.take(sizeof(double) * 6 * n),

@@ -387,8 +387,7 @@ extern "C" int slslam_po_covariance(const slslam_po_graph* g, double po_huber_de
   if (!g || !po_graph_arrays_ok(g, true) || !po_huber_ok(po_huber_delta) || !po_graph_entries_ok(g, true)) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (num_pairs < 0 || (cov_pairs && num_pairs > 0 && (!pair_a || !pair_b))) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (pair_a && pair_b && !po_cov_pairs_ok(g->num_poses, num_pairs, pair_a, pair_b)) return SLSLAM_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   const int N = g->num_poses, E = g->num_edges;
   const int P = (cov_pairs && pair_a && pair_b) ? num_pairs : 0;
   if (status) *status = SLSLAM_COV_OK;

@@ -302,8 +302,7 @@ extern "C" int slslam_po_edge_statistics(const slslam_po_edge_items* it, int* st
       !po_all_finite(it->cov_meas, 36 * n))
     return SLSLAM_ERR_INVALID_ARGUMENT;
   if (n == 0) return SLSLAM_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   try {
     PoCarve a;
     const size_t o_pa = a.take(sizeof(double) * 6 * n), o_pb = a.take(sizeof(double) * 6 * n), o_c = a.take(sizeof(double) * 6 * n);
@@ -366,8 +365,7 @@ extern "C" int slslam_po_gate(const slslam_po_graph* g, double po_huber_delta, c
     if (rc == SLSLAM_OK && cov_status) *cov_status = SLSLAM_COV_OK;
     return rc;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
   try {
     PoSymbolic S;
     po_analyse(N, E, g->pose_index_1, g->pose_index_2, false, &S);

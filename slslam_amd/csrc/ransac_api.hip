@@ -17,12 +17,13 @@
 #include <vector>
 
 #include "../../include/slslam_hip.h"
-#include "hip_status.h"
+#include "call_block.h"
 #include "ransac_device.h"
 #include "ransac_front.h"
 
 using namespace slslam_ransac;
 using slslam::align256;
+using slslam::device_present;
 
 namespace {
 
@@ -149,11 +150,6 @@ bool frame_valid(const slslam_ransac_trials& tr, const double* lines, bool score
   for (long long i = 0; i < (long long)H * s; ++i)
     if (tr.samples[i] < 0 || tr.samples[i] >= K) return false;
   return true;
-}
-
-bool device_present() {
-  int ndev = 0;
-  return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
 }
 
 }  // namespace

@@ -16,8 +16,7 @@
 #include <vector>
 
 #include "../../include/slslam_hip.h"
-#include "grow_buf.h"
-#include "hip_status.h"
+#include "call_block.h"
 #include "lba_triangulate.h"
 
 using namespace slslam;
@@ -47,10 +46,7 @@ extern "C" int slslam_line_triangulator_create(int device, const slslam_solver_o
 extern "C" void slslam_line_triangulator_destroy(slslam_line_triangulator* t) { delete t; }
 
 extern "C" int slslam_line_triangulator_stats(const slslam_line_triangulator* t, long long* calls, long long* allocations) {
-  if (!t) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (calls) *calls = t->calls;
-  if (allocations) *allocations = t->allocations;
-  return SLSLAM_OK;
+  return handle_stats(t, calls, allocations);
 }
 
 extern "C" int slslam_line_triangulator_run(slslam_line_triangulator* t, int n, const slslam_lba_window* windows, int method,
@@ -71,10 +67,7 @@ extern "C" int slslam_line_triangulator_run(slslam_line_triangulator* t, int n, 
     ++t->calls;
 
     if (P.ngroups > 0) {
-      int ndev = 0;
-      if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
-      if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
-      else HIP_TRY(hipGetDevice(&t->device));
+      if ((rc = use_device(t->device)) != SLSLAM_OK) return rc;
 
       // the buffers are made for the capacities of create (whole waves per window, rows padded to a group's longest line) or for
       // this call, whichever is larger

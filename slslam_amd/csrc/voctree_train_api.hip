@@ -12,13 +12,11 @@
 
 #include "../../include/slslam_hip.h"
 #include "../host/voctree_host.h"
-#include "grow_buf.h"
-#include "hip_status.h"
+#include "call_block.h"
 #include "voctree_train.h"
 
 using namespace slslam_vtrain;
 namespace vh = slslam_voctree_host;
-using slslam::align256;
 using slslam::GrowBuf;
 using slslam::Mem;
 
@@ -49,16 +47,17 @@ struct Layout {
 
 Layout layout(size_t n, size_t D, size_t centre_floats, size_t rows) {
   Layout y;
-  y.o_desc = 0;
-  y.o_node = y.o_desc + align256(4 * n * D);
-  y.o_label = y.o_node + align256(4 * n);
-  y.o_perm = y.o_label + align256(4 * n);
-  y.o_centres = y.o_perm + align256(4 * n);
-  y.o_acc = y.o_centres + align256(4 * centre_floats);
-  y.o_count = y.o_acc + align256(8 * rows * D);                       // (changed follows count: one memset clears both)
-  y.o_changed = y.o_count + align256(8 * rows);
-  y.o_partial = y.o_changed + 256;
-  y.bytes = y.o_partial + align256(8 * (size_t)step_blocks((long long)n));
+  slslam::Carve c;
+  y.o_desc = c.take(4 * n * D);
+  y.o_node = c.take(4 * n);
+  y.o_label = c.take(4 * n);
+  y.o_perm = c.take(4 * n);
+  y.o_centres = c.take(4 * centre_floats);
+  y.o_acc = c.take(8 * rows * D);
+  y.o_count = c.take(8 * rows);                                       // (changed follows count: one memset clears both)
+  y.o_changed = c.take(256);
+  y.o_partial = c.take(8 * (size_t)step_blocks((long long)n));
+  y.bytes = c.at;
   return y;
 }
 
@@ -76,8 +75,7 @@ struct Session {
 };
 
 int open_session(Session* s, int device, int K, int D, size_t n, const float* desc, size_t centre_floats, size_t rows) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
+  if (!slslam::device_present()) return SLSLAM_ERR_NO_DEVICE;
   if (device >= 0) HIP_TRY(hipSetDevice(device));
   s->K = K; s->D = D; s->n = n;
   s->y = layout(n, (size_t)D, centre_floats, rows);
