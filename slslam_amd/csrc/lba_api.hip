@@ -31,6 +31,7 @@
 #include "call_block.h"
 #include "host_pool.h"
 #include "pinned_registry.h"
+#include "lba_batch.h"
 
 #include <functional>
 #include <memory>
@@ -98,183 +99,6 @@ extern "C" const char* slslam_status_string(int s) {
 
 namespace {
 
-// The owners below free what they hold when they go; they are not copied (a copy would free it twice) and not moved (a DeviceArena
-// keeps the addresses of the DevBufs it fills in).
-struct NoCopy {
-  NoCopy() = default;
-  NoCopy(const NoCopy&) = delete;
-  NoCopy& operator=(const NoCopy&) = delete;
-};
-
-template <typename T>
-struct DevBuf : NoCopy {
-  T* p = nullptr;
-  size_t n = 0;
-  bool in_arena = false;            // carved out of a DeviceArena: the arena frees it
-  ~DevBuf() { release(); }
-  int alloc(size_t count) {
-    release();
-    if (count > 0) HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-    n = count;
-    return SLSLAM_OK;
-  }
-  void release() { if (p && !in_arena) (void)hipFree(p); p = nullptr; n = 0; in_arena = false; }
-};
-
-// Results on the host: pageable, or pinned for a batch that is refilled (its downloads are asynchronous copies).
-template <typename T>
-struct HostArr : NoCopy {
-  T* p = nullptr;
-  size_t n = 0;
-  bool pinned = false;
-  std::vector<T> v;
-  ~HostArr() { release(); }
-  int alloc(size_t count, bool pin, bool zero = true) {        // (zero = false: a staging block, written before it is read)
-    release();
-    if (pin && count > 0) { HIP_TRY(hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault)); pinned = true; if (zero) std::memset((void*)p, 0, count * sizeof(T)); }
-    else { v.assign(count, T()); p = v.data(); }
-    n = count;
-    return SLSLAM_OK;
-  }
-  void release() { if (pinned && p) (void)hipHostFree(p); p = nullptr; n = 0; pinned = false; std::vector<T>().swap(v); }
-  T* data() { return p; }
-  const T* data() const { return p; }
-  size_t size() const { return n; }
-  bool empty() const { return n == 0; }
-  T& operator[](size_t i) { return p[i]; }
-  const T& operator[](size_t i) const { return p[i]; }
-};
-
-// A derived result of a resident batch (its posterior covariances, its report, its segments): device arrays that kernels of its own
-// fill at the batch's current parameters, and their copies on the host.  ONE protocol: the first call makes the buffers and they are
-// kept; a call leaves its result ENQUEUED on the device, the next download copies it with the other results (COPYING), its arrival
-// makes it READY for the getter; a refill replaces the windows and with them the result (NONE).
-struct DerivedResult : NoCopy {
-  enum State { NONE, ENQUEUED, COPYING, READY };
-  struct Mirror {                    // bytes on the device and, where the host reads them, as many on the host
-    DevBuf<char> d; HostArr<char> h;
-    bool active = true;              // part of the last call's result: a download copies it
-    template <typename T> T* dev() const { return reinterpret_cast<T*>(d.p); }
-    template <typename T> const T* host() const { return reinterpret_cast<const T*>(h.p); }
-  };
-  struct Shape { size_t bytes; bool zeroed, mirrored; };
-  Mirror m[4];
-  State state = NONE;                // where the result of the LAST call is
-  long long calls = 0, allocations = 0;
-  bool allocated(int first = 0) const { return m[first].d.p != nullptr; }
-  // Makes m[first ...] (the host side pinned when the downloads are asynchronous copies) and zeroes on `s` what is to read as zeros where
-  // no launch writes.  A failure leaves them unallocated: the next call tries again.
-  int allocate(int first, std::initializer_list<Shape> shapes, bool pin, hipStream_t s) {
-    int rc = SLSLAM_OK, k = first;
-    long long made = 0;
-    for (const Shape& sh : shapes) {
-      Mirror& x = m[k++];
-      if ((rc = x.d.alloc(sh.bytes)) || (sh.mirrored && (rc = x.h.alloc(sh.bytes, pin)))) break;
-      made += sh.mirrored ? 2 : 1;
-    }
-    if (rc != SLSLAM_OK) {
-      for (int q = first; q < k; ++q) { m[q].d.release(); m[q].h.release(); }
-      return rc;
-    }
-    allocations += made;
-    k = first;
-    for (const Shape& sh : shapes) {
-      if (sh.zeroed) HIP_TRY(hipMemsetAsync(m[k].d.p, 0, sh.bytes, s));
-      ++k;
-    }
-    return SLSLAM_OK;
-  }
-  int launched() { HIP_TRY(hipGetLastError()); state = ENQUEUED; return SLSLAM_OK; }      // behind a call's launches
-  // what was enqueued since the last download comes back with it
-  int download(hipStream_t s) {
-    if (state != ENQUEUED) return SLSLAM_OK;
-    for (Mirror& x : m)
-      if (x.active && x.h.size() > 0) HIP_TRY(hipMemcpyAsync(x.h.data(), x.d.p, x.h.size(), hipMemcpyDeviceToHost, s));
-    state = COPYING;
-    return SLSLAM_OK;
-  }
-  void arrive() { if (state == COPYING) state = READY; }
-  void invalidate() { state = NONE; }
-};
-
-// All device arrays of a batch in ONE allocation, everything the host fills in ONE host-to-device copy: the build of
-// a single window (slslam_lba_solve, the per-keyframe call of the reference) is dominated by per-call driver overheads
-// otherwise (~35 hipMalloc + ~20 synchronous hipMemcpy).
-// The uploaded arrays have a host IMAGE with the same offsets (`stage`): the batch build writes every window's slices straight into
-// it (fill_window, one window per host thread) and the image goes up in one copy.  A batch that is to be refilled
-// (slslam_solver_options.refill_headroom_percent > 0) keeps the image, in pinned memory: slslam_lba_batch_refill packs the next set of
-// windows into it and uploads the arrays with asynchronous copies on the caller's stream.
-struct DeviceArena : NoCopy {
-  struct Item { void** pp; size_t bytes; const void* host; size_t host_bytes; int group; size_t off; };   // group 0 uploaded, 1 scratch, 2 zeroed
-  std::vector<Item> items;
-  char* base = nullptr;
-  size_t bytes = 0;
-  int device = 0;
-  bool cached = false;              // one-shot solves: the block comes from / returns to the thread's DeviceBlockCache
-  char* stage = nullptr;            // host image of the uploaded arrays (offsets as on the device)
-  bool stage_pinned = false;        // hipHostMalloc'ed and kept for refills; otherwise a vector that lives until push()
-  bool keep_stage = false;
-  std::vector<char> stage_vec;
-  ~DeviceArena() { release(); }
-  template <typename T>
-  void add(DevBuf<T>& d, size_t count, const T* host, size_t host_count, int group) {
-    d.n = count; d.in_arena = true; d.p = nullptr;
-    items.push_back(Item{ (void**)&d.p, count * sizeof(T), host, host_count * sizeof(T), group, 0 });
-  }
-  template <typename T> void upload(DevBuf<T>& d, const std::vector<T>& h) { add(d, h.size(), h.data(), h.size(), 0); }
-  // uploaded, `count` elements of room; the caller writes host_of(d) between layout() and push()
-  template <typename T> void staged(DevBuf<T>& d, size_t count) { add(d, count, (const T*)nullptr, 0, 0); }
-  template <typename T> void scratch(DevBuf<T>& d, size_t count) { add(d, count, (const T*)nullptr, 0, 1); }
-  template <typename T> void zeroed(DevBuf<T>& d, size_t count) { add(d, count, (const T*)nullptr, 0, 2); }
-  template <typename T> T* host_of(const DevBuf<T>& d) const { return reinterpret_cast<T*>(stage + ((char*)d.p - base)); }
-  size_t upload_end = 0, zero_begin = 0;
-  int layout() {
-    size_t off = 0;
-    upload_end = 0; zero_begin = 0;
-    for (int group = 0; group < 3; ++group) {        // uploaded arrays first, then scratch, then the zero-initialised ones
-      if (group == 2) zero_begin = off;
-      for (Item& it : items) {
-        if (it.group != group) continue;
-        it.off = off;
-        off += (it.bytes + 255) & ~(size_t)255;
-      }
-      if (group == 0) upload_end = off;
-    }
-    bytes = off;
-    if (off == 0) { items.clear(); return SLSLAM_OK; }
-    if (cached) HIP_TRY(DeviceBlockCache::acquire(off, device, &base));
-    else HIP_TRY(hipMalloc((void**)&base, off));
-    if (keep_stage) {
-      HIP_TRY(hipHostMalloc((void**)&stage, std::max<size_t>(upload_end, 256), hipHostMallocDefault));
-      stage_pinned = true;
-      std::memset(stage, 0, upload_end);
-    } else {
-      stage_vec.assign(upload_end, 0);
-      stage = stage_vec.data();
-    }
-    for (const Item& it : items) {
-      *it.pp = base + it.off;
-      if (it.host && it.host_bytes) std::memcpy(stage + it.off, it.host, it.host_bytes);
-    }
-    items.clear();
-    return SLSLAM_OK;
-  }
-  int push() {
-    if (bytes == 0) return SLSLAM_OK;
-    if (upload_end) HIP_TRY(hipMemcpy(base, stage, upload_end, hipMemcpyHostToDevice));
-    if (bytes > zero_begin) HIP_TRY(hipMemset(base + zero_begin, 0, bytes - zero_begin));
-    if (!stage_pinned) { std::vector<char>().swap(stage_vec); stage = nullptr; }
-    return SLSLAM_OK;
-  }
-  int commit() { const int rc = layout(); return rc != SLSLAM_OK ? rc : push(); }
-  void release() {
-    if (base) { if (cached) DeviceBlockCache::give_back(base, bytes, device); else (void)hipFree(base); }
-    if (stage_pinned && stage) (void)hipHostFree(stage);
-    stage = nullptr; stage_pinned = false; std::vector<char>().swap(stage_vec);
-    base = nullptr; items.clear();
-  }
-};
-
 // The timing builds (variant libraries of tools/k1_phases.py, chunk_timeline.py, solve_phases.py and their kin; never the product library):
 // only they have kernels that stamp BatchPtrs::dbg_cycles, and only they allocate it.
 #if (defined(SLSLAM_K1_TIMING) && SLSLAM_K1_TIMING) || (defined(SLSLAM_K1_WALL) && SLSLAM_K1_WALL) || (defined(SLSLAM_SOLVE_TIMING) && SLSLAM_SOLVE_TIMING)
@@ -297,153 +121,16 @@ Policy make_policy(const slslam_solver_options& o) {
   return p;
 }
 
-enum { FAM_LIN = 0, FAM_SOLVE = 1, FAM_BACKSUB = 2, FAM_TRIG = 3, FAM_COST = 4, FAM_UPDATE = 5, FAM_INIT = 6, FAM_N = 8 };
-
-// The mirrors (DerivedResult::m) of a batch's derived results
-enum { COV_M_HDR, COV_M_CAMS, COV_M_LINES };                  // posterior covariances (lba_covariance.h): int [B][kCovHdr], double [B][stride], and -
-                                                              // made by the first call that asks for them, active when the last one did - the lines' blocks, double [lines][16]
-enum { REP_M_OBS, REP_M_LINES, REP_M_CAMS, REP_M_CAM_PART };  // the report (lba_report.h): double [2 obs], RepLine [lines], RepCam [cams]; double, device only
-enum { SEG_M_STATUS, SEG_M_RANGE, SEG_M_LINES };              // the 3-D segments (lba_segments.h): int [obs], double [2 obs], SegLine [lines]
+// The automatic chunk policy of the batch as plan_layout (lba_pack.h) takes it
+CutPolicy cut_policy(const slslam_lba_batch* b) {
+  CutPolicy c;
+  c.chunks_per_window = b->opt.chunks_per_window; c.reproducible = b->opt.reproducible;
+  c.elim_waves = b->elim_waves; c.elim_mode = b->elim_mode; c.num_cus = b->num_cus; c.big_mode = b->big_mode;
+  c.auto_rounds = b->auto_rounds; c.auto_cpw = b->auto_cpw;
+  return c;
+}
 
 }  // namespace
-
-struct slslam_lba_batch {
-  int device = 0;
-  bool finalized = false;
-  std::vector<PackedWindow> wins;
-  slslam_solver_options opt;
-  Policy pol;
-  // host mirrors
-  std::vector<WinDesc> h_wins;
-  std::vector<long long> h_param_off;     // per window offset into the exported parameter vector
-  long long total_params = 0;
-  std::vector<LMState> h_state0;
-  HostArr<LMState> h_state;
-  HostArr<IterRec> h_trace;
-  HostArr<double> h_params;
-  // refills (slslam_lba_batch_refill): the device arrays have room for `refill_headroom_percent` more than the first windows needed; the
-  // kernels' view of the batch (BatchPtrs: pointers, strides, counts) and with it the captured graph never change
-  bool refillable = false;
-  long long used_ncam = 0, used_nline = 0, used_nobs = 0, used_tiles = 0, used_items = 0;   // of the room the device arrays have
-  int cap_maxC = 0, cap_maxn = 0;            // the LDS sizes of the launches were made for these
-  int auto_rounds = 0, auto_cpw = 0;         // the automatic chunk policy as finalize resolved it: a refill cuts its windows the same way
-  std::vector<int> sys_map_off_of_cf;        // per free-camera count: its table in d_sys_map, or -1
-  hipEvent_t ev_stage_free = nullptr;        // recorded behind the uploads of a refill: the host image may be written again
-  hipEvent_t ev_results = nullptr;           // recorded behind the copies of an asynchronous download
-  bool results_pending = false;
-  HostPool* ext_pool = nullptr;              // host threads lent by a stream object; else own_pool, made on demand
-  std::unique_ptr<HostPool> own_pool;
-  std::vector<PackedWindow> wins_spare;      // what a refill packs into; swapped with `wins` when the refill is accepted
-  std::vector<int> h_ob_orig_off;          // per window offset into d_ob_orig
-  bool downloaded = false;
-  // device
-  DeviceArena arena;
-  DevBuf<uint16_t> d_sys_map;
-  DevBuf<WinDesc> d_wins; DevBuf<Tile> d_tiles; DevBuf<Chunk> d_chunks; DevBuf<uint8_t> d_items; DevBuf<uint16_t> d_lane_map; DevBuf<int32_t> d_lane_ctx;
-  DevBuf<uint32_t> d_line_desc;
-  DevBuf<unsigned long long> d_dbg_cycles;
-  int elim_mode = 0, elim_waves = 1;     // see BatchPtrs
-  bool elim_mixed = false;               // ... its steady sweeps in mixed precision (lba_precision = 1: k_eliminate_grouped<false, false, true>)
-  bool elim_grouped = false;             // elim_mode 1 with group-local accumulators (lba_eliminate_grouped.h); the windows are packed with grouping = 1
-  size_t lds_elim = 0;
-  DevBuf<unsigned long long> d_iter_counter;
-  DevBuf<unsigned int> d_active;
-  DevBuf<double> d_cam_x, d_cam_x0, d_cam_scale, d_cam_tab; DevBuf<int> d_cam_cf, d_cam_win;
-  DevBuf<double> d_line_x, d_line_x0, d_line_scale; DevBuf<int> d_line_ptr, d_line_flags, d_line_win, d_line_orig;
-  DevBuf<double> d_ob; DevBuf<int> d_ob_cam, d_ob_orig;
-  DevBuf<double> d_ob_raw;                   // refillable batches: a refill's observations as the caller holds them, permuted into d_ob on the device (k_permute_obs)
-  // the build stage on the device (lba_device_build.h): a refill whose windows go up as the caller holds them
-  DevBuf<RawWin> d_rawwin; DevBuf<BuildWin> d_buildwin; DevBuf<uint32_t> d_raw_idx, d_fmask; DevBuf<double> d_line_raw; DevBuf<uint8_t> d_lflags;
-  DevBuf<int> d_item_base, d_totals, d_line_pos;
-  DevBuf<uint32_t> d_mid_keys; DevBuf<BuildLine> d_mid_li; DevBuf<uint4> d_mid_rows; DevBuf<uint16_t> d_mid_next, d_mid_trows, d_mid_tptr; DevBuf<BuildMid> d_mid;
-  HostArr<RawWin> h_rawwin;                  // pinned [B]: what the device reads of every window (uploaded per refill)
-  HostArr<BuildWin> h_buildwin;              // pinned [B]: what came of every window (downloaded with the results)
-  HostArr<WinDesc> h_wins_dl;                // pinned [B]: the descriptors the device made
-  HostArr<int> h_totals;                     // pinned [8]
-  HostArr<char> h_raw_stage;                 // pinned, made on demand: pageable inputs are copied here (indices narrowed on the way)
-  DevBuf<char> d_stage_in;                   // device, made on demand: where the copy engine puts a refill's arrays (k_ingest reads them from here)
-  std::vector<RawWin> host_src;              // per window: host-readable pointers to what the device was given (the callers' page-locked arrays, or the staging copy)
-  bool ingest_pinned = false;                // ... its observations and parameters were read where the caller holds them (page-locked), no staging copy
-  bool device_built = false;                 // the batch's present windows were built on the device
-  bool inplace_export = false;               // ... and their `parameters` arrays are pinned: results can be written straight into them
-  bool results_inplace = false;              // the last download wrote them there
-  std::vector<slslam_lba_window> src_windows;   // the callers' descriptors of a device-built refill (the in-place export's parameter arrays)
-  std::vector<int> build_status;             // per window, after wait(): 0 or the SLSLAM_ERR_* a flagged window is reported with
-  long long n_device_builds = 0, n_zero_copy = 0;
-  // windows beyond the tiled sweeps (lba_big.h)
-  bool big_mode = false;
-  BigPtrs big;
-  std::vector<long long> h_big_sys_off, h_big_linv_off;
-  DevBuf<int> d_big_ob_line, d_big_cam_ptr, d_big_cam_obs, d_big_pair_ptr, d_big_pair_row, d_big_pair_col, d_big_pair_desc, d_big_flags;
-  DevBuf<double> d_big_J, d_big_F, d_big_cost, d_big_camtab, d_big_line_acc, d_big_sys, d_big_scal, d_big_linv;
-  DevBuf<long long> d_big_sys_off;
-  DevBuf<double> d_slab_sum;
-  long long slab_sum_stride = 0;           // > 0: k_slab_reduce runs ahead of the reduced solve
-  bool slab_sum_image = false;             // ... and writes the LDS image of the reduced solve (BatchPtrs.slab_sum_image)
-  int line_elim_stride = kLineElim;
-  DevBuf<double> d_slab, d_bs_part, d_cost_part, d_ysys, d_params_out, d_fstore, d_line_elim, d_line_h;
-  DevBuf<LMState> d_state; DevBuf<IterRec> d_trace; DevBuf<long long> d_param_off;
-  BatchPtrs ptrs;
-  int nchunk = 0, nline = 0, ncam = 0;
-  long long nobs = 0;
-  int num_cus = 256;
-  bool fused_motion_only = false;
-  bool share_cam_tab = false;            // the sweeps read the camera tables of a window from d_cam_tab (BatchPtrs.cam_tab)
-  size_t lds_motion_only = 0;
-  size_t lds_lin = 0, lds_solve = 0, lds_bs = 0, lds_bs_stream = 0, lds_cost = 0;
-  // graph
-  hipGraphExec_t graph_exec = nullptr;
-  hipStream_t capture_stream = nullptr;
-  // A batch that mixes oversize windows with ordinary ones is solved as TWO batches side by side: part[0] holds the ordinary
-  // windows (tiled sweeps), part[1] the oversize ones (lba_big.h), the second on a stream of its own between a fork and a join on
-  // the caller's.  This object then only routes: window i of the caller is window route[i].second of part[route[i].first].
-  slslam_lba_batch* part[2] = { nullptr, nullptr };
-  std::vector<std::pair<int, int>> route;
-  std::vector<int> h_win_graded;             // per window: 0, or the number of slot rounds its graded chunk sizes were made for (finalize)
-  std::vector<long long> part_param_off[2];  // per window of a part: where its parameters go in the caller's export layout
-  DevBuf<long long> d_part_off[2];           // [3 nwin] per window of a part: offset in the part's export | offset in the caller's | length (k_scatter_windows)
-  hipStream_t part_stream = nullptr;
-  hipEvent_t part_fork = nullptr, part_join = nullptr;
-  DevBuf<double> d_part_out[2];
-  int num_windows() const { return part[0] ? (int)route.size() : (int)wins.size(); }
-  size_t dbg_words() const { return std::max((size_t)32 * std::max(1, nchunk), (size_t)16 * std::max<size_t>(1, wins.size())); }   // d_dbg_cycles (timing builds)
-  // the derived results (DerivedResult) and their mirrors.  A new one: a member, a place in `derived`, its enqueue function and its getter
-  DerivedResult cov, rep, seg;
-  DerivedResult* const derived[3] = { &cov, &rep, &seg };      // what downloads and refills go through
-  long long cov_cam_stride = 0;                               // cov.m[COV_M_CAMS] = double [B][cov_cam_stride]
-  size_t rep_cap_obs = 0;                                     // rep.m[REP_M_OBS] = double sq_norm [rep_cap_obs] | weight [rep_cap_obs]
-  // profiling
-  bool profiling = false;
-  double fam_ms[FAM_N] = { 0 };
-  int fam_launches[FAM_N] = { 0 };
-  std::vector<hipEvent_t> ev_pool;            // created once, reused by every profiled solve
-  std::vector<std::pair<int, int>> ev_used;   // (family, index of start event); stop = start + 1
-  size_t ev_next = 0;                         // first unused event of the pool
-  // folds the recorded event pairs into fam_ms / fam_launches and frees them for reuse (waits for the last one)
-  void harvest_events() {
-    if (ev_used.empty()) { ev_next = 0; return; }
-    (void)hipEventSynchronize(ev_pool[ev_used.back().second + 1]);
-    for (const auto& u : ev_used) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ev_pool[u.second], ev_pool[u.second + 1]) == hipSuccess) { fam_ms[u.first] += ms; fam_launches[u.first]++; }
-    }
-    ev_used.clear(); ev_next = 0;
-  }
-
-  // what the batch owns (the DevBufs of the arena only point into it; the parts of a mixed batch: drop_parts)
-  void release() {
-    arena.release();
-    d_stage_in.release();
-    h_state.release(); h_trace.release(); h_params.release();
-    h_rawwin.release(); h_buildwin.release(); h_wins_dl.release(); h_totals.release(); h_raw_stage.release();
-    if (ev_stage_free) { (void)hipEventDestroy(ev_stage_free); ev_stage_free = nullptr; }
-    if (ev_results) { (void)hipEventDestroy(ev_results); ev_results = nullptr; }
-    if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
-    if (capture_stream) { (void)hipStreamDestroy(capture_stream); capture_stream = nullptr; }
-    for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
-    ev_pool.clear();
-  }
-};
 
 extern "C" int slslam_lba_batch_create(int device, slslam_lba_batch** out) {
   if (!out) return SLSLAM_ERR_INVALID_ARGUMENT;
@@ -562,118 +249,9 @@ int on_both_parts(slslam_lba_batch* b, hipStream_t s, Fn fn) {
 namespace {
 
 // ------------------------------------------------------------------------------------------
-// The batch-wide layout of a set of packed windows.  plan_layout: where every window's slices go (prefix sums) and how its tiles are
-// cut into chunks - serial and cheap.  fill_window: the slices themselves, written into the host image of the device arrays; windows
-// are independent, one per host thread.  Used by slslam_lba_batch_finalize and by slslam_lba_batch_refill.
-struct LayoutPlan {
-  std::vector<WinDesc> wins;
-  std::vector<long long> param_off;             // per window: offset into the exported parameter vector
-  std::vector<int> ob_orig_off, item_base, win_graded;
-  std::vector<Chunk> chunks;                    // dispatch order
-  long long ncam = 0, nline = 0, nobs = 0, ntiles = 0, nitems = 0, sys = 0, slab = 0, params = 0;
-  int maxC = 1, maxn = 0, max_chunks = 0, max_sys = 0;
-  std::vector<uint16_t> sys_map;                // (finalize) the reduced solve's LDS maps, one per system order
-};
-
-int plan_layout(slslam_lba_batch* b, const std::vector<PackedWindow>& wins, bool frozen, LayoutPlan* out) {
-  LayoutPlan& L = *out;
-  const int B = (int)wins.size();
-  long long total_tiles = 0;
-  for (const PackedWindow& P : wins) total_tiles += (long long)P.tiles.size();
-  if (!frozen) {
-    // the sweeps run 8 one-wave workgroups per CU (LDS): the same number of chunks for every window, chosen so that
-    // the batch fills whole rounds of the chip's wave slots with about 36 tiles per chunk at most
-    // (1024 bench windows: 6 chunks of 33 tiles = 6144 waves = 3 rounds of 256 CUs x 8)
-    const long long slots = (8LL / b->elim_waves) * b->num_cus;      // chunk workgroups resident per round
-    const long long per_round = 36LL * b->elim_waves * slots;
-    const long long rounds = std::max<long long>(1, (total_tiles + per_round - 1) / per_round);
-    b->auto_rounds = (int)std::min<long long>(rounds, 1 << 20);
-    b->auto_cpw = (int)std::min<long long>(std::max<long long>(1, (slots * rounds) / std::max(1, B)), 1 << 20);
-  }
-  L.wins.resize((size_t)B); L.param_off.resize((size_t)B); L.ob_orig_off.resize((size_t)B); L.item_base.resize((size_t)B);
-  L.win_graded.assign((size_t)B, 0);
-  std::vector<int> chunk_rank;           // per chunk (window-major): 0 dispatched in the first class, 1 in the second (graded sizes)
-  std::vector<Chunk> chunks;
-  for (int wi = 0; wi < B; ++wi) {
-    const PackedWindow& P = wins[wi];
-    WinDesc& wd = L.wins[wi];
-    std::memset(&wd, 0, sizeof(wd));
-    wd.C = P.C; wd.Cf = P.Cf; wd.L = P.L; wd.M = P.M;
-    wd.cam_off = (int)L.ncam; wd.line_off = (int)L.nline; wd.obs_off = (int)L.nobs;
-    wd.tile_off = (int)L.ntiles; wd.ntiles = (int)P.tiles.size();
-    wd.n = 6 * P.Cf; wd.sys_off = (int)L.sys; wd.nfree_params = P.nfree_params; wd.nkept = P.nkept;
-    L.maxC = std::max(L.maxC, P.C); L.maxn = std::max(L.maxn, wd.n);
-    L.param_off[wi] = L.params; L.params += 6LL * P.C + 4LL * P.L;
-    L.ob_orig_off[wi] = (int)L.nobs;
-    L.item_base[wi] = (int)L.nitems;
-    // chunks: runs of tiles handled by one wave.  Few long chunks keep the per-chunk partial of
-    // the reduced system (a slab in HBM) small against the observation stream; many short chunks
-    // fill the chip when the batch is small.
-    int per_chunk;
-    int graded_chunks = 0, graded_rounds = 0;             // > 0: graded chunk sizes (below)
-    if (b->opt.chunks_per_window < 0) {                   // the caller asks for the graded cut a batch reported (slslam_lba_batch_window_chunks < 0):
-      graded_rounds = (-b->opt.chunks_per_window) / 1000; graded_chunks = (-b->opt.chunks_per_window) % 1000;        // -(1000 rounds + chunks)
-      if (graded_rounds < 2 || graded_chunks < graded_rounds) return SLSLAM_ERR_INVALID_ARGUMENT;
-      per_chunk = 1;
-    } else
-    if (b->opt.chunks_per_window > 0) per_chunk = std::max(1, (wd.ntiles + b->opt.chunks_per_window - 1) / b->opt.chunks_per_window);
-    else {
-      // automatic: the batch-wide numbers above - or, with slslam_solver_options.reproducible, a function of the WINDOW alone (what the
-      // automatic choice gives the windows of a batch that fills the chip: chunks of at most 34 tiles, graded for three rounds of the
-      // wave slots), so that a window is cut the same way whatever batch it sits in
-      long long rounds = b->auto_rounds, cpw = b->auto_cpw;
-      if (b->opt.reproducible) { cpw = std::max(1, (wd.ntiles + 33) / 34); rounds = 3; }
-      // (down to ONE tile per wave when the chip has room: since the camera tables are shared through memory, the partials of a
-      // many-chunk window summed chip-wide (k_slab_reduce) and the first tile's loads requested ahead of the set-up, a second tile
-      // costs a resident window more than a second chunk does - 0.44 / 0.60 / 0.98 -> 0.38 / 0.50 / 0.89 ms at W = 5 / 10 / 20,
-      // round 4; rounds 2-3 kept at least two tiles per wave)
-      per_chunk = (int)std::max<long long>(b->elim_waves, (wd.ntiles + cpw - 1) / cpw);
-      // GRADED sizes when every wave slot runs several chunks (rounds >= 2) of many tiles.  A launch ends when the slowest slot has
-      // finished its LAST chunk; with equal chunks - exactly `rounds` per slot, so nothing is left to balance with - that wait was a
-      // fifth of the sweep (tools/chunk_timeline.py: 2048 slots 81 % busy, chunk durations 206-442 us around 297).  Now the chunks a
-      // window contributes to the first round of the slots carry 70 % of a slot's share of the tiles, those of the second round 20 %
-      // (30 % when there are only two), the rest what is left, and the chunk array - the dispatch order - lists the classes one after
-      // the other: a slot that is late with its long chunk takes fewer short ones.  The slab count per window - what the reduced
-      // solve reads - does not change.
-      if (rounds >= 2 && cpw >= rounds && cpw < 1000 && b->elim_waves == 1 && wd.ntiles >= 8 * cpw) {
-        graded_chunks = (int)cpw; graded_rounds = (int)rounds;
-      }
-    }
-    int weights[1000];
-    for (int c = 0; c < graded_chunks; ++c) {
-      const int q = (int)(((long long)c * graded_rounds) / graded_chunks);           // the round of the slots this chunk belongs to
-      weights[c] = q == 0 ? 84 : q == 1 ? (graded_rounds == 2 ? 36 : 24) : std::max(1, 12 / (graded_rounds - 2));
-    }
-    std::vector<int> bounds = graded_chunks > 0 ? chunk_boundaries_graded(wd.ntiles, graded_chunks, weights) : chunk_boundaries(wd.ntiles, per_chunk);
-    L.win_graded[wi] = (graded_chunks > 0 && (int)bounds.size() - 1 == graded_chunks) ? graded_rounds : 0;
-    if (b->big_mode) { bounds.assign(2, 0); }            // no tiles: one chunk per window carries its step statistics
-    wd.chunk_off = (int)chunks.size(); wd.nchunks = (int)bounds.size() - 1;
-    wd.slab_off = (int)L.slab;
-    const int nsys = b->elim_mode == 1 ? sys_doubles_mfma(wd.n) : sys_doubles(wd.n);
-    const long long slab_stride = (long long)nsys + kSlabScalars;
-    L.max_chunks = std::max(L.max_chunks, wd.nchunks); L.max_sys = std::max(L.max_sys, nsys);
-    for (int c = 0; c < wd.nchunks; ++c) {
-      Chunk ck; ck.win = wi; ck.tile_begin = wd.tile_off + bounds[c]; ck.tile_end = wd.tile_off + bounds[c + 1];
-      ck.slab_off = (int)L.slab; L.slab += slab_stride;
-      ck.id = (int)chunks.size();
-      chunks.push_back(ck);
-      chunk_rank.push_back(L.win_graded[wi] ? (int)(((long long)c * graded_rounds) / graded_chunks) : 0);
-    }
-    if (L.slab > 0x7fffffffLL) return SLSLAM_ERR_UNSUPPORTED;
-    L.ncam += P.C; L.nline += P.L; L.nobs += P.M; L.sys += wd.n;
-    L.ntiles += (long long)P.tiles.size(); L.nitems += (long long)(P.items.size() / 2);
-    if (L.nobs > 0x7fffffffLL || L.nitems > 0x7fffffffLL) return SLSLAM_ERR_UNSUPPORTED;
-  }
-  // dispatch order: the long chunks of the graded windows (and every chunk of the others) first, the short ones after them; inside a class
-  // the order of the ids (a stable partition: ids, slabs and partial sums keep their window-major places)
-  {
-    int max_rank = 0;
-    for (int r : chunk_rank) max_rank = std::max(max_rank, r);
-    L.chunks.clear(); L.chunks.reserve(chunks.size());
-    for (int r = 0; r <= max_rank; ++r) for (size_t i = 0; i < chunks.size(); ++i) if (chunk_rank[i] == r) L.chunks.push_back(chunks[i]);
-  }
-  return SLSLAM_OK;
-}
+// The batch-wide layout of a set of packed windows is planned by lba_pack.h::plan_layout (serial and cheap).  fill_window: the slices
+// themselves, written into the host image of the device arrays; windows are independent, one per host thread.  Used by
+// slslam_lba_batch_finalize and by slslam_lba_batch_refill.
 
 // The host image of the uploaded arrays (DeviceArena::stage), by array.
 struct HostImage {
@@ -835,13 +413,6 @@ hipError_t allow_lds(std::initializer_list<const void*> kernels, size_t bytes) {
   return hipSuccess;
 }
 
-// The slab-sum stride of windows whose sums go straight into the LDS image of the reduced solve (BatchPtrs.slab_sum_image)
-long long slab_sum_image_stride(const std::vector<WinDesc>& wins) {
-  long long ext = 0;
-  for (const WinDesc& wd : wins) { const int N = solve_pad(wd.n); ext = std::max<long long>(ext, (long long)N * solve_stride(wd.n) + 6LL * N); }
-  return ((ext + kSlabScalars + 1) / 2) * 2;
-}
-
 // ---- which elimination sweep: the matrix-core one (lba_eliminate_mfma.h) needs the reduced system in the registers of
 // one workgroup (<= 10 free cameras) and one observation per (line, free camera); everything else takes the LDS-atomic sweep.
 // *mixed: the batch was finalized as a mixed batch (finalize_mixed), with that result.
@@ -903,8 +474,10 @@ int choose_sweep(slslam_lba_batch* b, bool* mixed) {
 int plan_capacities(slslam_lba_batch* b, LayoutPlan& plan) {
   const int B = (int)b->wins.size();
   {
-    const int prc = plan_layout(b, b->wins, /*frozen=*/false, &plan);
+    CutPolicy cut = cut_policy(b);
+    const int prc = plan_layout(cut, b->wins, /*frozen=*/false, &plan);
     if (prc != SLSLAM_OK) return prc;
+    b->auto_rounds = cut.auto_rounds; b->auto_cpw = cut.auto_cpw;
   }
   b->h_wins = plan.wins; b->h_param_off = plan.param_off; b->h_ob_orig_off = plan.ob_orig_off; b->h_win_graded = plan.win_graded;
   if (b->h_win_graded.empty()) b->h_win_graded.assign(1, 0);
@@ -914,22 +487,7 @@ int plan_capacities(slslam_lba_batch* b, LayoutPlan& plan) {
   b->refillable = b->opt.refill_headroom_percent > 0 && !b->big_mode;
   const size_t cap_cam = std::max<size_t>(1, room(b, plan.ncam)), cap_line = std::max<size_t>(1, room(b, plan.nline)), cap_obs = std::max<size_t>(1, room(b, plan.nobs));
   if (cap_obs > 0x7fffffffULL || cap_line > 0x7fffffffULL) return SLSLAM_ERR_UNSUPPORTED;
-  // reduced solve: where each entry of a chunk partial goes in its LDS image, one table per distinct system order (a refillable batch:
-  // one per free-camera count up to the largest of its first windows - the next windows may have any of them)
-  std::vector<uint16_t>& sys_map = plan.sys_map;
-  sys_map.assign(1, (uint16_t)0xFFFF);
-  b->sys_map_off_of_cf.assign((size_t)plan.maxn / 6 + 1, -1);
-  if (!b->big_mode) {
-    for (int cf = 0; cf <= plan.maxn / 6; ++cf) {
-      bool wanted = b->refillable;
-      for (const WinDesc& wd : b->h_wins) if (wd.n == 6 * cf) wanted = true;
-      if (!wanted) continue;
-      b->sys_map_off_of_cf[(size_t)cf] = (int)sys_map.size();
-      sys_map.resize(sys_map.size() + (size_t)sys_doubles(6 * cf));
-      sys_map_build(6 * cf, sys_map.data() + b->sys_map_off_of_cf[(size_t)cf]);
-    }
-  }
-  for (WinDesc& wd : b->h_wins) { const int off = b->sys_map_off_of_cf[(size_t)wd.n / 6]; wd.map_off = off < 0 ? 0 : off; }
+  plan_sys_maps(b->h_wins, plan.maxn, /*every_order=*/b->refillable, /*tables=*/!b->big_mode, &plan.sys_map, &b->sys_map_off_of_cf);
   // (the chunk array too: a refill may cut its windows into a few more chunks; the launches cover the whole array, unused entries are marked)
   b->total_params = plan.params; b->nchunk = (int)room(b, (long long)plan.chunks.size()); b->nline = (int)cap_line; b->ncam = (int)cap_cam;
   b->used_ncam = plan.ncam; b->used_nline = plan.nline; b->used_nobs = plan.nobs; b->used_tiles = plan.ntiles; b->used_items = plan.nitems;
@@ -1554,7 +1112,9 @@ __global__ __launch_bounds__(256) void k_export_inplace(BatchPtrs p, const RawWi
   }
 }
 
-int download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
+}  // namespace
+
+int slslam::download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
   if (!b) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (!b->finalized) return SLSLAM_ERR_STATE;
   HIP_TRY(hipSetDevice(b->device));
@@ -1598,6 +1158,7 @@ int download_async_impl(slslam_lba_batch* b, void* stream, bool allow_inplace) {
   return SLSLAM_OK;
 }
 
+namespace {
 // after the copies of a download have arrived: the host mirrors of a device-built refill
 void adopt_device_build(slslam_lba_batch* b) {
   if (!b->device_built) return;
@@ -1693,9 +1254,11 @@ hipError_t allow_build_lds() {
   return allow_lds({ (const void*)k_build_lines, (const void*)k_build_rows, (const void*)k_build_order, (const void*)k_build_tiles }, 158 * 1024);
 }
 
+}  // namespace
+
 // One window's index words as the device reads them (RawWin::packed): its three index arrays narrowed (index_word), or the caller's words
 // (`packed`) copied.  Nonzero: an index outside [0, C) x [0, L), or a word with a bit above the flags set.
-unsigned narrow_indices(size_t M, const int* cam, const int* line, const int* fixed, const uint32_t* packed, int C, int L, uint32_t* out) {
+unsigned slslam::narrow_indices(size_t M, const int* cam, const int* line, const int* fixed, const uint32_t* packed, int C, int L, uint32_t* out) {
   unsigned oob = 0;
   if (packed) {
     for (size_t q = 0; q < M; ++q) { const uint32_t v = packed[q]; oob |= word_bad(v, C, L); out[q] = v; }
@@ -1710,7 +1273,7 @@ unsigned narrow_indices(size_t M, const int* cam, const int* line, const int* fi
 }
 
 // The three index arrays of M index words, held by `store`, as w's camera_index / line_index / fixed_index
-void expand_indices(const uint32_t* words, size_t M, std::vector<int>& store, slslam_lba_window* w) {
+void slslam::expand_indices(const uint32_t* words, size_t M, std::vector<int>& store, slslam_lba_window* w) {
   store.resize(4 * M);
   for (size_t q = 0; q < M; ++q) {
     const uint32_t x = words[q];
@@ -1719,6 +1282,7 @@ void expand_indices(const uint32_t* words, size_t M, std::vector<int>& store, sl
   w->camera_index = store.data(); w->line_index = store.data() + M; w->fixed_index = store.data() + 2 * M;
 }
 
+namespace {
 // The SLSLAM_REFILL_TIMING printouts of both refill paths
 double ms_between(std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); }
 
@@ -2055,6 +1619,8 @@ int refill_enqueue(slslam_lba_batch* b, int B, const RefillPlan& z, hipStream_t 
   return device_init_after_upload(b, s);
 }
 
+}  // namespace
+
 // The LBAProblem::build stage of a refill ON THE DEVICE (lba_device_build.h).  SLSLAM_OK: taken; SLSLAM_ERR_UNSUPPORTED: not this path's
 // business - nothing was touched, the caller goes on with the host packer; anything else: the refill failed.
 // Two streams: the ingest (the host link's business: few workgroups for ~20 ms per 1024 x 2000-line batch) is enqueued on `s_in`, everything
@@ -2064,7 +1630,7 @@ int refill_enqueue(slslam_lba_batch* b, int B, const RefillPlan& z, hipStream_t 
 // solves share the chip - measured 37 ms per batch against 20).
 // packed (optional): packed[i] != nullptr replaces window i's three index arrays by the narrowed form (slslam_pack_indices: one 32-bit word per
 // observation) - 68 instead of 80 bytes per observation over the host link.
-int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, hipStream_t s, hipStream_t s_in, const unsigned int* const* packed = nullptr) {
+int slslam::refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, hipStream_t s, hipStream_t s_in, const unsigned int* const* packed) {
   if (b->opt.device_build < 0 || b->d_rawwin.n < (size_t)std::max(1, B) || !b->d_ob_raw.p) return SLSLAM_ERR_UNSUPPORTED;
   // (k_build_layout dispatches graded chunks in at most kLayoutMaxRank classes: a batch cut for more rounds of the wave slots - several
   // thousand 2000-line windows - keeps the host packer)
@@ -2096,10 +1662,11 @@ int refill_device(slslam_lba_batch* b, const slslam_lba_window* windows, int B, 
 
 // "Can this batch be refilled as it is": the captured solve's launches were made for this many windows of the tiled sweeps or of the
 // fused motion-only solve
-bool refillable_as_is(const slslam_lba_batch* b, int n) {
+bool slslam::refillable_as_is(const slslam_lba_batch* b, int n) {
   return b->finalized && b->refillable && !b->part[0] && !b->big_mode && !b->opt.reuse_elimination && (int)b->wins.size() == n;
 }
 
+namespace {
 // The motion_only_ba shape (reference src/slam.cpp:578-675) of ONE window, from its index arrays (or its narrowed words): exactly one
 // camera that is observed and never flagged constant, and every observed line flagged constant - what set_lds_limits asks of every
 // window before it gives a batch the fused solve (pack_window's Cf == 1 and nfree_params == 6; a block is constant when one of its
@@ -2124,16 +1691,18 @@ bool motion_only_shape(const slslam_lba_window& w, const unsigned int* packed) {
   for (int l = 0; l < L; ++l) if (line_seen[(size_t)l] && !line_const[(size_t)l]) return false;
   return true;
 }
+}  // namespace
 
 // A batch that takes the fused motion-only solve runs one wave per window on the 6 x 6 system of ONE free camera: refilled, it can only
 // take windows of that shape (anything else would be solved wrong) - checked on the host before anything is touched
-bool fits_batch_path(const slslam_lba_batch* b, const slslam_lba_window* windows, const unsigned int* const* packed, int n) {
+bool slslam::fits_batch_path(const slslam_lba_batch* b, const slslam_lba_window* windows, const unsigned int* const* packed, int n) {
   if (!b->fused_motion_only) return true;
   for (int i = 0; i < n; ++i)
     if (!motion_only_shape(windows[i], packed ? packed[i] : nullptr)) return false;
   return true;
 }
 
+namespace {
 // The placeholders of a resident refill (lba_refill_resident): k_reset made them kRunning, nothing is to run
 __global__ __launch_bounds__(256) void k_park_windows(LMState* state, int from, int to) {
   const int w = from + (int)(blockIdx.x * 256 + threadIdx.x);
@@ -2235,7 +1804,8 @@ extern "C" int slslam_lba_batch_refill(slslam_lba_batch* b, const slslam_lba_win
   }
   // ---- layout, cut like the batch's first windows, and does it fit
   LayoutPlan plan;
-  rc = plan_layout(b, wins, /*frozen=*/true, &plan);
+  CutPolicy cut = cut_policy(b);
+  rc = plan_layout(cut, wins, /*frozen=*/true, &plan);
   if (rc != SLSLAM_OK) return rc;
   bool fits = (size_t)plan.ncam <= b->d_cam_cf.n && (size_t)plan.nline <= b->d_line_win.n && plan.nobs <= img.ob_stride &&
               (size_t)plan.ntiles <= b->d_tiles.n && (size_t)plan.nitems * 2 <= b->d_items.n && (int)plan.chunks.size() <= b->nchunk &&
@@ -2732,37 +2302,6 @@ extern "C" int slslam_lba_solve(const slslam_lba_window* w, const slslam_solver_
   });
 }
 
-// ------------------------------------------------------------------------------------------
-// Page-locked host memory the GPU reads and writes in place (include/slslam_hip.h)
-extern "C" int slslam_pinned_alloc(size_t bytes, void** out) {
-  if (!out) return SLSLAM_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
-  HIP_TRY(PinnedRegistry::get().alloc(bytes, out));
-  return SLSLAM_OK;
-}
-extern "C" int slslam_pinned_free(void* p) {
-  if (!p) return SLSLAM_OK;
-  return PinnedRegistry::get().free(p) == 0 ? SLSLAM_OK : SLSLAM_ERR_INVALID_ARGUMENT;
-}
-extern "C" int slslam_pinned_register(void* p, size_t bytes) {
-  if (!p || !bytes) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (!device_present()) return SLSLAM_ERR_NO_DEVICE;
-  HIP_TRY(PinnedRegistry::get().register_range(p, bytes));
-  return SLSLAM_OK;
-}
-extern "C" int slslam_pinned_unregister(void* p) {
-  if (!p) return SLSLAM_OK;
-  return PinnedRegistry::get().unregister_range(p) == 0 ? SLSLAM_OK : SLSLAM_ERR_INVALID_ARGUMENT;
-}
-extern "C" int slslam_pinned_contains(const void* p, size_t bytes) { return PinnedRegistry::get().contains(p, bytes) ? 1 : 0; }
-extern "C" int slslam_pack_indices(int n, const int* camera_index, const int* line_index, const int* fixed_index, unsigned int* packed) {
-  if (n < 0 || (n > 0 && (!camera_index || !line_index || !fixed_index || !packed))) return SLSLAM_ERR_INVALID_ARGUMENT;
-  // (what the word's fields hold: cameras 0 - 255, lines 0 - 65534)
-  const unsigned oob = narrow_indices((size_t)n, camera_index, line_index, fixed_index, nullptr, 0x100, 0xffff, packed);
-  return oob ? SLSLAM_ERR_UNSUPPORTED : SLSLAM_OK;
-}
-
 // Test hook (tests/test_gpu_device_build.py): ONE window through the device build alone - k_ingest, k_build_lines / _rows / _order, k_build_layout,
 // k_build_tiles on temporary device arrays - everything pack_window emits comes back in the form tests/host_math::hm_pack_g returns the
 // host packer's output in, so that the two are compared byte for byte.  status_out: the BuildWin.status bits (0: built).
@@ -2853,315 +2392,6 @@ extern "C" int slslam_debug_device_pack_timed(const slslam_lba_window* w, int gr
     for (size_t t = 0; t < ht.size() && tiles; ++t) { tiles[4 * t] = ht[t].line_begin; tiles[4 * t + 1] = ht[t].nlines; tiles[4 * t + 2] = ht[t].flags; tiles[4 * t + 3] = ht[t].nitems; }
   }
   HIP_TRY(e);
-  return SLSLAM_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// A STREAM of windows (BASELINE config 4 taken literally: every window arrives as the five host arrays the reference builds per
-// window, src/slam.cpp:899-921): `depth` refillable batches in flight, each on a HIP stream of its own - while the GPU solves batch k
-// and its copy engine uploads batch k + 1, the host threads pack batch k + 2.
-struct slslam_lba_stream {
-  int device = 0;
-  slslam_solver_options opt;
-  int depth = 3;
-  std::unique_ptr<HostPool> pool;
-  struct Slot {
-    slslam_lba_batch* batch = nullptr;
-    hipStream_t stream = nullptr;
-    int n = 0;                                  // windows of the batch in the slot
-    long long ticket = -1;
-    bool in_flight = false;
-    std::vector<double*> out_params;            // the callers' parameter arrays (solved in place, written by collect)
-  };
-  std::vector<Slot> slots;
-  hipStream_t ingest_stream = nullptr, solve_stream = nullptr;      // shared by the slots whose refills are built on the device (see refill_device)
-  hipStream_t build_stream = nullptr;        // ... the build kernels of batch k + 1 run BESIDE the solve of batch k: they are latency-bound (one wave walks a window's lines) and
-                                             // leave the chip mostly idle - and a chip that idles for 3 ms between two solves starts the next one at lower clocks (measured: the
-                                             // first solve after a light-load gap 16.6 ms against 15.0 back to back, tools/first_solve_after_refill.py)
-  hipStream_t result_stream = nullptr;       // ... and where their results leave: the export over the link and the state / trace copies of batch k
-  hipEvent_t ev_solved = nullptr, ev_built = nullptr;
-  long long next_ticket = 0;
-  // host-side accounting (ms, wall clock of the calling thread)
-  double ms_submit = 0, ms_collect_wait = 0, ms_collect_copy = 0;
-  long long n_refills = 0, n_builds = 0, n_windows = 0, n_iterations = 0;
-  long long n_device_builds = 0, n_zero_copy = 0, n_fallback_windows = 0;
-};
-
-namespace {
-// A batch the stream's host threads were lent to
-void destroy_lent(slslam_lba_batch* b) {
-  b->ext_pool = nullptr;
-  slslam_lba_batch_destroy(b);
-}
-
-// A new batch for a slot: the set packed by the stream's host threads, finalized with the stream's options
-int make_slot_batch(slslam_lba_stream* st, const slslam_lba_window* ws, int n, slslam_lba_batch** out) {
-  slslam_lba_batch* b = nullptr;
-  int rc = slslam_lba_batch_create(st->device, &b);
-  if (rc != SLSLAM_OK) return rc;
-  b->ext_pool = st->pool.get();
-  b->wins.resize((size_t)n);
-  std::vector<int> ps((size_t)n, SLSLAM_OK);
-  if (!st->pool->run(n, [&](int i) { ps[(size_t)i] = pack_window(&ws[i], &b->wins[(size_t)i]); })) rc = SLSLAM_ERR_NO_MEMORY;
-  for (int r : ps) if (r != SLSLAM_OK) rc = r;
-  if (rc == SLSLAM_OK) rc = slslam_lba_batch_finalize(b, &st->opt);
-  if (rc != SLSLAM_OK) { destroy_lent(b); return rc; }
-  *out = b;
-  return SLSLAM_OK;
-}
-
-// The slot's batch destroyed, once every stream that may still use it has drained
-int drop_slot_batch(slslam_lba_stream* st, slslam_lba_stream::Slot& sl) {
-  if (sl.stream) HIP_TRY(hipStreamSynchronize(sl.stream));
-  HIP_TRY(hipStreamSynchronize(st->solve_stream)); HIP_TRY(hipStreamSynchronize(st->build_stream)); HIP_TRY(hipStreamSynchronize(st->result_stream));
-  destroy_lent(sl.batch);
-  sl.batch = nullptr;
-  return SLSLAM_OK;
-}
-}  // namespace
-
-extern "C" int slslam_lba_stream_create(int device, const slslam_solver_options* opt, int depth, slslam_lba_stream** out) {
-  if (!out) return SLSLAM_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  const int ndev = device_count();
-  if (ndev <= 0) return SLSLAM_ERR_NO_DEVICE;
-  if (device < 0) { if (hipGetDevice(&device) != hipSuccess) return SLSLAM_ERR_NO_DEVICE; }
-  if (device >= ndev || depth < 1 || depth > 8) return SLSLAM_ERR_INVALID_ARGUMENT;
-  slslam_lba_stream* st = new (std::nothrow) slslam_lba_stream();
-  if (!st) return SLSLAM_ERR_HIP;
-  st->device = device; st->depth = depth;
-  if (opt) st->opt = *opt; else slslam_default_options(&st->opt);
-  if (st->opt.refill_headroom_percent <= 0) st->opt.refill_headroom_percent = 10;
-  st->opt.use_graph = 1;
-  int threads = st->opt.host_threads;
-  if (threads <= 0) threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
-  st->opt.host_threads = threads;
-  st->pool.reset(new HostPool(threads));
-  st->slots.resize((size_t)depth);
-  if (hipSetDevice(device) != hipSuccess) { delete st; return SLSLAM_ERR_NO_DEVICE; }
-  // TWO streams serve every slot whose batches are built on the device: ingest (the host link) and build + solve + results.  A process has
-  // few hardware queues (4 unless GPU_MAX_HW_QUEUES says otherwise) and streams that share one run one behind the other: the slots' own
-  // streams - what the host-packer path overlaps its uploads with - are made when that path is first taken, not before.
-  // The ingest stream gets the highest priority: its few workgroups must find wave slots while a solve's thousands are queued.
-  int pr_lo = 0, pr_hi = 0;
-  (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
-  if (hipStreamCreateWithPriority(&st->ingest_stream, hipStreamNonBlocking, pr_hi) != hipSuccess || hipStreamCreateWithFlags(&st->solve_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithPriority(&st->build_stream, hipStreamNonBlocking, 0) != hipSuccess ||
-      hipStreamCreateWithFlags(&st->result_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&st->ev_solved, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&st->ev_built, hipEventDisableTiming) != hipSuccess) {
-    slslam_lba_stream_destroy(st);
-    return SLSLAM_ERR_HIP;
-  }
-  *out = st;
-  return SLSLAM_OK;
-}
-
-extern "C" void slslam_lba_stream_destroy(slslam_lba_stream* st) {
-  if (!st) return;
-  (void)hipSetDevice(st->device);
-  const hipStream_t shared[] = { st->ingest_stream, st->solve_stream, st->build_stream, st->result_stream };
-  for (hipStream_t q : shared) if (q) (void)hipStreamSynchronize(q);
-  for (auto& sl : st->slots) {
-    if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-    if (sl.batch) destroy_lent(sl.batch);
-    if (sl.stream) (void)hipStreamDestroy(sl.stream);
-  }
-  for (hipStream_t q : shared) if (q) (void)hipStreamDestroy(q);
-  if (st->ev_solved) (void)hipEventDestroy(st->ev_solved);
-  if (st->ev_built) (void)hipEventDestroy(st->ev_built);
-  delete st;
-}
-
-namespace {
-int stream_submit_impl(slslam_lba_stream* st, const slslam_lba_window* windows, const unsigned int* const* packed, int n, int* ticket);
-}
-extern "C" int slslam_lba_stream_submit(slslam_lba_stream* st, const slslam_lba_window* windows, int n, int* ticket) {
-  return stream_submit_impl(st, windows, nullptr, n, ticket);
-}
-extern "C" int slslam_lba_stream_submit_packed(slslam_lba_stream* st, const slslam_lba_window* windows, const unsigned int* const* packed_index, int n, int* ticket) {
-  return stream_submit_impl(st, windows, packed_index, n, ticket);
-}
-namespace {
-int stream_submit_impl(slslam_lba_stream* st, const slslam_lba_window* windows, const unsigned int* const* packed, int n, int* ticket) {
-  if (!st || !windows || n <= 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-  const auto t0 = std::chrono::steady_clock::now();
-  // windows whose indices came narrowed and that end up on the host packer (the slot's first batch, a refill the device build does not take)
-  // get their three index arrays back first
-  std::vector<slslam_lba_window> expanded;
-  std::vector<std::vector<int>> exp_idx;
-  auto expand = [&]() -> const slslam_lba_window* {
-    if (!packed) return windows;
-    if (!expanded.empty()) return expanded.data();
-    expanded.assign(windows, windows + n);
-    exp_idx.resize((size_t)n);
-    for (int i = 0; i < n; ++i)
-      if (packed[i]) expand_indices(packed[i], (size_t)std::max(0, windows[i].num_observations), exp_idx[(size_t)i], &expanded[(size_t)i]);
-    return expanded.data();
-  };
-  auto& sl = st->slots[(size_t)(st->next_ticket % st->depth)];
-  if (sl.in_flight) return SLSLAM_ERR_STATE;             // its results have not been collected
-  HIP_TRY(hipSetDevice(st->device));
-  int rc = SLSLAM_ERR_UNSUPPORTED;
-  hipStream_t run = st->solve_stream;                     // where this ticket's solve and download go
-  if (sl.batch && sl.n == n) {
-    slslam_lba_batch* b = sl.batch;
-    // the build stage on the device: ingest on the stream's ONE ingest stream, build + solve + results on its ONE solve stream
-    if (refillable_as_is(b, n) && fits_batch_path(b, windows, packed, n)) {
-      rc = refill_device(b, windows, n, st->build_stream, st->ingest_stream, packed);
-      if (rc == SLSLAM_OK) {
-        run = st->solve_stream;
-        HIP_TRY(hipEventRecord(st->ev_built, st->build_stream));
-        HIP_TRY(hipStreamWaitEvent(run, st->ev_built, 0));
-      }
-    }
-    if (rc == SLSLAM_ERR_UNSUPPORTED) {
-      // the host packer (or refused: a new batch below): its uploads overlap the other slots' solves on a stream of the slot's own
-      if (!sl.stream) HIP_TRY(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-      rc = slslam_lba_batch_refill(b, expand(), n, (void*)sl.stream);
-      if (rc == SLSLAM_OK) run = sl.stream;
-    }
-  }
-  if (rc == SLSLAM_OK) { ++st->n_refills; if (sl.batch->device_built) { ++st->n_device_builds; if (sl.batch->ingest_pinned) ++st->n_zero_copy; } }
-  else if (rc == SLSLAM_ERR_UNSUPPORTED) {
-    // the first batch of the slot, another number of windows, or windows that do not fit the room the slot's arrays have: a new batch
-    if (sl.batch && (rc = drop_slot_batch(st, sl)) != SLSLAM_OK) return rc;
-    slslam_lba_batch* b = nullptr;
-    if ((rc = make_slot_batch(st, expand(), n, &b)) != SLSLAM_OK) return rc;
-    sl.batch = b; sl.n = n;
-    ++st->n_builds;
-  } else return rc;
-  if ((rc = slslam_lba_batch_solve(sl.batch, (void*)run)) != SLSLAM_OK) return rc;
-  if (run == st->solve_stream) {
-    // the results leave on a stream of their own, behind the solve: the next batch's build does not wait for this batch's export
-    HIP_TRY(hipEventRecord(st->ev_solved, run));
-    HIP_TRY(hipStreamWaitEvent(st->result_stream, st->ev_solved, 0));
-    run = st->result_stream;
-  }
-  if ((rc = download_async_impl(sl.batch, (void*)run, /*allow_inplace=*/true)) != SLSLAM_OK) return rc;
-  sl.out_params.resize((size_t)n);
-  for (int i = 0; i < n; ++i) sl.out_params[(size_t)i] = windows[i].parameters;
-  sl.ticket = st->next_ticket; sl.in_flight = true;
-  if (ticket) *ticket = (int)st->next_ticket;
-  ++st->next_ticket; st->n_windows += n;
-  st->ms_submit += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return SLSLAM_OK;
-}
-}  // namespace
-
-extern "C" int slslam_lba_stream_collect(slslam_lba_stream* st, int ticket, slslam_summary* summaries) {
-  if (!st || ticket < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-  auto& sl = st->slots[(size_t)(ticket % st->depth)];
-  if (!sl.in_flight || sl.ticket != ticket) return SLSLAM_ERR_STATE;
-  HIP_TRY(hipSetDevice(st->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = slslam_lba_batch_wait(sl.batch);
-  if (rc != SLSLAM_OK) return rc;
-  const auto t1 = std::chrono::steady_clock::now();
-  std::vector<int> rs((size_t)sl.n, SLSLAM_OK);
-  // (the step counts through get_summary, which routes a window of a MIXED batch - oversize windows among ordinary ones - to the part
-  // that solved it: the top-level batch of such a slot holds no LM states of its own)
-  std::vector<int> steps((size_t)sl.n, 0);
-  slslam_lba_batch* bt = sl.batch;
-  bool dev = bt->device_built && !bt->part[0];
-  std::vector<int> flagged;
-  if (dev) for (int i = 0; i < sl.n; ++i) if (bt->build_status[(size_t)i] != SLSLAM_OK) flagged.push_back(i);
-  // A window as submit() handed it over, from what the device read (bt->host_src: the staging copy of pageable arrays, or the caller's
-  // page-locked ones), its initial parameters put back into the caller's `parameters` first: results depend only on what the caller's arrays
-  // held at submit time - a pageable array may have been reused or freed since, and `parameters` is written here, never read.
-  std::vector<std::vector<int>> idx((size_t)sl.n);
-  auto as_submitted = [&](int i) -> slslam_lba_window {
-    const RawWin& r = bt->host_src[(size_t)i];
-    slslam_lba_window w{};
-    w.num_cameras = r.C; w.num_lines = r.L; w.num_observations = r.M; w.observations = r.obs; w.parameters = sl.out_params[(size_t)i];
-    const size_t np = (size_t)6 * r.C + (size_t)4 * r.L;
-    if (np && r.params_in != w.parameters) std::memcpy(w.parameters, r.params_in, np * sizeof(double));
-    if (r.packed) expand_indices(r.packed, (size_t)r.M, idx[(size_t)i], &w);
-    else { w.camera_index = r.cam; w.line_index = r.line; w.fixed_index = r.fixed; }
-    return w;
-  };
-  // A refill that did not fit the room the slot's arrays have (only the device knows the tiles a set needs: k_build_layout flags the refill as
-  // a whole) is what submit answers with a new batch when the HOST can see it: the same here, late - the set is packed by the host threads into
-  // a batch of its own size (plus the stream's headroom), solved as ONE batch, and that batch takes the slot, so that the sets that follow fit.
-  // (Solving 1024 flagged windows one by one would take a second, and the next set of that shape would be flagged again.)  The layout's fit flag
-  // decides, whatever else the windows were flagged for: the host packer takes a window for the host path (a camera that sees a line twice)
-  // in its stride - only a window with bad input, which the packer refuses, keeps the set on the per-window path below.
-  bool whole_nofit = dev && sl.n > 0 && !bt->h_buildwin.empty() && !bt->h_totals.empty() && bt->h_totals[3] == 0 && (int)bt->host_src.size() == sl.n;
-  for (int i = 0; whole_nofit && i < sl.n; ++i) if (bt->h_buildwin[i].status & kBuildInvalid) whole_nofit = false;
-  if (whole_nofit) {
-    const int n = sl.n;
-    std::vector<slslam_lba_window> ws((size_t)n);
-    for (int i = 0; i < n; ++i) ws[(size_t)i] = as_submitted(i);
-    slslam_lba_batch* nb = nullptr;
-    if ((rc = make_slot_batch(st, ws.data(), n, &nb)) != SLSLAM_OK) return rc;
-    rc = slslam_lba_batch_solve(nb, (void*)st->solve_stream);
-    if (rc == SLSLAM_OK) rc = download_async_impl(nb, (void*)st->solve_stream, /*allow_inplace=*/false);
-    if (rc == SLSLAM_OK) rc = slslam_lba_batch_wait(nb);
-    if (rc != SLSLAM_OK) { destroy_lent(nb); return rc; }
-    if ((rc = drop_slot_batch(st, sl)) != SLSLAM_OK) return rc;
-    sl.batch = bt = nb;
-    ++st->n_builds; st->n_fallback_windows += n;
-    dev = false; flagged.clear();
-  }
-  auto one = [&](int i) {
-    if (dev && bt->build_status[(size_t)i] != SLSLAM_OK) return;                 // below
-    int r = SLSLAM_OK;
-    if (!(dev && bt->results_inplace)) r = slslam_lba_batch_get_parameters(bt, i, sl.out_params[(size_t)i]);     // (in place: the device wrote them there)
-    slslam_summary sm;
-    if (r == SLSLAM_OK) r = slslam_lba_batch_get_summary(bt, i, &sm);
-    if (r == SLSLAM_OK) { steps[(size_t)i] = sm.num_successful_steps + sm.num_unsuccessful_steps; if (summaries) summaries[i] = sm; }
-    rs[(size_t)i] = r;
-  };
-  if (dev && bt->results_inplace) { for (int i = 0; i < sl.n; ++i) one(i); }      // (summaries only: not worth waking the pool)
-  else st->pool->run(sl.n, one);
-  // windows the device build flagged (a camera that sees a line twice, a line with more than 64 observations, more than 20 free cameras,
-  // no room in the slot's arrays, bad input): solved here through the host path, one by one, from what the device read - their status is
-  // whatever that path says
-  for (int i : flagged) {
-    slslam_lba_window w = as_submitted(i);
-    slslam_solver_options o = st->opt;
-    o.refill_headroom_percent = 0; o.host_threads = 1; o.device_build = -1;
-    slslam_summary sm;
-    const int fr = slslam_lba_solve(&w, &o, &sm, nullptr, 0, nullptr);
-    if (fr == SLSLAM_OK) { steps[(size_t)i] = sm.num_successful_steps + sm.num_unsuccessful_steps; if (summaries) summaries[i] = sm; }
-    rs[(size_t)i] = fr;
-    ++st->n_fallback_windows;
-  }
-  for (int r : rs) if (r != SLSLAM_OK) rc = r;
-  for (int i = 0; i < sl.n; ++i) st->n_iterations += steps[(size_t)i];   // reference src/slam.cpp:949-950
-  sl.in_flight = false;
-  const auto t2 = std::chrono::steady_clock::now();
-  st->ms_collect_wait += std::chrono::duration<double, std::milli>(t1 - t0).count();
-  st->ms_collect_copy += std::chrono::duration<double, std::milli>(t2 - t1).count();
-  return rc;
-}
-
-extern "C" int slslam_lba_stream_build_stats(const slslam_lba_stream* st, long long* device_builds, long long* zero_copy, long long* fallback_windows) {
-  if (!st) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (device_builds) *device_builds = st->n_device_builds;
-  if (zero_copy) *zero_copy = st->n_zero_copy;
-  if (fallback_windows) *fallback_windows = st->n_fallback_windows;
-  return SLSLAM_OK;
-}
-
-extern "C" int slslam_lba_stream_batch(slslam_lba_stream* st, int ticket, slslam_lba_batch** batch) {
-  if (!st || !batch || ticket < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-  auto& sl = st->slots[(size_t)(ticket % st->depth)];
-  if (sl.ticket != ticket || !sl.batch) return SLSLAM_ERR_STATE;
-  *batch = sl.batch;
-  return SLSLAM_OK;
-}
-
-extern "C" int slslam_lba_stream_stats(const slslam_lba_stream* st, double* ms_submit, double* ms_collect_wait, double* ms_collect_copy,
-                                       long long* refills, long long* builds, long long* windows, long long* lm_iterations, int* host_threads) {
-  if (!st) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (ms_submit) *ms_submit = st->ms_submit;
-  if (ms_collect_wait) *ms_collect_wait = st->ms_collect_wait;
-  if (ms_collect_copy) *ms_collect_copy = st->ms_collect_copy;
-  if (refills) *refills = st->n_refills;
-  if (builds) *builds = st->n_builds;
-  if (windows) *windows = st->n_windows;
-  if (lm_iterations) *lm_iterations = st->n_iterations;
-  if (host_threads) *host_threads = st->pool ? st->pool->threads() : 1;
   return SLSLAM_OK;
 }
 

@@ -27,29 +27,6 @@ enum { kBlGmax = 0, kBlXn2 = 1, kBlFail = 2, kBlModel = 3, kBlDn2 = 4, kBlXn2New
 enum { kBigCam = 21 };         // R[9] JL[9] t[3] per camera and buffer (accepted, candidate)
 enum { kBgFail = 4, kBgWasFresh = 5, kBgScal = 8 };
 
-struct BigPtrs {
-  const int* ob_line;          // [nobs] sorted line of every sorted observation
-  const int* cam_win;          // [ncam]
-  double* J;                   // [nobs][kBigObs]
-  double* F;                   // [nobs][kBigF]
-  double* cost;                // [2][nobs] block cost of every observation at the accepted / at the candidate point (dense: the
-                               // per-window sums stream them)
-  double* camtab;              // [ncam][2][kBigCam]
-  double* line_acc;            // [nline][kBigLine]
-  double* sys;                 // per window: S [n x ld] | b [n] | g [n] | h [n] | y [n] | Jacobi scale of the unknowns [n]
-  const long long* sys_off;    // [nwin]
-  // gather lists, built on the host: every sum of the path is formed by ONE thread group walking a list in a fixed order - no
-  // atomics, results bitwise reproducible
-  const int* cam_ptr;          // [ncam + 1] observations (sorted index, ascending) of every camera
-  const int* cam_obs;
-  const int* pair_ptr;         // [npairs + 1] per (window, camera pair r >= c): the line's two observations (row camera r, column camera c)
-  const int* pair_row;
-  const int* pair_col;
-  const int* pair_desc;        // [npairs] window | r << 16 | c << 24
-  double* scal;                // [nwin][kBgScal]
-  int* flags;                  // [nwin][2] factorisation failure (PoPtrs.flags)
-  long long npairs, nobs;
-};
 __host__ __device__ inline int big_ld(int n) { return ((n + 7) / 8) * 8 + 8; }
 __host__ __device__ inline long long big_sys_doubles(int n) { return (long long)(n > 0 ? n : 1) * big_ld(n) + 5LL * (n > 0 ? n : 1); }
 

@@ -1,7 +1,7 @@
 // slslam_amd/csrc/lba_device_build.h — the LBAProblem::build stage ON THE DEVICE (round 6).
 //
 // What the reference does per window before the solve - wire M residual blocks from five arrays, src/lba_problem.cpp:54-93, fed by
-// src/slam.cpp:899-921 - is lba_pack.cpp::pack_window + lba_api.hip::plan_layout / fill_window on the host: validation, counting sorts,
+// src/slam.cpp:899-921 - is lba_pack.cpp::pack_window / plan_layout + lba_api.hip::fill_window on the host: validation, counting sorts,
 // grouping by first free camera, best-fit bin packing of the lines into 16-lane rows, lane layout, tile descriptors, chunk cuts.  For a
 // STREAM of windows (BASELINE config 4) that host work bounded the product (17.5 ms of packing on 16 host threads per 1024-window batch
 // against 15 ms of GPU).  Here the same build runs as four kernels on the arrays as the caller holds them:
@@ -15,7 +15,7 @@
 //                   sequential: a wave walks its lines, the 17 open-row lists live one per lane (ballots pick the list, the rows of a list
 //                   are chained through LDS)
 //   k_build_order   one workgroup per window: row order, line order, line pointers, the stable sort of every line's observations by camera
-//   k_build_layout  one workgroup: prefix sums over the windows, the (graded) chunk cuts and the dispatch order of plan_layout, the
+//   k_build_layout  one workgroup: prefix sums over the windows, the (graded) chunk cuts and the dispatch order of lba_pack.cpp::plan_layout, the
 //                   fit test against the room the batch's arrays have
 //   k_build_tiles   thread <-> tile over inputs staged in LDS, then wave <-> tile for the stable descriptor sort: lane map, skew flags,
 //                   line descriptors (sorted per tile for the grouped sweep), pair items
@@ -37,38 +37,6 @@
 #include "lba_eliminate_mfma_maps.h"
 
 namespace slslam {
-
-// One per window of a refill, written by the host (pointers the DEVICE can read: pinned host memory or device memory).
-struct RawWin {
-  const int* cam;             // [M] camera_index, or nullptr when `packed` is given
-  const int* line;            // [M] line_index
-  const int* fixed;           // [2M] fixed_index
-  const uint32_t* packed;     // [M] line | camera << 16 | camera constant << 24 | line constant << 25 (the narrowed form), or nullptr
-  const double* obs;          // [8M]
-  const double* params_in;    // [6C + 4L] the initial parameters (where the ingest reads them)
-  double* params;             // [6C + 4L] where the solved parameters go when they are written in place (the caller's array), or null
-  long long param_off;        // offset of the window in the batch's exported parameter vector
-  int C, L, M;
-  int cam_off, line_off, obs_off;     // the window's place in the batch arrays
-  int pad;
-};
-
-enum { kBuildInvalid = 1, kBuildHostPath = 2, kBuildNoFit = 4 };     // BuildWin.status bits
-struct BuildWin {
-  int status;                 // 0, or why the window was not built (emitted empty)
-  int Cf, ntiles, nitems, nfree_params, nkept;
-  int nchunks, graded;        // (k_build_layout) the cut: chunk count and, for graded sizes, the number of slot rounds
-};
-
-struct BuildLine;
-// What the stages of a window's build hand to each other (device only).
-struct BuildMid {
-  unsigned long long freeset, constset;   // cameras: free (used and not constant) | constant
-  int ok;                     // 0: the window was flagged, the later stages skip it
-  int Cf, free_lines, nitems;
-  int n_long, n_cls0;         // (k_build_lines) lines with more than 16 observations | of at least 4 lanes among the others: their runs in the packing order
-  int nrows, ntr, ntp, cls_row[4];        // (k_build_rows) rows made | row entries and tile ranges of the long lines | row range of each length class
-};
 
 // Everything the build kernels touch, by value.
 struct BuildPtrs {
@@ -104,7 +72,7 @@ struct BuildPtrs {
   unsigned long long* dbg;    // timing experiments (tools/build_phases.py): constant-clock (100 MHz) stamps of window 0's build, or null
 };
 
-// How k_build_layout cuts (the batch-wide numbers slslam_lba_batch_finalize resolved: plan_layout with frozen = true) and what has to fit.
+// How k_build_layout cuts (the batch-wide numbers slslam_lba_batch_finalize resolved: lba_pack.h::CutPolicy, plan_layout with frozen = true) and what has to fit.
 struct LayoutArgs {
   int chunks_per_window, reproducible, auto_rounds, auto_cpw, elim_waves, elim_mode;
   int cap_tiles, cap_items, cap_chunks, cap_maxn, slab_sum, slab_sum_image;
@@ -745,7 +713,7 @@ __global__ __launch_bounds__(256) void k_build_order(BuildPtrs P) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// plan_layout (lba_api.hip) with frozen = true, on the device: one workgroup, thread <-> a run of consecutive windows.
+// plan_layout (lba_pack.cpp) with frozen = true, on the device: one workgroup, thread <-> a run of consecutive windows.
 __device__ inline int layout_window_chunks(const LayoutArgs& a, int ntiles, int* graded_chunks, int* graded_rounds, int* per_chunk) {
   int gc = 0, gr = 0, per = 1;
   if (a.chunks_per_window < 0) { gr = (-a.chunks_per_window) / 1000; gc = (-a.chunks_per_window) % 1000; per = 1; }

@@ -6,6 +6,7 @@
 #define SLSLAM_LBA_ELIMINATE_MFMA_MAPS_H_
 
 #include "lba_math.h"     // SLS_HD
+#include "lba_types.h"    // kDiagRec, kPTiles, sys_doubles_mfma: the slab layout the host plans with
 
 namespace slslam {
 
@@ -13,11 +14,7 @@ enum { kPanelPlane = 400 };        // doubles per plane of the F panel: 64 lanes
 enum { kPanelDoubles = 4 * kPanelPlane };        // the pad of every plane (rows 384..399) stays zero: the slab of "lane 64", what rows of
                                                  // cameras that do not see a line read
 enum { kGatherLines = 32 };        // lines per tile the gather table holds (tiles with more derive the sources from the masks)
-enum { kDiagRec = 33, kDiagB = 21, kDiagG = 27 };   // camera record: J_c'^T J_c' lower triangle [21] | b' [6] | g' [6]
-enum { kPTiles = 10, kPTileDoubles = 256 };
 enum { kMfmaMaxFree = 10 };
-
-SLS_HD constexpr int sys_doubles_mfma(int n) { return kPTiles * kPTileDoubles + (n / 6) * kDiagRec; }
 
 // free cameras with a row in the 16-row block I of the stacked system (camera cf owns rows 6 cf .. 6 cf + 5)
 SLS_HD constexpr unsigned block_cam_mask(int I) {

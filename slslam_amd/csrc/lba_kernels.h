@@ -41,16 +41,7 @@ namespace slslam {
 enum { kCamTab = 21 };   // doubles per camera in LDS: R[9] JL[9] t[3]; odd stride (42 dwords): conflict-free
                          // ds_read_b64 across cameras.  The Jacobi scale (6 per FREE camera) is a second table.
 
-// The wave's partial of the reduced camera system, in LDS and (verbatim) in its HBM slab.  Laid out by
-// BLOCK, with odd strides in 8-byte units so that the ds_add_f64 of lanes working on different
-// cameras / camera pairs fall on different banks (a packed lower triangle puts the 45 pair blocks of
-// a 10-camera window on only 8 distinct bank offsets):
-//   camera record cf  (kCamAcc = 39):  diagonal block, lower triangle [21] | b[6] | g[6] | hdiag[6]
-//   pair block (cj > ci) (kPairAcc = 37): 6x6, row a of cj, column b of ci [36] | pad
-// 20 cameras / 10 free: 3360 + 480 + 16440 + 24 = 20 304 B -> 8 workgroups per CU.
-enum { kCamAcc = 39, kPairAcc = 37, kRecB = 21, kRecG = 27, kRecH = 33 };
 enum { kMfmaTiles = kPTiles, kMfmaRec = kDiagRec };   // slab of the matrix-core elimination: 10 accumulator tiles | camera records
-__host__ __device__ inline int sys_doubles(int n) { const int cf = n / 6; return cf * kCamAcc + ((cf * (cf - 1)) / 2) * kPairAcc; }
 __device__ __forceinline__ int pair_base(int ncf, int cj, int ci) { return ncf * kCamAcc + ((cj * (cj - 1)) / 2 + ci) * kPairAcc; }
 
 __device__ __forceinline__ int tri_index(int r, int c) { return (r * (r + 1)) / 2 + c; }  // r >= c
@@ -929,36 +920,6 @@ __device__ __forceinline__ void patch_trace(BatchPtrs& p, int w, const LMState* 
   if (st->ntrace > 0 && st->ntrace <= kMaxTrace) p.trace[(long long)w * kMaxTrace + st->ntrace - 1].gradient_max_norm = gm;
 }
 
-__host__ __device__ inline int solve_pad(int n) { return ((n + 15) / 16) * 16; }
-__host__ __device__ inline int solve_stride(int n) { return ((solve_pad(n) + 30) / 32) * 32 + 1; }  // == 1 (mod 32) doubles
-// Where entry q of a chunk partial (camera records | pair blocks, see kCamAcc / kPairAcc) lives in the reduced solve's LDS image
-// A (N x ld, lower triangle) | b | g | hdiag; 0xFFFF = padding.  One table per distinct n of a batch, built on the host.
-inline void sys_map_build(int n, unsigned short* out) {
-  const int ncf = n / 6, N = solve_pad(n), ld = solve_stride(n);
-  for (int q = 0; q < sys_doubles(n); ++q) {
-    int off = 0xFFFF;
-    if (q < ncf * kCamAcc) {
-      const int cf = q / kCamAcc, ee = q - cf * kCamAcc;
-      if (ee < kRecB) {
-        int a = 0;
-        while (((a + 1) * (a + 2)) / 2 <= ee) ++a;
-        off = (6 * cf + a) * ld + 6 * cf + (ee - (a * (a + 1)) / 2);
-      } else {
-        const int v2 = (ee - kRecB) / 6, a = (ee - kRecB) - 6 * v2;      // 0 = b, 1 = g, 2 = hdiag
-        off = N * ld + v2 * N + 6 * cf + a;
-      }
-    } else {
-      const int pq = q - ncf * kCamAcc, pr = pq / kPairAcc, ee = pq - pr * kPairAcc;
-      if (ee < 36) {
-        int cj = 1;
-        while (((cj + 1) * cj) / 2 <= pr) ++cj;
-        const int ci = pr - (cj * (cj - 1)) / 2;
-        off = (6 * cj + ee / 6) * ld + 6 * ci + (ee % 6);
-      }
-    }
-    out[q] = (unsigned short)off;
-  }
-}
 // The inverse of a diagonal tile's factor is kept IN the tile: strictly lower part transposed into the tile's
 // (otherwise unused) strict upper triangle, its diagonal 1 / L[r][r] in a vector: 36.5 KB of LDS for n = 60,
 // i.e. 4 workgroups per CU and the whole 1024-window batch resident in one round.

@@ -556,6 +556,129 @@ std::vector<int> chunk_boundaries_graded(int ntiles, int nchunks, const int* wei
   return b;
 }
 
+int plan_layout(CutPolicy& cut, const std::vector<PackedWindow>& wins, bool frozen, LayoutPlan* out) {
+  LayoutPlan& L = *out;
+  const int B = (int)wins.size();
+  long long total_tiles = 0;
+  for (const PackedWindow& P : wins) total_tiles += (long long)P.tiles.size();
+  if (!frozen) {
+    // the sweeps run 8 one-wave workgroups per CU (LDS): the same number of chunks for every window, chosen so that
+    // the batch fills whole rounds of the chip's wave slots with about 36 tiles per chunk at most
+    // (1024 bench windows: 6 chunks of 33 tiles = 6144 waves = 3 rounds of 256 CUs x 8)
+    const long long slots = (8LL / cut.elim_waves) * cut.num_cus;      // chunk workgroups resident per round
+    const long long per_round = 36LL * cut.elim_waves * slots;
+    const long long rounds = std::max<long long>(1, (total_tiles + per_round - 1) / per_round);
+    cut.auto_rounds = (int)std::min<long long>(rounds, 1 << 20);
+    cut.auto_cpw = (int)std::min<long long>(std::max<long long>(1, (slots * rounds) / std::max(1, B)), 1 << 20);
+  }
+  L.wins.resize((size_t)B); L.param_off.resize((size_t)B); L.ob_orig_off.resize((size_t)B); L.item_base.resize((size_t)B);
+  L.win_graded.assign((size_t)B, 0);
+  std::vector<int> chunk_rank;           // per chunk (window-major): 0 dispatched in the first class, 1 in the second (graded sizes)
+  std::vector<Chunk> chunks;
+  for (int wi = 0; wi < B; ++wi) {
+    const PackedWindow& P = wins[wi];
+    WinDesc& wd = L.wins[wi];
+    std::memset(&wd, 0, sizeof(wd));
+    wd.C = P.C; wd.Cf = P.Cf; wd.L = P.L; wd.M = P.M;
+    wd.cam_off = (int)L.ncam; wd.line_off = (int)L.nline; wd.obs_off = (int)L.nobs;
+    wd.tile_off = (int)L.ntiles; wd.ntiles = (int)P.tiles.size();
+    wd.n = 6 * P.Cf; wd.sys_off = (int)L.sys; wd.nfree_params = P.nfree_params; wd.nkept = P.nkept;
+    L.maxC = std::max(L.maxC, P.C); L.maxn = std::max(L.maxn, wd.n);
+    L.param_off[wi] = L.params; L.params += 6LL * P.C + 4LL * P.L;
+    L.ob_orig_off[wi] = (int)L.nobs;
+    L.item_base[wi] = (int)L.nitems;
+    // chunks: runs of tiles handled by one wave.  Few long chunks keep the per-chunk partial of
+    // the reduced system (a slab in HBM) small against the observation stream; many short chunks
+    // fill the chip when the batch is small.
+    int per_chunk;
+    int graded_chunks = 0, graded_rounds = 0;             // > 0: graded chunk sizes (below)
+    if (cut.chunks_per_window < 0) {                   // the caller asks for the graded cut a batch reported (slslam_lba_batch_window_chunks < 0):
+      graded_rounds = (-cut.chunks_per_window) / 1000; graded_chunks = (-cut.chunks_per_window) % 1000;        // -(1000 rounds + chunks)
+      if (graded_rounds < 2 || graded_chunks < graded_rounds) return SLSLAM_ERR_INVALID_ARGUMENT;
+      per_chunk = 1;
+    } else
+    if (cut.chunks_per_window > 0) per_chunk = std::max(1, (wd.ntiles + cut.chunks_per_window - 1) / cut.chunks_per_window);
+    else {
+      // automatic: the batch-wide numbers above - or, with slslam_solver_options.reproducible, a function of the WINDOW alone (what the
+      // automatic choice gives the windows of a batch that fills the chip: chunks of at most 34 tiles, graded for three rounds of the
+      // wave slots), so that a window is cut the same way whatever batch it sits in
+      long long rounds = cut.auto_rounds, cpw = cut.auto_cpw;
+      if (cut.reproducible) { cpw = std::max(1, (wd.ntiles + 33) / 34); rounds = 3; }
+      // (down to ONE tile per wave when the chip has room: since the camera tables are shared through memory, the partials of a
+      // many-chunk window summed chip-wide (k_slab_reduce) and the first tile's loads requested ahead of the set-up, a second tile
+      // costs a resident window more than a second chunk does - 0.44 / 0.60 / 0.98 -> 0.38 / 0.50 / 0.89 ms at W = 5 / 10 / 20,
+      // round 4; rounds 2-3 kept at least two tiles per wave)
+      per_chunk = (int)std::max<long long>(cut.elim_waves, (wd.ntiles + cpw - 1) / cpw);
+      // GRADED sizes when every wave slot runs several chunks (rounds >= 2) of many tiles.  A launch ends when the slowest slot has
+      // finished its LAST chunk; with equal chunks - exactly `rounds` per slot, so nothing is left to balance with - that wait was a
+      // fifth of the sweep (tools/chunk_timeline.py: 2048 slots 81 % busy, chunk durations 206-442 us around 297).  Now the chunks a
+      // window contributes to the first round of the slots carry 70 % of a slot's share of the tiles, those of the second round 20 %
+      // (30 % when there are only two), the rest what is left, and the chunk array - the dispatch order - lists the classes one after
+      // the other: a slot that is late with its long chunk takes fewer short ones.  The slab count per window - what the reduced
+      // solve reads - does not change.
+      if (rounds >= 2 && cpw >= rounds && cpw < 1000 && cut.elim_waves == 1 && wd.ntiles >= 8 * cpw) {
+        graded_chunks = (int)cpw; graded_rounds = (int)rounds;
+      }
+    }
+    int weights[1000];
+    for (int c = 0; c < graded_chunks; ++c) {
+      const int q = (int)(((long long)c * graded_rounds) / graded_chunks);           // the round of the slots this chunk belongs to
+      weights[c] = q == 0 ? 84 : q == 1 ? (graded_rounds == 2 ? 36 : 24) : std::max(1, 12 / (graded_rounds - 2));
+    }
+    std::vector<int> bounds = graded_chunks > 0 ? chunk_boundaries_graded(wd.ntiles, graded_chunks, weights) : chunk_boundaries(wd.ntiles, per_chunk);
+    L.win_graded[wi] = (graded_chunks > 0 && (int)bounds.size() - 1 == graded_chunks) ? graded_rounds : 0;
+    if (cut.big_mode) { bounds.assign(2, 0); }            // no tiles: one chunk per window carries its step statistics
+    wd.chunk_off = (int)chunks.size(); wd.nchunks = (int)bounds.size() - 1;
+    wd.slab_off = (int)L.slab;
+    const int nsys = cut.elim_mode == 1 ? sys_doubles_mfma(wd.n) : sys_doubles(wd.n);
+    const long long slab_stride = (long long)nsys + kSlabScalars;
+    L.max_chunks = std::max(L.max_chunks, wd.nchunks); L.max_sys = std::max(L.max_sys, nsys);
+    for (int c = 0; c < wd.nchunks; ++c) {
+      Chunk ck; ck.win = wi; ck.tile_begin = wd.tile_off + bounds[c]; ck.tile_end = wd.tile_off + bounds[c + 1];
+      ck.slab_off = (int)L.slab; L.slab += slab_stride;
+      ck.id = (int)chunks.size();
+      chunks.push_back(ck);
+      chunk_rank.push_back(L.win_graded[wi] ? (int)(((long long)c * graded_rounds) / graded_chunks) : 0);
+    }
+    if (L.slab > 0x7fffffffLL) return SLSLAM_ERR_UNSUPPORTED;
+    L.ncam += P.C; L.nline += P.L; L.nobs += P.M; L.sys += wd.n;
+    L.ntiles += (long long)P.tiles.size(); L.nitems += (long long)(P.items.size() / 2);
+    if (L.nobs > 0x7fffffffLL || L.nitems > 0x7fffffffLL) return SLSLAM_ERR_UNSUPPORTED;
+  }
+  // dispatch order: the long chunks of the graded windows (and every chunk of the others) first, the short ones after them; inside a class
+  // the order of the ids (a stable partition: ids, slabs and partial sums keep their window-major places)
+  {
+    int max_rank = 0;
+    for (int r : chunk_rank) max_rank = std::max(max_rank, r);
+    L.chunks.clear(); L.chunks.reserve(chunks.size());
+    for (int r = 0; r <= max_rank; ++r) for (size_t i = 0; i < chunks.size(); ++i) if (chunk_rank[i] == r) L.chunks.push_back(chunks[i]);
+  }
+  return SLSLAM_OK;
+}
+
+long long slab_sum_image_stride(const std::vector<WinDesc>& wins) {
+  long long ext = 0;
+  for (const WinDesc& wd : wins) { const int N = solve_pad(wd.n); ext = std::max<long long>(ext, (long long)N * solve_stride(wd.n) + 6LL * N); }
+  return ((ext + kSlabScalars + 1) / 2) * 2;
+}
+
+void plan_sys_maps(std::vector<WinDesc>& wins, int maxn, bool every_order, bool tables, std::vector<uint16_t>* sys_map_out, std::vector<int>* off_of_cf) {
+  std::vector<uint16_t>& sys_map = *sys_map_out;
+  sys_map.assign(1, (uint16_t)0xFFFF);
+  off_of_cf->assign((size_t)maxn / 6 + 1, -1);
+  if (tables) {
+    for (int cf = 0; cf <= maxn / 6; ++cf) {
+      bool wanted = every_order;
+      for (const WinDesc& wd : wins) if (wd.n == 6 * cf) wanted = true;
+      if (!wanted) continue;
+      (*off_of_cf)[(size_t)cf] = (int)sys_map.size();
+      sys_map.resize(sys_map.size() + (size_t)sys_doubles(6 * cf));
+      sys_map_build(6 * cf, sys_map.data() + (*off_of_cf)[(size_t)cf]);
+    }
+  }
+  for (WinDesc& wd : wins) { const int off = (*off_of_cf)[(size_t)wd.n / 6]; wd.map_off = off < 0 ? 0 : off; }
+}
+
 std::vector<AddrRange> plan_copy_runs(const CopyRange* ranges, size_t n, const AddrRange* regs, size_t nregs, int* barrier_run) {
   // the registration that holds [lo, hi) whole, or -1
   auto reg_of = [&](uintptr_t lo, uintptr_t hi) -> long {

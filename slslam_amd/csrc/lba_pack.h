@@ -67,6 +67,41 @@ std::vector<int> chunk_boundaries(int ntiles, int tiles_per_chunk);
 // ends with everybody's LAST chunk - the shorter that one is, the less the slots wait for the slowest); every chunk gets at least one tile
 std::vector<int> chunk_boundaries_graded(int ntiles, int nchunks, const int* weights);
 
+// ------------------------------------------------------------------------------------------
+// The batch-wide layout of a set of packed windows: where every window's slices go (prefix sums) and how its tiles are cut into chunks -
+// serial and cheap.  Planned for slslam_lba_batch_finalize and for slslam_lba_batch_refill (lba_api.hip); k_build_layout
+// (lba_device_build.h) restates the frozen form on the device.
+struct LayoutPlan {
+  std::vector<WinDesc> wins;
+  std::vector<long long> param_off;             // per window: offset into the exported parameter vector
+  std::vector<int> ob_orig_off, item_base, win_graded;
+  std::vector<Chunk> chunks;                    // dispatch order
+  long long ncam = 0, nline = 0, nobs = 0, ntiles = 0, nitems = 0, sys = 0, slab = 0, params = 0;
+  int maxC = 1, maxn = 0, max_chunks = 0, max_sys = 0;
+  std::vector<uint16_t> sys_map;                // (finalize) the reduced solve's LDS maps, one per system order
+};
+
+// What decides the cut: the caller's options, the batch's sweep, the chip - and the automatic policy as the batch's first plan resolved
+// it (plan_layout with frozen = false writes auto_rounds / auto_cpw; frozen = true reads them: a refill cuts its windows the same way).
+struct CutPolicy {
+  int chunks_per_window = 0;      // slslam_solver_options: > 0 forced, < 0 the graded request -(1000 rounds + chunks), 0 automatic
+  int reproducible = 0;           // slslam_solver_options: the automatic cut is a function of the window alone
+  int elim_waves = 1, elim_mode = 0;     // see BatchPtrs
+  int num_cus = 256;
+  bool big_mode = false;          // windows beyond the tiled sweeps (lba_big.h): one chunk per window, no tiles
+  int auto_rounds = 0, auto_cpw = 0;
+};
+// Reads of a window only C, Cf, L, M, nfree_params, nkept and the sizes of `tiles` and `items`.
+int plan_layout(CutPolicy& cut, const std::vector<PackedWindow>& wins, bool frozen, LayoutPlan* out);
+
+// The slab-sum stride of windows whose sums go straight into the LDS image of the reduced solve (BatchPtrs.slab_sum_image)
+long long slab_sum_image_stride(const std::vector<WinDesc>& wins);
+
+// The reduced solve's sys_map tables (lba_types.h::sys_map_build), one per distinct system order of `wins` up to maxn - every_order: one
+// per free-camera count up to maxn / 6, a refillable batch's next windows may have any of them - or none (tables = false); off_of_cf:
+// per free-camera count its table's offset in sys_map, or -1; every window's map_off is set.
+void plan_sys_maps(std::vector<WinDesc>& wins, int maxn, bool every_order, bool tables, std::vector<uint16_t>* sys_map, std::vector<int>* off_of_cf);
+
 // The copies the copy engine makes of a refill whose arrays are all page-locked (lba_api.hip::refill_device): arrays that lie next to each
 // other go up as one run.  ranges: sorted by lo; barrier = the narrowed index block, a run of its own that nothing merges across.  regs: the
 // page-locked registrations (slslam_pinned_alloc / _register), sorted by lo, disjoint.  A range joins the run before it when it starts at most

@@ -170,5 +170,113 @@ __host__ __device__
 #endif
 inline long long line_rec(const BatchPtrs& p, long long ls, int buf) { return ((long long)buf * p.nline + ls) * kLineRec; }
 
+// ---- the reduced camera system: sizes the kernels (lba_kernels.h) and the host's layout planning (lba_pack.cpp::plan_layout) share.
+// The wave's partial of the reduced camera system, in LDS and (verbatim) in its HBM slab.  Laid out by
+// BLOCK, with odd strides in 8-byte units so that the ds_add_f64 of lanes working on different
+// cameras / camera pairs fall on different banks (a packed lower triangle puts the 45 pair blocks of
+// a 10-camera window on only 8 distinct bank offsets):
+//   camera record cf  (kCamAcc = 39):  diagonal block, lower triangle [21] | b[6] | g[6] | hdiag[6]
+//   pair block (cj > ci) (kPairAcc = 37): 6x6, row a of cj, column b of ci [36] | pad
+// 20 cameras / 10 free: 3360 + 480 + 16440 + 24 = 20 304 B -> 8 workgroups per CU.
+enum { kCamAcc = 39, kPairAcc = 37, kRecB = 21, kRecG = 27, kRecH = 33 };
+#if defined(__HIPCC__)      // (as line_rec above: this header is also read before the HIP runtime's, and by the host-only packer)
+#define SLS_TYPES_HD __host__ __device__ inline
+#else
+#define SLS_TYPES_HD inline
+#endif
+SLS_TYPES_HD int sys_doubles(int n) { const int cf = n / 6; return cf * kCamAcc + ((cf * (cf - 1)) / 2) * kPairAcc; }
+// ... and of the matrix-core elimination (lba_eliminate_mfma.h): ten accumulator tiles | camera records
+enum { kDiagRec = 33, kDiagB = 21, kDiagG = 27 };   // camera record: J_c'^T J_c' lower triangle [21] | b' [6] | g' [6]
+enum { kPTiles = 10, kPTileDoubles = 256 };
+SLS_TYPES_HD constexpr int sys_doubles_mfma(int n) { return kPTiles * kPTileDoubles + (n / 6) * kDiagRec; }
+SLS_TYPES_HD int solve_pad(int n) { return ((n + 15) / 16) * 16; }
+SLS_TYPES_HD int solve_stride(int n) { return ((solve_pad(n) + 30) / 32) * 32 + 1; }  // == 1 (mod 32) doubles
+// Where entry q of a chunk partial (camera records | pair blocks, see kCamAcc / kPairAcc) lives in the reduced solve's LDS image
+// A (N x ld, lower triangle) | b | g | hdiag; 0xFFFF = padding.  One table per distinct n of a batch, built on the host.
+inline void sys_map_build(int n, unsigned short* out) {
+  const int ncf = n / 6, N = solve_pad(n), ld = solve_stride(n);
+  for (int q = 0; q < sys_doubles(n); ++q) {
+    int off = 0xFFFF;
+    if (q < ncf * kCamAcc) {
+      const int cf = q / kCamAcc, ee = q - cf * kCamAcc;
+      if (ee < kRecB) {
+        int a = 0;
+        while (((a + 1) * (a + 2)) / 2 <= ee) ++a;
+        off = (6 * cf + a) * ld + 6 * cf + (ee - (a * (a + 1)) / 2);
+      } else {
+        const int v2 = (ee - kRecB) / 6, a = (ee - kRecB) - 6 * v2;      // 0 = b, 1 = g, 2 = hdiag
+        off = N * ld + v2 * N + 6 * cf + a;
+      }
+    } else {
+      const int pq = q - ncf * kCamAcc, pr = pq / kPairAcc, ee = pq - pr * kPairAcc;
+      if (ee < 36) {
+        int cj = 1;
+        while (((cj + 1) * cj) / 2 <= pr) ++cj;
+        const int ci = pr - (cj * (cj - 1)) / 2;
+        off = (6 * cj + ee / 6) * ld + 6 * ci + (ee % 6);
+      }
+    }
+    out[q] = (unsigned short)off;
+  }
+}
+
+// ---- the build stage on the device (lba_device_build.h): the records the host writes and reads
+// One per window of a refill, written by the host (pointers the DEVICE can read: pinned host memory or device memory).
+struct RawWin {
+  const int* cam;             // [M] camera_index, or nullptr when `packed` is given
+  const int* line;            // [M] line_index
+  const int* fixed;           // [2M] fixed_index
+  const uint32_t* packed;     // [M] line | camera << 16 | camera constant << 24 | line constant << 25 (the narrowed form), or nullptr
+  const double* obs;          // [8M]
+  const double* params_in;    // [6C + 4L] the initial parameters (where the ingest reads them)
+  double* params;             // [6C + 4L] where the solved parameters go when they are written in place (the caller's array), or null
+  long long param_off;        // offset of the window in the batch's exported parameter vector
+  int C, L, M;
+  int cam_off, line_off, obs_off;     // the window's place in the batch arrays
+  int pad;
+};
+
+enum { kBuildInvalid = 1, kBuildHostPath = 2, kBuildNoFit = 4 };     // BuildWin.status bits
+struct BuildWin {
+  int status;                 // 0, or why the window was not built (emitted empty)
+  int Cf, ntiles, nitems, nfree_params, nkept;
+  int nchunks, graded;        // (k_build_layout) the cut: chunk count and, for graded sizes, the number of slot rounds
+};
+
+struct BuildLine;
+// What the stages of a window's build hand to each other (device only).
+struct BuildMid {
+  unsigned long long freeset, constset;   // cameras: free (used and not constant) | constant
+  int ok;                     // 0: the window was flagged, the later stages skip it
+  int Cf, free_lines, nitems;
+  int n_long, n_cls0;         // (k_build_lines) lines with more than 16 observations | of at least 4 lanes among the others: their runs in the packing order
+  int nrows, ntr, ntp, cls_row[4];        // (k_build_rows) rows made | row entries and tile ranges of the long lines | row range of each length class
+};
+
+// ---- windows beyond the tiled sweeps (lba_big.h)
+struct BigPtrs {
+  const int* ob_line;          // [nobs] sorted line of every sorted observation
+  const int* cam_win;          // [ncam]
+  double* J;                   // [nobs][kBigObs]
+  double* F;                   // [nobs][kBigF]
+  double* cost;                // [2][nobs] block cost of every observation at the accepted / at the candidate point (dense: the
+                               // per-window sums stream them)
+  double* camtab;              // [ncam][2][kBigCam]
+  double* line_acc;            // [nline][kBigLine]
+  double* sys;                 // per window: S [n x ld] | b [n] | g [n] | h [n] | y [n] | Jacobi scale of the unknowns [n]
+  const long long* sys_off;    // [nwin]
+  // gather lists, built on the host: every sum of the path is formed by ONE thread group walking a list in a fixed order - no
+  // atomics, results bitwise reproducible
+  const int* cam_ptr;          // [ncam + 1] observations (sorted index, ascending) of every camera
+  const int* cam_obs;
+  const int* pair_ptr;         // [npairs + 1] per (window, camera pair r >= c): the line's two observations (row camera r, column camera c)
+  const int* pair_row;
+  const int* pair_col;
+  const int* pair_desc;        // [npairs] window | r << 16 | c << 24
+  double* scal;                // [nwin][kBgScal]
+  int* flags;                  // [nwin][2] factorisation failure (PoPtrs.flags)
+  long long npairs, nobs;
+};
+
 }  // namespace slslam
 #endif

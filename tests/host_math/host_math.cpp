@@ -205,3 +205,34 @@ int hm_plan_copy_runs(int n, const unsigned long long* lo, const unsigned long l
   return (int)runs.size();
 }
 }
+
+// ---- the batch-wide layout plan (lba_pack.cpp::plan_layout): B windows of ntiles[i] tiles and cf[i] free cameras (plan_layout reads of a
+// window only its counts).  policy[8] = CutPolicy in the order of its members, written back (auto_rounds / auto_cpw as resolved).
+// win_out [B][5]: tile_off, chunk_off, nchunks, slab_off, win_graded; chunks_out [cap][5], dispatch order: win, tile_begin, tile_end, slab_off, id.
+extern "C" int hm_plan_layout(int B, const int* ntiles, const int* cf, int* policy, int frozen, int* win_out, int* chunks_out, int cap, int* nchunks) {
+  std::vector<slslam::PackedWindow> wins((size_t)B);
+  for (int i = 0; i < B; ++i) {
+    slslam::PackedWindow& P = wins[(size_t)i];
+    P.C = 2 * cf[i]; P.Cf = cf[i]; P.L = 10 * ntiles[i]; P.M = 40 * ntiles[i];
+    P.tiles.resize((size_t)ntiles[i]); P.items.resize((size_t)(2 * ntiles[i]));
+  }
+  slslam::CutPolicy cut;
+  cut.chunks_per_window = policy[0]; cut.reproducible = policy[1]; cut.elim_waves = policy[2]; cut.elim_mode = policy[3];
+  cut.num_cus = policy[4]; cut.big_mode = policy[5] != 0; cut.auto_rounds = policy[6]; cut.auto_cpw = policy[7];
+  slslam::LayoutPlan plan;
+  const int rc = slslam::plan_layout(cut, wins, frozen != 0, &plan);
+  policy[6] = cut.auto_rounds; policy[7] = cut.auto_cpw;
+  if (rc != 0) return rc;
+  for (int i = 0; i < B; ++i) {
+    const slslam::WinDesc& wd = plan.wins[(size_t)i];
+    int* o = win_out + 5 * i;
+    o[0] = wd.tile_off; o[1] = wd.chunk_off; o[2] = wd.nchunks; o[3] = wd.slab_off; o[4] = plan.win_graded[(size_t)i];
+  }
+  *nchunks = (int)plan.chunks.size();
+  for (size_t c = 0; c < plan.chunks.size() && (int)c < cap; ++c) {
+    const slslam::Chunk& ck = plan.chunks[c];
+    int* o = chunks_out + 5 * c;
+    o[0] = ck.win; o[1] = ck.tile_begin; o[2] = ck.tile_end; o[3] = ck.slab_off; o[4] = ck.id;
+  }
+  return 0;
+}

@@ -889,6 +889,176 @@ def test_graded_chunk_boundaries(host_math):
             assert b == equal(nt, (nt + m - 1) // m), (nt, nc, b)
 
 
+def _plan(host_math, ntiles, policy, cf=10, frozen=False):
+    """plan_layout (lba_pack.cpp) of windows with ntiles[i] tiles and cf free cameras under a CutPolicy (dict).  Returns (rc, per-window
+    rows (tile_off, chunk_off, nchunks, slab_off, win_graded), the chunk array in dispatch order (win, tile_begin, tile_end, slab_off, id),
+    the policy with auto_rounds / auto_cpw as resolved)."""
+    B = len(ntiles)
+    nt = np.ascontiguousarray(ntiles, dtype=np.int32)
+    cfs = np.full(B, cf, dtype=np.int32) if np.isscalar(cf) else np.ascontiguousarray(cf, dtype=np.int32)
+    keys = ("chunks_per_window", "reproducible", "elim_waves", "elim_mode", "num_cus", "big_mode", "auto_rounds", "auto_cpw")
+    full = dict(chunks_per_window=0, reproducible=0, elim_waves=1, elim_mode=0, num_cus=256, big_mode=0, auto_rounds=0, auto_cpw=0)
+    full.update(policy)
+    pol = np.array([full[k] for k in keys], dtype=np.int32)
+    cap = int(nt.sum()) + B + 8
+    wins, chunks, n = np.zeros((max(B, 1), 5), dtype=np.int32), np.zeros((cap, 5), dtype=np.int32), C.c_int(0)
+    rc = host_math.hm_plan_layout(B, _ip(nt), _ip(cfs), _ip(pol), int(frozen), _ip(wins), _ip(chunks), cap, C.byref(n))
+    assert n.value <= cap
+    return rc, wins[:B], chunks[:n.value], dict(zip(keys, (int(x) for x in pol)))
+
+
+def _slab_stride(cf, elim_mode):
+    # doubles of a chunk's partial of the reduced system (lba_types.h: camera records of 39, pair blocks of 37; the matrix-core sweep:
+    # ten 256-double accumulator tiles and camera records of 33, lba_eliminate_mfma.h) + its kSlabScalars = 8 scalars
+    return (10 * 256 + 33 * cf if elim_mode == 1 else 39 * cf + 37 * (cf * (cf - 1) // 2)) + 8
+
+
+def _check_plan(ntiles, cf, pol, wins, chunks):
+    """What holds for every plan: each window's chunks tile its tiles once and in order, ids are window-major, slabs are disjoint and follow
+    the ids, and the chunk array is a stable partition of the ids by the round class of the graded windows.  Returns the cuts per window."""
+    B = len(ntiles)
+    cfs = [cf] * B if np.isscalar(cf) else list(cf)
+    by_id = chunks[np.argsort(chunks[:, 4], kind="stable")]
+    assert list(by_id[:, 4]) == list(range(len(chunks)))                          # every id once
+    tile_off = chunk_off = slab = 0
+    rank, cuts = {}, []
+    for wi in range(B):
+        t0, c0, nc, s0, graded = (int(x) for x in wins[wi])
+        assert (t0, c0, s0) == (tile_off, chunk_off, slab), (wi, wins[wi])
+        mine = by_id[c0:c0 + nc]
+        assert np.all(mine[:, 0] == wi)                                           # window-major ids
+        if pol["big_mode"]:
+            assert nc == 1 and (int(mine[0, 1]), int(mine[0, 2])) == (t0, t0)         # (one chunk carries the window's step statistics, no tiles)
+        else:
+            edges = [t0] + [int(e) for e in mine[:, 2]]
+            assert [int(b) for b in mine[:, 1]] == edges[:-1] and edges[-1] == t0 + ntiles[wi]      # [tile_off, tile_off + ntiles) once, in order
+            assert all(y > x for x, y in zip(edges, edges[1:])) and (nc > 0) == (ntiles[wi] > 0)
+        stride = _slab_stride(cfs[wi], pol["elim_mode"])
+        assert [int(s) for s in mine[:, 3]] == [slab + k * stride for k in range(nc)]
+        for k in range(nc):
+            rank[c0 + k] = (k * graded) // nc if graded else 0
+        cuts.append(([int(e) - t0 for e in mine[:, 1]] + [ntiles[wi]] if nc and not pol["big_mode"] else [0], graded))
+        tile_off += ntiles[wi]; chunk_off += nc; slab += nc * stride
+    assert chunk_off == len(chunks)
+    order = [(rank[int(i)], int(i)) for i in chunks[:, 4]]
+    assert order == sorted(order)                                                 # classes one after the other, ids ascending inside a class
+    return cuts
+
+
+def _auto_policy(ntiles, pol):
+    # the automatic policy as plan_layout's comment states it: whole rounds of the chip's wave slots at 36 tiles per chunk at most
+    slots = (8 // pol["elim_waves"]) * pol["num_cus"]
+    per_round = 36 * pol["elim_waves"] * slots
+    rounds = max(1, -(-sum(ntiles) // per_round))
+    return rounds, max(1, (slots * rounds) // max(1, len(ntiles)))
+
+
+PLAN_MODES = [dict(chunks_per_window=1), dict(chunks_per_window=6), dict(chunks_per_window=-3006), dict(chunks_per_window=-2008), dict(),
+              dict(elim_waves=2, elim_mode=1), dict(elim_mode=1), dict(reproducible=1), dict(reproducible=1, elim_waves=2, elim_mode=1), dict(big_mode=1)]
+
+
+@pytest.mark.parametrize("mode", PLAN_MODES, ids=lambda m: ",".join("%s=%d" % kv for kv in m.items()) or "auto")
+def test_plan_layout_invariants(host_math, mode):
+    """plan_layout (lba_pack.cpp) under every cut mode - forced, the graded request, automatic, reproducible, oversize windows, one and two
+    waves per chunk - on windows of 0, 1, 7, 8 cpw - 1, 8 cpw (the graded threshold) and 200 tiles, in batches of 1, 3 and 1024 windows."""
+    req = mode.get("chunks_per_window", 0)
+    cpw = (-req) % 1000 if req < 0 else req if req > 0 else 6          # (automatic: 1024 windows of ~200 tiles resolve to 3 rounds, 6 chunks)
+    sizes = [0, 1, 7, 8 * cpw - 1, 8 * cpw, 200]
+    batches = [[s] for s in sizes] + [sizes[i:i + 3] for i in range(4)] + [[200] * 3] + [sizes[:5] + [200] * 1019] + [[200] * 1024]
+    alone = {}
+    for nts in batches:
+        cf = [1 + (i % 10) for i in range(len(nts))]                                  # systems of every order up to the sweeps' ten
+        rc, wins, chunks, pol = _plan(host_math, nts, dict(mode, num_cus=256), cf=cf)
+        assert rc == 0
+        cuts = _check_plan(nts, cf, pol, wins, chunks)
+        assert (pol["auto_rounds"], pol["auto_cpw"]) == _auto_policy(nts, pol)
+        for nt, (edges, graded) in zip(nts, cuts):
+            sz = [y - x for x, y in zip(edges, edges[1:])]
+            if pol["big_mode"]:
+                continue
+            if req > 0:                                                # forced: chunks of at most ceil(nt / cpw) tiles
+                per = max(1, -(-nt // req))
+                assert graded == 0 and len(sz) == -(-nt // per) and all(s <= per for s in sz) and (not sz or max(sz) - min(sz) <= 1)
+                continue
+            if req < 0:                                                # the graded request: taken by a window with two tiles per chunk, else the equal cut
+                rounds, nc = (-req) // 1000, (-req) % 1000
+                assert graded == (rounds if len(sz) == nc else 0) and (len(sz) == nc or nt < 2 * nc), (nt, graded)
+            else:
+                rounds, nc = (3, max(1, -(-nt // 34))) if pol["reproducible"] else (pol["auto_rounds"], pol["auto_cpw"])
+                want = rounds >= 2 and nc >= rounds and pol["elim_waves"] == 1 and nt >= 8 * nc
+                assert graded == (rounds if want else 0), (nt, nts[:6], graded)
+                if not graded:
+                    per = max(pol["elim_waves"], -(-nt // nc))
+                    assert len(sz) == -(-nt // per) and all(s <= per for s in sz) and (not sz or max(sz) - min(sz) <= 1)
+            if graded and nt >= 2 * nc:                                 # the chunks of a later round of the slots are no longer than those before
+                assert len(sz) == nc
+                cls = [[s for k, s in enumerate(sz) if (k * rounds) // nc == r] for r in range(rounds)]
+                assert all(min(a) >= max(b) for a, b in zip(cls, cls[1:])), sz
+            if pol["reproducible"]:                                     # a function of the window alone
+                assert alone.setdefault(nt, (edges, graded)) == (edges, graded)
+    # the headline window under the graded request it reports: the cut of test_graded_chunk_boundaries
+    if req == -3006:
+        rc, wins, chunks, pol = _plan(host_math, [200], mode)
+        assert [tuple(c[1:3]) for c in chunks[np.argsort(chunks[:, 4])]] == [(0, 70), (70, 140), (140, 160), (160, 180), (180, 190), (190, 200)]
+        assert [int(i) for i in chunks[:, 4]] == [0, 1, 2, 3, 4, 5] and int(wins[0, 4]) == 3
+
+
+def test_plan_layout_refuses_bad_graded_requests_and_reports_small_windows(host_math):
+    """-(1000 rounds + chunks) with fewer than two rounds or fewer chunks than rounds is an invalid argument; a graded request on a window too
+    small for it (fewer than two tiles per chunk) falls back to the equal cut and, where that cut makes another number of chunks, says so:
+    win_graded == 0 ((ADVICE round 4), the positive chunk count slslam_lba_batch_window_chunks then reports cuts the window the same way,
+    test_graded_chunk_boundaries)."""
+    for req in (-1006, -6, -3002, -2001):
+        assert _plan(host_math, [200], dict(chunks_per_window=req))[0] == 1, req        # SLSLAM_ERR_INVALID_ARGUMENT
+    for req in (-2002, -3003, -3006):
+        assert _plan(host_math, [200, 7, 200], dict(chunks_per_window=req))[0] == 0, req
+    rc, wins, chunks, pol = _plan(host_math, [200, 7, 5, 12], dict(chunks_per_window=-3006))
+    assert rc == 0 and [int(g) for g in wins[:, 4]] == [3, 0, 0, 3]
+    assert [int(n) for n in wins[:, 2]] == [6, 4, 5, 6]                # 7 tiles: at most ceil(7 / 6) = 2 to a chunk -> four chunks
+    _, w2, c2, _ = _plan(host_math, [7], dict(chunks_per_window=4))
+    small = chunks[chunks[:, 0] == 1]
+    assert [(int(b) - 200, int(e) - 200) for b, e in small[np.argsort(small[:, 4])][:, 1:3]] == [(int(b), int(e)) for b, e in c2[:, 1:3]]
+
+
+def test_plan_layout_headline_cut(host_math):
+    """The cut of the headline batch without a GPU: 1024 windows of the tile count the host packer gives synth's 10 + 10 keyframe, 2000-line
+    window under the grouped sweep's packing, on 256 CUs at one wave per chunk: 6 chunks per window in 3 rounds of the wave slots
+    (plan_layout's comment), which slslam_lba_batch_window_chunks reports as -3006 (tests/test_gpu_stream.py asserts it on the device)."""
+    rc, P = _pack(host_math, synth.make_window(0, num_lines=2000), grouping=1)
+    assert rc == 0 and P["Cf"] == 10
+    nt = P["ntiles"]
+    rc, wins, chunks, pol = _plan(host_math, [nt] * 1024, dict(num_cus=256, elim_waves=1, elim_mode=1))
+    assert rc == 0
+    _check_plan([nt] * 1024, 10, pol, wins, chunks)
+    assert (pol["auto_rounds"], pol["auto_cpw"]) == (3, 6) and len(chunks) == 6144 == 3 * 8 * 256
+    reported = [-(1000 * int(g) + int(n)) if g else int(n) for n, g in wins[:, [2, 4]]]
+    assert reported == [-3006] * 1024
+    # the dispatch order: the two long chunks of every window, then the two of the second round, then the short ones
+    assert [int(i) for i in chunks[:6, 4]] == [0, 1, 6, 7, 12, 13] and [int(i) for i in chunks[2048:2052, 4]] == [2, 3, 8, 9]
+    sizes = chunks[np.argsort(chunks[:, 4])][:6]
+    sizes = [int(e - b) for b, e in sizes[:, 1:3]]
+    assert sum(sizes) == nt and max(sizes) <= 36 * 2 and sizes[0] >= sizes[2] >= sizes[4]
+    # handed back as chunks_per_window, the reported cut is the same cut
+    rc, w2, c2, _ = _plan(host_math, [nt] * 1024, dict(num_cus=256, elim_waves=1, elim_mode=1, chunks_per_window=-3006))
+    assert rc == 0 and np.array_equal(w2, wins) and np.array_equal(c2, chunks)
+
+
+def test_plan_layout_frozen_reproduces_the_first_plan(host_math):
+    """What refills rely on: planning the same windows with frozen = true under the policy a frozen = false run resolved gives that run's
+    plan exactly - and does not touch the resolved numbers, whatever the windows (a refill's windows differ from the first ones)."""
+    rng = np.random.default_rng(11)
+    for mode in PLAN_MODES:
+        for nts in ([200] * 1024, [int(x) for x in rng.integers(0, 260, size=300)], [7, 48, 200]):
+            rc, wins, chunks, pol = _plan(host_math, nts, mode)
+            assert rc == 0
+            rc, w2, c2, p2 = _plan(host_math, nts, pol, frozen=True)
+            assert rc == 0 and p2 == pol and np.array_equal(w2, wins) and np.array_equal(c2, chunks)
+            other = [max(0, n - 3) for n in nts]
+            rc, w3, c3, p3 = _plan(host_math, other, pol, frozen=True)
+            assert rc == 0 and p3 == pol
+            _check_plan(other, 10, p3, w3, c3)
+
+
 def _copy_runs(host_math, ranges, regs):
     U = C.c_ulonglong
     n, nr = len(ranges), len(regs)

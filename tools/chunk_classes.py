@@ -28,7 +28,7 @@ t0 = start[end > start].min()
 start -= t0; end -= t0
 dur = end - start
 print("cut code", code, "chunks", nchunk, "makespan %.1f us, perfectly packed %.1f us" % (end.max(), dur.sum() / 2048))
-# stamps are indexed by the chunk id: window-major, chunk c of window w = w * cpw + c (plan_layout); dispatch class of chunk c = c * rounds / cpw
+# stamps are indexed by the chunk id: window-major, chunk c of window w = w * cpw + c (lba_pack.cpp::plan_layout); dispatch class of chunk c = c * rounds / cpw
 rounds = abs(code) // 1000 if code < 0 else 1
 D, S, E = dur.reshape(nwin, cpw), start.reshape(nwin, cpw), end.reshape(nwin, cpw)
 for c in range(cpw):

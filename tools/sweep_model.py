@@ -11,7 +11,7 @@ Inputs, all measured elsewhere (nothing here is fitted to the launch times):
     the next one on that slot (profiles/round5_launch_anatomy.txt, items 2 and 4) - of which a SIMD whose other slot is busy loses only the part
     the lone wave cannot fill;
   * the schedule: every window is cut into 6 graded chunks (70 70 20 20 10 10 of its 200 tiles), dispatched class by class onto 1024 SIMDs x 2
-    wave slots, a free slot takes the next chunk of the array (lba_api.hip::plan_layout).
+    wave slots, a free slot takes the next chunk of the array (lba_pack.cpp::plan_layout).
   * the issue arbiter serves the OLDER of a SIMD's two waves first: of two equal 70-tile chunks that start together the one in the lower slot takes
     521 us, the other 699 (same file, item 3): shares 0.573 / 0.427 of the pair's issue.
 The simulation is event-driven per SIMD: two resident waves share the SIMD's issue 0.573 : 0.427 (older : younger), a lone wave advances at 0.68 of
