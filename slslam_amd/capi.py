@@ -608,26 +608,38 @@ def lba_refine_lines(w, params=None, **opt):
     return arr.params, res, _summary_dict(tot)
 
 
-class LineRefiner(_CountedHandle):
-    """slslam_line_refiner: every line of every window of a run refined in one launch, buffers reused between runs."""
-    _H, _DESTROY, _STATS = "h", "slslam_line_refiner_destroy", "slslam_line_refiner_stats"
+class _LineHandle(_CountedHandle):
+    """What LineRefiner and LineTriangulator share: create (_CREATE) for a capacity; per run the slslam_lba_window array (_windows, with
+    the _WindowArrays that keep it alive) and one pointer per window to its result array (_pointers)."""
+    _H, _CREATE = "h", None
 
     def __init__(self, max_lines, max_observations, device=-1, **opt):
         self.h = C.c_void_p()
         o = default_options(**opt)
-        _check(lib().slslam_line_refiner_create(device, C.byref(o), int(max_lines), int(max_observations), C.byref(self.h)),
-               "slslam_line_refiner_create")
+        _check(getattr(lib(), self._CREATE)(device, C.byref(o), int(max_lines), int(max_observations), C.byref(self.h)), self._CREATE)
+
+    @staticmethod
+    def _windows(windows, params=None):
+        arrs = [_WindowArrays(w, None if params is None else params[i]) for i, w in enumerate(windows)]
+        return arrs, (LBAWindow * max(len(arrs), 1))(*[a.c for a in arrs])
+
+    @staticmethod
+    def _pointers(arrays, ctype):
+        return (C.POINTER(ctype) * max(len(arrays), 1))(*[a.ctypes.data_as(C.POINTER(ctype)) for a in arrays])
+
+
+class LineRefiner(_LineHandle):
+    """slslam_line_refiner: every line of every window of a run refined in one launch, buffers reused between runs."""
+    _DESTROY, _STATS, _CREATE = "slslam_line_refiner_destroy", "slslam_line_refiner_stats", "slslam_line_refiner_create"
 
     def run(self, windows, params=None):
         """windows: dicts as for lba_solve (params: their start vectors, else each window's own).
         Returns (list of parameter vectors, list of per-line structured arrays, list of totals dicts)."""
-        arrs = [_WindowArrays(w, None if params is None else params[i]) for i, w in enumerate(windows)]
+        arrs, cw = self._windows(windows, params)
         n = len(arrs)
-        cw = (LBAWindow * max(n, 1))(*[a.c for a in arrs])
         res = [_line_results(w["num_lines"]) for w in windows]
-        rp = (C.POINTER(LineResult) * max(n, 1))(*[r.ctypes.data_as(C.POINTER(LineResult)) for r in res])
         tot = (Summary * max(n, 1))()
-        _check(lib().slslam_line_refiner_run(self.h, n, cw, rp, tot), "slslam_line_refiner_run")
+        _check(lib().slslam_line_refiner_run(self.h, n, cw, self._pointers(res, LineResult), tot), "slslam_line_refiner_run")
         return [a.params for a in arrs], res, [_summary_dict(tot[i]) for i in range(n)]
 
 
@@ -644,26 +656,17 @@ def lba_triangulate_lines(w, method=1, inverse_depth=0.1, min_parallax=0.0, **op
     return arr.params, res, av
 
 
-class LineTriangulator(_CountedHandle):
+class LineTriangulator(_LineHandle):
     """slslam_line_triangulator: every line of every window of a run made in one launch, buffers reused between runs."""
-    _H, _DESTROY, _STATS = "h", "slslam_line_triangulator_destroy", "slslam_line_triangulator_stats"
-
-    def __init__(self, max_lines, max_observations, device=-1, **opt):
-        self.h = C.c_void_p()
-        o = default_options(**opt)
-        _check(lib().slslam_line_triangulator_create(device, C.byref(o), int(max_lines), int(max_observations), C.byref(self.h)),
-               "slslam_line_triangulator_create")
+    _DESTROY, _STATS, _CREATE = "slslam_line_triangulator_destroy", "slslam_line_triangulator_stats", "slslam_line_triangulator_create"
 
     def run(self, windows, method=1, inverse_depth=0.1, min_parallax=0.0):
         """windows: dicts as for lba_solve.  Returns (list of parameter vectors, list of per-line structured arrays, list of lines_av)."""
-        arrs = [_WindowArrays(w) for w in windows]
-        n = len(arrs)
-        cw = (LBAWindow * max(n, 1))(*[a.c for a in arrs])
+        arrs, cw = self._windows(windows)
         res = [np.zeros(max(int(w["num_lines"]), 0), dtype=np.dtype(TriangulatedLine)) for w in windows]
         avs = [np.full((max(int(w["num_lines"]), 0), 6), np.nan) for w in windows]
-        rp = (C.POINTER(TriangulatedLine) * max(n, 1))(*[r.ctypes.data_as(C.POINTER(TriangulatedLine)) for r in res])
-        ap = (C.POINTER(C.c_double) * max(n, 1))(*[_dp(a) for a in avs])
-        _check(lib().slslam_line_triangulator_run(self.h, n, cw, int(method), float(inverse_depth), float(min_parallax), rp, ap),
+        _check(lib().slslam_line_triangulator_run(self.h, len(arrs), cw, int(method), float(inverse_depth), float(min_parallax),
+                                                  self._pointers(res, TriangulatedLine), self._pointers(avs, C.c_double)),
                "slslam_line_triangulator_run")
         return [a.params for a in arrs], res, avs
 

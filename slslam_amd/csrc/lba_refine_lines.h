@@ -16,22 +16,12 @@
 #define SLSLAM_LBA_REFINE_LINES_H_
 
 #include "lba_kernels.h"
+#include "lba_refine_host.h"
 
 namespace slslam {
 
-struct RefineGroup {       // one wave's work
-  long long row_base;      // first row (64 observation slots) of the group
-  int cam_off, C;          // the window's cameras in RefinePtrs.cam_x
-  int depth;               // rows of the group = observations of its longest line
-  int pad;
-};
-struct RefineOut {         // per line slot
-  double u[4];             // the refined line (the start values after a numerical failure, as every solve here)
-  double initial_cost, final_cost;
-  int termination, n_success, n_unsuccess, pad;
-};
 struct RefinePtrs {
-  const RefineGroup* groups;
+  const RefineGroup* groups; // (LineGroup, line_call_plan.h; RefineOut: lba_refine_host.h)
   const double* cam_x;     // [ncam][6] (w, t)
   const double* u;         // [nslot][4], slot = 64 group + lane
   const int* cnt;          // [nslot] observations of the slot's line; 0: an unused slot

@@ -1,46 +1,29 @@
 // slslam_amd/csrc/triangulate_api.hip — the line triangulator (include/slslam_hip.h: slslam_line_triangulator_*,
 // slslam_lba_triangulate_lines): making a landmark, the link between the matcher / pose estimator and the refiner or the window solve.
 // Per call, whatever the number of windows:
-//   host     validation, what becomes of every line, the refiner's lane-interleaved layout, the camera tables (lba_triangulate_host.h)
+//   host     validation, the plan shared with the refiner (line_call_plan.h), the camera tables (lba_triangulate_host.h)
 //   upload   one block [groups | cameras (R, t) | counts | observation cameras | observations]
 //   launch   k_triangulate_lines (lba_triangulate.h): one wave per 64 lines of one window
 //   download one block [TriOut per line slot], scattered back under the caller's line numbering
 // No CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <chrono>
-#include <cmath>
-#include <cstring>
 #include <new>
-#include <vector>
 
 #include "../../include/slslam_hip.h"
-#include "call_block.h"
 #include "lba_triangulate.h"
+#include "line_call_handle.h"
 
 using namespace slslam;
 
-struct slslam_line_triangulator {
-  int device = -1;
-  slslam_solver_options opt;
-  long long cap_lines = 0, cap_obs = 0;
-  GrowBuf d_in{Mem::kDevice}, d_out{Mem::kDevice}, h_in{Mem::kPinned}, h_out{Mem::kPinned};
-  long long calls = 0, allocations = 0;
+struct slslam_line_triangulator : LineHandle {
   double last_ms[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };   // the last run: host layout, upload, kernel, download, scatter
-  TriPlan plan;              // host work arrays, kept for their capacity
 };
 
 extern "C" int slslam_line_triangulator_create(int device, const slslam_solver_options* opt, long long max_lines, long long max_observations,
                                                slslam_line_triangulator** out) {
-  if (!out || max_lines < 0 || max_observations < 0) return SLSLAM_ERR_INVALID_ARGUMENT;
-  slslam_line_triangulator* t = new (std::nothrow) slslam_line_triangulator();
-  if (!t) return SLSLAM_ERR_NO_MEMORY;
-  if (opt) t->opt = *opt; else slslam_default_options(&t->opt);
-  t->device = device;
-  t->cap_lines = max_lines; t->cap_obs = max_observations;
-  *out = t;
-  return SLSLAM_OK;
+  return line_handle_create(device, opt, max_lines, max_observations, out);
 }
 
 extern "C" void slslam_line_triangulator_destroy(slslam_line_triangulator* t) { delete t; }
@@ -69,17 +52,7 @@ extern "C" int slslam_line_triangulator_run(slslam_line_triangulator* t, int n, 
     if (P.ngroups > 0) {
       if ((rc = use_device(t->device)) != SLSLAM_OK) return rc;
 
-      // the buffers are made for the capacities of create (whole waves per window, rows padded to a group's longest line) or for
-      // this call, whichever is larger
-      const size_t cap_slot = (size_t)((t->cap_lines + kRefineLanes - 1) / kRefineLanes * kRefineLanes);
-      const size_t cap_elem = (size_t)((t->cap_obs + kRefineLanes - 1) / kRefineLanes * kRefineLanes);
-      const size_t cap_in = 5 * 256 + (cap_slot / kRefineLanes) * sizeof(TriGroup) + cap_slot * 4 + cap_elem * 68;
-      const size_t want_in = std::max(P.in_bytes, cap_in), want_out = std::max(P.out_bytes, cap_slot * sizeof(TriOut));
-      HIP_TRY(t->h_in.need(want_in, &t->allocations));
-      HIP_TRY(t->d_in.need(want_in, &t->allocations));
-      HIP_TRY(t->h_out.need(want_out, &t->allocations));
-      HIP_TRY(t->d_out.need(want_out, &t->allocations));
-
+      if ((rc = t->fit(tri_call())) != SLSLAM_OK) return rc;
       tri_fill_image(P, n, windows, [](const double* wt, double* T) { slslam_gc::wt_to_Rt(wt, T); }, t->h_in.p);
 
       // ---- one upload, one launch, one download
@@ -123,14 +96,11 @@ extern "C" int slslam_line_triangulator_timing(const slslam_line_triangulator* t
 extern "C" int slslam_lba_triangulate_lines(const slslam_lba_window* window, const slslam_solver_options* opt, int method,
                                             double inverse_depth, double min_parallax, slslam_triangulated_line* results, double* lines_av) {
   if (!window) return SLSLAM_ERR_INVALID_ARGUMENT;
-  slslam_line_triangulator* t = nullptr;
-  int rc = slslam_line_triangulator_create(-1, opt, 0, 0, &t);
-  if (rc != SLSLAM_OK) return rc;
+  slslam_line_triangulator t;
+  t.init(-1, opt, 0, 0);
   slslam_triangulated_line* res[1] = { results };
   double* av[1] = { lines_av };
-  rc = slslam_line_triangulator_run(t, 1, window, method, inverse_depth, min_parallax, results ? res : nullptr, lines_av ? av : nullptr);
-  slslam_line_triangulator_destroy(t);
-  return rc;
+  return slslam_line_triangulator_run(&t, 1, window, method, inverse_depth, min_parallax, results ? res : nullptr, lines_av ? av : nullptr);
 }
 
 // Test hook: ONE line through the functions of lba_triangulate.h on the host, in the kernel's order.

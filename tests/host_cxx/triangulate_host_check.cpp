@@ -1,5 +1,5 @@
-// tests/host_cxx/triangulate_host_check.cpp — the host side of the line triangulator (slslam_amd/csrc/lba_triangulate_host.h) without a
-// device: the validation of a call, what becomes of every line, the upload image (every observation of a line that runs lands once, in
+// tests/host_cxx/triangulate_host_check.cpp — the host side of the line triangulator (slslam_amd/csrc/lba_triangulate_host.h over the
+// plan it shares with the refiner, line_call_plan.h) without a device: the validation of a call, what becomes of every line, the upload image (every observation of a line that runs lands once, in
 // its line's lane, in the caller's order; counts, groups and camera tables where the kernel reads them) and the scatter of hand-made
 // records back under the caller's numbering - untouched outputs stay untouched.  Built with -fsanitize=address,undefined and run by
 // tests/test_lba_triangulate_cpu.py.  Prints "triangulate host ok" and exits 0, or says what is wrong and exits 1.

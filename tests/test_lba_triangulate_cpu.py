@@ -102,12 +102,23 @@ def test_header_functions_on_the_host_against_the_reference():
 
 
 def test_refine_layout_is_reused():
-    """One layout: the triangulator's host side calls the refiner's refine_layout_build and brings no sort or placement of its own."""
-    host = open(os.path.join(CSRC, "lba_triangulate_host.h")).read()
-    assert '#include "lba_refine_layout.h"' in host and host.count("refine_layout_build(") == 1
-    for f in ("lba_triangulate_host.h", "lba_triangulate.h", "triangulate_api.hip"):
+    """One layout, one plan: over all of csrc, refine_layout_build is called once - from the plan the refiner and the triangulator share
+    (line_call_plan.h) -, and neither call nor the shared files bring a sort or placement of their own."""
+    calls = {}
+    for f in sorted(os.listdir(CSRC)):
+        text = open(os.path.join(CSRC, f)).read()
+        k = text.count("refine_layout_build(") - text.count("inline void refine_layout_build(")
+        if k:
+            calls[f] = k
+    assert calls == {"line_call_plan.h": 1}, calls
+    plan = open(os.path.join(CSRC, "line_call_plan.h")).read()
+    assert '#include "lba_refine_layout.h"' in plan
+    for f in ("lba_triangulate_host.h", "lba_triangulate.h", "triangulate_api.hip", "lba_refine_host.h", "lba_refine_lines.h", "lba_refine_api.h",
+              "line_call_plan.h", "line_call_handle.h"):
         text = open(os.path.join(CSRC, f)).read()
         assert "bucket" not in text and "W.dest[" not in text.replace("W.dest[(size_t)k]", "") and "group_row.push_back" not in text, f
+    for f in ("lba_triangulate_host.h", "lba_refine_host.h"):
+        assert '#include "line_call_plan.h"' in open(os.path.join(CSRC, f)).read(), f
 
 
 def test_host_glue_under_the_sanitizers():

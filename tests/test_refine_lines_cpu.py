@@ -43,6 +43,17 @@ def test_layout_under_the_sanitizers():
     assert "refine layout ok" in r.stdout
 
 
+def test_host_side_under_the_sanitizers():
+    """The plan, the upload image and the scatter of a refiner run (csrc/lba_refine_host.h over csrc/line_call_plan.h), no device."""
+    os.makedirs(BUILD, exist_ok=True)
+    exe = os.path.join(BUILD, "refine_host_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "host_cxx", "refine_host_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "refine host ok" in r.stdout
+
+
 def test_structs_match_the_header():
     os.makedirs(BUILD, exist_ok=True)
     exe = os.path.join(BUILD, "refine_abi_probe")
