@@ -1227,6 +1227,81 @@ unsigned long long slslam_voctree_key(unsigned long long seed, unsigned long lon
 int  slslam_debug_voctree_step(int device, int K, int D, long long num_nodes, const float* centres, long long n, const float* descriptors,
                                const int* node, int* label, long long* acc, long long* count);
 
+/* ------------------------------------------------------------------ line descriptors from images: MSLD
+ * What makes the [n, D] float descriptors that slslam_place_db_*, slslam_voctree_train and slslam_descriptor_matcher_* take, from grey
+ * images and line segments (csrc/line_descriptor.h).  The reference assumes an external tracker for them
+ * (src/voctree_bf.h: DESC_DIM 72) and ships none; 72 floats are the shape of MSLD, the mean - standard-deviation line descriptor of Wang,
+ * Wu and Hu (Pattern Recognition 42, 2009): 9 bands x 4 gradient components x (mean, standard deviation).
+ *   inputs     per frame an 8-bit grey image[height][stride], row-major, stride >= width, 1 <= width, height <= 8192, and segments[n][4]
+ *              floats (x0, y0, x1, y1) in pixels; pixel centres lie at integers.
+ *   options    bands M in 1 .. 16 (default 9), band_width w in 1 .. 9 (default 5), M w <= 144, orient 0 / 1 (default 1); D = 8 M.
+ * Per segment, in real numbers (the device's precisions: DESIGN.md 6.7; tests/line_descriptor_reference.py restates this in fp64):
+ *   geometry   L = |p1 - p0|, evaluated as sqrt(dx dx + dy dy) in double; d_L = (p1 - p0) / L, d_perp = (-d_L.y, d_L.x).  N = floor(L)
+ *              samples along the line, centred on the segment: s_j = L / 2 + j - (N - 1) / 2, j = 0 .. N-1 - centring makes the
+ *              descriptor independent of the order of the end points.
+ *   rows       M w support rows at signed offsets rho_r = r - (M w - 1) / 2; the sample point of row r is q = p0 + s_j d_L + rho_r d_perp.
+ *   gradient   at integer pixels by central differences with coordinates clamped to the image (replicated border):
+ *              gx(x, y) = (I(min(x + 1, W - 1), y) - I(max(x - 1, 0), y)) / 2, gy likewise; at q by bilinear interpolation of gx and gy
+ *              from the four surrounding integer pixels, each clamped the same way.
+ *   components g_L = g . d_L, g_perp = g . d_perp; (max(g_perp, 0), max(-g_perp, 0), max(g_L, 0), max(-g_L, 0)).
+ *   weights    a fixed table of M w x 2 numbers, computed in double and rounded to float: with f_r = exp(-rho_r^2 / (2 sigma^2)),
+ *              sigma = (M w - 1) / 2 (1 when M w = 1), t_r = (r + 0.5) / w - 0.5, i0 = floor(t_r), a = t_r - i0, row r adds f_r (1 - a)
+ *              times its components to band i0 and f_r a times them to band i0 + 1; a band outside 0 .. M-1 is dropped.
+ *   statistics v[j][i][c] = the weighted sum over the rows for sample j, band i, component c; mu[i][c] its mean over j, s[i][c] its
+ *              population standard deviation over j (never negative).
+ *   polarity   = the sum over j and r of f_r g_perp.  With orient = 1 and polarity < 0 the descriptor is that of the segment with its end
+ *              points swapped - g_L and g_perp negated, the rows in reverse order - and -polarity is reported; polarity == 0 does not
+ *              flip.  The rows are symmetric about 0, so with orient = 1 swapping the end points of a segment changes nothing.
+ *   layout     the 4 M means are scaled to unit L2 norm, the 4 M standard deviations likewise, a half of norm 0 stays 0, both are
+ *              multiplied by 1 / sqrt 2: out[4 i + c] = mean part, out[4 M + 4 i + c] = std part.  A descriptor of two non-zero halves
+ *              has unit norm, which is what the recogniser's distance 1 - c . f assumes.
+ *   status     SLSLAM_MSLD_INVALID: a coordinate is not finite; else OUTSIDE: an end point lies outside [0, W-1] x [0, H-1] (support
+ *              rows that stick out of the image are fine: that is what the clamp is for); else TOO_SHORT: L < 2; else FLAT: both
+ *              halves have norm 0; else OK (one zero half is OK).  Unless OK the descriptor is all zeros; num_samples is N for OK and
+ *              FLAT and 0 otherwise, polarity 0 for a refused segment.
+ * Frames are independent: a frame's results do not depend on the rest of the call. */
+enum { SLSLAM_MSLD_MAX_BANDS = 16, SLSLAM_MSLD_MAX_BAND_WIDTH = 9, SLSLAM_MSLD_MAX_ROWS = 144, SLSLAM_MSLD_MAX_SIDE = 8192 };
+enum { SLSLAM_MSLD_OK = 0, SLSLAM_MSLD_FLAT = 1, SLSLAM_MSLD_TOO_SHORT = 2, SLSLAM_MSLD_OUTSIDE = 3, SLSLAM_MSLD_INVALID = 4 };
+typedef struct slslam_msld_options {
+  int bands;                     /* M */
+  int band_width;                /* w */
+  int orient;                    /* 1: flip on a negative polarity */
+} slslam_msld_options;
+typedef struct slslam_msld_frame {
+  int width, height;
+  long long stride;              /* bytes from one row to the next, >= width */
+  const unsigned char* image;
+  int num_segments;              /* n >= 0 */
+  const float* segments;         /* [n 4] */
+} slslam_msld_frame;
+typedef struct slslam_msld_result {
+  float* descriptors;            /* caller-owned arrays, any of them may be NULL.  [n D] */
+  int*   status;                 /* [n] SLSLAM_MSLD_* */
+  int*   num_samples;            /* [n] */
+  float* polarity;               /* [n], after a flip */
+} slslam_msld_result;
+typedef struct slslam_line_descriptor slslam_line_descriptor;
+
+/* bands 9, band_width 5, orient 1 */
+void slslam_msld_default_options(slslam_msld_options* opt);
+/* device < 0 selects the current HIP device.  options as above, fixed for the handle.  max_frames >= 1 frames of max_pixels >= 1 pixels
+ * and max_segments >= 1 segments each: what the one device block and the one page-locked block are made for at the first run.  A larger
+ * call makes larger ones and counts one allocation; a call that fits allocates nothing.  max_pixels <= 8192^2, max_frames x max_segments <= 2^24 and max_frames x max_pixels
+ * <= 2^32 (what the first run allocates), else SLSLAM_ERR_INVALID_ARGUMENT.  Touches no device. */
+int  slslam_line_descriptor_create(int device, const slslam_msld_options* options, int max_frames, long long max_pixels, int max_segments,
+                                   slslam_line_descriptor** out);
+void slslam_line_descriptor_destroy(slslam_line_descriptor* handle);
+/* frames[F], results[F].  Every argument is validated before an output is written or the device is asked - a negative count, a missing
+ * array, a size out of range, stride < width: SLSLAM_ERR_INVALID_ARGUMENT; more than 2^24 segments in one call: SLSLAM_ERR_UNSUPPORTED.
+ * Synchronous; host pointers; one upload (the images with `width` bytes per row: the stride stays on the host), one launch and one
+ * download per call whatever F. */
+int  slslam_line_descriptor_run(slslam_line_descriptor* handle, int num_frames, const slslam_msld_frame* frames,
+                                const slslam_msld_result* results);
+/* Since create: runs, and how often the blocks were made or made larger.  Either pointer may be NULL. */
+int  slslam_line_descriptor_stats(const slslam_line_descriptor* handle, long long* calls, long long* allocations);
+/* One frame, one call (its own buffers, made and freed). */
+int  slslam_describe_lines(const slslam_msld_options* options, const slslam_msld_frame* frame, const slslam_msld_result* result);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */
@@ -1235,6 +1310,10 @@ int slslam_po_set_profiling(int enable);
 /* Timing of the calling thread's last profiled slslam_po_solve: device time of the whole solve, of its slowest factorisation
  * (iterations enqueued after the solve has converged are no-ops), how many factorisations were enqueued, unknowns of the reduced program and of the junction block (0 with the dense factorisations). */
 int slslam_po_last_timing(double* total_ms, double* factor_ms, int* factor_calls, int* unknowns, int* junction_unknowns);
+/* For tools/line_descriptor_bench.py (the kernel alone, beside the call's wall time): enable > 0 brackets the launch of the handle's
+ * following runs with two events on its stream, enable == 0 stops that, enable < 0 leaves the switch as it is; *kernel_ms (may be NULL):
+ * the last bracketed launch, 0 before one. */
+int slslam_line_descriptor_timing(slslam_line_descriptor* handle, int enable, double* kernel_ms);
 /* Timing builds only (a variant library compiled with -DSLSLAM_K1_TIMING=1, -DSLSLAM_K1_WALL=1 or -DSLSLAM_SOLVE_TIMING=1: the elimination
  * sweeps / the reduced solve and k_big_solve): wave-clock cycles per phase summed over the batch since finalize; out[16].  The product
  * library has no stamps and no stamp buffer: SLSLAM_ERR_STATE there, from this call and the next. */

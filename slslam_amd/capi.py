@@ -131,6 +131,21 @@ class VocTreeTrainReport(C.Structure):
                 ("centre_ms", C.c_double * 4), ("upload_ms", C.c_double * 4), ("total_ms", C.c_double)]
 
 
+class MsldOptions(C.Structure):
+    _fields_ = [("bands", C.c_int), ("band_width", C.c_int), ("orient", C.c_int)]
+
+
+class MsldFrame(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("stride", C.c_longlong), ("image", C.POINTER(C.c_ubyte)),
+                ("num_segments", C.c_int), ("segments", C.POINTER(C.c_float))]
+
+
+class MsldResult(C.Structure):
+    _fields_ = [("descriptors", C.POINTER(C.c_float)), ("status", C.POINTER(C.c_int)), ("num_samples", C.POINTER(C.c_int)),
+                ("polarity", C.POINTER(C.c_float))]
+
+
+MSLD_STATUS = {0: "OK", 1: "FLAT", 2: "TOO_SHORT", 3: "OUTSIDE", 4: "INVALID"}
 PLACE_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_DESCRIPTOR"}
 DESC_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_DESCRIPTOR"}
 TRI_MULTIVIEW, TRI_STEREO, TRI_CONSTANT, TRI_NO_OBSERVATIONS, TRI_INVALID = 0, 1, 2, 3, 4
@@ -185,6 +200,8 @@ EXPORTS = [
     "slslam_place_filter_create", "slslam_place_filter_destroy", "slslam_place_filter_update",
     "slslam_descriptor_matcher_create", "slslam_descriptor_matcher_destroy", "slslam_descriptor_matcher_insert",
     "slslam_descriptor_matcher_run", "slslam_descriptor_matcher_size", "slslam_descriptor_matcher_stats", "slslam_match_descriptors",
+    "slslam_msld_default_options", "slslam_line_descriptor_create", "slslam_line_descriptor_destroy", "slslam_line_descriptor_run",
+    "slslam_line_descriptor_stats", "slslam_line_descriptor_timing", "slslam_describe_lines",
     "slslam_voctree_train", "slslam_voctree_save", "slslam_voctree_centres", "slslam_voctree_key", "slslam_debug_voctree_step", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -365,6 +382,16 @@ def lib():
         L.slslam_voctree_key.argtypes = [C.c_ulonglong, C.c_ulonglong]
         L.slslam_voctree_key.restype = C.c_ulonglong
         L.slslam_debug_voctree_step.argtypes = [C.c_int, C.c_int, C.c_int, C.c_longlong, fp, C.c_longlong, fp, ip, ip, lp, lp]
+    if hasattr(L, "slslam_describe_lines"):     # (likewise: a library built before the line descriptor existed)
+        L.slslam_msld_default_options.argtypes = [C.POINTER(MsldOptions)]
+        L.slslam_msld_default_options.restype = None
+        L.slslam_line_descriptor_create.argtypes = [C.c_int, C.POINTER(MsldOptions), C.c_int, C.c_longlong, C.c_int, C.POINTER(vp)]
+        L.slslam_line_descriptor_destroy.argtypes = [vp]
+        L.slslam_line_descriptor_destroy.restype = None
+        L.slslam_line_descriptor_run.argtypes = [vp, C.c_int, C.POINTER(MsldFrame), C.POINTER(MsldResult)]
+        L.slslam_line_descriptor_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+        L.slslam_line_descriptor_timing.argtypes = [vp, C.c_int, dp]
+        L.slslam_describe_lines.argtypes = [C.POINTER(MsldOptions), C.POINTER(MsldFrame), C.POINTER(MsldResult)]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -1925,3 +1952,72 @@ def loop_matches(matcher, frame, candidates, ratio=1.5, max_distance=float("inf"
         if r["status"] == "OK" and (best is None or (r["num_matched"], -r["candidate"]) > (best["num_matched"], -best["candidate"])):
             best = r
     return (best["candidate"], best) if best is not None else (-1, None)
+
+
+# ----------------------------------------------------------------------------- line descriptors from images (slslam_line_descriptor_*)
+def msld_options(bands=9, band_width=5, orient=True):
+    return MsldOptions(int(bands), int(band_width), int(bool(orient)))
+
+
+def _msld_frame(image, segments, D):
+    """(MsldFrame, MsldResult, the arrays both point to).  An image whose rows are contiguous passes its stride; any other is copied."""
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise ValueError("an image is uint8 [H, W]")
+    if img.shape[0] > 0 and img.shape[1] > 0 and (img.strides[1] != 1 or img.strides[0] < img.shape[1]):
+        img = np.ascontiguousarray(img)
+    seg = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
+    n = len(seg)
+    b = {"descriptors": np.zeros((max(n, 1), D), dtype=np.float32), "status": np.full(max(n, 1), -1, dtype=np.int32),
+         "num_samples": np.zeros(max(n, 1), dtype=np.int32), "polarity": np.zeros(max(n, 1), dtype=np.float32)}
+    fr = MsldFrame(img.shape[1], img.shape[0], img.strides[0] if img.shape[0] > 0 else 0, img.ctypes.data_as(C.POINTER(C.c_ubyte)), n,
+                   _fp(seg))
+    return fr, MsldResult(_fp(b["descriptors"]), _ip(b["status"]), _ip(b["num_samples"]), _fp(b["polarity"])), (img, seg, b)
+
+
+def _msld_dict(keep):
+    _, seg, b = keep
+    n = len(seg)
+    return {"descriptors": b["descriptors"][:n], "status": [MSLD_STATUS[s] for s in b["status"][:n].tolist()],
+            "num_samples": b["num_samples"][:n], "polarity": b["polarity"][:n]}
+
+
+def describe_lines(image, segments, **options):
+    """slslam_describe_lines: the MSLD descriptors of the segments [n, 4] (x0, y0, x1, y1) of one uint8 image [H, W].  Returns
+    dict(descriptors [n, 8 bands] float32, status [n] of MSLD_STATUS's names, num_samples [n], polarity [n] float32)."""
+    opt = msld_options(**options)
+    fr, res, keep = _msld_frame(image, segments, 8 * max(opt.bands, 1))
+    _check(lib().slslam_describe_lines(C.byref(opt), C.byref(fr), C.byref(res)), "slslam_describe_lines")
+    return _msld_dict(keep)
+
+
+class LineDescriptor(_CountedHandle):
+    """slslam_line_descriptor: MSLD descriptors for the segments of many frames per call; buffers kept between calls.  A frame is
+    (image uint8 [H, W], segments [n, 4])."""
+    _DESTROY, _STATS = "slslam_line_descriptor_destroy", "slslam_line_descriptor_stats"
+
+    def __init__(self, bands=9, band_width=5, orient=True, max_frames=2, max_pixels=752 * 480, max_segments=512, device=-1):
+        self.opt = msld_options(bands, band_width, orient)
+        self.D = 8 * self.opt.bands
+        self._h = C.c_void_p()
+        _check(lib().slslam_line_descriptor_create(int(device), C.byref(self.opt), int(max_frames), int(max_pixels), int(max_segments),
+                                                   C.byref(self._h)), "slslam_line_descriptor_create")
+
+    def run(self, frames):
+        """Returns one dict per frame, as describe_lines returns it."""
+        n = len(frames)
+        frs, outs, keep = (MsldFrame * max(n, 1))(), (MsldResult * max(n, 1))(), []
+        for i, (image, segments) in enumerate(frames):
+            frs[i], outs[i], k = _msld_frame(image, segments, self.D)
+            keep.append(k)
+        _check(lib().slslam_line_descriptor_run(self._h, n, frs, outs), "slslam_line_descriptor_run")
+        return [_msld_dict(k) for k in keep]
+
+    def set_timing(self, enable):
+        _check(lib().slslam_line_descriptor_timing(self._h, int(bool(enable)), None), "slslam_line_descriptor_timing")
+
+    def kernel_ms(self):
+        """The last run's launch by events (after set_timing(True))."""
+        ms = C.c_double(0.0)
+        _check(lib().slslam_line_descriptor_timing(self._h, -1, C.byref(ms)), "slslam_line_descriptor_timing")      # (-1: the switch stays)
+        return ms.value

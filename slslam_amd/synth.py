@@ -541,3 +541,77 @@ def make_descriptor_pair(seed, n=150, dim=72, noise=0.03, outliers=0):
     row_of[ids[1][kf_rows]] = kf_rows
     return {"query": views[0], "keyframe": views[1], "query_id": ids[0], "keyframe_id": ids[1],
             "truth": row_of[ids[0]]}
+
+
+def _line_scene(seed, height, width, num_segments, min_length, max_length, margin):
+    """A grey scene as a function of the plane: sinusoidal texture plus one soft edge per segment, each edge a smoothed step across its
+    segment that fades out beyond the segment's ends and away from its line."""
+    rng = np.random.default_rng(np.random.SeedSequence([16, int(seed)]))
+    n = int(num_segments)
+    lo_x, hi_x, lo_y, hi_y = margin, width - 1 - margin, margin, height - 1 - margin
+    if hi_x <= lo_x or hi_y <= lo_y:
+        raise ValueError("the margin leaves no room in the image")
+    seg = np.zeros((n, 4))
+    for i in range(n):
+        while True:
+            length = rng.uniform(min_length, max_length)
+            th = rng.uniform(0.0, 2.0 * np.pi)
+            c = np.array([rng.uniform(lo_x, hi_x), rng.uniform(lo_y, hi_y)])
+            h = 0.5 * length * np.array([np.cos(th), np.sin(th)])
+            p = np.concatenate([c - h, c + h])
+            if lo_x <= p[[0, 2]].min() and p[[0, 2]].max() <= hi_x and lo_y <= p[[1, 3]].min() and p[[1, 3]].max() <= hi_y:
+                seg[i] = p
+                break
+    return {"segments": seg,
+            "amplitude": rng.uniform(25.0, 60.0, n) * rng.choice([-1.0, 1.0], n), "softness": rng.uniform(0.8, 2.5, n),
+            "reach": rng.uniform(4.0, 10.0, n),
+            "waves": np.stack([rng.uniform(0.05, 0.45, 6), rng.uniform(0.0, 2.0 * np.pi, 6), rng.uniform(0.0, 2.0 * np.pi, 6),
+                               rng.uniform(5.0, 11.0, 6)], axis=1)}                     # frequency (rad / px), direction, phase, amplitude
+
+
+def _render_scene(scene, height, width, shift=(0.0, 0.0), gain=1.0, offset=0.0):
+    """uint8 [height, width]: gain * scene(x - shift.x, y - shift.y) + offset at the pixel centres, rounded and clipped."""
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+    u, v = xx - shift[0], yy - shift[1]
+    val = np.full((height, width), 118.0)
+    for k, th, ph, a in scene["waves"]:
+        val += a * np.sin(k * (np.cos(th) * u + np.sin(th) * v) + ph)
+    for (x0, y0, x1, y1), amp, soft, reach in zip(scene["segments"], scene["amplitude"], scene["softness"], scene["reach"]):
+        pad = 4.0 * reach + 8.0                                                        # beyond it the edge has faded to nothing
+        c0 = max(int(np.floor(min(x0, x1) + shift[0] - pad)), 0), max(int(np.floor(min(y0, y1) + shift[1] - pad)), 0)
+        c1 = min(int(np.ceil(max(x0, x1) + shift[0] + pad)) + 1, width), min(int(np.ceil(max(y0, y1) + shift[1] + pad)) + 1, height)
+        if c1[0] <= c0[0] or c1[1] <= c0[1]:
+            continue
+        du, dv = u[c0[1]:c1[1], c0[0]:c1[0]] - 0.5 * (x0 + x1), v[c0[1]:c1[1], c0[0]:c1[0]] - 0.5 * (y0 + y1)
+        length = np.hypot(x1 - x0, y1 - y0)
+        ex, ey = (x1 - x0) / length, (y1 - y0) / length
+        along, across = du * ex + dv * ey, dv * ex - du * ey
+        fade = 0.5 * (1.0 + np.tanh((0.5 * length + 2.0 - np.abs(along)) / 2.0)) * np.exp(-0.5 * (across / reach) ** 2)
+        val[c0[1]:c1[1], c0[0]:c1[0]] += amp * np.tanh(across / soft) * fade
+    return np.clip(np.rint(gain * val + offset), 0, 255).astype(np.uint8)
+
+
+def make_line_image(seed, height, width, num_segments, min_length=12.0, max_length=80.0, margin=26.0):
+    """A seeded grey image of soft edges over sinusoidal texture, and the line segments that follow the edges: every segment lies on the
+    edge that was drawn for it, at least `margin` pixels inside the image, between min_length and max_length pixels long, at sub-pixel
+    end points.  Stands in for a camera image and a line detector.  Returns dict(image uint8 [height, width], segments [n, 4] float32
+    (x0, y0, x1, y1))."""
+    scene = _line_scene(seed, height, width, num_segments, min_length, max_length, margin)
+    return {"image": _render_scene(scene, height, width), "segments": scene["segments"].astype(np.float32)}
+
+
+def make_line_image_pair(seed, height, width, num_segments, shift=(2.3, -1.6), gain=0.8, offset=15.0, **kw):
+    """make_line_image and a second view of the same scene: moved by a sub-pixel `shift` (x, y), its grey values gain * I + offset, its
+    segments moved along and listed in a shuffled order.  Returns dict(image, segments: the first view; image2, segments2: the second;
+    truth [n]: the row of segments2 that shows segment a of the first view)."""
+    kw.setdefault("margin", 26.0)
+    scene = _line_scene(seed, height, width, num_segments, kw.get("min_length", 12.0), kw.get("max_length", 80.0),
+                        kw["margin"] + max(abs(shift[0]), abs(shift[1])))
+    rng = np.random.default_rng(np.random.SeedSequence([17, int(seed)]))
+    perm = rng.permutation(int(num_segments))                                          # row b of the second view shows segment perm[b]
+    moved = scene["segments"] + np.array([shift[0], shift[1], shift[0], shift[1]])
+    truth = np.empty(int(num_segments), dtype=np.int32)
+    truth[perm] = np.arange(int(num_segments), dtype=np.int32)
+    return {"image": _render_scene(scene, height, width), "segments": scene["segments"].astype(np.float32),
+            "image2": _render_scene(scene, height, width, shift, gain, offset), "segments2": moved[perm].astype(np.float32),
+            "truth": truth}
