@@ -1302,6 +1302,92 @@ int  slslam_line_descriptor_stats(const slslam_line_descriptor* handle, long lon
 /* One frame, one call (its own buffers, made and freed). */
 int  slslam_describe_lines(const slslam_msld_options* options, const slslam_msld_frame* frame, const slslam_msld_result* result);
 
+/* ------------------------------------------------------------------ line segments from images: the detector
+ * What makes the segments[n][4] that slslam_line_descriptor_run takes, from grey images alone (csrc/line_detect.h).  The
+ * reference assumes an external tracker for them and ships none, so there is no code to restate: this block is the contract, a function
+ * of the image and the options alone whatever order a device visits the pixels in.  It is the region idea of LSD (Grompone von Gioi et
+ * al., PAMI 32, 2010) without the sequential region growing: connected components of aligned gradients, each fitted by its moments.
+ * tests/line_detect_reference.py restates it in numpy.
+ *   inputs     per frame an 8-bit grey image[height][stride], row-major, stride >= width, 1 <= width, height <= 8192; pixel centres lie at
+ *              integers; the pixel index of (x, y) is y width + x.
+ *   options    grad_threshold T in 1 .. 1024 (default 24); tol_num / tol_den = tan^2 of the angle two linked gradients may differ by, 0 <=
+ *              tol_num, 1 <= tol_den, both <= 2^20 (default 11 / 64, about 22.5 degrees); min_pixels >= 1 (12); min_length >= 0 (10.0)
+ *              and max_thickness >= 0 (3.0) in pixels, finite; max_segments in 1 .. 2^20 (512), the segments written per frame.
+ *   1 gradient in integers, not halved: gx(x, y) = I(min(x + 1, W - 1), y) - I(max(x - 1, 0), y), gy likewise; m2 = gx gx + gy gy.  A pixel
+ *              is strong when m2 >= T T; its weight w is the largest integer with w w <= m2, exactly.
+ *   2 links    two 8-neighbours a and b are linked when both are strong, dot = ga . gb > 0 and tol_den cross^2 <= tol_num dot^2 with
+ *              cross = ga.x gb.y - ga.y gb.x; all in 64-bit integers.
+ *   3 components  the connected components of the link graph.  A component's label is the smallest pixel index in it; components are
+ *              numbered in ascending label order, which is the order of every output.
+ *   4 sums     in 64-bit integers per component, with u = x - xr, v = y - yr the offsets from the label's pixel (xr, yr): n, Sw, Swu, Swv,
+ *              Swuu, Swuv, Swvv, Sgx, Sgy.  None can overflow at 8192 x 8192.
+ *   5 fit      in double, every operation rounded on its own, in this order: cx = Swu / Sw, cy = Swv / Sw; sxx = Swuu / Sw - cx cx,
+ *              syy = Swvv / Sw - cy cy, sxy = Swuv / Sw - cx cy; h = (sxx - syy) / 2, rt = sqrt(h h + sxy sxy), lmin = (sxx + syy) / 2 - rt;
+ *              the axis e = (h + rt, sxy) when h >= 0, else (sxy, rt - h), divided by its norm sqrt(ex ex + ey ey) - a norm of 0 is the
+ *              status ISOTROPIC; thickness = sqrt(max(lmin, 0)), the RMS distance of the weight from the line.
+ *   6 extent   over the component's pixels t = (u - cx) ex + (v - cy) ey; tmin and tmax are exact whatever the order; length = tmax - tmin;
+ *              the end point at t is (xr + cx) + t ex, (yr + cy) + t ey.
+ *   7 orientation  p0 is the end point at tmin and p1 the one at tmax when ex Sgy - ey Sgx >= 0, else the two are swapped: cross(p1 - p0,
+ *              (Sgx, Sgy)) >= 0, the sign of the MSLD polarity above, so orient = 1 there leaves a detected segment as it is.
+ *   8 status   SMALL: n < min_pixels (no fit is made); else ISOTROPIC; else SHORT: length < min_length; else THICK: thickness >
+ *              max_thickness (how curved chains and blobs leave); else OK.  Only OK components become segments.
+ *   9 outputs  per frame, any pointer may be NULL: of the first num_written = min(num_ok, max_segments) OK components in label order
+ *              (truncation never reorders) segments (x0, y0, x1, y1) rounded to float, length, thickness and strength = Sw / n in double,
+ *              pixels = n and label; num_components, num_ok, num_written, status_counts[5] indexed by SLSLAM_LSD_*; and the label plane
+ *              labels[height][width], -1 where a pixel is not strong (for viewers and tests; it is a download of 4 bytes a pixel).
+ * Links are pairwise: two lines joined by a smoothly rounded corner are one component and leave as THICK.  No NFA validation, no image
+ * pyramid, no smoothing.  Frames are independent: a frame's results do not depend on the rest of the call. */
+enum { SLSLAM_LSD_MAX_SIDE = 8192, SLSLAM_LSD_TILE = 32 };     /* TILE: the side of the labelling's tiles, for tests at its borders */
+enum { SLSLAM_LSD_OK = 0, SLSLAM_LSD_SMALL = 1, SLSLAM_LSD_ISOTROPIC = 2, SLSLAM_LSD_SHORT = 3, SLSLAM_LSD_THICK = 4 };
+typedef struct slslam_line_detect_options {
+  int grad_threshold;            /* T, on the scale of the gradient that is not halved */
+  int tol_num, tol_den;
+  int min_pixels;
+  double min_length, max_thickness;
+  int max_segments;
+} slslam_line_detect_options;
+typedef struct slslam_line_detect_frame {
+  int width, height;
+  long long stride;              /* bytes from one row to the next, >= width */
+  const unsigned char* image;
+} slslam_line_detect_frame;
+typedef struct slslam_line_detect_result {
+  float*  segments;              /* caller-owned arrays, any of them may be NULL.  [max_segments 4]: what slslam_msld_frame.segments takes */
+  double* length;                /* [max_segments] */
+  double* thickness;
+  double* strength;
+  int*    pixels;
+  int*    label;
+  int*    num_components;        /* one int each */
+  int*    num_ok;
+  int*    num_written;
+  int*    status_counts;         /* [5] */
+  int*    labels;                /* [height width] */
+} slslam_line_detect_result;
+typedef struct slslam_line_detector slslam_line_detector;
+
+/* grad_threshold 24, tol 11 / 64, min_pixels 12, min_length 10, max_thickness 3, max_segments 512 */
+void slslam_line_detect_default_options(slslam_line_detect_options* opt);
+/* device < 0 selects the current HIP device.  options as above, fixed for the handle.  max_frames >= 1 frames of max_pixels >= 1 pixels
+ * each: what the one device block and the one page-locked block are made for at the first run (about 21 bytes a pixel on the device at
+ * the default min_pixels: 128 / min_pixels + 10.  The page-locked block holds no label plane until a call asks for one).  A larger call
+ * makes larger ones and counts one allocation; a call that fits allocates nothing.  max_pixels <= 8192^2, max_frames x max_pixels <= 2^30
+ * and max_frames x max_segments <= 2^24, else SLSLAM_ERR_INVALID_ARGUMENT.  Touches no device. */
+int  slslam_line_detector_create(int device, const slslam_line_detect_options* options, int max_frames, long long max_pixels,
+                                 slslam_line_detector** out);
+void slslam_line_detector_destroy(slslam_line_detector* handle);
+/* frames[F], results[F].  Every argument is validated before an output is written or the device is asked - a negative count, a missing
+ * array or image, a size out of range, stride < width: SLSLAM_ERR_INVALID_ARGUMENT; more than 65535 frames, 2^24 segments or 2^32 pixels
+ * in one call: SLSLAM_ERR_UNSUPPORTED.  Synchronous; host pointers; one upload (the images with `width` bytes per row: the stride stays on
+ * the host), eleven launches and one download per call whatever F. */
+int  slslam_line_detector_run(slslam_line_detector* handle, int num_frames, const slslam_line_detect_frame* frames,
+                              const slslam_line_detect_result* results);
+/* Since create: runs, and how often the blocks were made or made larger.  Either pointer may be NULL. */
+int  slslam_line_detector_stats(const slslam_line_detector* handle, long long* calls, long long* allocations);
+/* One frame, one call (its own buffers, made and freed). */
+int  slslam_detect_lines(const slslam_line_detect_options* options, const slslam_line_detect_frame* frame,
+                         const slslam_line_detect_result* result);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */
@@ -1314,6 +1400,8 @@ int slslam_po_last_timing(double* total_ms, double* factor_ms, int* factor_calls
  * following runs with two events on its stream, enable == 0 stops that, enable < 0 leaves the switch as it is; *kernel_ms (may be NULL):
  * the last bracketed launch, 0 before one. */
 int slslam_line_descriptor_timing(slslam_line_descriptor* handle, int enable, double* kernel_ms);
+/* The same for the line detector (tools/line_detect_bench.py): the events bracket the eleven launches of a run. */
+int slslam_line_detector_timing(slslam_line_detector* handle, int enable, double* kernel_ms);
 /* Timing builds only (a variant library compiled with -DSLSLAM_K1_TIMING=1, -DSLSLAM_K1_WALL=1 or -DSLSLAM_SOLVE_TIMING=1: the elimination
  * sweeps / the reduced solve and k_big_solve): wave-clock cycles per phase summed over the batch since finalize; out[16].  The product
  * library has no stamps and no stamp buffer: SLSLAM_ERR_STATE there, from this call and the next. */

@@ -145,7 +145,25 @@ class MsldResult(C.Structure):
                 ("polarity", C.POINTER(C.c_float))]
 
 
+class LineDetectOptions(C.Structure):
+    _fields_ = [("grad_threshold", C.c_int), ("tol_num", C.c_int), ("tol_den", C.c_int), ("min_pixels", C.c_int),
+                ("min_length", C.c_double), ("max_thickness", C.c_double), ("max_segments", C.c_int)]
+
+
+class LineDetectFrame(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("stride", C.c_longlong), ("image", C.POINTER(C.c_ubyte))]
+
+
+class LineDetectResult(C.Structure):
+    _fields_ = [("segments", C.POINTER(C.c_float)), ("length", C.POINTER(C.c_double)), ("thickness", C.POINTER(C.c_double)),
+                ("strength", C.POINTER(C.c_double)), ("pixels", C.POINTER(C.c_int)), ("label", C.POINTER(C.c_int)),
+                ("num_components", C.POINTER(C.c_int)), ("num_ok", C.POINTER(C.c_int)), ("num_written", C.POINTER(C.c_int)),
+                ("status_counts", C.POINTER(C.c_int)), ("labels", C.POINTER(C.c_int))]
+
+
 MSLD_STATUS = {0: "OK", 1: "FLAT", 2: "TOO_SHORT", 3: "OUTSIDE", 4: "INVALID"}
+LSD_STATUS = {0: "OK", 1: "SMALL", 2: "ISOTROPIC", 3: "SHORT", 4: "THICK"}
+LSD_TILE = 32                                           # SLSLAM_LSD_TILE: the side of the detector's labelling tiles
 PLACE_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_DESCRIPTOR"}
 DESC_STATUS = {0: "OK", 1: "EMPTY", 2: "INVALID_DESCRIPTOR"}
 TRI_MULTIVIEW, TRI_STEREO, TRI_CONSTANT, TRI_NO_OBSERVATIONS, TRI_INVALID = 0, 1, 2, 3, 4
@@ -202,6 +220,8 @@ EXPORTS = [
     "slslam_descriptor_matcher_run", "slslam_descriptor_matcher_size", "slslam_descriptor_matcher_stats", "slslam_match_descriptors",
     "slslam_msld_default_options", "slslam_line_descriptor_create", "slslam_line_descriptor_destroy", "slslam_line_descriptor_run",
     "slslam_line_descriptor_stats", "slslam_line_descriptor_timing", "slslam_describe_lines",
+    "slslam_line_detect_default_options", "slslam_line_detector_create", "slslam_line_detector_destroy", "slslam_line_detector_run",
+    "slslam_line_detector_stats", "slslam_line_detector_timing", "slslam_detect_lines",
     "slslam_voctree_train", "slslam_voctree_save", "slslam_voctree_centres", "slslam_voctree_key", "slslam_debug_voctree_step", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -392,6 +412,16 @@ def lib():
         L.slslam_line_descriptor_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
         L.slslam_line_descriptor_timing.argtypes = [vp, C.c_int, dp]
         L.slslam_describe_lines.argtypes = [C.POINTER(MsldOptions), C.POINTER(MsldFrame), C.POINTER(MsldResult)]
+    if hasattr(L, "slslam_detect_lines"):       # (likewise: a library built before the line detector existed)
+        L.slslam_line_detect_default_options.argtypes = [C.POINTER(LineDetectOptions)]
+        L.slslam_line_detect_default_options.restype = None
+        L.slslam_line_detector_create.argtypes = [C.c_int, C.POINTER(LineDetectOptions), C.c_int, C.c_longlong, C.POINTER(vp)]
+        L.slslam_line_detector_destroy.argtypes = [vp]
+        L.slslam_line_detector_destroy.restype = None
+        L.slslam_line_detector_run.argtypes = [vp, C.c_int, C.POINTER(LineDetectFrame), C.POINTER(LineDetectResult)]
+        L.slslam_line_detector_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+        L.slslam_line_detector_timing.argtypes = [vp, C.c_int, dp]
+        L.slslam_detect_lines.argtypes = [C.POINTER(LineDetectOptions), C.POINTER(LineDetectFrame), C.POINTER(LineDetectResult)]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -2021,3 +2051,96 @@ class LineDescriptor(_CountedHandle):
         ms = C.c_double(0.0)
         _check(lib().slslam_line_descriptor_timing(self._h, -1, C.byref(ms)), "slslam_line_descriptor_timing")      # (-1: the switch stays)
         return ms.value
+
+
+# ----------------------------------------------------------------------------- line segments from images (slslam_line_detector_*)
+def line_detect_options(grad_threshold=24, tol_num=11, tol_den=64, min_pixels=12, min_length=10.0, max_thickness=3.0, max_segments=512):
+    return LineDetectOptions(int(grad_threshold), int(tol_num), int(tol_den), int(min_pixels), float(min_length), float(max_thickness),
+                             int(max_segments))
+
+
+def _image_rows(image):
+    """A uint8 [H, W] array whose rows the library can walk: an image whose rows are contiguous passes its stride, any other is copied."""
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise ValueError("an image is uint8 [H, W]")
+    if img.shape[0] > 0 and img.shape[1] > 0 and (img.strides[1] != 1 or img.strides[0] < img.shape[1]):
+        img = np.ascontiguousarray(img)
+    return img
+
+
+def _detect_frame(image, max_segments, labels):
+    """(LineDetectFrame, LineDetectResult, the arrays both point to)."""
+    img = _image_rows(image)
+    s = max(int(max_segments), 1)
+    b = {"segments": np.zeros((s, 4), dtype=np.float32), "length": np.zeros(s), "thickness": np.zeros(s), "strength": np.zeros(s),
+         "pixels": np.zeros(s, dtype=np.int32), "label": np.full(s, -1, dtype=np.int32), "counts": np.full(3, -1, dtype=np.int32),
+         "status_counts": np.zeros(5, dtype=np.int32), "labels": np.full(img.shape, -1, dtype=np.int32) if labels else None}
+    fr = LineDetectFrame(img.shape[1], img.shape[0], img.strides[0] if img.shape[0] > 0 else 0, img.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    c = b["counts"].ctypes.data
+    res = LineDetectResult(_fp(b["segments"]), _dp(b["length"]), _dp(b["thickness"]), _dp(b["strength"]), _ip(b["pixels"]), _ip(b["label"]),
+                           C.cast(c, C.POINTER(C.c_int)), C.cast(c + 4, C.POINTER(C.c_int)), C.cast(c + 8, C.POINTER(C.c_int)),
+                           _ip(b["status_counts"]), _ip(b["labels"]) if labels else None)
+    return fr, res, (img, b)
+
+
+def _detect_dict(keep):
+    _, b = keep
+    n = max(int(b["counts"][2]), 0)
+    out = {k: b[k][:n] for k in ("segments", "length", "thickness", "strength", "pixels", "label")}
+    out.update(num_components=int(b["counts"][0]), num_ok=int(b["counts"][1]), num_written=int(b["counts"][2]),
+               status_counts={LSD_STATUS[i]: int(v) for i, v in enumerate(b["status_counts"])})
+    if b["labels"] is not None:
+        out["labels"] = b["labels"]
+    return out
+
+
+def detect_lines(image, labels=False, **options):
+    """slslam_detect_lines: the line segments of one uint8 image [H, W].  Returns dict(segments [n, 4] float32 (x0, y0, x1, y1), length,
+    thickness, strength [n] float64, pixels, label [n] int32, num_components, num_ok, num_written = n, status_counts: a dict over
+    LSD_STATUS's names; with labels=True also labels [H, W] int32, -1 where a pixel is not strong)."""
+    opt = line_detect_options(**options)
+    fr, res, keep = _detect_frame(image, opt.max_segments, labels)
+    _check(lib().slslam_detect_lines(C.byref(opt), C.byref(fr), C.byref(res)), "slslam_detect_lines")
+    return _detect_dict(keep)
+
+
+class LineDetector(_CountedHandle):
+    """slslam_line_detector: the line segments of many frames per call; buffers kept between calls.  A frame is an image uint8 [H, W]."""
+    _DESTROY, _STATS = "slslam_line_detector_destroy", "slslam_line_detector_stats"
+
+    def __init__(self, max_frames=2, max_pixels=752 * 480, device=-1, **options):
+        self.opt = line_detect_options(**options)
+        self._h = C.c_void_p()
+        _check(lib().slslam_line_detector_create(int(device), C.byref(self.opt), int(max_frames), int(max_pixels), C.byref(self._h)),
+               "slslam_line_detector_create")
+
+    def run(self, images, labels=False):
+        """Returns one dict per frame, as detect_lines returns it."""
+        n = len(images)
+        frs, outs, keep = (LineDetectFrame * max(n, 1))(), (LineDetectResult * max(n, 1))(), []
+        for i, image in enumerate(images):
+            frs[i], outs[i], k = _detect_frame(image, self.opt.max_segments, labels)
+            keep.append(k)
+        _check(lib().slslam_line_detector_run(self._h, n, frs, outs), "slslam_line_detector_run")
+        return [_detect_dict(k) for k in keep]
+
+    def set_timing(self, enable):
+        _check(lib().slslam_line_detector_timing(self._h, int(bool(enable)), None), "slslam_line_detector_timing")
+
+    def kernel_ms(self):
+        """The last run's launches by events (after set_timing(True))."""
+        ms = C.c_double(0.0)
+        _check(lib().slslam_line_detector_timing(self._h, -1, C.byref(ms)), "slslam_line_detector_timing")         # (-1: the switch stays)
+        return ms.value
+
+
+def detect_and_describe(detector, descriptor, images):
+    """The segments of every image (detector: a LineDetector) and their MSLD descriptors (descriptor: a LineDescriptor): two calls, the
+    images go to the device once for each.  Returns per frame the detector's dict with the descriptor's `descriptors`, `status` (as
+    `descriptor_status`), `num_samples` and `polarity` added."""
+    found = detector.run(images)
+    described = descriptor.run([(image, f["segments"]) for image, f in zip(images, found)])
+    for f, d in zip(found, described):
+        f.update(descriptors=d["descriptors"], descriptor_status=d["status"], num_samples=d["num_samples"], polarity=d["polarity"])
+    return found

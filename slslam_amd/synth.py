@@ -615,3 +615,24 @@ def make_line_image_pair(seed, height, width, num_segments, shift=(2.3, -1.6), g
     return {"image": _render_scene(scene, height, width), "segments": scene["segments"].astype(np.float32),
             "image2": _render_scene(scene, height, width, shift, gain, offset), "segments2": moved[perm].astype(np.float32),
             "truth": truth}
+
+
+def make_edge_image(height, width, segments, amplitude=60.0, softness=1.5, reach=6.0):
+    """A grey image of clean edges on a flat background, with no texture: per segment (x0, y0, x1, y1) a smoothed step of +-amplitude
+    grey levels across its line, amplitude tanh(across / softness), that runs between exactly the end points given and fades out within
+    about a pixel beyond them and, across the line, with a Gaussian of `reach` pixels.  The profile is antisymmetric about the line, so
+    the gradient's weight is centred on it: analytic ground truth for a detector.  amplitude and softness are scalars or one value per
+    segment; the peak gradient is amplitude / softness grey levels per pixel.  Returns uint8 [height, width]."""
+    seg = np.asarray(segments, dtype=np.float64).reshape(-1, 4)
+    amp = np.broadcast_to(np.asarray(amplitude, dtype=np.float64), (len(seg),))
+    soft = np.broadcast_to(np.asarray(softness, dtype=np.float64), (len(seg),))
+    v, u = np.mgrid[0:height, 0:width].astype(np.float64)
+    val = np.full((height, width), 118.0)
+    for (x0, y0, x1, y1), a, s in zip(seg, amp, soft):
+        length = np.hypot(x1 - x0, y1 - y0)
+        ex, ey = (x1 - x0) / length, (y1 - y0) / length
+        du, dv = u - 0.5 * (x0 + x1), v - 0.5 * (y0 + y1)
+        along, across = du * ex + dv * ey, dv * ex - du * ey
+        fade = 0.5 * (1.0 + np.tanh(0.5 * length - np.abs(along))) * np.exp(-0.5 * (across / reach) ** 2)
+        val += a * np.tanh(across / s) * fade
+    return np.clip(np.rint(val), 0, 255).astype(np.uint8)
