@@ -1388,6 +1388,96 @@ int  slslam_line_detector_stats(const slslam_line_detector* handle, long long* c
 int  slslam_detect_lines(const slslam_line_detect_options* options, const slslam_line_detect_frame* frame,
                          const slslam_line_detect_result* result);
 
+/* ------------------------------------------------------------------ stereo line matching: a left and a right segment become one observation
+ * What makes the stereo line observation - eight doubles x0 y0 x1 y1 (left) x2 y2 x3 y3 (right), normalised with the left camera's
+ * intrinsics: slslam_frame.observations (host/sequence_io.h), the input of slslam_line_matcher_run, slslam_ransac_motion,
+ * slslam_pose_estimator_run, the triangulator and the LBA - from the segments and descriptors of a rectified left and right image
+ * (csrc/stereo_match.h).
+ * Replaces: nothing the reference ships.  It reads its observations from the files of an external tracker (SLAM::grab_new_frame,
+ * src/slam.cpp:62-135) and has no code that pairs the two images' segments; this block produces the eight numbers of one line of such
+ * a file, after SLAM::insert_curr_obs (src/slam.cpp:121-135).  So there is no code to restate: this block is the contract, a function
+ * of the arguments alone; tests/stereo_match_reference.py restates it in numpy.
+ *   inputs     per stereo frame n left segments [n 4] float (x0, y0, x1, y1) in pixels of the rectified left image with their descriptors
+ *              [n D] float, and m right segments [m 4] with [m D]; n, m <= 512; D a multiple of 8, 8 <= D <= 128.
+ *   segment    in double from the float end points, every operation rounded on its own (no contraction), here and below:
+ *              lo = min(y0, y1), hi = max(y0, y1), ext = hi - lo (= |y1 - y0|), dx = x1 - x0, dy = y1 - y0, slope = dx / dy;
+ *              x(y) = x0 + (y - y0) * slope.  A segment is valid when its four floats and its D descriptor floats are finite.
+ *   admissible a pair (left a, right b) when both are valid and all of these hold, in this order:
+ *              rows       ext_a >= min_rows and ext_b >= min_rows;
+ *              overlap    top = max(lo_a, lo_b), bot = min(hi_a, hi_b), o = bot - top: o >= min_overlap * min(ext_a, ext_b) and o > 0;
+ *              direction  dot = dx_a dx_b + dy_a dy_b, cross = dx_a dy_b - dy_a dx_b: cross cross <= max_tan2 * (dot dot) and dot != 0;
+ *              disparity  yc = 0.5 * (top + bot), d = x_a(yc) - x_b(yc): min_disparity <= d and d <= max_disparity;
+ *              distance   r = 1.0f; for i in 0 .. D-1: r -= left[a][i] * right[b][i] - the float chain of slslam_match_descriptors, in
+ *                         that order: r is finite and (double)r < max_distance.
+ *   per a      best = the admissible b of the smallest r, the lowest b on ties (-1: none); best_distance, second_distance (+inf each
+ *              when absent), num_admissible: as slslam_descriptor_result has them;
+ *   per b      best_left = the admissible a of the smallest r, the lowest a on ties (-1: none);
+ *   match[a]   best[a] when best[a] >= 0, best_left[best[a]] == a and (double)best_distance[a] * ratio <= (double)second_distance[a]
+ *              (ratio <= 1 switches this test off), else -1.
+ *   segment_status[a]  INVALID: a is not valid; else FLAT: ext_a < min_rows (the segment lies along the epipolar line and carries no depth:
+ *              no pair of it is admissible); else MATCHED: match[a] >= 0; else UNMATCHED.
+ *   observations[a]  for MATCHED a only, b = match[a]: (x0, y0, x1, y1) of a, then of b - b's two end points swapped when dot < 0, so
+ *              that right end point 0 answers left end point 0 - each value v as v / fx - cx / fx (x) or v / fy - cy / fy (y): the
+ *              operation order of SLAM::insert_curr_obs, the left camera's intrinsics for both images.
+ *   disparity[a]  for MATCHED a only: x0_a - x_b(y0_a), x1_a - x_b(y1_a), in pixels: the right LINE (from b's end point 0 as given, not
+ *              swapped) evaluated at the rows of the left end points; what a caller turns into depth.
+ * Frame status: EMPTY when n = 0 or m = 0 (then nothing is admissible), else OK.  Minima, counts and per-row arithmetic only: a
+ * frame's results do not depend on the other frames of the call or on the order of evaluation. */
+enum { SLSLAM_STEREO_MAX_D = 128, SLSLAM_STEREO_MAX_SEGMENTS = 512 };
+enum { SLSLAM_STEREO_OK = 0, SLSLAM_STEREO_EMPTY = 1 };
+enum { SLSLAM_STEREO_MATCHED = 0, SLSLAM_STEREO_UNMATCHED = 1, SLSLAM_STEREO_FLAT = 2, SLSLAM_STEREO_INVALID = 3 };
+typedef struct slslam_stereo_match_options {
+  double min_disparity, max_disparity;   /* px, finite, min <= max                                                          */
+  double max_tan2;                       /* squared tangent of the largest direction difference, finite, >= 0               */
+  double min_rows;                       /* px, finite, >= 0                                                                */
+  double min_overlap;                    /* in [0, 1]: the share of the shorter row extent the common rows must cover       */
+  double ratio, max_distance;            /* as slslam_descriptor_matcher_run takes them; neither may be NaN                 */
+  double fx, fy, cx, cy;                 /* the left camera; finite, fx and fy not 0                                        */
+} slslam_stereo_match_options;
+typedef struct slslam_stereo_frame {
+  int num_left;                          /* n >= 0, at most the matcher's max_segments */
+  const float* left_segments;            /* [n 4] */
+  const float* left_descriptors;         /* [n D] row-major */
+  int num_right;                         /* m */
+  const float* right_segments;           /* [m 4] */
+  const float* right_descriptors;        /* [m D] */
+} slslam_stereo_frame;
+typedef struct slslam_stereo_result {
+  int     status;                        /* SLSLAM_STEREO_OK / _EMPTY                                                        */
+  int     num_matched;                   /* match[a] >= 0                                                                    */
+  int*    match;                         /* caller-owned arrays, any of them may be NULL.  [n]                               */
+  int*    best;                          /* [n] */
+  float*  best_distance;                 /* [n] */
+  float*  second_distance;               /* [n] */
+  int*    num_admissible;                /* [n] */
+  int*    best_left;                     /* [m] */
+  int*    segment_status;                /* [n] SLSLAM_STEREO_MATCHED ... _INVALID */
+  double* observations;                  /* [n 8]; only the rows of MATCHED segments are written */
+  double* disparity;                     /* [n 2]; likewise */
+} slslam_stereo_result;
+typedef struct slslam_stereo_matcher slslam_stereo_matcher;
+
+/* disparity 0 .. 128 px, max_tan2 0.03 (about 10 degrees), min_rows 3, min_overlap 0.5, ratio 1.5, max_distance 0.25, fx = fy = 1,
+ * cx = cy = 0 (pixels stay pixels) */
+void slslam_stereo_match_default_options(slslam_stereo_match_options* opt);
+/* device < 0 selects the current HIP device.  D as above, fixed for the handle.  max_frames >= 1 stereo frames of max_segments in
+ * 1 .. 512 segments per image: what the one device block and the one page-locked block are made for at the first run.  A run of more
+ * frames makes larger ones and counts one allocation; a run that fits allocates nothing.  Touches no device. */
+int  slslam_stereo_matcher_create(int device, int D, int max_frames, int max_segments, slslam_stereo_matcher** out);
+void slslam_stereo_matcher_destroy(slslam_stereo_matcher* matcher);
+/* frames[F], out[F].  Every argument is validated before an output is written or the device is asked - missing or invalid options, a
+ * negative count, a count beyond max_segments, a missing array of a non-zero count: SLSLAM_ERR_INVALID_ARGUMENT, outputs untouched.
+ * Synchronous; host pointers; one upload, three launches (pairs, finish, emit) and one download per call whatever F. */
+int  slslam_stereo_matcher_run(slslam_stereo_matcher* matcher, const slslam_stereo_match_options* options, int num_frames,
+                               const slslam_stereo_frame* frames, slslam_stereo_result* out);
+/* Since create: runs, and how often the blocks were made or made larger.  Either pointer may be NULL. */
+int  slslam_stereo_matcher_stats(const slslam_stereo_matcher* matcher, long long* calls, long long* allocations);
+/* For tools/stereo_match_bench.py: enable > 0 brackets the three launches of the handle's following runs with two events on its
+ * stream, enable == 0 stops that, enable < 0 leaves the switch as it is; *kernel_ms (may be NULL): the last bracketed run, 0 before one. */
+int  slslam_stereo_matcher_timing(slslam_stereo_matcher* matcher, int enable, double* kernel_ms);
+/* One stereo frame, one call (its own buffers, made and freed); n, m <= 512. */
+int  slslam_match_stereo(int D, const slslam_stereo_match_options* options, const slslam_stereo_frame* frame, slslam_stereo_result* out);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */

@@ -161,6 +161,25 @@ class LineDetectResult(C.Structure):
                 ("status_counts", C.POINTER(C.c_int)), ("labels", C.POINTER(C.c_int))]
 
 
+class StereoMatchOptions(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("min_disparity", "max_disparity", "max_tan2", "min_rows", "min_overlap", "ratio",
+                                          "max_distance", "fx", "fy", "cx", "cy")]
+
+
+class StereoFrame(C.Structure):
+    _fields_ = [("num_left", C.c_int), ("left_segments", C.POINTER(C.c_float)), ("left_descriptors", C.POINTER(C.c_float)),
+                ("num_right", C.c_int), ("right_segments", C.POINTER(C.c_float)), ("right_descriptors", C.POINTER(C.c_float))]
+
+
+class StereoResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("num_matched", C.c_int), ("match", C.POINTER(C.c_int)), ("best", C.POINTER(C.c_int)),
+                ("best_distance", C.POINTER(C.c_float)), ("second_distance", C.POINTER(C.c_float)),
+                ("num_admissible", C.POINTER(C.c_int)), ("best_left", C.POINTER(C.c_int)), ("segment_status", C.POINTER(C.c_int)),
+                ("observations", C.POINTER(C.c_double)), ("disparity", C.POINTER(C.c_double))]
+
+
+STEREO_STATUS = {0: "OK", 1: "EMPTY"}
+STEREO_SEGMENT_STATUS = {0: "MATCHED", 1: "UNMATCHED", 2: "FLAT", 3: "INVALID"}
 MSLD_STATUS = {0: "OK", 1: "FLAT", 2: "TOO_SHORT", 3: "OUTSIDE", 4: "INVALID"}
 LSD_STATUS = {0: "OK", 1: "SMALL", 2: "ISOTROPIC", 3: "SHORT", 4: "THICK"}
 LSD_TILE = 32                                           # SLSLAM_LSD_TILE: the side of the detector's labelling tiles
@@ -222,6 +241,8 @@ EXPORTS = [
     "slslam_line_descriptor_stats", "slslam_line_descriptor_timing", "slslam_describe_lines",
     "slslam_line_detect_default_options", "slslam_line_detector_create", "slslam_line_detector_destroy", "slslam_line_detector_run",
     "slslam_line_detector_stats", "slslam_line_detector_timing", "slslam_detect_lines",
+    "slslam_stereo_match_default_options", "slslam_stereo_matcher_create", "slslam_stereo_matcher_destroy", "slslam_stereo_matcher_run",
+    "slslam_stereo_matcher_stats", "slslam_stereo_matcher_timing", "slslam_match_stereo",
     "slslam_voctree_train", "slslam_voctree_save", "slslam_voctree_centres", "slslam_voctree_key", "slslam_debug_voctree_step", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -422,6 +443,17 @@ def lib():
         L.slslam_line_detector_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
         L.slslam_line_detector_timing.argtypes = [vp, C.c_int, dp]
         L.slslam_detect_lines.argtypes = [C.POINTER(LineDetectOptions), C.POINTER(LineDetectFrame), C.POINTER(LineDetectResult)]
+    if hasattr(L, "slslam_match_stereo"):       # (likewise: a library built before the stereo line matcher existed)
+        fp = C.POINTER(C.c_float)
+        L.slslam_stereo_match_default_options.argtypes = [C.POINTER(StereoMatchOptions)]
+        L.slslam_stereo_match_default_options.restype = None
+        L.slslam_stereo_matcher_create.argtypes = [C.c_int] * 4 + [C.POINTER(vp)]
+        L.slslam_stereo_matcher_destroy.argtypes = [vp]
+        L.slslam_stereo_matcher_destroy.restype = None
+        L.slslam_stereo_matcher_run.argtypes = [vp, C.POINTER(StereoMatchOptions), C.c_int, C.POINTER(StereoFrame), C.POINTER(StereoResult)]
+        L.slslam_stereo_matcher_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+        L.slslam_stereo_matcher_timing.argtypes = [vp, C.c_int, dp]
+        L.slslam_match_stereo.argtypes = [C.c_int, C.POINTER(StereoMatchOptions), C.POINTER(StereoFrame), C.POINTER(StereoResult)]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -2144,3 +2176,126 @@ def detect_and_describe(detector, descriptor, images):
     for f, d in zip(found, described):
         f.update(descriptors=d["descriptors"], descriptor_status=d["status"], num_samples=d["num_samples"], polarity=d["polarity"])
     return found
+
+
+# ----------------------------------------------------------------------------- stereo line matching (slslam_stereo_matcher_*)
+def stereo_match_options(**options):
+    """slslam_stereo_match_default_options with the given fields replaced: min_disparity, max_disparity, max_tan2, min_rows,
+    min_overlap, ratio, max_distance, fx, fy, cx, cy."""
+    o = StereoMatchOptions()
+    lib().slslam_stereo_match_default_options(C.byref(o))
+    for k, v in options.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown stereo match option %r" % k)
+        setattr(o, k, float(v))
+    return o
+
+
+def _stereo_side(side):
+    """(segments [n, 4], descriptors [n, D]) of one image: a pair of arrays, or a dict with those two keys (what detect_and_describe
+    returns per image)."""
+    seg, desc = (side["segments"], side["descriptors"]) if isinstance(side, dict) else side
+    seg = np.ascontiguousarray(seg, dtype=np.float32).reshape(-1, 4)
+    desc = np.ascontiguousarray(desc, dtype=np.float32)
+    desc = desc.reshape(len(seg), -1) if len(seg) else desc.reshape(0, desc.shape[-1] if desc.ndim == 2 else 0)
+    return seg, desc
+
+
+def _stereo_frame(left, right, D=None):
+    """(StereoFrame, StereoResult, the arrays both point to, D)."""
+    (ls, ld), (rs, rd) = _stereo_side(left), _stereo_side(right)
+    dims = {d.shape[1] for s, d in ((ls, ld), (rs, rd)) if len(s)} | ({int(D)} if D is not None else set())
+    if len(dims) > 1:
+        raise ValueError("the descriptors of a stereo frame must all have the matcher's D floats")
+    n, m = len(ls), len(rs)
+    r, b = _mutual_buffers(StereoResult, ("match", "best", "best_distance", "second_distance", "num_admissible", "best_left"), n, m)
+    b["segment_status"] = np.full(max(n, 1), -1, dtype=np.int32)
+    b["observations"] = np.full((max(n, 1), 8), np.nan)
+    b["disparity"] = np.full((max(n, 1), 2), np.nan)
+    r.segment_status, r.observations, r.disparity = _ip(b["segment_status"]), _dp(b["observations"]), _dp(b["disparity"])
+    fr = StereoFrame(n, _fp(ls), _fp(ld), m, _fp(rs), _fp(rd))
+    return fr, r, (ls, ld, rs, rd, b), (dims.pop() if dims else 8)
+
+
+def _stereo_dict(r, keep):
+    ls, _, rs, _, b = keep
+    out = _mutual_dict(STEREO_STATUS, r, b, len(ls), len(rs))
+    out["segment_status"] = [STEREO_SEGMENT_STATUS.get(s, "?") for s in out["segment_status"].tolist()]
+    return out
+
+
+def match_stereo(left, right, **options):
+    """slslam_match_stereo: the segments and descriptors of a rectified left image against those of the right one.  left, right:
+    (segments [n, 4] float32, descriptors [n, D] float32) or a dict with those keys.  Returns dict(status, num_matched, match [n], best
+    [n], best_distance [n] float32, second_distance [n] float32, num_admissible [n], best_left [m], segment_status [n] of
+    STEREO_SEGMENT_STATUS's names, observations [n, 8] and disparity [n, 2] float64 - NaN in the rows that are not MATCHED, which
+    the library leaves untouched)."""
+    opt = stereo_match_options(**options)
+    fr, r, keep, D = _stereo_frame(left, right)
+    _check(lib().slslam_match_stereo(D, C.byref(opt), C.byref(fr), C.byref(r)), "slslam_match_stereo")
+    return _stereo_dict(r, keep)
+
+
+class StereoMatcher(_CountedHandle):
+    """slslam_stereo_matcher: many stereo frames per call; buffers kept between calls.  A frame is (left, right) as match_stereo
+    takes them.  The options given here are the defaults of run."""
+    _DESTROY, _STATS = "slslam_stereo_matcher_destroy", "slslam_stereo_matcher_stats"
+
+    def __init__(self, D, max_frames=2, max_segments=512, device=-1, **options):
+        self.D = int(D)
+        self.options = dict(options)
+        stereo_match_options(**self.options)                        # (an unknown name fails here)
+        self._h = C.c_void_p()
+        _check(lib().slslam_stereo_matcher_create(int(device), self.D, int(max_frames), int(max_segments), C.byref(self._h)),
+               "slslam_stereo_matcher_create")
+
+    def run(self, frames, **options):
+        """Returns one dict per frame, as match_stereo returns it."""
+        opt = stereo_match_options(**dict(self.options, **options))
+        n = len(frames)
+        frs, outs, keep = (StereoFrame * max(n, 1))(), (StereoResult * max(n, 1))(), []
+        for i, (left, right) in enumerate(frames):
+            frs[i], outs[i], k, _ = _stereo_frame(left, right, self.D)
+            keep.append(k)
+        _check(lib().slslam_stereo_matcher_run(self._h, C.byref(opt), n, frs, outs), "slslam_stereo_matcher_run")
+        return [_stereo_dict(outs[i], keep[i]) for i in range(n)]
+
+    def set_timing(self, enable):
+        _check(lib().slslam_stereo_matcher_timing(self._h, int(bool(enable)), None), "slslam_stereo_matcher_timing")
+
+    def kernel_ms(self):
+        """The last run's three launches by events (after set_timing(True))."""
+        ms = C.c_double(0.0)
+        _check(lib().slslam_stereo_matcher_timing(self._h, -1, C.byref(ms)), "slslam_stereo_matcher_timing")          # (-1: the switch stays)
+        return ms.value
+
+
+def stereo_observations(result):
+    """From a stereo match result to what match_lines, PoseEstimator and the triangulator take: (observations [k, 8] float64 of the
+    MATCHED left segments in ascending order, their left indices [k])."""
+    idx = np.nonzero(np.asarray(result["match"]) >= 0)[0]
+    return np.ascontiguousarray(np.asarray(result["observations"])[idx]), idx
+
+
+def detect_describe_and_pair(detector, descriptor, matcher, stereo_images, **options):
+    """The whole image front end for rectified stereo pairs: the segments of every image (detector: a LineDetector), their MSLD
+    descriptors (descriptor: a LineDescriptor) and the pairing of every frame's left and right segments (matcher: a StereoMatcher;
+    options: what its run takes) - three calls whatever the number of frames.  stereo_images: (left, right) uint8 images per frame.
+    Only segments whose descriptor came out OK are paired.  Returns per frame dict(left, right: what detect_and_describe returns for
+    the image; left_rows, right_rows: the rows of those that were paired; stereo: the matcher's result over those rows;
+    observations [k, 8]: the stereo line observations of the matched pairs, as match_lines and PoseEstimator take them; left_index,
+    right_index [k]: the detector's rows of each observation)."""
+    flat = [img for pair in stereo_images for img in pair]
+    found = detect_and_describe(detector, descriptor, flat)
+    sides, rows = [], []
+    for f in found:
+        keep = np.nonzero(np.array([s == "OK" for s in f["descriptor_status"]], dtype=bool))[0]
+        rows.append(keep)
+        sides.append((f["segments"][keep], f["descriptors"][keep].reshape(len(keep), descriptor.D)))
+    results = matcher.run([(sides[2 * i], sides[2 * i + 1]) for i in range(len(stereo_images))], **options)
+    out = []
+    for i, r in enumerate(results):
+        obs, idx = stereo_observations(r)
+        out.append(dict(left=found[2 * i], right=found[2 * i + 1], left_rows=rows[2 * i], right_rows=rows[2 * i + 1], stereo=r,
+                        observations=obs, left_index=rows[2 * i][idx], right_index=rows[2 * i + 1][r["match"][idx]]))
+    return out

@@ -47,11 +47,7 @@ struct PairDesc {
 
 using Out = slslam::MatchOut;         // best_value / second_value = the distances, best_row = best_query
 
-// float bits -> an unsigned that orders as the float does (finite r; -0 counts as +0, as it does under <)
-__device__ __forceinline__ unsigned ordered(float r) {
-  const unsigned u = __float_as_uint(r + 0.0f);
-  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
+using slslam::ordered;                 // (mutual_match.h: the stereo matcher's keys carry the same word)
 
 // blockIdx = (64 query descriptors, pair); dynamic LDS pairs_lds_bytes(D)
 __global__ __launch_bounds__(64) void k_desc_pairs(const PairDesc* __restrict__ pairs, const float* __restrict__ qd,

@@ -30,6 +30,13 @@ struct MatchOut {
   int* best_row;
 };
 
+// float bits -> an unsigned that orders as the float does (finite r; -0 counts as +0, as it does under <): the word of a key whose
+// value may be below zero (descriptor_match.h, stereo_match.h)
+__device__ __forceinline__ unsigned ordered(float r) {
+  const unsigned u = __float_as_uint(r + 0.0f);
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
 // One wave of 64 lanes; wave-uniform keys and slot
 __device__ __forceinline__ void offer_key(bool adm, unsigned word, int row, unsigned long long* __restrict__ keys, long long slot) {
   if (__ballot(adm) != 0ull) {

@@ -636,3 +636,33 @@ def make_edge_image(height, width, segments, amplitude=60.0, softness=1.5, reach
         fade = 0.5 * (1.0 + np.tanh(0.5 * length - np.abs(along))) * np.exp(-0.5 * (across / reach) ** 2)
         val += a * np.tanh(across / s) * fade
     return np.clip(np.rint(val), 0, 255).astype(np.uint8)
+
+
+def make_stereo_line_pair(seed, height, width, num_segments, disparity=(4.0, 24.0), slant=0.05, gain=0.8, offset=15.0,
+                          min_length=12.0, max_length=80.0, margin=26.0):
+    """A rectified stereo pair of one make_line_image scene.  Every segment gets a disparity per end point - d0, d1 inside
+    `disparity` = (lo, hi), their difference at most `slant` pixels per pixel of the segment's length -: the right segment has the
+    same rows and x_right = x_left - d.  The texture of the right view is shifted by the mean disparity, its grey values are
+    gain * I + offset, and its segments are listed in a shuffled order.  Left segments keep `margin` + hi pixels from the border, so
+    the right ones keep `margin`.  Returns dict(left, right: uint8 [height, width]; left_segments, right_segments [n, 4] float32;
+    disparity [n, 2]: d0, d1 of left segment a; truth [n]: the row of right_segments that shows left segment a)."""
+    lo, hi = float(disparity[0]), float(disparity[1])
+    if not 0.0 <= lo <= hi:
+        raise ValueError("disparity = (lo, hi) with 0 <= lo <= hi")
+    n = int(num_segments)
+    scene = _line_scene(seed, height, width, n, min_length, max_length, margin + hi)
+    rng = np.random.default_rng(np.random.SeedSequence([18, int(seed)]))
+    seg = scene["segments"]
+    length = np.hypot(seg[:, 2] - seg[:, 0], seg[:, 3] - seg[:, 1])
+    base = rng.uniform(lo, hi, n)
+    half = 0.5 * rng.uniform(-slant, slant, n) * length
+    d = np.clip(np.stack([base - half, base + half], axis=1), lo, hi)
+    perm = rng.permutation(n)                                                          # row b of the right view shows segment perm[b]
+    mean = float(d.mean()) if n else 0.0
+    right = seg - np.stack([d[:, 0], np.zeros(n), d[:, 1], np.zeros(n)], axis=1)
+    # the right scene in scene coordinates: rendered with shift (-mean, 0), which moves its texture and puts its segments at `right`
+    scene2 = dict(scene, segments=right + np.array([mean, 0.0, mean, 0.0]))
+    truth = np.empty(n, dtype=np.int32)
+    truth[perm] = np.arange(n, dtype=np.int32)
+    return {"left": _render_scene(scene, height, width), "right": _render_scene(scene2, height, width, (-mean, 0.0), gain, offset),
+            "left_segments": seg.astype(np.float32), "right_segments": right[perm].astype(np.float32), "disparity": d, "truth": truth}
