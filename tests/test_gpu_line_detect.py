@@ -70,6 +70,57 @@ def test_truncation_keeps_the_first():
         assert got[key].tobytes() == full[key][:2].tobytes(), key
 
 
+ARRAYS = ("segments", "length", "thickness", "strength", "pixels", "label")
+
+
+@pytest.mark.parametrize("name", ["field_512x512", "field_513x512", "field_520x512", "many", "dense", "wide_2049x3", "tall_3x2049",
+                                  "stripes", "spiral"])
+def test_past_one_pass(name):
+    """Where k_scan (more than 256 chunks) and k_emit (more than 256 fitted slots) take a second pass and k_fit a second block; a chunk
+    with more fitted roots than threads and two roots among a thread's four pixels (stripes); neighbours one and two chunks away (wide,
+    tall); one component wound through 23 tiles (spiral).  What each input is, test_line_detect_cpu.py asserts."""
+    check(run(name), name)
+
+
+def test_truncation_about_the_pass_boundary():
+    """max_segments one below, at and one above k_emit's pass of 256, at the default (in the third pass) and beyond num_ok: each is the
+    beginning of the untruncated result, byte for byte, and counts the same OK components."""
+    full = run("dense_all")
+    check(full, "dense_all")
+    assert full["num_written"] == full["num_ok"] > 2 * T.BLOCK
+    for name in ("dense_%d" % (T.BLOCK - 1), "dense_%d" % T.BLOCK, "dense_%d" % (T.BLOCK + 1), "dense"):
+        got = run(name)
+        check(got, name)
+        n = got["num_written"]
+        assert n == T.gpu_inputs()[name][1]["max_segments"] < got["num_ok"] == full["num_ok"], name
+        for key in ARRAYS:
+            assert got[key].shape[0] == n and got[key].tobytes() == full[key][:n].tobytes(), (name, key)
+        assert got["labels"].tobytes() == full["labels"].tobytes() and got["status_counts"] == full["status_counts"], name
+
+
+def test_a_large_frame_behind_a_small_one():
+    """A frame of two k_scan passes as frame 1 of a call: its first pixel, chunk and slot are not 0, and the frame behind it has more
+    than 256 fitted slots of its own."""
+    names = ["frames_0", "field_513x512", "many"]
+    frames = [T.gpu_inputs()[n][0] for n in names]
+    assert all(T.gpu_inputs()[n][1].get("max_segments", T.MAX_SEGMENTS) == T.MAX_SEGMENTS for n in names)       # the handle's default
+    d = capi.LineDetector(max_frames=3, max_pixels=frames[1].size)
+    together = d.run(frames, labels=True)
+    for i, name in enumerate(names):
+        check(together[i], name)
+        alone = d.run([frames[i]], labels=True)[0]
+        for key in ARRAYS + ("labels",):
+            assert together[i][key].tobytes() == alone[key].tobytes(), (name, key)
+        assert together[i]["status_counts"] == alone["status_counts"], name
+        assert [together[i][k] for k in ("num_components", "num_ok", "num_written")] == [alone[k] for k in ("num_components", "num_ok", "num_written")]
+    again = d.run(frames, labels=True)                          # integer atomics: the order of the waves changes nothing
+    for i, name in enumerate(names):
+        for key in ARRAYS + ("labels",):
+            assert again[i][key].tobytes() == together[i][key].tobytes(), (name, key)
+        assert again[i]["status_counts"] == together[i]["status_counts"] and again[i]["num_ok"] == together[i]["num_ok"], name
+    d.close()
+
+
 def test_without_the_label_plane_and_with_null_outputs():
     image, opt = T.gpu_inputs()["field_63x65"]
     with_plane, without = capi.detect_lines(image, labels=True), capi.detect_lines(image)

@@ -23,7 +23,11 @@ import line_detect_reference as R  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID_ARGUMENT, NO_DEVICE = 1, 2
 T = capi.LSD_TILE
-SUMS = ("n", "sw", "swu", "swv", "swuu", "swuv", "swvv", "sgx", "sgy")
+# kChunk and kBlock of csrc/line_detect_layout.h (test_the_gpu_inputs_are_what_their_tests_say reads them there): a block of the per-pixel
+# kernels takes CHUNK pixels; k_scan, k_emit and k_fit take BLOCK chunks or slots a pass or a block
+CHUNK, BLOCK = 1024, 256
+MAX_SEGMENTS = capi.line_detect_options().max_segments    # the default, 512: what a run without the option truncates at
+SUMS =("n", "sw", "swu", "swv", "swuu", "swuv", "swvv", "sgx", "sgy")
 
 
 # ---- hand-computed cases
@@ -262,6 +266,28 @@ def serpentine_image():
     return np.clip(np.rint(gaussian_filter(30.0 + 170.0 * (dist < 3.5), 1.2)), 0, 255).astype(np.uint8)
 
 
+def spiral_image(size=160, r0=10.0, pitch=16.0, turns=3.75):
+    """size x size: a band of half-width 3.5 about the spiral r = r0 + pitch phi / (2 pi) around the centre, phi from 0 over `turns`
+    turns (the radius 10 -> 70), with round ends; smoothed as the serpentine is.  Its outline is one closed edge that runs out along one
+    flank and back along the other: about 1900 pixels long, through nearly every tile of the frame, several times through most."""
+    yy, xx = np.mgrid[0:size, 0:size].astype(np.float64)
+    dx, dy = xx - (size - 1) / 2.0, yy - (size - 1) / 2.0
+    r, theta = np.hypot(dx, dy), np.mod(np.arctan2(dy, dx), 2 * np.pi)
+    phi = theta + 2 * np.pi * np.rint((r - r0 - pitch * theta / (2 * np.pi)) / pitch)       # the turn nearest to the pixel, along its ray
+    dist = np.where((phi >= 0) & (phi <= 2 * np.pi * turns), np.abs(r - r0 - pitch * phi / (2 * np.pi)), np.inf)
+    for end in (0.0, 2 * np.pi * turns):
+        rho = r0 + pitch * end / (2 * np.pi)
+        dist = np.minimum(dist, np.hypot(dx - rho * np.cos(end), dy - rho * np.sin(end)))
+    return np.clip(np.rint(gaussian_filter(30.0 + 170.0 * (dist < 3.5), 1.2)), 0, 255).astype(np.uint8)
+
+
+def stripes_image(width=1030, height=40):
+    """Vertical stripes three pixels wide, 0 and 200: every edge is a component of two columns whose root lies in row 0, three pixels
+    from the next one's."""
+    yy, xx = np.mgrid[0:height, 0:width]
+    return (((xx // 3) % 2) * 200).astype(np.uint8)
+
+
 def ridge_image(broken):
     """96 x 96: a bright ridge one pixel wide on x = y + 1.  Its two flanks x = y and x = y + 2 are chains whose pixels touch only
     diagonally; the chain x = y passes the tile corners (31, 31) -> (32, 32) and (63, 63) -> (64, 64).  broken: from row 64 on the
@@ -300,6 +326,25 @@ def gpu_inputs():
     p = pair()
     inputs["pair_a"] = (p["image"], {})
     inputs["pair_b"] = (p["image2"], {})
+    # Beyond one pass of the in-kernel loops.  k_scan takes BLOCK chunks a pass: 512 x 512 is the last frame of one pass, 513 x 512 the
+    # first of two (its last chunk half full), 520 x 512 has full chunks in the second.  k_emit takes BLOCK fitted slots a pass and k_fit
+    # a block: `many` is a small frame with more than BLOCK of them, `dense` has four passes.  Where more components are OK than the
+    # default max_segments, the option is written out: the reference truncates only when it is given.
+    cut = dict(max_segments=MAX_SEGMENTS)
+    inputs["field_512x512"] = (field(75, 512, 512), cut)
+    inputs["field_513x512"] = (field(76, 512, 513), cut)
+    inputs["field_520x512"] = (field(70, 512, 520), cut)
+    inputs["many"] = (field(71, 200, 240), {})
+    # (the lengths below are not integers: an axis-parallel run of 3 or 4 pixels would sit on the threshold otherwise)
+    dense, dense_opt = field(73, 128, 128, sigma=1.2, contrast=500.0), dict(min_pixels=4, min_length=3.5)
+    inputs["dense"] = (dense, dict(dense_opt, **cut))
+    for s in (BLOCK - 1, BLOCK, BLOCK + 1):                     # truncation on both sides of k_emit's first pass boundary
+        inputs["dense_%d" % s] = (dense, dict(dense_opt, max_segments=s))
+    inputs["dense_all"] = (dense, dict(dense_opt, max_segments=4 * BLOCK))
+    inputs["wide_2049x3"] = (field(72, 3, 2049), dict(min_pixels=3, min_length=2.5))       # a row longer than two chunks
+    inputs["tall_3x2049"] = (field(74, 2049, 3), dict(min_pixels=3, min_length=2.5))
+    inputs["stripes"] = (stripes_image(), {})
+    inputs["spiral"] = (spiral_image(), {})
     return inputs
 
 
@@ -342,6 +387,51 @@ def test_the_gpu_inputs_are_what_their_tests_say():
     assert (total > 0).all(), total
     for name in ("field_8x8", "field_1x70", "field_70x1", "field_%dx%d" % (T, T)):
         assert reference(name)["num_components"] >= 1, name
+
+    # ---- beyond one pass of k_scan, k_emit and k_fit
+    layout = open(os.path.join(ROOT, "slslam_amd", "csrc", "line_detect_layout.h")).read()
+    assert "constexpr int kBlock = %d, kChunk = %d;" % (BLOCK, CHUNK) in layout and CHUNK == 4 * BLOCK and MAX_SEGMENTS == 2 * BLOCK
+    chunks = lambda name: -(-gpu_inputs()[name][0].size // CHUNK)  # noqa: E731
+    roots = lambda name: np.array([c["label"] for c in reference(name)["all"]])  # noqa: E731
+    fitted = lambda name: [c for c in reference(name)["all"] if c["status"] != R.SMALL]  # noqa: E731
+    second = BLOCK * CHUNK                                    # the first pixel of k_scan's second pass
+    assert chunks("field_512x512") == BLOCK                   # the last frame of one pass
+    assert chunks("field_513x512") == BLOCK + 1 and gpu_inputs()["field_513x512"][0].size % CHUNK == CHUNK // 2
+    assert (roots("field_513x512") >= second).any()           # num_components goes through the second pass
+    assert chunks("field_520x512") >= BLOCK + 4
+    assert max(c["label"] for c in fitted("field_520x512")) >= second          # a slot that depends on the carried base_f
+    for name in ("field_512x512", "field_513x512", "field_520x512"):
+        assert gpu_inputs()[name][1] == dict(max_segments=MAX_SEGMENTS) and len(fitted(name)) > BLOCK
+    assert len(fitted("many")) > BLOCK and gpu_inputs()["many"][0].size < second // 4 and gpu_inputs()["many"][1] == {}
+    assert reference("many")["num_ok"] < MAX_SEGMENTS
+    assert len(fitted("dense")) > 3 * BLOCK
+    # truncation by the default max_segments lies behind k_emit's second pass: the first two hold at most 2 BLOCK = 512 OK components
+    for name in ("dense", "field_513x512"):
+        assert reference(name)["num_ok"] > MAX_SEGMENTS == reference(name)["num_written"], name
+    passes = {i // BLOCK for i, c in enumerate(fitted("dense")) if c["status"] == R.OK}
+    assert passes == {0, 1, 2, 3}, passes                     # OK components among the fitted of each of four passes
+    full = reference("dense_all")
+    assert full["num_written"] == full["num_ok"] == reference("dense")["num_ok"] > BLOCK + 1
+    for s in (BLOCK - 1, BLOCK, BLOCK + 1):
+        r = reference("dense_%d" % s)
+        assert gpu_inputs()["dense_%d" % s][1]["max_segments"] == s == r["num_written"] and r["num_ok"] == full["num_ok"]
+        assert np.array_equal(r["label"], full["label"][:s]) and np.array_equal(r["segments"], full["segments"][:s])
+    for name, (w, h) in (("wide_2049x3", (2 * CHUNK + 1, 3)), ("tall_3x2049", (3, 2 * CHUNK + 1))):
+        image = gpu_inputs()[name][0]
+        assert image.shape == (h, w) and len(fitted(name)) > BLOCK and reference(name)["num_ok"] >= 1, name
+    # stripes: every root in row 0, more of them in chunk 0 than its block has threads, two among one thread's four pixels
+    s, lab = reference("stripes"), roots("stripes")
+    width = gpu_inputs()["stripes"][0].shape[1]
+    assert width > CHUNK and (lab < width).all() and (lab >= CHUNK).any()
+    assert (lab < CHUNK).sum() > BLOCK
+    assert (np.bincount(lab // 4) >= 2).any()
+    assert s["num_ok"] == s["num_components"] == len(lab) and s["status_counts"] == [len(lab), 0, 0, 0, 0]
+    # the spiral: one component through many tiles, many times longer than the side
+    sp = reference("spiral")
+    big = max(sp["all"], key=lambda c: c["sums"]["n"])
+    ys, xs = np.nonzero(sp["labels"] == big["label"])
+    assert len(set(zip((ys // T).tolist(), (xs // T).tolist()))) >= 16
+    assert big["sums"]["n"] >= 3000 and big["status"] == R.THICK and sp["labels"].shape == (160, 160)
 
 
 def test_no_component_sits_on_a_threshold():

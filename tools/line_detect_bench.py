@@ -5,8 +5,9 @@
 Shapes: a stereo pair (2 frames per call) and 64 frames per call of width x height from synth.make_line_image with `segments` drawn
 segments each, at the default options.  Warm (three untimed calls first), median and spread of `repeats` calls.  Per shape: the wall
 time of the call - synchronous: packing the images into the page-locked block, upload, eleven launches, download, scatter - and the
-launches alone between two events on the handle's stream (slslam_line_detector_timing), also per launch.  A measurement, not a gate:
-needs a GPU and fails without one."""
+launches alone between two events on the handle's stream (slslam_line_detector_timing), also per launch.  Before anything is timed the
+first stereo pair's results are compared with the reference's (verify); a difference ends the tool with a non-zero status and no timing
+line.  A measurement, not a gate: needs a GPU and fails without one."""
 import argparse
 import os
 import statistics
@@ -17,6 +18,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 LAUNCHES = 11
+
+
+def verify(capi, R, views, max_pixels):
+    """The device against the reference on `views`, untimed: the integer results equal, the fp64 ones within R.DEVICE_TOLERANCE (the float
+    segments within that and half a float's spacing).  Ends the tool on the first difference."""
+    import numpy as np
+    d = capi.LineDetector(max_frames=len(views), max_pixels=max_pixels)          # (a handle of its own: the timed one keeps its buffers)
+    got = d.run(views, labels=True)
+    d.close()
+    for f, (g, view) in enumerate(zip(got, views)):
+        r = R.detect(view, max_segments=d.opt.max_segments)
+        bad = [k for k in ("num_components", "num_ok", "num_written") if g[k] != r[k]]
+        bad += [k for k in ("labels", "pixels", "label") if not np.array_equal(g[k], r[k])]
+        if [g["status_counts"][s] for s in R.STATUS] != r["status_counts"]:
+            bad.append("status_counts")
+        for k in ("segments", "length", "thickness", "strength"):
+            slack = 0.5 * np.spacing(np.abs(r[k]).astype(np.float32)).astype(np.float64) if k == "segments" else 0.0
+            if g[k].shape != r[k].shape or not (np.abs(g[k].astype(np.float64) - r[k]) <= R.DEVICE_TOLERANCE + slack).all():
+                bad.append(k)
+        if bad:
+            raise SystemExit("line_detect_bench: frame %d differs from the reference in %s: nothing is timed" % (f, ", ".join(bad)))
 
 
 def main():
@@ -37,6 +59,7 @@ def main():
     W, H, S = a.width, a.height, a.segments
     views = [synth.make_line_image(9800 + i, H, W, S)["image"] for i in range(4)]
     lines = ["line_detect_bench: %d x %d, %d drawn segments per frame, default options, max_segments 512" % (W, H, S)]
+    verify(capi, R, views[:2], W * H)                           # what is timed below is what the reference computes
 
     d = capi.LineDetector(max_frames=64, max_pixels=W * H)
     d.set_timing(True)
