@@ -1478,6 +1478,103 @@ int  slslam_stereo_matcher_timing(slslam_stereo_matcher* matcher, int enable, do
 /* One stereo frame, one call (its own buffers, made and freed); n, m <= 512. */
 int  slslam_match_stereo(int D, const slslam_stereo_match_options* options, const slslam_stereo_frame* frame, slslam_stereo_result* out);
 
+/* ------------------------------------------------------------------ line tracking: which segment of this frame is which feature of the last
+ * Gives every segment of every frame a persistent feature id - the `id` in front of the eight numbers of a line of the reference's
+ * frame files (SLAM::grab_new_frame, src/slam.cpp:62-108), by which curr_obs, lms.find, the id merge of pose_estimation
+ * (slslam_pose_estimation_inputs), the window packer and match_lookup are keyed (csrc/line_track.h).
+ * Replaces: nothing the reference ships; its ids come from the files of an external tracker.  So there is no code to restate: this
+ * block is the contract; tests/line_track_reference.py restates it in numpy.
+ *   inputs     a run is T >= 1 frames in time order, each n_t <= 512 segments [n 4] float (x0, y0, x1, y1) in pixels of the left image
+ *              with their descriptors [n D] float, D a multiple of 8, 8 <= D <= 128, and optionally predict[6] = a11 a12 tx a21 a22 ty
+ *              (finite): an affine map from the previous frame's pixel coordinates to this frame's; NULL: the identity.
+ *   state      the handle keeps the carried frame - segments, descriptors, validity, ids and ages of the last frame of the run before -
+ *              and next_id.  After create: no carried segments, next_id = 0; _reset empties the former and sets the latter.
+ *   problem t  rows: the segments of frame t; columns: those of frame t - 1, for frame 0 the carried frame.
+ *   segment    in double from the float end points, every operation rounded on its own (no contraction), here and below; no division:
+ *              dx = x1 - x0, dy = y1 - y0, len2 = dx dx + dy dy, m = (0.5 (x0 + x1), 0.5 (y0 + y1)).  A segment is valid when its four
+ *              floats and its D descriptor floats are finite; a carried segment that got no id counts as not valid.  It is short when
+ *              len2 < min_length^2, of the segment as it lies in its own frame.
+ *   warp       the end points of a column b go through predict first: x' = (a11 x + a12 y) + tx, y' = (a21 x + a22 y) + ty; all of
+ *              b's quantities below are of the warped segment.
+ *   admissible a pair (row a, column b) when both are valid, neither is short and all of these hold, in this order:
+ *              direction  dot = dx_a dx_b + dy_a dy_b, cross = dx_a dy_b - dy_a dx_b: cross cross <= max_tan2 * (dot dot) and dot != 0;
+ *              shift      e = m_a - m_b: e.x e.x + e.y e.y <= max_shift^2;
+ *              offset     e_ab = (m_a.x - x0_b) dy_b - (m_a.y - y0_b) dx_b: e_ab e_ab <= max_offset^2 * len2_b; and the same with a and
+ *                         b exchanged (each midpoint lies near the other's line);
+ *              overlap    s0 = (x0_b - x0_a) dx_a + (y0_b - y0_a) dy_a, s1 likewise of b's other end; lo = min(s0, s1),
+ *                         hi = max(s0, s1), o = min(hi, len2_a) - max(lo, 0): o >= min_overlap * min(len2_a, hi - lo) and o > 0;
+ *              distance   r = 1.0f; for i in 0 .. D-1: r -= row[i] * col[i] - the float chain of slslam_match_descriptors, in that
+ *                         order: r is finite and (double)r < max_distance.
+ *   per a / b  best, best_distance, second_distance, num_admissible [n_t], best_row [the columns] and match [n_t] - mutual, then the
+ *              ratio test - exactly as the stereo block above defines best .. match (best_row as its best_left): the lowest index on
+ *              ties, ratio <= 1 switches the test off.  match[a] is an index into the frame before.
+ *   segment_status[a]  INVALID: a is not valid; else SHORT; else CONTINUED: match[a] >= 0; else NEW.
+ *   id, age    INVALID, SHORT: -1, 0.  CONTINUED: the id of prev[match[a]], its age + 1.  NEW: age 1 and
+ *              id = next_id + the NEW segments of frames 0 .. t-1 of this run + the NEW segments a' < a of frame t:
+ *              fresh ids ascend in (frame, row) order.
+ *   after      next_id grows by the run's NEW segments; the run's last frame becomes the carried frame (a frame with n = 0 ends every
+ *              track: a track does not survive a frame its segment is missing from).
+ * Frame status: EMPTY when n = 0 or there are no columns, else OK.  The outputs are a function of the frames and the handle's state
+ * alone: T frames in one run give the same bytes as one frame per run, and as any other cut.  Minima, counts and per-row arithmetic
+ * only. */
+enum { SLSLAM_TRACK_MAX_D = 128, SLSLAM_TRACK_MAX_SEGMENTS = 512 };
+enum { SLSLAM_TRACK_OK = 0, SLSLAM_TRACK_EMPTY = 1 };
+enum { SLSLAM_TRACK_CONTINUED = 0, SLSLAM_TRACK_NEW = 1, SLSLAM_TRACK_SHORT = 2, SLSLAM_TRACK_INVALID = 3 };
+typedef struct slslam_line_track_options {
+  double max_tan2;                       /* squared tangent of the largest direction difference, finite, >= 0                 */
+  double max_shift;                      /* px between the midpoints, finite, >= 0                                            */
+  double max_offset;                     /* px of a midpoint from the other segment's line, finite, >= 0                      */
+  double min_overlap;                    /* in [0, 1]: the share of the shorter extent along a the common part must cover     */
+  double min_length;                     /* px, finite, >= 0                                                                  */
+  double ratio, max_distance;            /* as slslam_descriptor_matcher_run takes them; neither may be NaN                   */
+} slslam_line_track_options;
+typedef struct slslam_line_track_frame {
+  int num_segments;                      /* n >= 0, at most the tracker's max_segments */
+  const float* segments;                 /* [n 4] */
+  const float* descriptors;              /* [n D] row-major */
+  const double* predict;                 /* [6] or NULL */
+} slslam_line_track_frame;
+typedef struct slslam_line_track_result {
+  int     status;                        /* SLSLAM_TRACK_OK / _EMPTY                                                          */
+  int     num_continued, num_new;
+  int*    id;                            /* caller-owned arrays, any of them may be NULL.  [n]                                */
+  int*    age;                           /* [n] */
+  int*    segment_status;                /* [n] SLSLAM_TRACK_CONTINUED ... _INVALID */
+  int*    match;                         /* [n] */
+  int*    best;                          /* [n] */
+  float*  best_distance;                 /* [n] */
+  float*  second_distance;               /* [n] */
+  int*    num_admissible;                /* [n] */
+  int*    best_row;                      /* [the segments of the frame before; for frame 0 the carried segments] */
+} slslam_line_track_result;
+typedef struct slslam_line_tracker slslam_line_tracker;
+
+/* max_tan2 0.03, max_shift 40 px, max_offset 12 px, min_overlap 0.5, min_length 8 px, ratio 1.5, max_distance 0.25 */
+void slslam_line_track_default_options(slslam_line_track_options* opt);
+/* device < 0 selects the current HIP device.  D as above, fixed for the handle.  max_frames >= 1 frames of max_segments in 1 .. 512
+ * segments: what the one device block and the one page-locked block are made for at the first run, with the carried frame's block.
+ * A run of more frames makes larger ones and counts one allocation; a run that fits allocates nothing.  Touches no device. */
+int  slslam_line_tracker_create(int device, int D, int max_frames, int max_segments, slslam_line_tracker** out);
+void slslam_line_tracker_destroy(slslam_line_tracker* tracker);
+/* frames[T], out[T].  Every argument is validated before an output is written, the device is asked or the state changes - missing or
+ * invalid options, a negative count, a count beyond max_segments, a missing array of a non-zero count, a predict that is not finite,
+ * next_id + the run's segments beyond INT_MAX: SLSLAM_ERR_INVALID_ARGUMENT, outputs and state untouched.  T = 0 changes nothing
+ * and is not counted as a run.
+ * Synchronous; host pointers; one upload, seven launches and one download per run whatever T; the carried frame stays on the device. */
+int  slslam_line_tracker_run(slslam_line_tracker* tracker, const slslam_line_track_options* options, int num_frames,
+                             const slslam_line_track_frame* frames, slslam_line_track_result* out);
+/* Empties the carried frame and sets next_id (>= 0). */
+int  slslam_line_tracker_reset(slslam_line_tracker* tracker, int next_id);
+/* Either pointer may be NULL. */
+int  slslam_line_tracker_state(const slslam_line_tracker* tracker, int* next_id, int* carried_segments);
+/* Since create: runs, and how often the blocks were made or made larger.  Either pointer may be NULL. */
+int  slslam_line_tracker_stats(const slslam_line_tracker* tracker, long long* calls, long long* allocations);
+/* For benches: as slslam_stereo_matcher_timing; the events bracket the launches of a run. */
+int  slslam_line_tracker_timing(slslam_line_tracker* tracker, int enable, double* kernel_ms);
+/* A sequence without a handle: no carried frame, next_id = 0 (its own buffers, made and freed). */
+int  slslam_track_lines(int D, const slslam_line_track_options* options, int num_frames, const slslam_line_track_frame* frames,
+                        slslam_line_track_result* out);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */

@@ -178,7 +178,25 @@ class StereoResult(C.Structure):
                 ("observations", C.POINTER(C.c_double)), ("disparity", C.POINTER(C.c_double))]
 
 
+class LineTrackOptions(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("max_tan2", "max_shift", "max_offset", "min_overlap", "min_length", "ratio", "max_distance")]
+
+
+class LineTrackFrame(C.Structure):
+    _fields_ = [("num_segments", C.c_int), ("segments", C.POINTER(C.c_float)), ("descriptors", C.POINTER(C.c_float)),
+                ("predict", C.POINTER(C.c_double))]
+
+
+class LineTrackResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("num_continued", C.c_int), ("num_new", C.c_int), ("id", C.POINTER(C.c_int)),
+                ("age", C.POINTER(C.c_int)), ("segment_status", C.POINTER(C.c_int)), ("match", C.POINTER(C.c_int)),
+                ("best", C.POINTER(C.c_int)), ("best_distance", C.POINTER(C.c_float)), ("second_distance", C.POINTER(C.c_float)),
+                ("num_admissible", C.POINTER(C.c_int)), ("best_row", C.POINTER(C.c_int))]
+
+
 STEREO_STATUS = {0: "OK", 1: "EMPTY"}
+TRACK_STATUS = {0: "OK", 1: "EMPTY"}
+TRACK_SEGMENT_STATUS = {0: "CONTINUED", 1: "NEW", 2: "SHORT", 3: "INVALID"}
 STEREO_SEGMENT_STATUS = {0: "MATCHED", 1: "UNMATCHED", 2: "FLAT", 3: "INVALID"}
 MSLD_STATUS = {0: "OK", 1: "FLAT", 2: "TOO_SHORT", 3: "OUTSIDE", 4: "INVALID"}
 LSD_STATUS = {0: "OK", 1: "SMALL", 2: "ISOTROPIC", 3: "SHORT", 4: "THICK"}
@@ -243,6 +261,9 @@ EXPORTS = [
     "slslam_line_detector_stats", "slslam_line_detector_timing", "slslam_detect_lines",
     "slslam_stereo_match_default_options", "slslam_stereo_matcher_create", "slslam_stereo_matcher_destroy", "slslam_stereo_matcher_run",
     "slslam_stereo_matcher_stats", "slslam_stereo_matcher_timing", "slslam_match_stereo",
+    "slslam_line_track_default_options", "slslam_line_tracker_create", "slslam_line_tracker_destroy", "slslam_line_tracker_run",
+    "slslam_line_tracker_reset", "slslam_line_tracker_state", "slslam_line_tracker_stats", "slslam_line_tracker_timing",
+    "slslam_track_lines",
     "slslam_voctree_train", "slslam_voctree_save", "slslam_voctree_centres", "slslam_voctree_key", "slslam_debug_voctree_step", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -454,6 +475,18 @@ def lib():
         L.slslam_stereo_matcher_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
         L.slslam_stereo_matcher_timing.argtypes = [vp, C.c_int, dp]
         L.slslam_match_stereo.argtypes = [C.c_int, C.POINTER(StereoMatchOptions), C.POINTER(StereoFrame), C.POINTER(StereoResult)]
+    if hasattr(L, "slslam_track_lines"):        # (likewise: a library built before the line tracker existed)
+        L.slslam_line_track_default_options.argtypes = [C.POINTER(LineTrackOptions)]
+        L.slslam_line_track_default_options.restype = None
+        L.slslam_line_tracker_create.argtypes = [C.c_int] * 4 + [C.POINTER(vp)]
+        L.slslam_line_tracker_destroy.argtypes = [vp]
+        L.slslam_line_tracker_destroy.restype = None
+        L.slslam_line_tracker_run.argtypes = [vp, C.POINTER(LineTrackOptions), C.c_int, C.POINTER(LineTrackFrame), C.POINTER(LineTrackResult)]
+        L.slslam_line_tracker_reset.argtypes = [vp, C.c_int]
+        L.slslam_line_tracker_state.argtypes = [vp, ip, ip]
+        L.slslam_line_tracker_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+        L.slslam_line_tracker_timing.argtypes = [vp, C.c_int, dp]
+        L.slslam_track_lines.argtypes = [C.c_int, C.POINTER(LineTrackOptions), C.c_int, C.POINTER(LineTrackFrame), C.POINTER(LineTrackResult)]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -2298,4 +2331,126 @@ def detect_describe_and_pair(detector, descriptor, matcher, stereo_images, **opt
         obs, idx = stereo_observations(r)
         out.append(dict(left=found[2 * i], right=found[2 * i + 1], left_rows=rows[2 * i], right_rows=rows[2 * i + 1], stereo=r,
                         observations=obs, left_index=rows[2 * i][idx], right_index=rows[2 * i + 1][r["match"][idx]]))
+    return out
+
+
+# ----------------------------------------------------------------------------- line tracking (slslam_line_tracker_*)
+def line_track_options(**options):
+    """slslam_line_track_default_options with the given fields replaced: max_tan2, max_shift, max_offset, min_overlap, min_length,
+    ratio, max_distance."""
+    o = LineTrackOptions()
+    lib().slslam_line_track_default_options(C.byref(o))
+    for k, v in options.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown line track option %r" % k)
+        setattr(o, k, float(v))
+    return o
+
+
+_TRACK_KEYS = ("match", "best", "best_distance", "second_distance", "num_admissible", "best_row")
+
+
+def _track_frame(frame, m, D=None):
+    """(LineTrackFrame, LineTrackResult, the arrays both point to, D); m: the segments of the frame before."""
+    if isinstance(frame, dict):
+        seg, desc, predict = frame["segments"], frame["descriptors"], frame.get("predict")
+    else:
+        seg, desc, predict = (tuple(frame) + (None,))[:3]
+    seg, desc = _stereo_side((seg, desc))
+    if len(seg) and D is not None and desc.shape[1] != int(D):
+        raise ValueError("the descriptors of a frame must have the tracker's D floats")
+    n = len(seg)
+    r, b = _mutual_buffers(LineTrackResult, _TRACK_KEYS, n, m)
+    for k in ("id", "age", "segment_status"):
+        b[k] = np.full(max(n, 1), -2, dtype=np.int32)
+        setattr(r, k, _ip(b[k]))
+    r.num_continued = r.num_new = -1
+    pre = None if predict is None else np.ascontiguousarray(predict, dtype=np.float64).reshape(6)
+    fr = LineTrackFrame(n, _fp(seg), _fp(desc), _dp(pre) if pre is not None else None)
+    return fr, r, (seg, desc, pre, b, m), (desc.shape[1] if len(seg) else (int(D) if D is not None else 8))
+
+
+def _track_dict(r, keep):
+    seg, _, _, b, m = keep
+    n = len(seg)
+    out = dict(status=TRACK_STATUS[r.status], num_continued=r.num_continued, num_new=r.num_new)
+    out.update({k: b[k][:m if k == "best_row" else n] for k in _TRACK_KEYS + ("id", "age")})
+    out["segment_status"] = [TRACK_SEGMENT_STATUS.get(s, "?") for s in b["segment_status"][:n].tolist()]
+    return out
+
+
+def _track_frames(frames, carried, D):
+    n = len(frames)
+    frs, outs, keep, m = (LineTrackFrame * max(n, 1))(), (LineTrackResult * max(n, 1))(), [], carried
+    for i, frame in enumerate(frames):
+        frs[i], outs[i], k, D = _track_frame(frame, m, D)
+        keep.append(k)
+        m = frs[i].num_segments
+    return frs, outs, keep, D
+
+
+def track_lines(frames, **options):
+    """slslam_track_lines: a sequence of frames from an empty tracker (no carried frame, next_id 0).  A frame is (segments [n, 4]
+    float32, descriptors [n, D] float32[, predict [6] float64 or None]) or a dict with those keys.  Returns per frame dict(status,
+    num_continued, num_new, id, age, match, best, num_admissible [n], best_distance, second_distance [n] float32, best_row [the
+    segments of the frame before], segment_status [n] of TRACK_SEGMENT_STATUS's names)."""
+    opt = line_track_options(**options)
+    frs, outs, keep, D = _track_frames(frames, 0, None)
+    _check(lib().slslam_track_lines(int(D if D is not None else 8), C.byref(opt), len(frames), frs, outs), "slslam_track_lines")
+    return [_track_dict(outs[i], keep[i]) for i in range(len(frames))]
+
+
+class LineTracker(_CountedHandle):
+    """slslam_line_tracker: persistent feature ids for the segments of many frames per call; the last frame and the next id are kept
+    on the device and in the handle between calls.  A frame is what track_lines takes.  The options given here are the defaults
+    of run."""
+    _DESTROY, _STATS = "slslam_line_tracker_destroy", "slslam_line_tracker_stats"
+
+    def __init__(self, D, max_frames=2, max_segments=512, device=-1, **options):
+        self.D = int(D)
+        self.options = dict(options)
+        line_track_options(**self.options)                          # (an unknown name fails here)
+        self._h = C.c_void_p()
+        _check(lib().slslam_line_tracker_create(int(device), self.D, int(max_frames), int(max_segments), C.byref(self._h)),
+               "slslam_line_tracker_create")
+
+    def run(self, frames, **options):
+        """Returns one dict per frame, as track_lines returns it."""
+        opt = line_track_options(**dict(self.options, **options))
+        frs, outs, keep, _ = _track_frames(frames, self.state()["carried_segments"], self.D)
+        _check(lib().slslam_line_tracker_run(self._h, C.byref(opt), len(frames), frs, outs), "slslam_line_tracker_run")
+        return [_track_dict(outs[i], keep[i]) for i in range(len(frames))]
+
+    def reset(self, next_id=0):
+        _check(lib().slslam_line_tracker_reset(self._h, int(next_id)), "slslam_line_tracker_reset")
+
+    def state(self):
+        a, b = C.c_int(0), C.c_int(0)
+        _check(lib().slslam_line_tracker_state(self._h, C.byref(a), C.byref(b)), "slslam_line_tracker_state")
+        return {"next_id": a.value, "carried_segments": b.value}
+
+    def set_timing(self, enable):
+        _check(lib().slslam_line_tracker_timing(self._h, int(bool(enable)), None), "slslam_line_tracker_timing")
+
+    def kernel_ms(self):
+        """The last run's launches by events (after set_timing(True))."""
+        ms = C.c_double(0.0)
+        _check(lib().slslam_line_tracker_timing(self._h, -1, C.byref(ms)), "slslam_line_tracker_timing")              # (-1: the switch stays)
+        return ms.value
+
+
+def detect_describe_pair_and_track(detector, descriptor, matcher, tracker, stereo_images, predicts=None, **stereo_options):
+    """detect_describe_and_pair, then the tracker over the left segments that were paired on (tracker: a LineTracker; predicts: per
+    frame None or the six doubles of its predict) - four calls whatever the number of frames.  Returns per frame the dict of
+    detect_describe_and_pair with `track` (the tracker's result over left_rows), and `ids` [k]: the feature id of every row of
+    `observations` - with fx = fy = 1, cx = cy = 0 the [k] ids and [k, 8] pixels of one of the reference's frame files."""
+    out = detect_describe_and_pair(detector, descriptor, matcher, stereo_images, **stereo_options)
+    frames = []
+    for i, o in enumerate(out):
+        keep = o["left_rows"]
+        frames.append((o["left"]["segments"][keep], o["left"]["descriptors"][keep].reshape(len(keep), descriptor.D),
+                       None if predicts is None else predicts[i]))
+    for o, t in zip(out, tracker.run(frames)):
+        o["track"] = t
+        o["ids"] = t["id"][stereo_observations(o["stereo"])[1]]
     return out

@@ -98,6 +98,44 @@ int slslam_read_frame_file(const char* path, const slslam_intrinsics* K, const i
   return slslam_parse_frame_text(text.data(), text.size(), K, alias_from, alias_to, n_alias, out);
 }
 
+long slslam_format_frame_text(int n, const int* ids, const double* observations_px, char* buf, size_t cap) {
+  if (n < 0 || (n > 0 && (!ids || !observations_px)) || (cap > 0 && !buf)) return -1;
+  size_t at = 0;
+  if (cap > 0) buf[0] = 0;
+  for (int i = 0; i < n; ++i) {
+    char line[256];
+    int k = std::snprintf(line, sizeof line, "%d", ids[i]);
+    for (int q = 0; q < 8; ++q) {
+      // nine digits name a float; the reader takes the text as a double (atof), so a value those digits do not hit gets seventeen
+      const double v = observations_px[8 * i + q];
+      char num[40];
+      std::snprintf(num, sizeof num, "%.9g", v);
+      if (!(std::strtod(num, nullptr) == v)) std::snprintf(num, sizeof num, "%.17g", v);
+      k += std::snprintf(line + k, sizeof line - (size_t)k, " %s", num);
+    }
+    line[k++] = '\n';
+    if (at + 1 < cap) {
+      const size_t room = cap - 1 - at, take = (size_t)k < room ? (size_t)k : room;
+      std::memcpy(buf + at, line, take);
+      buf[at + take] = 0;
+    }
+    at += (size_t)k;
+  }
+  return (long)at;
+}
+
+int slslam_write_frame_file(const char* path, int n, const int* ids, const double* observations_px) {
+  if (!path) return 2;
+  const long len = slslam_format_frame_text(n, ids, observations_px, nullptr, 0);
+  if (len < 0) return 2;
+  std::string text((size_t)len + 1, '\0');
+  slslam_format_frame_text(n, ids, observations_px, &text[0], text.size());
+  std::FILE* f = std::fopen(path, "wb");
+  if (!f) return 1;
+  const bool ok = std::fwrite(text.data(), 1, (size_t)len, f) == (size_t)len;
+  return (std::fclose(f) == 0 && ok) ? 0 : 1;
+}
+
 int slslam_frame_path(const char* obs_dir, int frame_id, char* buf, size_t cap) {
   const int n = std::snprintf(buf, cap, "%s/%04d.txt", obs_dir, frame_id);
   return n > 0 && (size_t)n < cap ? 0 : 2;

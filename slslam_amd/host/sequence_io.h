@@ -1,6 +1,7 @@
 // slslam_amd/host/sequence_io.h — the data formats on either side of the hot path,
 // restated on plain arrays for callers that replay sequences:
 //   tracked-line frame reader   SLAM::grab_new_frame + SLAM::insert_curr_obs   reference src/slam.cpp:62-135
+//   tracked-line frame writer   the file that reader takes, from the line tracker's ids and the stereo matcher's pixels
 //   metric embedding            SLAM::metric_embedding                          reference src/slam.cpp:1317-1366
 //   trajectory writer           SLAM::save_trajectory                           reference src/slam.cpp:1470-1496
 //   landmark writer             SLAM::save_landmark                             reference src/slam.cpp:1431-1468
@@ -38,6 +39,17 @@ int  slslam_parse_frame_text(const char* text, size_t len, const slslam_intrinsi
 /* obs_dir/%04d.txt (src/slam.cpp:73) */
 int  slslam_frame_path(const char* obs_dir, int frame_id, char* buf, size_t cap);
 void slslam_free_frame(slslam_frame* f);
+
+/* The writer of such a file: line i = "ids[i] x0 y0 x1 y1 x2 y2 x3 y3\n", blanks between.  observations_px [8 n]: PIXELS - the
+ * stereo matcher's observations made with fx = fy = 1, cx = cy = 0 (slslam_stereo_matcher_run), which are float values; ids: the line
+ * tracker's (slslam_line_tracker_run) of the same rows.  A value is written as %.9g where the reader's atof gives it back exactly,
+ * else as %.17g: nine digits name a float among floats, but the reader takes the text as a double, and only the exact double makes
+ * its normalisation under K the matcher's under K, bit for bit.  A line is at most 11 + 8 * 25 = 211 characters, below the reader's
+ * 255.  slslam_format_frame_text writes up to cap - 1 characters and a 0 into buf (may be NULL with cap 0) and returns the length the
+ * whole text has, as snprintf does, or -1 for a missing array; slslam_write_frame_file returns 0, 1 when the file cannot be written,
+ * 2 for a missing argument. */
+long slslam_format_frame_text(int n, const int* ids, const double* observations_px, char* buf, size_t cap);
+int  slslam_write_frame_file(const char* path, int n, const int* ids, const double* observations_px);
 
 /* Pose-graph edge as edges[(from, to)].T: the pose of keyframe `to` relative to keyframe `from`. */
 typedef struct slslam_me_edge { int from, to; slslam_pose T; } slslam_me_edge;

@@ -666,3 +666,39 @@ def make_stereo_line_pair(seed, height, width, num_segments, disparity=(4.0, 24.
     truth[perm] = np.arange(n, dtype=np.int32)
     return {"left": _render_scene(scene, height, width), "right": _render_scene(scene2, height, width, (-mean, 0.0), gain, offset),
             "left_segments": seg.astype(np.float32), "right_segments": right[perm].astype(np.float32), "disparity": d, "truth": truth}
+
+
+def make_line_sequence(seed, height, width, num_segments, num_frames, shifts, drop=0.15, disparity=None, gain=0.8, offset=15.0,
+                       min_length=12.0, max_length=80.0, margin=26.0):
+    """A sequence of views of one make_line_image scene for a tracker.  Frame t shows the scene moved by the sub-pixel shifts[t] =
+    (x, y) - shifts: [num_frames, 2] -; every segment is absent from (not drawn in) a frame with probability `drop`, never from
+    frame 0; the rows of every frame are listed in a shuffled order.  disparity = d > 0 adds a rectified right view per frame: the
+    same frame's scene moved a further d pixels to the left, its grey values gain * I + offset, its rows shuffled on their own.
+    Segments keep `margin` pixels from the border in every view.  Returns dict(images: uint8 [height, width] per frame; segments:
+    [n_t, 4] float32 per frame; labels: [n_t] int32 per frame, the scene's segment - the true track - of every row; with a disparity
+    also right_images, right_segments, right_labels)."""
+    shifts = np.asarray(shifts, dtype=np.float64).reshape(int(num_frames), 2)
+    d = 0.0 if disparity is None else float(disparity)
+    if d < 0.0:
+        raise ValueError("disparity >= 0")
+    reach = float(np.abs(shifts).max()) if len(shifts) else 0.0
+    scene = _line_scene(seed, height, width, num_segments, min_length, max_length, margin + reach + d)
+    rng = np.random.default_rng(np.random.SeedSequence([19, int(seed)]))
+    n = int(num_segments)
+    out = {"images": [], "segments": [], "labels": []}
+    if disparity is not None:
+        out.update(right_images=[], right_segments=[], right_labels=[])
+    for t in range(int(num_frames)):
+        here = np.nonzero((rng.uniform(size=n) >= drop) | (t == 0))[0]
+        part = dict(scene, **{k: scene[k][here] for k in ("segments", "amplitude", "softness", "reach")})
+        sx, sy = shifts[t]
+        rows = rng.permutation(len(here))
+        out["images"].append(_render_scene(part, height, width, (sx, sy)))
+        out["segments"].append((part["segments"][rows] + np.array([sx, sy, sx, sy])).astype(np.float32))
+        out["labels"].append(here[rows].astype(np.int32))
+        if disparity is not None:
+            rows = rng.permutation(len(here))
+            out["right_images"].append(_render_scene(part, height, width, (sx - d, sy), gain, offset))
+            out["right_segments"].append((part["segments"][rows] + np.array([sx - d, sy, sx - d, sy])).astype(np.float32))
+            out["right_labels"].append(here[rows].astype(np.int32))
+    return out
