@@ -1,10 +1,13 @@
 """The place recogniser on the device (include/slslam_hip.h: slslam_voctree_*, slslam_place_db_*) against the numpy reference
 (tests/place_reference.py): words, status, touched and top_k exactly, scores bit for bit, likelihoods within 1e-6 relative (the double
 reductions of mean and sigma are reordered on the device, ~1e-13, and the result is rounded once to float, 2^-24: 1e-6 is about 16 float
-ulps) wherever the reference has no score within 1e-9 max(1, |mean|) of mean + 2 sigma."""
+ulps) wherever the reference has no score within 1e-9 max(1, |mean|) of mean + 2 sigma.  The largest likelihood difference seen is
+printed.  The inputs past one pass of the kernels' loops and their references are those of tests/test_place_cpu.py: made once, shared,
+never written to."""
 import ctypes as C
 import os
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -13,11 +16,13 @@ from slslam_amd import synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import place_reference as R  # noqa: E402
+import test_place_cpu as T  # noqa: E402
 from test_place_cpu import SEQ, seq_inputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 63, 64, 65, 512]
+WORST = {"likelihood": 0.0}             # the largest relative likelihood difference check() has seen
 
 
 def bits(a):
@@ -34,6 +39,7 @@ def check(got, ref, top_k=0):
         assert np.array_equal(got["top_id"], ref["top_id"]) and bits(got["top_score"]) == bits(ref["top_score"])
     if ref["status"] == R.OK and ref["mean"] != 0.0:
         assert ref["margin"] > 1e-9
+    WORST["likelihood"] = max(WORST["likelihood"], float(np.max(np.abs(got["likelihood"] - ref["likelihood"]) / np.abs(ref["likelihood"]))))
     assert np.all(np.abs(got["likelihood"] - ref["likelihood"]) <= 1e-6 * np.abs(ref["likelihood"])), (got["likelihood"], ref["likelihood"])
 
 
@@ -45,8 +51,8 @@ def same_bytes(a, b):
 class Pair:
     """a device database and the reference's, fed alike"""
 
-    def __init__(self, hip, K, L, D, seed, recent, navg, max_docs=160, max_words=512, max_frames=8):
-        nodes = synth.make_voctree(seed, K, L, D)
+    def __init__(self, hip, K, L, D, seed, recent, navg, max_docs=160, max_words=512, max_frames=8, nodes=None):
+        nodes = synth.make_voctree(seed, K, L, D) if nodes is None else nodes
         self.ref_tree = R.Tree(K, L, D, nodes)
         self.tree = hip.VocTree(K, L, D, nodes)
         self.db = hip.PlaceDB(self.tree, max_docs=max_docs, max_words=max_words, max_frames=max_frames, recent=recent, num_avg_words=navg)
@@ -117,6 +123,118 @@ def test_other_trees(hip, shape):
     queries = [p.frame(65), p.frame(1), p.frame(40)]
     for g, q in zip(p.db.run(queries, top_k=3), queries):
         check(g, p.ref.query(q, top_k=3), top_k=3)
+    p.close()
+
+
+def worst():
+    print("largest relative likelihood difference so far: %.3g" % WORST["likelihood"])
+
+
+@pytest.mark.parametrize("walk", ["virtual", "plain"])
+def test_walk_past_the_trips_and_chunks_of_finish(hip, walk):
+    """One database grown to 1300 visible documents (test_place_cpu.WALK) and queried at 255, 256, 257 (k_place_finish's strided loops
+    take a second trip from state 256 on), 1023 .. 1026 (its ordered fill sum carries from one chunk of 1024 states into the next) and
+    1300, with and without a virtual document (`first` moves every boundary by a state).  Copies of two of the queries sit on either
+    side of each boundary and again more than 256 documents away: bit-equal scores that top_k orders by document across trips; most
+    states are untouched, so the fill decides their score.  The reference's side is test_place_cpu.walk_reference, made once."""
+    K, L, D = T.WALK["tree"]
+    inp, ref = T.walk_inputs(), T.walk_reference(walk)
+    ref_tree = R.Tree(K, L, D, inp["nodes"])
+    want_words = [ref_tree.words(fr) for fr in inp["frames"]]
+    names, queries = list(inp["queries"]), list(inp["queries"].values())
+    tree = hip.VocTree(K, L, D, inp["nodes"])
+    db = hip.PlaceDB(tree, max_docs=T.WALK["max_docs"], max_words=T.WALK["max_words"], max_frames=len(queries), recent=0,
+                     num_avg_words=T.WALK["navg"][walk])
+    seen = []
+    t0 = time.perf_counter()
+    for k, fr in enumerate(inp["frames"]):
+        st = db.insert(fr)
+        assert st["status"] == "OK" and np.array_equal(st["words"], want_words[k]), k
+        if k in T.WALK["points"]:                                # recent = 0: k + 1 inserted, k visible
+            assert db.size() == {"inserted": k + 1, "visible": k, "doc_size": k + (walk == "virtual")}
+            for name, g in zip(names, db.run(queries, top_k=T.WALK["top_k"])):
+                check(g, ref[k][name], top_k=T.WALK["top_k"])
+                assert g["has_virtual"] == (walk == "virtual")
+            seen.append(k)
+    print("walk %s: %d inserts and %d queries in %.2f s" % (walk, len(inp["frames"]), len(seen) * len(queries), time.perf_counter() - t0))
+    assert seen == list(T.WALK["points"]) and db.stats()["allocations"] == 1
+    db.close()
+    tree.close()
+    worst()
+
+
+def test_documents_at_the_word_limit(hip):
+    """(64, 2, 16), max_words 512 (test_place_cpu.LIMIT): documents of 63, 64 and 65 distinct words (the run starts of k_place_document
+    about one wave), of 511 and of 512 (every thread starts a run), and 512 descriptors in 256 words; first as queries only, then also
+    stored in a database of more than 1024 columns: 512 query words against 512 stored ones, and 1 against 512.  The stored
+    documents' lengths show in df, hence in the virtual document and in every score."""
+    K, L, D = T.LIMIT["tree"]
+    inp, ref = T.limit_inputs(), T.limit_reference()
+    p = Pair(hip, K, L, D, seed=0, recent=0, navg=T.LIMIT["navg"], max_docs=T.LIMIT["max_docs"], max_words=T.LIMIT["max_words"],
+             max_frames=len(inp["queries"]), nodes=inp["nodes"])
+    queries = [inp["frames"][q] for q in inp["queries"]]
+    for stage in ("first", "then"):
+        for name in T.LIMIT[stage]:
+            st = p.insert(inp["frames"][name])
+            assert np.array_equal(st["words"], p.ref_tree.words(inp["frames"][name])), name
+        assert np.array_equal(p.db.virtual_words(), ref[stage + "_virtual"]) and np.array_equal(p.ref.virtual, ref[stage + "_virtual"])
+        assert p.db.size()["doc_size"] == p.ref.doc_size
+        for q, g in zip(inp["queries"], p.db.run(queries, top_k=T.LIMIT["top_k"])):
+            check(g, ref[stage][q], top_k=T.LIMIT["top_k"])
+    assert p.db.size() == {"inserted": 11, "visible": 10, "doc_size": 11}
+    p.close()
+    worst()
+
+
+def small_database(hip, shape, inp, recent, navg):
+    """a dozen inserts and the queries of `inp` against the reference fed alike, as test_other_trees does"""
+    K, L, D = shape
+    p = Pair(hip, K, L, D, seed=0, recent=recent, navg=navg, max_docs=16, max_words=T.EDGE_MAX_WORDS, nodes=inp["nodes"])
+    for fr in inp["inserts"]:
+        st = p.insert(fr)
+        assert np.array_equal(st["words"], p.ref_tree.words(fr))
+    got = p.db.run(inp["queries"], top_k=3)
+    for g, q in zip(got, inp["queries"]):
+        check(g, p.ref.query(q, top_k=3), top_k=3)
+    p.close()
+    return got
+
+
+@pytest.mark.parametrize("shape", T.EDGE_TREES)
+def test_trees_at_the_child_block_edges_and_the_limits(hip, shape):
+    """8 and 16 children (whole blocks of nearest_child's 8), 9 (a block of one real child), four levels, the largest root and 64
+    children over two levels; an insert of one descriptor per reachable word."""
+    small_database(hip, shape, T.edge_tree_inputs(shape), recent=1, navg=3)
+    worst()
+
+
+@pytest.mark.parametrize("name", sorted(T.TIE_TREES))
+def test_equal_children_go_to_the_lower(hip, name):
+    """(16, 2, 8) with two equal root children, in one block of 8 and in two: the descriptors nearest to them go down the lower one."""
+    of, _ = T.TIE_TREES[name]
+    inp = T.tie_tree_inputs(name)
+    got = small_database(hip, (16, 2, 8), inp, recent=0, navg=5)
+    assert len(got[0]["words"]) >= 20 and (got[0]["words"] // 16 == of).all()
+    worst()
+
+
+def test_top_k_beyond_the_database(hip):
+    """top_k = 32 against 1, 6 and 31 visible documents: the head is the documents in order, the tail -1 / +0.0f"""
+    p = Pair(hip, 5, 2, 8, seed=9, recent=0, navg=10)
+    queries = [p.frame(12), p.frame(1)]
+    done = []
+    while p.ref.visible < 31:
+        p.insert(p.frame(5 + p.ref.visible % 7))
+        v = p.ref.visible
+        if v in (1, 6, 31):
+            assert p.db.size()["visible"] == v
+            for g, q in zip(p.db.run(queries, top_k=32), queries):
+                ref = p.ref.query(q, top_k=32)
+                check(g, ref, top_k=32)
+                assert sorted(g["top_id"][:v].tolist()) == list(range(v))
+                assert g["top_id"][v:].tolist() == [-1] * (32 - v) and bits(g["top_score"][v:]) == [0] * (32 - v)
+            done.append(v)
+    assert done == [1, 6, 31]
     p.close()
 
 

@@ -1,7 +1,9 @@
 """The place recogniser without a device (include/slslam_hip.h: slslam_voctree_*, slslam_place_db_*, slslam_place_filter_*): hand-computed
 cases that pin the numpy reference (tests/place_reference.py), the host Bayes filter through the C ABI against the numpy filter, the
-tree file loader, and the property of the synthetic place sequence that the GPU test relies on."""
+tree file loader, and the property of the synthetic place sequence that the GPU test relies on.  The inputs with which test_gpu_place.py
+goes past one pass of the kernels' loops are made here, and tests here assert on the reference alone what each of them is."""
 import ctypes as C
+import functools
 import math
 import os
 import sys
@@ -13,6 +15,8 @@ from slslam_amd import capi, synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import place_reference as R  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # The place sequence of the end-to-end tests (here and in test_gpu_place.py): tree (10, 3, 16) of seed 1; sequence of seed 3, 60 places of
 # 30 words, noise 0.03, revisit of places 10 .. 24; recent 10, 20 average words; filter sigma 1.0, threshold 0.5, seq_len 5, min_docs 10.
@@ -27,6 +31,159 @@ def seq_inputs():
     nodes = synth.make_voctree(SEQ["tree_seed"], K, L, D)
     s = synth.make_place_sequence(SEQ["seed"], SEQ["places"], SEQ["words"], SEQ["noise"], SEQ["revisit"], dim=D)
     return R.Tree(K, L, D, nodes), nodes, s
+
+
+# ---- inputs of the GPU tests beyond one pass of the in-kernel loops (test_gpu_place.py imports them; what each is,
+# the test_the_..._what_..._gpu_test_says tests below assert on the reference).  Seeded, made once, shared, never written to.
+# The sizes are the kernels' (csrc/place_recognition.h; the test below reads them there): k_place_finish walks the states in trips of
+# FINISH_THREADS from state `first` = 1 - has_virtual (the keys of top_k from state 1), its ordered fill sum takes FILL_CHUNK states at a
+# time from state `first`; nearest_child takes CHILD_BLOCK children at a time; a document holds at most MAX_WORDS words.
+FINISH_THREADS, FILL_CHUNK, CHILD_BLOCK, MAX_WORDS, MAX_TOP_K, MAX_K, MAX_L, MAX_D = 256, 1024, 8, 512, 32, 64, 4, 128
+
+
+def unit(rng, n, D):
+    d = rng.standard_normal((n, D))
+    return (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+
+
+def frozen(a):
+    a.setflags(write=False)
+    return a
+
+
+# The walk: one database that grows to 1300 visible documents, queried on the way.  Document d is state d + 1.  Frame `a` is inserted as
+# the documents 254 .. 257 (states 255 .. 258: about the second trip, which begins at state 256 with a virtual document and at 257
+# without, and for the keys always at 257) and again as document 700; frame `b` as the documents 1022 .. 1025 (states 1023 .. 1026, about
+# the second chunk at state 1024 or 1025) and before that as document 300.  Copies of one frame score alike bit for bit, so top_k has to
+# order them by document number across trips.  `b` begins with two descriptors of `a`, the 12-descriptor query with one, and the
+# 1-descriptor query is a's first: every query touches every copy.
+WALK = dict(tree=(40, 2, 8), tree_seed=11, seed=12, inserts=1301, max_docs=1400, max_words=64, top_k=MAX_TOP_K,
+            points=(255, 256, 257, 1023, 1024, 1025, 1026, 1300), navg={"virtual": 10, "plain": 2000},
+            a_at=(254, 255, 256, 257, 700), b_at=(300, 1022, 1023, 1024, 1025))
+
+
+@functools.lru_cache(maxsize=None)
+def walk_inputs():
+    K, L, D = WALK["tree"]
+    rng = np.random.default_rng(WALK["seed"])
+    a = unit(rng, 9, D)
+    b = np.vstack([a[:2], unit(rng, 6, D)])
+    frames = [unit(rng, int(rng.integers(6, 11)), D) for _ in range(WALK["inserts"])]
+    for d in WALK["a_at"]:
+        frames[d] = a
+    for d in WALK["b_at"]:
+        frames[d] = b
+    queries = {"twelve": np.vstack([a[1:2], unit(rng, 11, D)]), "one": a[:1].copy(), "a": a, "b": b}
+    for f in frames + list(queries.values()):
+        frozen(f)
+    return dict(nodes=frozen(synth.make_voctree(WALK["tree_seed"], K, L, D)), frames=frames, queries=queries)
+
+
+@functools.lru_cache(maxsize=None)
+def walk_reference(walk):
+    """walk: "virtual" (10 average words: a virtual document from early on, first = 0) or "plain" (2000: never one, first = 1).  Returns
+    {visible: {query name: the reference's result}} at the WALK's points and "virtual_from": the number of visible documents at which
+    the virtual document appeared (None: never)."""
+    K, L, D = WALK["tree"]
+    inp = walk_inputs()
+    db = R.Database(R.Tree(K, L, D, inp["nodes"]), 0, WALK["navg"][walk])
+    out = {"virtual_from": None}
+    for fr in inp["frames"]:
+        assert db.insert(fr) == R.OK
+        if out["virtual_from"] is None and len(db.virtual):
+            out["virtual_from"] = db.visible
+        assert out["virtual_from"] is None or len(db.virtual)          # once there, it stays
+        if db.visible in WALK["points"]:
+            out[db.visible] = {name: db.query(q, top_k=WALK["top_k"]) for name, q in inp["queries"].items()}
+    return out
+
+
+# Documents at the word limit: tree (64, 2, 16), 4096 words.  Frames of exactly 63, 64, 65 (about a wave of run starts), 511 and 512
+# distinct words, one descriptor each in a shuffled order; `twice`: 512 descriptors, 256 distinct words twice each; `one`: a word of
+# the 64, the 511, the 512 and `twice`.  The 511 are words of the 512.
+LIMIT = dict(tree=(64, 2, 16), tree_seed=13, seed=14, max_docs=1100, max_words=MAX_WORDS, navg=100, top_k=8,
+             counts={"w63": 63, "w64": 64, "w65": 65, "w511": 511, "w512": 512, "twice": 256, "one": 1},
+             first=("plain0", "plain1", "w63", "plain2", "w64", "w65", "plain3"), then=("w511", "w512", "twice", "plain4"))
+
+
+@functools.lru_cache(maxsize=None)
+def limit_inputs():
+    K, L, D = LIMIT["tree"]
+    nodes = frozen(synth.make_voctree(LIMIT["tree_seed"], K, L, D))
+    tree = R.Tree(K, L, D, nodes)
+    rng = np.random.default_rng(LIMIT["seed"])
+    drawn = unit(rng, 3000, D)
+    pool, row = np.unique(tree.words(drawn), return_index=True)            # the words random descriptors reach, and one descriptor of each
+    assert len(pool) >= 600
+    pool = pool.tolist()
+    words = {"w512": pool[:512], "w511": pool[1:512], "w65": pool[500:565], "w64": pool[0:512:8], "w63": pool[5:572:9],
+             "twice": pool[256:512] * 2, "one": pool[304:305]}
+    frames = {}
+    for name, w in words.items():
+        d = drawn[row[np.searchsorted(pool, w)]]
+        frames[name] = frozen(d[rng.permutation(len(d))])
+    for k in range(5):
+        frames["plain%d" % k] = frozen(unit(rng, 20 + 5 * k, D))
+    return dict(nodes=nodes, frames=frames, queries=("w63", "w64", "w65", "w511", "w512", "twice", "one", "plain4"))
+
+
+@functools.lru_cache(maxsize=None)
+def limit_reference():
+    """the reference's results of every query after the `first` inserts and after the `then` inserts, and its database"""
+    K, L, D = LIMIT["tree"]
+    inp = limit_inputs()
+    db = R.Database(R.Tree(K, L, D, inp["nodes"]), 0, LIMIT["navg"])
+    out = {}
+    for stage in ("first", "then"):
+        for name in LIMIT[stage]:
+            assert db.insert(inp["frames"][name]) == R.OK
+        out[stage] = {q: db.query(inp["frames"][q], top_k=LIMIT["top_k"]) for q in inp["queries"]}
+        out[stage + "_virtual"] = db.virtual.copy()
+    out["db"] = db
+    return out
+
+
+# Trees at the child-block edges and at the limits: 8 and 16 children (no padding in the last block of CHILD_BLOCK), 9 (a block with one
+# real child), L = 4, the largest root (64 x 128 floats = 32 KB of LDS) and 64 children over two levels.
+EDGE_MAX_WORDS, EDGE_TREE_SEED = 96, 13          # (the seed: a (3, 4, 8) tree whose 81 words random descriptors all reach)
+EDGE_TREES = [(8, 2, 8), (9, 2, 8), (16, 2, 8), (3, 4, 8), (64, 1, 128), (64, 2, 16)]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_tree_inputs(shape):
+    K, L, D = shape
+    rng = np.random.default_rng(100 * K + 10 * L + D)
+    nodes = frozen(synth.make_voctree(EDGE_TREE_SEED, K, L, D))
+    inserts = [frozen(unit(rng, n, D)) for n in (65, 7, 33, 64, 1, 20, 65, 12, 80, 41, 8, 64)]
+    drawn = unit(rng, 2000 * (MAX_D // D), D)
+    _, row = np.unique(R.Tree(K, L, D, nodes).words(drawn), return_index=True)
+    inserts.insert(6, frozen(drawn[row[:EDGE_MAX_WORDS]]))          # one descriptor of each word that many random ones reach, up to max_words
+    return dict(nodes=nodes, inserts=inserts, queries=[frozen(unit(rng, 65, D)), inserts[0][:1], frozen(unit(rng, 40, D))])
+
+
+# Two equal children: (16, 2, 8) with root child `copy` an exact copy of root child `of`: in different blocks of CHILD_BLOCK (11 of 3)
+# and in one (5 of 2).  The descriptors are those, among random ones, whose nearest root child is the doubled one: the strict < sends
+# them down the lower.  `control` is the same tree with the copy's centre negated instead.
+TIE_TREES = {"across_blocks": (3, 11), "within_a_block": (2, 5)}
+
+
+@functools.lru_cache(maxsize=None)
+def tie_tree_inputs(name):
+    K, L, D = 16, 2, 8
+    of, copy = TIE_TREES[name]
+    nodes = synth.make_voctree(16, K, L, D).copy()
+    control = nodes.copy()
+    nodes[0, copy] = nodes[0, of]
+    control[0, copy] = -nodes[0, of]
+    tree = R.Tree(K, L, D, nodes)
+    rng = np.random.default_rng(17 + copy)
+    tied = np.zeros((0, D), np.float32)
+    while len(tied) < 20:
+        d = unit(rng, 256, D)
+        tied = np.vstack([tied, d[np.isin(tree.words(d) // K, (of, copy))]])
+    return dict(nodes=frozen(nodes), control=frozen(control), tied=frozen(tied),
+                inserts=[frozen(np.vstack([tied[i::3], unit(rng, 10 + i, D)])) for i in range(3)] + [frozen(unit(rng, 30, D)) for _ in range(4)],
+                queries=[tied, frozen(np.vstack([tied[:5], unit(rng, 20, D)])), tied[:1]])
 
 
 def test_hand_computed_scores_and_likelihoods():
@@ -178,3 +335,144 @@ def test_place_sequence_closes_the_loop_on_the_reference():
     hits = [(i, kf) for i, (loop, kf) in enumerate(out) if loop]
     assert hits and all(abs(kf - int(s["place"][i])) <= 1 for i, kf in hits)
     assert flt.margin > 1e-4
+
+
+# ---- the inputs of the GPU tests beyond one pass of the in-kernel loops
+def _clear(res):
+    """no score of the reference within 1e-9 max(1, |mean|) of the bar: the GPU test may compare the likelihoods"""
+    return res["status"] == R.OK and res["mean"] != 0.0 and res["margin"] > 1e-9
+
+
+def test_the_sizes_are_the_kernels():
+    src = open(os.path.join(ROOT, "slslam_amd", "csrc", "place_recognition.h")).read()
+    assert "constexpr int kMaxK = %d, kMaxL = %d, kMaxD = %d, kMaxWords = %d, kMaxTopK = %d;" % (MAX_K, MAX_L, MAX_D, MAX_WORDS, MAX_TOP_K) in src
+    for line in ("kFinishThreads = %d;" % FINISH_THREADS, "kFillChunk = %d;" % FILL_CHUNK, "kChildBlock = %d;" % CHILD_BLOCK,
+                 "kDocThreads = %d;" % MAX_WORDS, "const int first = 1 - has_virtual;"):
+        assert line in src, line
+
+
+@pytest.mark.parametrize("walk", ["virtual", "plain"])
+def test_the_walk_is_what_its_gpu_test_says(walk):
+    inp, ref = walk_inputs(), walk_reference(walk)
+    K, L, D = WALK["tree"]
+    assert len(inp["frames"]) == WALK["inserts"] <= WALK["max_docs"] and WALK["max_docs"] >= 1400
+    assert all(6 <= len(f) <= 10 for f in inp["frames"]) and max(len(q) for q in inp["queries"].values()) <= WALK["max_words"]
+    assert [len(inp["queries"][q]) for q in ("twelve", "one")] == [12, 1]
+    assert sorted(k for k in ref if k != "virtual_from") == list(WALK["points"])
+    # a virtual document throughout the first walk, never one in the second: first = 0 and first = 1
+    has_virtual = walk == "virtual"
+    assert (ref["virtual_from"] is not None and ref["virtual_from"] < WALK["points"][0]) if has_virtual else ref["virtual_from"] is None
+    first = 0 if has_virtual else 1
+    copies = {"a": WALK["a_at"], "b": WALK["b_at"]}
+    # the copies lie about both trip boundaries (of the state loops and of the key loop) and about the chunk boundary of either walk
+    for lo, hi, at in ((FINISH_THREADS, FINISH_THREADS + 1, WALK["a_at"]), (FILL_CHUNK, FILL_CHUNK + 1, WALK["b_at"])):
+        states = [d + 1 for d in at]
+        assert {lo - 1, lo, hi, hi + 1} <= set(states)
+    assert WALK["a_at"][-1] - WALK["a_at"][0] > FINISH_THREADS and WALK["b_at"][1] - WALK["b_at"][0] > FINISH_THREADS
+    for visible in WALK["points"]:
+        for name, res in ref[visible].items():
+            assert res["has_virtual"] == has_virtual and len(res["score"]) == visible + 1
+            assert _clear(res), (visible, name, res["margin"])
+            t = res["touched"].astype(bool)
+            assert all(t[d + 1] for at in copies.values() for d in at if d < visible), (visible, name)      # every copy is touched
+            if visible > FILL_CHUNK:                             # the second chunk has touched states, the first too; the fill matters
+                assert t[first:first + FILL_CHUNK].any() and t[first + FILL_CHUNK:].any()
+                assert (~t[first:]).sum() >= 300, (visible, name, (~t[first:]).sum())
+            assert t[first:].sum() >= 3 or visible < FINISH_THREADS + 2
+        # bit-for-bit ties that the lower document number decides, from different trips of the key loop
+        for name, at in copies.items():
+            res, seen = ref[visible][name], [d for d in at if d < visible]
+            assert res["top_id"][:len(seen)].tolist() == seen, (visible, name)
+            assert len(seen) == 0 or len(set(res["top_score"][:len(seen)].view(np.uint32).tolist())) == 1
+            assert len(seen) == len(at) or visible < 1026
+            if seen:
+                assert res["top_score"][len(seen)] < res["top_score"][0]
+        assert (ref[visible]["a"]["top_id"] >= 0).all()           # 32 documents to name at every point
+    last = ref[WALK["points"][-1]]
+    assert last["a"]["top_id"][:5].tolist() == list(WALK["a_at"]) and last["b"]["top_id"][:5].tolist() == list(WALK["b_at"])
+    assert sum(d // FINISH_THREADS for d in WALK["a_at"]) > 0 and len({d // FINISH_THREADS for d in WALK["a_at"]}) >= 3
+
+
+def test_the_limit_documents_are_what_their_gpu_test_says():
+    K, L, D = LIMIT["tree"]
+    inp, ref = limit_inputs(), limit_reference()
+    tree = R.Tree(K, L, D, inp["nodes"])
+    for name, distinct in LIMIT["counts"].items():
+        w = tree.words(inp["frames"][name])
+        assert len(set(w.tolist())) == distinct, name
+        assert len(w) == (512 if name == "twice" else distinct)
+        assert not np.array_equal(w, np.sort(w)) or len(w) == 1, name                  # the sort has work to do
+    assert np.array_equal(np.unique(tree.words(inp["frames"]["twice"]), return_counts=True)[1], np.full(256, 2))
+    assert set(tree.words(inp["frames"]["w511"]).tolist()) < set(tree.words(inp["frames"]["w512"]).tolist())
+    assert LIMIT["max_words"] == MAX_WORDS == 512 and LIMIT["max_docs"] > FILL_CHUNK       # the column stride of a stored document
+    assert len(inp["queries"]) == 8 and set(LIMIT["first"] + LIMIT["then"]) >= set(LIMIT["counts"]) - {"one"}
+    db = ref["db"]
+    assert db.visible == len(LIMIT["first"]) + len(LIMIT["then"]) - 1 and len(ref["then_virtual"]) == LIMIT["navg"]
+    assert [len(db.docs[len(LIMIT["first"]) + i][0]) for i in range(3)] == [511, 512, 256]
+    for stage in ("first", "then"):
+        for q, res in ref[stage].items():
+            assert _clear(res), (stage, q, res.get("margin"))
+    s511 = len(LIMIT["first"]) + 1                               # the states of the 511-word, the 512-word and the `twice` document
+    for q in ("w512", "w511", "one", "twice", "w64"):
+        assert ref["then"][q]["touched"][s511:s511 + 3].all(), q
+    assert ref["first"]["one"]["touched"][LIMIT["first"].index("w64") + 1]
+    assert ref["then"]["w511"]["top_id"][0] == s511 - 1 and ref["then"]["w512"]["top_id"][0] == s511 and ref["then"]["twice"]["top_id"][0] == s511 + 1
+
+
+@pytest.mark.parametrize("shape", EDGE_TREES)
+def test_the_edge_trees_are_what_their_gpu_test_says(shape):
+    K, L, D = shape
+    inp = edge_tree_inputs(shape)
+    tree = R.Tree(K, L, D, inp["nodes"])
+    assert K <= MAX_K and L <= MAX_L and D <= MAX_D
+    words = np.concatenate([tree.words(f) for f in inp["inserts"] + inp["queries"]])
+    last_block = CHILD_BLOCK * ((K - 1) // CHILD_BLOCK)
+    for level in range(L):                                       # at every level: child 0, the first child of the last block, the last child
+        child = (words // K ** (L - 1 - level)) % K
+        assert {0, last_block, K - 1} <= set(child.tolist()), (shape, level)
+    if shape == (3, 4, 8):
+        assert len(set(words.tolist())) == 81
+    if K == 9:
+        assert last_block == 8 == K - 1                          # a block that holds one real child and seven copies of it
+    if K in (8, 16):
+        assert K % CHILD_BLOCK == 0
+    if shape == (64, 1, 128):
+        assert 4 * K * D == 32768
+    db = R.Database(tree, 1, 3)
+    for f in inp["inserts"]:
+        assert db.insert(f) == R.OK
+    assert db.visible == 11 and len(db.virtual) == 3 and max(len(f) for f in inp["inserts"]) <= EDGE_MAX_WORDS
+    for q in inp["queries"]:
+        assert _clear(db.query(q, top_k=3))
+
+
+@pytest.mark.parametrize("name", sorted(TIE_TREES))
+def test_the_tie_trees_are_what_their_gpu_test_says(name):
+    K, L, D = 16, 2, 8
+    of, copy = TIE_TREES[name]
+    inp = tie_tree_inputs(name)
+    assert (of // CHILD_BLOCK != copy // CHILD_BLOCK) == (name == "across_blocks") and of < copy
+    tree, control = R.Tree(K, L, D, inp["nodes"]), R.Tree(K, L, D, inp["control"])
+    assert np.array_equal(tree.nodes[0, of], tree.nodes[0, copy]) and not np.array_equal(tree.nodes[of + 1], tree.nodes[copy + 1])
+    tied = inp["tied"]
+    assert len(tied) >= 20
+    # the distances to the two children are equal bit for bit and below every other child's: a tie and nothing else decides
+    r = np.ones((len(tied), K), dtype=np.float32)
+    for i in range(D):
+        r = r - tree.nodes[0][None, :, i] * tied[:, i, None]
+    assert (r[:, of].view(np.uint32) == r[:, copy].view(np.uint32)).all()
+    others = np.delete(r, [of, copy], axis=1)
+    assert (r[:, of] < others.min(axis=1)).all() and (r[:, of] < 1.0).all()
+    # the reference sends every one down the lower child; with the copy taken away the same descriptors pick the same child and word
+    w = tree.words(tied)
+    assert (w // K == of).all()
+    assert np.array_equal(control.words(tied), w)
+    # the higher child's subtree would give other words
+    swapped = inp["nodes"].copy()
+    swapped[of + 1] = inp["nodes"][copy + 1]
+    assert (R.Tree(K, L, D, swapped).words(tied) // K == of).all()
+    db = R.Database(tree, 0, 5)
+    for f in inp["inserts"]:
+        assert db.insert(f) == R.OK
+    for q in inp["queries"]:
+        assert _clear(db.query(q, top_k=3))
