@@ -540,6 +540,41 @@ class _CountedHandle(_Handle):
         return {"calls": c.value, "allocations": a.value}
 
 
+class _TimedHandle(_CountedHandle):
+    """A handle whose runs can time their launches by events (_TIMING: the library's switch and getter)."""
+    _TIMING = None
+
+    def set_timing(self, enable):
+        _check(getattr(lib(), self._TIMING)(self._h, int(bool(enable)), None), self._TIMING)
+
+    def kernel_ms(self):
+        """The last timed run's launches by events (after set_timing(True))."""
+        ms = C.c_double(0.0)
+        _check(getattr(lib(), self._TIMING)(self._h, -1, C.byref(ms)), self._TIMING)      # (-1: the switch stays)
+        return ms.value
+
+
+def _float_options(o, default, what, options):
+    """The library's defaults (default: the *_default_options symbol) in the struct o with the given float fields replaced."""
+    getattr(lib(), default)(C.byref(o))
+    for k, v in options.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown %s option %r" % (what, k))
+        setattr(o, k, float(v))
+    return o
+
+
+def _frame_arrays(Frame, Result, items, make):
+    """(Frame[n], Result[n], keep) for a run over items: make(item) -> (frame, result, what both point to, ...)."""
+    n = len(items)
+    frs, outs, keep = (Frame * max(n, 1))(), (Result * max(n, 1))(), []
+    for i, item in enumerate(items):
+        made = make(item)
+        frs[i], outs[i] = made[0], made[1]
+        keep.append(made[2])
+    return frs, outs, keep
+
+
 def default_options(**kw):
     o = SolverOptions()
     lib().slslam_default_options(C.byref(o))
@@ -2054,13 +2089,19 @@ def msld_options(bands=9, band_width=5, orient=True):
     return MsldOptions(int(bands), int(band_width), int(bool(orient)))
 
 
-def _msld_frame(image, segments, D):
-    """(MsldFrame, MsldResult, the arrays both point to).  An image whose rows are contiguous passes its stride; any other is copied."""
+def _image_rows(image):
+    """A uint8 [H, W] array whose rows the library can walk: an image whose rows are contiguous passes its stride, any other is copied."""
     img = np.asarray(image)
     if img.dtype != np.uint8 or img.ndim != 2:
         raise ValueError("an image is uint8 [H, W]")
     if img.shape[0] > 0 and img.shape[1] > 0 and (img.strides[1] != 1 or img.strides[0] < img.shape[1]):
         img = np.ascontiguousarray(img)
+    return img
+
+
+def _msld_frame(image, segments, D):
+    """(MsldFrame, MsldResult, the arrays both point to)."""
+    img = _image_rows(image)
     seg = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
     n = len(seg)
     b = {"descriptors": np.zeros((max(n, 1), D), dtype=np.float32), "status": np.full(max(n, 1), -1, dtype=np.int32),
@@ -2086,10 +2127,10 @@ def describe_lines(image, segments, **options):
     return _msld_dict(keep)
 
 
-class LineDescriptor(_CountedHandle):
+class LineDescriptor(_TimedHandle):
     """slslam_line_descriptor: MSLD descriptors for the segments of many frames per call; buffers kept between calls.  A frame is
     (image uint8 [H, W], segments [n, 4])."""
-    _DESTROY, _STATS = "slslam_line_descriptor_destroy", "slslam_line_descriptor_stats"
+    _DESTROY, _STATS, _TIMING = "slslam_line_descriptor_destroy", "slslam_line_descriptor_stats", "slslam_line_descriptor_timing"
 
     def __init__(self, bands=9, band_width=5, orient=True, max_frames=2, max_pixels=752 * 480, max_segments=512, device=-1):
         self.opt = msld_options(bands, band_width, orient)
@@ -2100,38 +2141,15 @@ class LineDescriptor(_CountedHandle):
 
     def run(self, frames):
         """Returns one dict per frame, as describe_lines returns it."""
-        n = len(frames)
-        frs, outs, keep = (MsldFrame * max(n, 1))(), (MsldResult * max(n, 1))(), []
-        for i, (image, segments) in enumerate(frames):
-            frs[i], outs[i], k = _msld_frame(image, segments, self.D)
-            keep.append(k)
-        _check(lib().slslam_line_descriptor_run(self._h, n, frs, outs), "slslam_line_descriptor_run")
+        frs, outs, keep = _frame_arrays(MsldFrame, MsldResult, frames, lambda f: _msld_frame(f[0], f[1], self.D))
+        _check(lib().slslam_line_descriptor_run(self._h, len(frames), frs, outs), "slslam_line_descriptor_run")
         return [_msld_dict(k) for k in keep]
-
-    def set_timing(self, enable):
-        _check(lib().slslam_line_descriptor_timing(self._h, int(bool(enable)), None), "slslam_line_descriptor_timing")
-
-    def kernel_ms(self):
-        """The last run's launch by events (after set_timing(True))."""
-        ms = C.c_double(0.0)
-        _check(lib().slslam_line_descriptor_timing(self._h, -1, C.byref(ms)), "slslam_line_descriptor_timing")      # (-1: the switch stays)
-        return ms.value
 
 
 # ----------------------------------------------------------------------------- line segments from images (slslam_line_detector_*)
 def line_detect_options(grad_threshold=24, tol_num=11, tol_den=64, min_pixels=12, min_length=10.0, max_thickness=3.0, max_segments=512):
     return LineDetectOptions(int(grad_threshold), int(tol_num), int(tol_den), int(min_pixels), float(min_length), float(max_thickness),
                              int(max_segments))
-
-
-def _image_rows(image):
-    """A uint8 [H, W] array whose rows the library can walk: an image whose rows are contiguous passes its stride, any other is copied."""
-    img = np.asarray(image)
-    if img.dtype != np.uint8 or img.ndim != 2:
-        raise ValueError("an image is uint8 [H, W]")
-    if img.shape[0] > 0 and img.shape[1] > 0 and (img.strides[1] != 1 or img.strides[0] < img.shape[1]):
-        img = np.ascontiguousarray(img)
-    return img
 
 
 def _detect_frame(image, max_segments, labels):
@@ -2170,9 +2188,9 @@ def detect_lines(image, labels=False, **options):
     return _detect_dict(keep)
 
 
-class LineDetector(_CountedHandle):
+class LineDetector(_TimedHandle):
     """slslam_line_detector: the line segments of many frames per call; buffers kept between calls.  A frame is an image uint8 [H, W]."""
-    _DESTROY, _STATS = "slslam_line_detector_destroy", "slslam_line_detector_stats"
+    _DESTROY, _STATS, _TIMING = "slslam_line_detector_destroy", "slslam_line_detector_stats", "slslam_line_detector_timing"
 
     def __init__(self, max_frames=2, max_pixels=752 * 480, device=-1, **options):
         self.opt = line_detect_options(**options)
@@ -2182,22 +2200,10 @@ class LineDetector(_CountedHandle):
 
     def run(self, images, labels=False):
         """Returns one dict per frame, as detect_lines returns it."""
-        n = len(images)
-        frs, outs, keep = (LineDetectFrame * max(n, 1))(), (LineDetectResult * max(n, 1))(), []
-        for i, image in enumerate(images):
-            frs[i], outs[i], k = _detect_frame(image, self.opt.max_segments, labels)
-            keep.append(k)
-        _check(lib().slslam_line_detector_run(self._h, n, frs, outs), "slslam_line_detector_run")
+        frs, outs, keep = _frame_arrays(LineDetectFrame, LineDetectResult, images,
+                                        lambda image: _detect_frame(image, self.opt.max_segments, labels))
+        _check(lib().slslam_line_detector_run(self._h, len(images), frs, outs), "slslam_line_detector_run")
         return [_detect_dict(k) for k in keep]
-
-    def set_timing(self, enable):
-        _check(lib().slslam_line_detector_timing(self._h, int(bool(enable)), None), "slslam_line_detector_timing")
-
-    def kernel_ms(self):
-        """The last run's launches by events (after set_timing(True))."""
-        ms = C.c_double(0.0)
-        _check(lib().slslam_line_detector_timing(self._h, -1, C.byref(ms)), "slslam_line_detector_timing")         # (-1: the switch stays)
-        return ms.value
 
 
 def detect_and_describe(detector, descriptor, images):
@@ -2215,13 +2221,7 @@ def detect_and_describe(detector, descriptor, images):
 def stereo_match_options(**options):
     """slslam_stereo_match_default_options with the given fields replaced: min_disparity, max_disparity, max_tan2, min_rows,
     min_overlap, ratio, max_distance, fx, fy, cx, cy."""
-    o = StereoMatchOptions()
-    lib().slslam_stereo_match_default_options(C.byref(o))
-    for k, v in options.items():
-        if not hasattr(o, k):
-            raise TypeError("unknown stereo match option %r" % k)
-        setattr(o, k, float(v))
-    return o
+    return _float_options(StereoMatchOptions(), "slslam_stereo_match_default_options", "stereo match", options)
 
 
 def _stereo_side(side):
@@ -2269,10 +2269,10 @@ def match_stereo(left, right, **options):
     return _stereo_dict(r, keep)
 
 
-class StereoMatcher(_CountedHandle):
+class StereoMatcher(_TimedHandle):
     """slslam_stereo_matcher: many stereo frames per call; buffers kept between calls.  A frame is (left, right) as match_stereo
     takes them.  The options given here are the defaults of run."""
-    _DESTROY, _STATS = "slslam_stereo_matcher_destroy", "slslam_stereo_matcher_stats"
+    _DESTROY, _STATS, _TIMING = "slslam_stereo_matcher_destroy", "slslam_stereo_matcher_stats", "slslam_stereo_matcher_timing"
 
     def __init__(self, D, max_frames=2, max_segments=512, device=-1, **options):
         self.D = int(D)
@@ -2285,22 +2285,9 @@ class StereoMatcher(_CountedHandle):
     def run(self, frames, **options):
         """Returns one dict per frame, as match_stereo returns it."""
         opt = stereo_match_options(**dict(self.options, **options))
-        n = len(frames)
-        frs, outs, keep = (StereoFrame * max(n, 1))(), (StereoResult * max(n, 1))(), []
-        for i, (left, right) in enumerate(frames):
-            frs[i], outs[i], k, _ = _stereo_frame(left, right, self.D)
-            keep.append(k)
-        _check(lib().slslam_stereo_matcher_run(self._h, C.byref(opt), n, frs, outs), "slslam_stereo_matcher_run")
-        return [_stereo_dict(outs[i], keep[i]) for i in range(n)]
-
-    def set_timing(self, enable):
-        _check(lib().slslam_stereo_matcher_timing(self._h, int(bool(enable)), None), "slslam_stereo_matcher_timing")
-
-    def kernel_ms(self):
-        """The last run's three launches by events (after set_timing(True))."""
-        ms = C.c_double(0.0)
-        _check(lib().slslam_stereo_matcher_timing(self._h, -1, C.byref(ms)), "slslam_stereo_matcher_timing")          # (-1: the switch stays)
-        return ms.value
+        frs, outs, keep = _frame_arrays(StereoFrame, StereoResult, frames, lambda f: _stereo_frame(f[0], f[1], self.D))
+        _check(lib().slslam_stereo_matcher_run(self._h, C.byref(opt), len(frames), frs, outs), "slslam_stereo_matcher_run")
+        return [_stereo_dict(outs[i], keep[i]) for i in range(len(frames))]
 
 
 def stereo_observations(result):
@@ -2338,13 +2325,7 @@ def detect_describe_and_pair(detector, descriptor, matcher, stereo_images, **opt
 def line_track_options(**options):
     """slslam_line_track_default_options with the given fields replaced: max_tan2, max_shift, max_offset, min_overlap, min_length,
     ratio, max_distance."""
-    o = LineTrackOptions()
-    lib().slslam_line_track_default_options(C.byref(o))
-    for k, v in options.items():
-        if not hasattr(o, k):
-            raise TypeError("unknown line track option %r" % k)
-        setattr(o, k, float(v))
-    return o
+    return _float_options(LineTrackOptions(), "slslam_line_track_default_options", "line track", options)
 
 
 _TRACK_KEYS = ("match", "best", "best_distance", "second_distance", "num_admissible", "best_row")
@@ -2380,13 +2361,13 @@ def _track_dict(r, keep):
 
 
 def _track_frames(frames, carried, D):
-    n = len(frames)
-    frs, outs, keep, m = (LineTrackFrame * max(n, 1))(), (LineTrackResult * max(n, 1))(), [], carried
-    for i, frame in enumerate(frames):
-        frs[i], outs[i], k, D = _track_frame(frame, m, D)
-        keep.append(k)
-        m = frs[i].num_segments
-    return frs, outs, keep, D
+    state = [carried, D]                    # the segments of the frame before, and D once a frame has shown it
+
+    def make(frame):
+        made = _track_frame(frame, state[0], state[1])
+        state[:] = made[0].num_segments, made[3]
+        return made
+    return _frame_arrays(LineTrackFrame, LineTrackResult, frames, make) + (state[1],)
 
 
 def track_lines(frames, **options):
@@ -2400,11 +2381,11 @@ def track_lines(frames, **options):
     return [_track_dict(outs[i], keep[i]) for i in range(len(frames))]
 
 
-class LineTracker(_CountedHandle):
+class LineTracker(_TimedHandle):
     """slslam_line_tracker: persistent feature ids for the segments of many frames per call; the last frame and the next id are kept
     on the device and in the handle between calls.  A frame is what track_lines takes.  The options given here are the defaults
     of run."""
-    _DESTROY, _STATS = "slslam_line_tracker_destroy", "slslam_line_tracker_stats"
+    _DESTROY, _STATS, _TIMING = "slslam_line_tracker_destroy", "slslam_line_tracker_stats", "slslam_line_tracker_timing"
 
     def __init__(self, D, max_frames=2, max_segments=512, device=-1, **options):
         self.D = int(D)
@@ -2428,15 +2409,6 @@ class LineTracker(_CountedHandle):
         a, b = C.c_int(0), C.c_int(0)
         _check(lib().slslam_line_tracker_state(self._h, C.byref(a), C.byref(b)), "slslam_line_tracker_state")
         return {"next_id": a.value, "carried_segments": b.value}
-
-    def set_timing(self, enable):
-        _check(lib().slslam_line_tracker_timing(self._h, int(bool(enable)), None), "slslam_line_tracker_timing")
-
-    def kernel_ms(self):
-        """The last run's launches by events (after set_timing(True))."""
-        ms = C.c_double(0.0)
-        _check(lib().slslam_line_tracker_timing(self._h, -1, C.byref(ms)), "slslam_line_tracker_timing")              # (-1: the switch stays)
-        return ms.value
 
 
 def detect_describe_pair_and_track(detector, descriptor, matcher, tracker, stereo_images, predicts=None, **stereo_options):

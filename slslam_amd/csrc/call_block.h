@@ -1,6 +1,6 @@
 // slslam_amd/csrc/call_block.h — the scaffold of an entry point that is "a handle, one upload block, a few launches, one download
-// block": whether there is a device, the handle's device and stream, its device block with the page-locked mirror, and the two
-// matchers' result block on the device (its layout and scatter need no HIP: call_layout.h).  Internal: not part of the C ABI.
+// block": whether there is a device, the handle's device and stream, the events of a handle that times its launches, its device
+// block with the page-locked mirror, and the matchers' result block on the device (its layout and scatter need no HIP: call_layout.h).  Internal: not part of the C ABI.
 #ifndef SLSLAM_CALL_BLOCK_H_
 #define SLSLAM_CALL_BLOCK_H_
 
@@ -22,6 +22,8 @@ inline int device_count() {
 }
 
 inline bool device_present() { return device_count() > 0; }
+
+constexpr int kMaxGridY = 65535;        // what the y dimension of a grid takes: problems go in slices of it
 
 // The device of a handle: dev >= 0 is made current, dev < 0 adopts the current one
 inline int use_device(int& dev) {
@@ -57,6 +59,50 @@ int handle_stats(const H* h, long long* calls, long long* allocations) {
   if (!h) return SLSLAM_ERR_INVALID_ARGUMENT;
   if (calls) *calls = h->calls;
   if (allocations) *allocations = h->allocations;
+  return SLSLAM_OK;
+}
+
+// A handle whose runs can time their launches by two events on its stream.  With timing off no member touches the runtime, and
+// last_kernel_ms keeps what the last timed run left.
+struct TimedHandle : Handle {
+  bool timing = false;
+  double last_kernel_ms = 0.0;          // the last timed run's launches
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;              // made at the first timed run
+  ~TimedHandle() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+  // before the launches
+  int timer_start() {
+    if (!timing) return SLSLAM_OK;
+    if (!ev0) {
+      HIP_TRY(hipEventCreate(&ev0));
+      HIP_TRY(hipEventCreate(&ev1));
+    }
+    HIP_TRY(hipEventRecord(ev0, stream));
+    return SLSLAM_OK;
+  }
+  // after them
+  int timer_stop() {
+    if (timing) HIP_TRY(hipEventRecord(ev1, stream));
+    return SLSLAM_OK;
+  }
+  // after the caller's hipStreamSynchronize
+  int timer_read() {
+    if (!timing) return SLSLAM_OK;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    last_kernel_ms = ms;
+    return SLSLAM_OK;
+  }
+};
+
+// The *_timing(enable, kernel_ms) of any TimedHandle: enable < 0 leaves the switch as it is
+template <typename H>
+int handle_timing(H* h, int enable, double* kernel_ms) {
+  if (!h) return SLSLAM_ERR_INVALID_ARGUMENT;
+  if (enable >= 0) h->timing = enable != 0;
+  if (kernel_ms) *kernel_ms = h->last_kernel_ms;
   return SLSLAM_OK;
 }
 

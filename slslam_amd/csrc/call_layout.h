@@ -1,10 +1,12 @@
 // slslam_amd/csrc/call_layout.h — where things lie in the one block a call uploads, works in and downloads: the builder every layout is
-// made with, and the result block the two matchers (mutual_match.h) share, with its scatter into the caller's arrays.  Plain C++ with
+// made with, the result block the matchers (mutual_match.h) share, with its scatter into the caller's arrays, the image copy of the
+// detector and the descriptor, and the limits, validation and upload of a gated problem (stereo matcher, tracker).  Plain C++ with
 // no HIP in it, so that tests/host_cxx/call_block_check.cpp checks it on the host; the HIP half is call_block.h.  Internal: not part of
 // the C ABI.
 #ifndef SLSLAM_CALL_LAYOUT_H_
 #define SLSLAM_CALL_LAYOUT_H_
 
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 
@@ -74,6 +76,42 @@ inline int match_scatter(const char* h_out, const MatchBlock& b, size_t p, const
   std::memcpy(&num_matched, h_out + 4 * p, 4);
   return num_matched;
 }
+
+// An image into the upload with `width` bytes per row: the stride stays with the caller
+inline void pack_rows(unsigned char* dst, const unsigned char* image, int width, int height, int stride) {
+  for (int r = 0; r < height; ++r) std::memcpy(dst + (size_t)r * (size_t)width, image + (size_t)r * (size_t)stride, (size_t)width);
+}
+
+// ---- a gated problem (gated_pairs.h): segments with descriptors of D floats, rows against columns in groups of kGroup.  The stereo
+// matcher and the line tracker take its limits and its validation by `using`.
+namespace gated {
+
+constexpr int kMaxD = 128, kMaxSegments = 512;
+constexpr int kGroup = 8;                                // columns whose chains a lane carries at a time
+constexpr int kMaxGroups = kMaxSegments / kGroup;        // 64: the groups of a problem are the bits of one 64-bit word
+
+inline bool shape_valid(int D, int max_frames, int max_segments) {
+  return D >= 8 && D <= kMaxD && D % 8 == 0 && max_frames >= 1 && max_segments >= 1 && max_segments <= kMaxSegments;
+}
+
+// valid: the four floats and the D descriptor floats are finite
+inline int segment_ok(const float* seg, const float* desc, int D) {
+  for (int q = 0; q < 4; ++q)
+    if (!std::isfinite(seg[q])) return 0;
+  for (int i = 0; i < D; ++i)
+    if (!std::isfinite(desc[i])) return 0;
+  return 1;
+}
+
+// n segments and their descriptors to places a0 .. a0 + n - 1 of the upload's regions, with their flags
+inline void fill_side(float* seg, float* desc, int* ok, size_t a0, const float* src_seg, const float* src_desc, size_t n, int D) {
+  if (n == 0) return;
+  std::memcpy(seg + 4 * a0, src_seg, 16 * n);
+  std::memcpy(desc + a0 * (size_t)D, src_desc, 4 * n * (size_t)D);
+  for (size_t i = 0; i < n; ++i) ok[a0 + i] = segment_ok(src_seg + 4 * i, src_desc + i * (size_t)D, D);
+}
+
+}  // namespace gated
 
 }  // namespace slslam
 

@@ -22,13 +22,12 @@
 
 using namespace slslam_desc;
 using slslam::device_present;
+using slslam::kMaxGridY;
 
 static_assert(kMaxD == SLSLAM_DESC_MAX_D && kMaxDescriptors == SLSLAM_DESC_MAX_DESCRIPTORS && kMaxCandidates == SLSLAM_DESC_MAX_CANDIDATES,
               "the header's limits are the kernels'");
 
 namespace {
-
-constexpr int kMaxGrid = 65535;         // what the y dimension of a grid takes: pairs go in slices of it
 
 // Where everything of a run lies: the upload (the same offsets on the host and on the device), the device's keys behind it, and the
 // result block (on the host behind the upload)
@@ -220,8 +219,8 @@ extern "C" int slslam_descriptor_matcher_run(slslam_descriptor_matcher* m, int n
 
   // ---- two launches for all pairs
   const unsigned tn = (unsigned)((maxN + 63) / 64), tm = (unsigned)((maxM + 63) / 64);
-  for (int p0 = 0; p0 < P; p0 += kMaxGrid) {
-    const unsigned np = (unsigned)std::min(P - p0, kMaxGrid);
+  for (int p0 = 0; p0 < P; p0 += kMaxGridY) {
+    const unsigned np = (unsigned)std::min(P - p0, kMaxGridY);
     Out op = o;
     op.num_matched += p0;
     if (tn > 0)

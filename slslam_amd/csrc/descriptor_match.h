@@ -3,11 +3,10 @@
 // (frame, candidate keyframe) pairs per launch, reduced to mutual, unambiguous matches.
 //
 //   k_desc_pairs    one wave per (pair, 64 query descriptors): lane <-> query descriptor.  The wave's 64 query descriptors are staged
-//                   transposed in LDS (value i of lane a at sq[i kQueryStride + a]: the lanes read neighbouring banks, and the stride of
-//                   65 keeps the staging writes - neighbouring lanes, neighbouring i - off a common bank as well).  The keyframe's
-//                   descriptors stream through LDS in groups of kGroup = 8 (a lane fetches the next group while the wave works on this
-//                   one); the store holds a group as [D][8], so value i of its eight descriptors is two 16-byte reads at one address for
-//                   the whole wave: a broadcast.  Each lane carries the eight chains r_j = 1.0f; r_j -= q[i] * k_j[i] side by side, as
+//                   transposed in LDS (gated_pairs.h: stage_rows).  The keyframe's descriptors stream through LDS in groups of
+//                   kGroup = 8 (a lane fetches the next group while the wave works on this one); the store holds a group as [D][8],
+//                   so value i of its eight descriptors is two 16-byte reads at one address for the whole wave: a broadcast.  Each
+//                   lane carries the eight chains r_j = 1.0f; r_j -= q[i] * k_j[i] side by side (gated_pairs.h: group_chains), as
 //                   slslam_place::nearest_child does with kChildBlock: one chain alone would wait D times for its own last subtraction.
 //                   Then per keyframe descriptor the compare and the lane's running (best, second, count).  Descriptors go by in
 //                   ascending j: the lowest j wins a tie (mutual_match.h: take_pair).  The key of keyframe descriptor j's best query
@@ -20,22 +19,18 @@
 
 #include <hip/hip_runtime.h>
 
+#include "gated_pairs.h"
 #include "mutual_match.h"
-
-// every product and difference of the chain is rounded on its own
-#pragma STDC FP_CONTRACT OFF
 
 namespace slslam_desc {
 
 constexpr int kMaxD = 128, kMaxDescriptors = 512, kMaxCandidates = 8;
-constexpr int kGroup = 8;               // keyframe descriptors whose chains a lane carries at a time
-constexpr int kQueryStride = 65;        // floats between value i and value i + 1 of the staged query descriptors
+using slslam::gated::kGroup;            // keyframe descriptors whose chains a lane carries at a time
+using slslam::gated::pairs_lds_bytes;   // dynamic LDS of k_desc_pairs
 constexpr int kGroupLoads = 2 * kMaxD / 64;       // 16-byte loads a lane makes for a group of the largest D
 
 // floats of a group in the store and in LDS: [D][kGroup]
 __host__ __device__ inline size_t group_floats(int D) { return (size_t)D * kGroup; }
-// dynamic LDS of k_desc_pairs
-inline size_t pairs_lds_bytes(int D) { return 4 * (group_floats(D) + (size_t)D * kQueryStride); }
 
 // Per (query frame, candidate keyframe), where its inputs lie and where its results go
 struct PairDesc {
@@ -66,14 +61,7 @@ __global__ __launch_bounds__(64) void k_desc_pairs(const PairDesc* __restrict__ 
   int best_j = -1, count = 0;
   if (pd.run) {
     // the wave's rows are contiguous in the upload: element e = row D + i, read coalesced; rows past n are zeros (never admissible)
-    const int rows = pd.span.n - a_base < 64 ? pd.span.n - a_base : 64;
-    const float* src = qd + pd.q + (size_t)a_base * D;
-    int row = 0, i = lane;
-    for (int e = lane; e < 64 * D; e += 64) {
-      while (i >= D) { i -= D; ++row; }
-      sq[i * kQueryStride + row] = row < rows ? src[e] : 0.0f;
-      i += 64;
-    }
+    slslam::gated::stage_rows(sq, qd + pd.q + (size_t)a_base * D, pd.span.n - a_base < 64 ? pd.span.n - a_base : 64, D, lane);
     const int ng = (pd.span.m + kGroup - 1) / kGroup;
     const int n4 = 2 * D;                                        // 16-byte words of a group
     const float4* kp = reinterpret_cast<const float4*>(store + pd.k);
@@ -100,18 +88,7 @@ __global__ __launch_bounds__(64) void k_desc_pairs(const PairDesc* __restrict__ 
         }
       }
       float r[kGroup];
-#pragma unroll
-      for (int j = 0; j < kGroup; ++j) r[j] = 1.0f;
-      for (int d = 0; d < D; ++d) {
-        const float qi = sq[d * kQueryStride + lane];
-        const float4 k0 = tile4[2 * d], k1 = tile4[2 * d + 1];
-        const float kv[kGroup] = { k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w };
-#pragma unroll
-        for (int j = 0; j < kGroup; ++j) {
-          const float p = qi * kv[j];
-          r[j] = r[j] - p;
-        }
-      }
+      slslam::gated::group_chains(sq, tile4, D, lane, r);
 #pragma unroll
       for (int jj = 0; jj < kGroup; ++jj) {
         const int j = g * kGroup + jj;

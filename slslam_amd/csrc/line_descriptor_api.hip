@@ -35,19 +35,12 @@ bool frame_valid(const slslam_msld_frame& f) {
 
 }  // namespace
 
-struct slslam_line_descriptor : slslam::Handle {
+struct slslam_line_descriptor : slslam::TimedHandle {
   slslam_msld_options opt;
   int rows = 0;
   long long max_frames = 0, max_pixels = 0, max_segments = 0;
   WeightRow table[kMaxRows];
   slslam::BlockPair block;
-  double last_kernel_ms = 0.0;                           // the last run's launch by events, when timing is on
-  bool timing = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~slslam_line_descriptor() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
 };
 
 extern "C" void slslam_msld_default_options(slslam_msld_options* opt) {
@@ -81,10 +74,7 @@ extern "C" int slslam_line_descriptor_stats(const slslam_line_descriptor* h, lon
 }
 
 extern "C" int slslam_line_descriptor_timing(slslam_line_descriptor* h, int enable, double* kernel_ms) {
-  if (!h) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (enable >= 0) h->timing = enable != 0;
-  if (kernel_ms) *kernel_ms = h->last_kernel_ms;
-  return SLSLAM_OK;
+  return slslam::handle_timing(h, enable, kernel_ms);
 }
 
 extern "C" int slslam_line_descriptor_run(slslam_line_descriptor* h, int num_frames, const slslam_msld_frame* frames,
@@ -127,8 +117,7 @@ extern "C" int slslam_line_descriptor_run(slslam_line_descriptor* h, int num_fra
     const slslam_msld_frame& fr = frames[f];
     fd[f].image = (long long)at;
     fd[f].width = fr.width; fd[f].height = fr.height;
-    for (int r = 0; r < fr.height; ++r)
-      std::memcpy(px + at + (size_t)r * (size_t)fr.width, fr.image + (size_t)r * (size_t)fr.stride, (size_t)fr.width);
+    slslam::pack_rows(px + at, fr.image, fr.width, fr.height, fr.stride);
     at += slslam::align256((size_t)fr.width * (size_t)fr.height);
     first[(size_t)f] = k;
     for (int i = 0; i < fr.num_segments; ++i, ++k) {
@@ -148,25 +137,17 @@ extern "C" int slslam_line_descriptor_run(slslam_line_descriptor* h, int num_fra
     o.status = reinterpret_cast<int*>(d_out + y.o_status);
     o.num_samples = reinterpret_cast<int*>(d_out + y.o_samples);
     o.polarity = reinterpret_cast<float*>(d_out + y.o_polarity);
-    if (h->timing && !h->ev0) {
-      HIP_TRY(hipEventCreate(&h->ev0));
-      HIP_TRY(hipEventCreate(&h->ev1));
-    }
-    if (h->timing) HIP_TRY(hipEventRecord(h->ev0, s));
+    if ((rc = h->timer_start()) != SLSLAM_OK) return rc;
     hipLaunchKernelGGL(k_line_descriptor, dim3((unsigned)S), dim3(kWave), 0, s, reinterpret_cast<const FrameDesc*>(dv),
                        reinterpret_cast<const SegDesc*>(dv + y.off_seg), reinterpret_cast<const WeightRow*>(dv + y.off_table),
                        reinterpret_cast<const unsigned char*>(dv + y.off_pixels), M, h->rows, h->opt.orient, o);
     HIP_TRY(hipGetLastError());
-    if (h->timing) HIP_TRY(hipEventRecord(h->ev1, s));
+    if ((rc = h->timer_stop()) != SLSLAM_OK) return rc;
 
     // ---- one download
     HIP_TRY(hipMemcpyAsync(hb + y.off_out, d_out, y.out_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (h->timing) {
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-      h->last_kernel_ms = ms;
-    }
+    if ((rc = h->timer_read()) != SLSLAM_OK) return rc;
   }
   const char* ho = hb + y.off_out;
   for (int f = 0; f < F; ++f) {

@@ -37,17 +37,10 @@ bool frame_valid(const slslam_line_detect_frame& f) { return slslam_lsd::frame_v
 
 }  // namespace
 
-struct slslam_line_detector : slslam::Handle {
+struct slslam_line_detector : slslam::TimedHandle {
   Options opt;
   long long max_frames = 0, max_pixels = 0;
   slslam::BlockPair block;
-  double last_kernel_ms = 0.0;                           // the last run's launches by events, when timing is on
-  bool timing = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~slslam_line_detector() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
 };
 
 extern "C" void slslam_line_detect_default_options(slslam_line_detect_options* opt) {
@@ -80,10 +73,7 @@ extern "C" int slslam_line_detector_stats(const slslam_line_detector* h, long lo
 }
 
 extern "C" int slslam_line_detector_timing(slslam_line_detector* h, int enable, double* kernel_ms) {
-  if (!h) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (enable >= 0) h->timing = enable != 0;
-  if (kernel_ms) *kernel_ms = h->last_kernel_ms;
-  return SLSLAM_OK;
+  return slslam::handle_timing(h, enable, kernel_ms);
 }
 
 extern "C" int slslam_line_detector_run(slslam_line_detector* h, int num_frames, const slslam_line_detect_frame* frames,
@@ -105,7 +95,7 @@ extern "C" int slslam_line_detector_run(slslam_line_detector* h, int num_frames,
     max_comps = std::max(max_comps, (int)comp_capacity(n, h->opt.min_pixels));
     labels = labels || results[f].labels != nullptr;
   }
-  if ((long long)F * (long long)S > kMaxCallSegments || F > 65535 || (long long)pixels > 4 * kMaxCapacityPixels) return SLSLAM_ERR_UNSUPPORTED;
+  if ((long long)F * (long long)S > kMaxCallSegments || F > slslam::kMaxGridY || (long long)pixels > 4 * kMaxCapacityPixels) return SLSLAM_ERR_UNSUPPORTED;
   int rc = h->ensure();
   if (rc != SLSLAM_OK) return rc;
   hipStream_t s = h->stream;
@@ -132,8 +122,7 @@ extern "C" int slslam_line_detector_run(slslam_line_detector* h, int num_frames,
     fd[f].width = fr.width; fd[f].height = fr.height;
     fd[f].comp_cap = (int)comp_capacity(n, h->opt.min_pixels);
     fd[f].chunk0 = (int)(at / kChunk);
-    for (int r = 0; r < fr.height; ++r)
-      std::memcpy(px + at + (size_t)r * (size_t)fr.width, fr.image + (size_t)r * (size_t)fr.stride, (size_t)fr.width);
+    slslam::pack_rows(px + at, fr.image, fr.width, fr.height, fr.stride);
     at += align_chunk(n);
     comp0 += comp_capacity(n, h->opt.min_pixels);
   }
@@ -157,11 +146,7 @@ extern "C" int slslam_line_detector_run(slslam_line_detector* h, int num_frames,
   G.npix = reinterpret_cast<int*>(d_out + y.o_npix);
   G.label = reinterpret_cast<int*>(d_out + y.o_label);
 
-  if (h->timing && !h->ev0) {
-    HIP_TRY(hipEventCreate(&h->ev0));
-    HIP_TRY(hipEventCreate(&h->ev1));
-  }
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev0, s));
+  if ((rc = h->timer_start()) != SLSLAM_OK) return rc;
   const Options& o = h->opt;
   const dim3 per_chunk((unsigned)max_chunks, (unsigned)F), per_tile((unsigned)max_tiles, (unsigned)F), per_frame((unsigned)F);
   const dim3 per_comp((unsigned)((max_comps + kBlock - 1) / kBlock), (unsigned)F), block(kBlock);
@@ -177,17 +162,13 @@ extern "C" int slslam_line_detector_run(slslam_line_detector* h, int num_frames,
   hipLaunchKernelGGL(k_extent, per_chunk, block, 0, s, P);
   hipLaunchKernelGGL(k_emit, per_frame, block, 0, s, P, G, o.min_length, o.max_thickness, o.max_segments);
   HIP_TRY(hipGetLastError());
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev1, s));
+  if ((rc = h->timer_stop()) != SLSLAM_OK) return rc;
 
   // ---- one download
   char* ho = hb + y.in_bytes;
   HIP_TRY(hipMemcpyAsync(ho, d_out, labels ? y.out_bytes_labels : y.out_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (h->timing) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->last_kernel_ms = ms;
-  }
+  if ((rc = h->timer_read()) != SLSLAM_OK) return rc;
   const FrameOut* fo = reinterpret_cast<const FrameOut*>(ho);
   for (int f = 0; f < F; ++f) {
     const slslam_line_detect_result& r = results[f];

@@ -7,15 +7,11 @@
 //   k_track_copy    the carried frame (segments, flags, descriptors, ids, ages) from the handle's carried block to the front of the
 //                   regions before the other launches, and the run's last frame to the carried block after them.  A segment without
 //                   an id is carried as not valid: it is nobody's partner.
-//   k_track_pairs   one wave per (frame, 64 rows): lane <-> row, its geometry in registers.  The problem's columns are staged in LDS
-//                   once, after the warp, as four doubles each, with one flag (valid and not short).
-//                   Pass 1, the gate: columns go by in ascending order in groups of kGroup = 8; a lane reads a column from one LDS
-//                   address for the whole wave (a broadcast) and keeps the group's eight verdicts as a byte at s_mask[group][lane];
-//                   a ballot per group says whether any lane admits any of its eight: bit g of the wave-uniform word `active`.
-//                   Pass 2, the chains: only the groups whose bit is set, in ascending order, exactly as k_stereo_pairs
-//                   (stereo_match.h) runs them - the tile [D][8], the next active group's fetch in flight, the eight chains
-//                   r_j = 1.0f; r_j -= q[i] * k_j[i] side by side - and per column offer_key / take_pair (mutual_match.h) under
-//                   (verdict, r finite, r < max_distance).  A skipped group would have offered and taken nothing.
+//   k_gated_pairs<Pairs>  (gated_pairs.h) one wave per (frame, 64 rows): lane <-> row, its geometry in registers.  Pairs below is
+//                   what that kernel asks of the tracker: the problem's columns staged in LDS once, after the warp, as four doubles
+//                   each, with one flag (valid and not short), and the temporal gate on a row and a staged column.  The gate pass,
+//                   the chains of the groups somebody admits and offer_key / take_pair are the shared kernel's, as the stereo
+//                   matcher runs them (stereo_match.h).
 //   k_mutual_finish (mutual_match.h), unchanged.
 //   k_track_status  one wave per frame: segment_status, and by ballots the rank of every NEW segment among those of its frame and
 //                   the frame's count of them.
@@ -29,18 +25,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include "gated_pairs.h"
 #include "line_track_layout.h"
-#include "mutual_match.h"
 
-// every product and difference of the chain and of the gate is rounded on its own
+// every product and difference of the gate is rounded on its own, as those of the chain are (gated_pairs.h)
 #pragma STDC FP_CONTRACT OFF
 
 namespace slslam_track {
 
-using slslam::ordered;
-
-constexpr int kQueryStride = 65;        // floats between value i and value i + 1 of the staged row descriptors (descriptor_match.h)
-constexpr int kTileLoads = kMaxD / 8;   // floats a lane fetches for a group of the largest D
+using slslam::gated::pairs_lds_bytes;
 
 using Out = slslam::MatchOut;           // best_value / second_value = the distances
 
@@ -66,9 +59,6 @@ struct FrameRef {
   int *id, *age;
 };
 
-// dynamic LDS of k_track_pairs: the group's tile [D][8] and the row descriptors [D][kQueryStride]
-inline size_t pairs_lds_bytes(int D) { return 4 * ((size_t)D * kGroup + (size_t)D * kQueryStride); }
-
 // any grid of 64-lane blocks; n <= kMaxSegments
 __global__ __launch_bounds__(64) void k_track_copy(FrameRef dst, FrameRef src, int n, int D) {
   const int i0 = blockIdx.x * 64 + threadIdx.x, step = gridDim.x * 64;
@@ -82,120 +72,35 @@ __global__ __launch_bounds__(64) void k_track_copy(FrameRef dst, FrameRef src, i
   for (int e = i0; e < n * D; e += step) dst.desc[e] = src.desc[e];
 }
 
-// blockIdx = (64 rows, frame); dynamic LDS pairs_lds_bytes(D)
-__global__ __launch_bounds__(64) void k_track_pairs(In in, int D, Gate gate, unsigned long long* __restrict__ keys, Out out) {
-  extern __shared__ __attribute__((aligned(16))) float s_mem[];
-  __shared__ Ends s_col[kMaxSegments];
-  __shared__ unsigned char s_cok[kMaxSegments];
-  __shared__ unsigned char s_mask[kMaxGroups * 64];
-  float* tile = s_mem;                                           // [D][8]: the group the wave works on
-  const float4* tile4 = reinterpret_cast<const float4*>(s_mem);
-  float* sq = s_mem + (size_t)D * kGroup;                        // [D][kQueryStride]
-  const FrameDesc fd = in.frames[blockIdx.y];
-  const slslam::Span sp = fd.span;
-  const int lane = threadIdx.x;
-  const int a_base = blockIdx.x * 64;
-  if (a_base >= sp.n) return;                                    // (the whole wave)
-  const int a = a_base + lane;
-  const bool avalid = a < sp.n;
-  float best = __builtin_huge_valf(), second = __builtin_huge_valf();
-  int best_j = -1, count = 0;
-  const int m = sp.m;
-  if (m > 0) {
-    // ---- the lane's row; the problem's columns, warped
-    const float4 rs = avalid ? in.seg[sp.a0 + a] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+// What k_gated_pairs (gated_pairs.h) asks of the tracker: rows = a frame's segments, columns = those of the frame before it, which lie
+// in the same regions (for frame 0 the carried frame, in front)
+struct Pairs {
+  using In = slslam_track::In;
+  using Gate = slslam_track::Gate;
+  using FrameDesc = slslam_track::FrameDesc;
+  using Segment = slslam_track::Segment;
+  struct Columns {                      // after the warp, four doubles each, with one flag: valid and not short
+    Ends col[kMaxSegments];
+    unsigned char ok[kMaxSegments];
+  };
+  static __device__ __forceinline__ Segment row(const In& in, long long at, bool valid, const Gate& gate, bool& ok) {
+    const float4 rs = valid ? in.seg[at] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const Segment A = segment_of(ends_of(rs.x, rs.y, rs.z, rs.w));
-    const bool aok = avalid && in.ok[sp.a0 + a] != 0 && !is_short(A, gate);
-    for (int b = lane; b < m; b += 64) {
-      const float4 cs = in.seg[sp.j0 + b];
-      const Ends e = ends_of(cs.x, cs.y, cs.z, cs.w);
-      s_col[b] = warped(e, fd.warp);
-      s_cok[b] = in.ok[sp.j0 + b] != 0 && !is_short(segment_of(e), gate) ? 1 : 0;
-    }
-    // the wave's row descriptors, transposed: rows are contiguous in the upload, read coalesced; rows past n are zeros
-    {
-      const int rows = sp.n - a_base < 64 ? sp.n - a_base : 64;
-      const float* src = in.desc + ((size_t)sp.a0 + (size_t)a_base) * D;
-      int row = 0, i = lane;
-      for (int e = lane; e < 64 * D; e += 64) {
-        while (i >= D) { i -= D; ++row; }
-        sq[i * kQueryStride + row] = row < rows ? src[e] : 0.0f;
-        i += 64;
-      }
-    }
-    __syncthreads();
-
-    // ---- pass 1: the gate
-    const int ng = (m + kGroup - 1) / kGroup;
-    unsigned long long active = 0ull;
-    for (int g = 0; g < ng; ++g) {
-      unsigned mask = 0u;
-#pragma unroll
-      for (int jj = 0; jj < kGroup; ++jj) {
-        const int j = g * kGroup + jj;
-        if (j < m) {                                             // (wave-uniform)
-          const Segment B = segment_of(s_col[j]);
-          const bool adm = aok && s_cok[j] != 0 && gate_admits(A, B, gate);
-          mask |= adm ? 1u << jj : 0u;
-        }
-      }
-      s_mask[g * 64 + lane] = (unsigned char)mask;               // (read back by this lane alone)
-      if (__ballot(mask != 0u) != 0ull) active |= 1ull << g;
-    }
-
-    // ---- pass 2: the chains of the groups somebody admits
-    const int nc = D / 8;                                        // floats a lane fetches per group
-    const int tj = lane & 7, ti = lane >> 3;
-    const float* cd = in.desc + (size_t)sp.j0 * D;
-    float nxt[kTileLoads];
-    int g = active != 0ull ? __ffsll((long long)active) - 1 : -1;
-    if (g >= 0) {
-      const int j = g * kGroup + tj;
-#pragma unroll
-      for (int c = 0; c < kTileLoads; ++c) nxt[c] = (c < nc && j < m) ? cd[(size_t)j * D + ti + 8 * c] : 0.0f;
-    }
-    while (g >= 0) {
-      __syncthreads();                                           // (the wave is done with the group before)
-#pragma unroll
-      for (int c = 0; c < kTileLoads; ++c)
-        if (c < nc) tile[lane + 64 * c] = nxt[c];
-      __syncthreads();
-      const unsigned long long rest = g + 1 < 64 ? active >> (g + 1) : 0ull;
-      const int gn = rest != 0ull ? g + 1 + (__ffsll((long long)rest) - 1) : -1;
-      if (gn >= 0) {
-        const int j = gn * kGroup + tj;
-#pragma unroll
-        for (int c = 0; c < kTileLoads; ++c) nxt[c] = (c < nc && j < m) ? cd[(size_t)j * D + ti + 8 * c] : 0.0f;
-      }
-      float r[kGroup];
-#pragma unroll
-      for (int j = 0; j < kGroup; ++j) r[j] = 1.0f;
-      for (int d = 0; d < D; ++d) {
-        const float qi = sq[d * kQueryStride + lane];
-        const float4 k0 = tile4[2 * d], k1 = tile4[2 * d + 1];
-        const float kv[kGroup] = { k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w };
-#pragma unroll
-        for (int j = 0; j < kGroup; ++j) {
-          const float p = qi * kv[j];
-          r[j] = r[j] - p;
-        }
-      }
-      const unsigned mask = s_mask[g * 64 + lane];
-#pragma unroll
-      for (int jj = 0; jj < kGroup; ++jj) {
-        const int j = g * kGroup + jj;
-        const float rj = r[jj];
-        const bool adm = ((mask >> jj) & 1u) != 0u && isfinite(rj) && (double)rj < gate.max_distance;
-        slslam::offer_key(adm, ordered(rj), a, keys, sp.j0 + j);
-        slslam::take_pair(adm, rj, j, best, second, best_j, count);
-      }
-      g = gn;
-    }
+    ok = valid && in.ok[at] != 0 && !is_short(A, gate);
+    return A;
   }
-  if (!avalid) return;
-  const long long at = sp.a0 + a;
-  out.best[at] = best_j; out.best_value[at] = best; out.second_value[at] = second; out.num_admissible[at] = count;
-}
+  static __device__ __forceinline__ void stage(Columns& c, const In& in, const FrameDesc& fd, const Gate& gate, int b) {
+    const float4 cs = in.seg[fd.span.j0 + b];
+    const Ends e = ends_of(cs.x, cs.y, cs.z, cs.w);
+    c.col[b] = warped(e, fd.warp);
+    c.ok[b] = in.ok[fd.span.j0 + b] != 0 && !is_short(segment_of(e), gate) ? 1 : 0;
+  }
+  static __device__ __forceinline__ bool admits(const Columns& c, const Segment& A, int j, const Gate& gate) {
+    return c.ok[j] != 0 && gate_admits(A, segment_of(c.col[j]), gate);
+  }
+  static __device__ __forceinline__ const float* row_descriptors(const In& in) { return in.desc; }
+  static __device__ __forceinline__ const float* column_descriptors(const In& in) { return in.desc; }
+};
 
 // blockIdx.x = frame; after k_mutual_finish
 __global__ __launch_bounds__(64) void k_track_status(In in, Gate gate, const int* __restrict__ match, Ids ids) {

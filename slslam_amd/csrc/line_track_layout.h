@@ -26,9 +26,11 @@
 
 namespace slslam_track {
 
-constexpr int kMaxD = 128, kMaxSegments = 512;
-constexpr int kGroup = 8;                                // previous segments whose chains a lane carries at a time (descriptor_match.h)
-constexpr int kMaxGroups = kMaxSegments / kGroup;        // 64: the groups of a frame are the bits of one 64-bit word
+// the limits and the validation of a gated problem (call_layout.h)
+using slslam::gated::kMaxD;
+using slslam::gated::kMaxSegments;
+using slslam::gated::segment_ok;
+using slslam::gated::shape_valid;
 constexpr int kScanWidth = 64;                           // frames k_track_prefix sums per pass: one wave
 
 // per-segment status: the values of SLSLAM_TRACK_* (the api file asserts it)
@@ -59,10 +61,6 @@ inline bool options_valid(const slslam_line_track_options* o) {
          o->min_length >= 0.0 && !std::isnan(o->ratio) && !std::isnan(o->max_distance);
 }
 
-inline bool shape_valid(int D, int max_frames, int max_segments) {
-  return D >= 8 && D <= kMaxD && D % 8 == 0 && max_frames >= 1 && max_segments >= 1 && max_segments <= kMaxSegments;
-}
-
 inline bool frame_valid(const slslam_line_track_frame& f, int max_segments) {
   if (f.num_segments < 0 || f.num_segments > max_segments) return false;
   if (f.num_segments > 0 && (!f.segments || !f.descriptors)) return false;
@@ -74,15 +72,6 @@ inline bool frame_valid(const slslam_line_track_frame& f, int max_segments) {
 
 // next_id + the run's segments must stay an int: every one of them may be NEW
 inline bool ids_fit(int next_id, long long segments) { return next_id >= 0 && (long long)next_id + segments <= (long long)INT_MAX; }
-
-// valid: the four floats and the D descriptor floats are finite
-inline int segment_ok(const float* seg, const float* desc, int D) {
-  for (int q = 0; q < 4; ++q)
-    if (!std::isfinite(seg[q])) return 0;
-  for (int i = 0; i < D; ++i)
-    if (!std::isfinite(desc[i])) return 0;
-  return 1;
-}
 
 inline Gate gate_of(const slslam_line_track_options& o) {
   return Gate{o.max_tan2, o.max_shift * o.max_shift, o.max_offset * o.max_offset, o.min_overlap, o.min_length * o.min_length, o.max_distance};

@@ -21,10 +21,9 @@
 
 using namespace slslam_match;
 using slslam::device_present;
+using slslam::kMaxGridY;
 
 namespace {
-
-constexpr int kMaxGrid = 65535;         // what the y dimension of a grid takes: frames go in slices of it
 
 // Where everything of a call lies: the upload (the same offsets on the host and on the device), the device's work arrays behind it,
 // and the result block (on the host behind the upload)
@@ -157,8 +156,8 @@ extern "C" int slslam_line_matcher_run(slslam_line_matcher* m, int num_frames, c
 
   // ---- three launches for all frames
   const unsigned tk = (unsigned)((maxK + 63) / 64), tl = (unsigned)((maxL + 63) / 64);
-  for (int f0 = 0; f0 < F; f0 += kMaxGrid) {
-    const unsigned nf = (unsigned)std::min(F - f0, kMaxGrid);
+  for (int f0 = 0; f0 < F; f0 += kMaxGridY) {
+    const unsigned nf = (unsigned)std::min(F - f0, kMaxGridY);
     Out of = o;
     of.num_matched += f0;
     if (tk > 0 && tl > 0)                                        // (a frame that runs has observations and lines)

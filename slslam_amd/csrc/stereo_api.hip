@@ -2,7 +2,7 @@
 // between the detector and MSLD, which give two unrelated lists of segments per stereo frame, and everything that takes a stereo line
 // observation.  Per run, whatever the number of frames:
 //   upload   one block [FrameDesc F | left segments | right segments | left flags | right flags | left descriptors | right descriptors]
-//   pairs    k_stereo_pairs: the epipolar gate, then the descriptor chains of the groups somebody admits -> per left segment (best,
+//   pairs    k_gated_pairs<Pairs> (gated_pairs.h): the epipolar gate, then the descriptor chains of the groups somebody admits -> per left segment (best,
 //            second, count), per right segment the key of its best left segment
 //   finish   k_mutual_finish (mutual_match.h): mutual and ratio tests, matches, num_matched
 //   emit     k_stereo_emit: segment_status, the eight normalised doubles and the two disparities of every matched left segment
@@ -22,27 +22,15 @@
 
 using namespace slslam_stereo;
 using slslam::device_present;
+using slslam::kMaxGridY;
 
 static_assert(kMaxD == SLSLAM_STEREO_MAX_D && kMaxSegments == SLSLAM_STEREO_MAX_SEGMENTS, "the header's limits are the kernels'");
 static_assert(kMatched == SLSLAM_STEREO_MATCHED && kUnmatched == SLSLAM_STEREO_UNMATCHED && kFlat == SLSLAM_STEREO_FLAT &&
               kInvalid == SLSLAM_STEREO_INVALID, "the header's statuses are the kernels'");
 
-namespace {
-
-constexpr int kMaxGrid = 65535;         // what the y dimension of a grid takes: frames go in slices of it
-
-}  // namespace
-
-struct slslam_stereo_matcher : slslam::Handle {
+struct slslam_stereo_matcher : slslam::TimedHandle {
   int D = 0, max_frames = 0, max_segments = 0;
   slslam::BlockPair block;
-  double last_kernel_ms = 0.0;                           // the last run's launches by events, when timing is on
-  bool timing = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~slslam_stereo_matcher() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
 };
 
 extern "C" void slslam_stereo_match_default_options(slslam_stereo_match_options* opt) {
@@ -75,10 +63,7 @@ extern "C" int slslam_stereo_matcher_stats(const slslam_stereo_matcher* h, long 
 }
 
 extern "C" int slslam_stereo_matcher_timing(slslam_stereo_matcher* h, int enable, double* kernel_ms) {
-  if (!h) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (enable >= 0) h->timing = enable != 0;
-  if (kernel_ms) *kernel_ms = h->last_kernel_ms;
-  return SLSLAM_OK;
+  return slslam::handle_timing(h, enable, kernel_ms);
 }
 
 extern "C" int slslam_stereo_matcher_run(slslam_stereo_matcher* h, const slslam_stereo_match_options* opt, int num_frames,
@@ -122,17 +107,8 @@ extern "C" int slslam_stereo_matcher_run(slslam_stereo_matcher* h, const slslam_
     const slslam_stereo_frame& fr = frames[f];
     const slslam::Span& sp = span[(size_t)f];
     fd[f].span = sp;
-    const size_t n = (size_t)sp.n, m = (size_t)sp.m, a0 = (size_t)sp.a0, j0 = (size_t)sp.j0;
-    if (n > 0) {
-      std::memcpy(lseg + 4 * a0, fr.left_segments, 16 * n);
-      std::memcpy(ldesc + a0 * (size_t)D, fr.left_descriptors, 4 * n * (size_t)D);
-      for (size_t i = 0; i < n; ++i) lok[a0 + i] = segment_ok(fr.left_segments + 4 * i, fr.left_descriptors + i * (size_t)D, D);
-    }
-    if (m > 0) {
-      std::memcpy(rseg + 4 * j0, fr.right_segments, 16 * m);
-      std::memcpy(rdesc + j0 * (size_t)D, fr.right_descriptors, 4 * m * (size_t)D);
-      for (size_t i = 0; i < m; ++i) rok[j0 + i] = segment_ok(fr.right_segments + 4 * i, fr.right_descriptors + i * (size_t)D, D);
-    }
+    slslam::gated::fill_side(lseg, ldesc, lok, (size_t)sp.a0, fr.left_segments, fr.left_descriptors, (size_t)sp.n, D);
+    slslam::gated::fill_side(rseg, rdesc, rok, (size_t)sp.j0, fr.right_segments, fr.right_descriptors, (size_t)sp.m, D);
   }
   HIP_TRY(hipMemcpyAsync(dv, hb, y.in_bytes, hipMemcpyHostToDevice, s));
   In in;
@@ -155,36 +131,28 @@ extern "C" int slslam_stereo_matcher_run(slslam_stereo_matcher* h, const slslam_
   // ---- three launches for all frames
   const Gate gate = gate_of(*opt);
   const Camera cam = camera_of(*opt);
-  if (h->timing && !h->ev0) {
-    HIP_TRY(hipEventCreate(&h->ev0));
-    HIP_TRY(hipEventCreate(&h->ev1));
-  }
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev0, s));
+  if ((rc = h->timer_start()) != SLSLAM_OK) return rc;
   const unsigned tn = (unsigned)((maxN + 63) / 64), tm = (unsigned)((maxM + 63) / 64);
-  for (int f0 = 0; f0 < F; f0 += kMaxGrid) {
-    const unsigned nf = (unsigned)std::min(F - f0, kMaxGrid);
+  for (int f0 = 0; f0 < F; f0 += kMaxGridY) {
+    const unsigned nf = (unsigned)std::min(F - f0, kMaxGridY);
     Out of = o;
     of.num_matched += f0;
     In inf = in;
     inf.frames += f0;
-    if (tn > 0) hipLaunchKernelGGL(k_stereo_pairs, dim3(tn, nf), dim3(64), pairs_lds_bytes(D), s, inf, D, gate, d_keys, of);
+    if (tn > 0) hipLaunchKernelGGL(slslam::gated::k_gated_pairs<Pairs>, dim3(tn, nf), dim3(64), pairs_lds_bytes(D), s, inf, D, gate, d_keys, of);
     if (std::max(tn, tm) > 0)
       hipLaunchKernelGGL(slslam::k_mutual_finish<FrameDesc>, dim3(std::max(tn, tm), nf), dim3(64), 0, s, inf.frames,
                          (const unsigned long long*)d_keys, opt->ratio, of);
     if (tn > 0) hipLaunchKernelGGL(k_stereo_emit, dim3(tn, nf), dim3(64), 0, s, inf, gate, cam, (const int*)o.match, eo);
   }
   HIP_TRY(hipGetLastError());
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev1, s));
+  if ((rc = h->timer_stop()) != SLSLAM_OK) return rc;
 
   // ---- one download
   char* h_out = hb + y.in_bytes;
   HIP_TRY(hipMemcpyAsync(h_out, d_out, y.out_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (h->timing) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->last_kernel_ms = ms;
-  }
+  if ((rc = h->timer_read()) != SLSLAM_OK) return rc;
   const int* st = reinterpret_cast<const int*>(h_out + y.o_status);
   for (int f = 0; f < F; ++f) {
     const slslam::Span& sp = span[(size_t)f];

@@ -25,9 +25,11 @@
 
 namespace slslam_stereo {
 
-constexpr int kMaxD = 128, kMaxSegments = 512;
-constexpr int kGroup = 8;                                // right segments whose chains a lane carries at a time (descriptor_match.h)
-constexpr int kMaxGroups = kMaxSegments / kGroup;        // 64: the groups of a frame are the bits of one 64-bit word
+// the limits and the validation of a gated problem (call_layout.h)
+using slslam::gated::kMaxD;
+using slslam::gated::kMaxSegments;
+using slslam::gated::segment_ok;
+using slslam::gated::shape_valid;
 
 // per-segment status: the values of SLSLAM_STEREO_* (the api file asserts it)
 enum Status { kMatched = 0, kUnmatched = 1, kFlat = 2, kInvalid = 3 };
@@ -55,24 +57,11 @@ inline bool options_valid(const slslam_stereo_match_options* o) {
          o->min_overlap <= 1.0 && !std::isnan(o->ratio) && !std::isnan(o->max_distance) && o->fx != 0.0 && o->fy != 0.0;
 }
 
-inline bool shape_valid(int D, int max_frames, int max_segments) {
-  return D >= 8 && D <= kMaxD && D % 8 == 0 && max_frames >= 1 && max_segments >= 1 && max_segments <= kMaxSegments;
-}
-
 inline bool frame_valid(const slslam_stereo_frame& f, int max_segments) {
   if (f.num_left < 0 || f.num_left > max_segments || f.num_right < 0 || f.num_right > max_segments) return false;
   if (f.num_left > 0 && (!f.left_segments || !f.left_descriptors)) return false;
   if (f.num_right > 0 && (!f.right_segments || !f.right_descriptors)) return false;
   return true;
-}
-
-// valid: the four floats and the D descriptor floats are finite
-inline int segment_ok(const float* seg, const float* desc, int D) {
-  for (int q = 0; q < 4; ++q)
-    if (!std::isfinite(seg[q])) return 0;
-  for (int i = 0; i < D; ++i)
-    if (!std::isfinite(desc[i])) return 0;
-  return 1;
 }
 
 inline Gate gate_of(const slslam_stereo_match_options& o) {

@@ -3,7 +3,7 @@
 // number of frames:
 //   upload   one block [FrameDesc T | segments | flags | descriptors], each region with room for the carried frame in front
 //   carry in k_track_copy: the carried frame from the handle's carried block into that room
-//   pairs    k_track_pairs: the temporal gate, then the descriptor chains of the groups somebody admits
+//   pairs    k_gated_pairs<Pairs> (gated_pairs.h): the temporal gate, then the descriptor chains of the groups somebody admits
 //   finish   k_mutual_finish (mutual_match.h): mutual and ratio tests, matches, the number continued
 //   status   k_track_status: segment_status, the rank and the count of the NEW segments of every frame
 //   prefix   k_track_prefix: the NEW segments before every frame
@@ -25,29 +25,17 @@
 
 using namespace slslam_track;
 using slslam::device_present;
+using slslam::kMaxGridY;
 
 static_assert(kMaxD == SLSLAM_TRACK_MAX_D && kMaxSegments == SLSLAM_TRACK_MAX_SEGMENTS, "the header's limits are the kernels'");
 static_assert(kContinued == SLSLAM_TRACK_CONTINUED && kNew == SLSLAM_TRACK_NEW && kShort == SLSLAM_TRACK_SHORT &&
               kInvalid == SLSLAM_TRACK_INVALID, "the header's statuses are the kernels'");
 
-namespace {
-
-constexpr int kMaxGrid = 65535;         // what the y dimension of a grid takes: frames go in slices of it
-
-}  // namespace
-
-struct slslam_line_tracker : slslam::Handle {
+struct slslam_line_tracker : slslam::TimedHandle {
   int D = 0, max_frames = 0, max_segments = 0;
   int next_id = 0, carried = 0;                          // the state: the carried frame's segments lie in `carry`
   slslam::BlockPair block;
   slslam::GrowBuf carry{slslam::Mem::kDevice};
-  double last_kernel_ms = 0.0;                           // the last run's launches by events, when timing is on
-  bool timing = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~slslam_line_tracker() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
 };
 
 extern "C" void slslam_line_track_default_options(slslam_line_track_options* opt) {
@@ -78,10 +66,7 @@ extern "C" int slslam_line_tracker_stats(const slslam_line_tracker* h, long long
 }
 
 extern "C" int slslam_line_tracker_timing(slslam_line_tracker* h, int enable, double* kernel_ms) {
-  if (!h) return SLSLAM_ERR_INVALID_ARGUMENT;
-  if (enable >= 0) h->timing = enable != 0;
-  if (kernel_ms) *kernel_ms = h->last_kernel_ms;
-  return SLSLAM_OK;
+  return slslam::handle_timing(h, enable, kernel_ms);
 }
 
 extern "C" int slslam_line_tracker_reset(slslam_line_tracker* h, int next_id) {
@@ -152,12 +137,7 @@ extern "C" int slslam_line_tracker_run(slslam_line_tracker* h, const slslam_line
     const slslam::Span& sp = span[(size_t)f];
     fd[f].span = sp;
     fd[f].warp = warp_of(fr.predict);
-    const size_t n = (size_t)sp.n, a0 = (size_t)sp.a0;
-    if (n > 0) {
-      std::memcpy(seg + 4 * a0, fr.segments, 16 * n);
-      std::memcpy(desc + a0 * (size_t)D, fr.descriptors, 4 * n * (size_t)D);
-      for (size_t i = 0; i < n; ++i) ok[a0 + i] = segment_ok(fr.segments + 4 * i, fr.descriptors + i * (size_t)D, D);
-    }
+    slslam::gated::fill_side(seg, desc, ok, (size_t)sp.a0, fr.segments, fr.descriptors, (size_t)sp.n, D);
   }
   HIP_TRY(hipMemcpyAsync(dv, hb, y.in_bytes, hipMemcpyHostToDevice, s));
   In in;
@@ -189,43 +169,35 @@ extern "C" int slslam_line_tracker_run(slslam_line_tracker* h, const slslam_line
 
   // ---- seven launches for all frames
   const Gate gate = gate_of(*opt);
-  if (h->timing && !h->ev0) {
-    HIP_TRY(hipEventCreate(&h->ev0));
-    HIP_TRY(hipEventCreate(&h->ev1));
-  }
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev0, s));
+  if ((rc = h->timer_start()) != SLSLAM_OK) return rc;
   const auto copy_grid = [D](int n) { return dim3((unsigned)std::min((n * D + 63) / 64, 256)); };
   if (C > 0) hipLaunchKernelGGL(k_track_copy, copy_grid(C), dim3(64), 0, s, front, kept, C, D);
   const unsigned tn = (unsigned)((maxN + 63) / 64), tm = (unsigned)((maxM + 63) / 64);
-  for (int f0 = 0; f0 < F; f0 += kMaxGrid) {
-    const unsigned nf = (unsigned)std::min(F - f0, kMaxGrid);
+  for (int f0 = 0; f0 < F; f0 += kMaxGridY) {
+    const unsigned nf = (unsigned)std::min(F - f0, kMaxGridY);
     Out of = o;
     of.num_matched += f0;
     In inf = in;
     inf.frames += f0;
-    if (tn > 0) hipLaunchKernelGGL(k_track_pairs, dim3(tn, nf), dim3(64), pairs_lds_bytes(D), s, inf, D, gate, d_keys, of);
+    if (tn > 0) hipLaunchKernelGGL(slslam::gated::k_gated_pairs<Pairs>, dim3(tn, nf), dim3(64), pairs_lds_bytes(D), s, inf, D, gate, d_keys, of);
     if (std::max(tn, tm) > 0)
       hipLaunchKernelGGL(slslam::k_mutual_finish<FrameDesc>, dim3(std::max(tn, tm), nf), dim3(64), 0, s, inf.frames,
                          (const unsigned long long*)d_keys, opt->ratio, of);
   }
   hipLaunchKernelGGL(k_track_status, dim3((unsigned)F), dim3(64), 0, s, in, gate, (const int*)o.match, ids);
   hipLaunchKernelGGL(k_track_prefix, dim3(1), dim3(kScanWidth), 0, s, F, ids);
-  for (int f0 = 0; f0 < F && tn > 0; f0 += kMaxGrid)
-    hipLaunchKernelGGL(k_track_ids, dim3(tn, (unsigned)std::min(F - f0, kMaxGrid)), dim3(64), 0, s, in.frames, f0, (const int*)o.match, ids,
+  for (int f0 = 0; f0 < F && tn > 0; f0 += kMaxGridY)
+    hipLaunchKernelGGL(k_track_ids, dim3(tn, (unsigned)std::min(F - f0, kMaxGridY)), dim3(64), 0, s, in.frames, f0, (const int*)o.match, ids,
                        h->next_id);
   if (last.n > 0) hipLaunchKernelGGL(k_track_copy, copy_grid(last.n), dim3(64), 0, s, kept, tail, last.n, D);
   HIP_TRY(hipGetLastError());
-  if (h->timing) HIP_TRY(hipEventRecord(h->ev1, s));
+  if ((rc = h->timer_stop()) != SLSLAM_OK) return rc;
 
   // ---- one download
   char* h_out = hb + y.in_bytes;
   HIP_TRY(hipMemcpyAsync(h_out, d_out, y.out_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (h->timing) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->last_kernel_ms = ms;
-  }
+  if ((rc = h->timer_read()) != SLSLAM_OK) return rc;
   const int* num_new = reinterpret_cast<const int*>(h_out + y.o_new);
   const int* new_before = reinterpret_cast<const int*>(h_out + y.o_before);
   for (int f = 0; f < F; ++f) {

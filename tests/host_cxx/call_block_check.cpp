@@ -1,10 +1,12 @@
 // tests/host_cxx/call_block_check.cpp — the host half of the call-block scaffold (slslam_amd/csrc/call_layout.h, place_layout.h), no
 // device: the layout builder gives the matchers' result block and the place database's two layouts the offsets their hand-written
 // sums gave (the sums are written out below), every region at a multiple of 256 bytes and none over another; the result scatter
-// writes exactly the ranges asked for, under NULL arrays and empty problems.  Built with -fsanitize=address,undefined and run by
+// writes exactly the ranges asked for, under NULL arrays and empty problems; the image copy drops the stride and nothing else; a gated
+// problem's upload copies its segments and descriptors to their places and flags the non-finite ones.  Built with -fsanitize=address,undefined and run by
 // tests/test_call_block_cpu.py.  Prints "call block ok" and exits 0, or says what is wrong and exits 1.
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <utility>
 #include <vector>
 
@@ -177,6 +179,73 @@ static void check_scatter() {
   }
 }
 
+// pack_rows: destinations of exactly width * height bytes on the heap; the bytes of a source row past `width` carry a poison value
+static void check_pack_rows() {
+  const unsigned char kPoison = 0xEE;
+  const int shapes[][3] = { { 5, 4, 5 }, { 5, 4, 9 }, { 7, 0, 7 }, { 1, 6, 1 }, { 1, 6, 3 }, { 64, 3, 100 } };      // width, height, stride
+  for (const auto& s : shapes) {
+    const int w = s[0], h = s[1], stride = s[2];
+    std::snprintf(ctx, sizeof ctx, "width %d, height %d, stride %d", w, h, stride);
+    std::vector<unsigned char> src((size_t)h * (size_t)stride, kPoison);
+    for (int r = 0; r < h; ++r)
+      for (int c = 0; c < w; ++c) src[(size_t)r * stride + c] = (unsigned char)((r * 31 + c * 7) % 200);        // (never the poison)
+    unsigned char* dst = new unsigned char[(size_t)w * (size_t)h];                // exactly: a write past it is the sanitizer's
+    std::memset(dst, 0x11, (size_t)w * (size_t)h);
+    slslam::pack_rows(dst, h > 0 ? src.data() : nullptr, w, h, stride);
+    for (int r = 0; r < h; ++r)
+      for (int c = 0; c < w; ++c)
+        EXPECT(dst[(size_t)r * w + c] == (unsigned char)((r * 31 + c * 7) % 200), "pack_rows (%s): row %d, column %d: %d", ctx, r, c,
+               dst[(size_t)r * w + c]);
+    delete[] dst;
+  }
+}
+
+// fill_side: regions of exactly a0 + n entries; the places below a0 stay as they were
+static void check_fill_side() {
+  const float kInf = std::numeric_limits<float>::infinity(), kNan = std::numeric_limits<float>::quiet_NaN();
+  {                                                            // nothing to copy: null sources are not read, nothing is written
+    std::vector<float> seg(4 * 3, 7.0f), desc(8 * 3, 7.0f);
+    std::vector<int> ok(3, 7);
+    slslam::gated::fill_side(seg.data(), desc.data(), ok.data(), 3, nullptr, nullptr, 0, 8);
+    for (float v : seg) EXPECT(v == 7.0f, "fill_side, n 0: a segment float was written");
+    for (float v : desc) EXPECT(v == 7.0f, "fill_side, n 0: a descriptor float was written");
+    for (int v : ok) EXPECT(v == 7, "fill_side, n 0: a flag was written");
+  }
+  const size_t cases[][3] = { { 1, 8, 0 }, { 1, 128, 2 }, { 5, 8, 3 }, { 5, 128, 0 }, { 65, 8, 1 } };            // n, D, a0
+  for (const auto& c : cases) {
+    const size_t n = c[0], D = c[1], a0 = c[2];
+    for (int bad = 0; bad < 3; ++bad) {                        // 0: all finite; 1: a segment float is not; 2: a descriptor float is not
+      const size_t victim = n / 2;
+      std::snprintf(ctx, sizeof ctx, "n %zu, D %zu, a0 %zu, bad %d", n, D, a0, bad);
+      std::vector<float> src_seg(4 * n), src_desc(D * n);
+      for (size_t i = 0; i < src_seg.size(); ++i) src_seg[i] = (float)i + 0.5f;
+      for (size_t i = 0; i < src_desc.size(); ++i) src_desc[i] = 0.001f * (float)i - 1.0f;
+      if (bad == 1) src_seg[4 * victim + 3] = kNan;
+      if (bad == 2) src_desc[D * victim + D - 1] = kInf;
+      std::vector<float> seg(4 * (a0 + n), -3.0f), desc(D * (a0 + n), -3.0f);      // exactly sized
+      std::vector<int> ok(a0 + n, -3);
+      slslam::gated::fill_side(seg.data(), desc.data(), ok.data(), a0, src_seg.data(), src_desc.data(), n, (int)D);
+      for (size_t i = 0; i < 4 * a0; ++i) EXPECT(seg[i] == -3.0f, "fill_side (%s): segment float %zu below a0 written", ctx, i);
+      for (size_t i = 0; i < D * a0; ++i) EXPECT(desc[i] == -3.0f, "fill_side (%s): descriptor float %zu below a0 written", ctx, i);
+      for (size_t i = 0; i < a0; ++i) EXPECT(ok[i] == -3, "fill_side (%s): flag %zu below a0 written", ctx, i);
+      EXPECT(std::memcmp(seg.data() + 4 * a0, src_seg.data(), 16 * n) == 0, "fill_side (%s): segments", ctx);
+      EXPECT(std::memcmp(desc.data() + D * a0, src_desc.data(), 4 * D * n) == 0, "fill_side (%s): descriptors", ctx);
+      for (size_t i = 0; i < n; ++i) {
+        const int want = bad != 0 && i == victim ? 0 : 1;
+        EXPECT(ok[a0 + i] == want, "fill_side (%s): flag %zu is %d, expected %d", ctx, i, ok[a0 + i], want);
+      }
+    }
+  }
+}
+
+// shape_valid: the table the stereo matcher's and the tracker's layout checks assert
+static void check_shape_valid() {
+  using slslam::gated::shape_valid;
+  EXPECT(shape_valid(8, 1, 1) && shape_valid(72, 64, 512) && shape_valid(128, 1, 512), "shape_valid refuses a valid shape");
+  EXPECT(!shape_valid(0, 1, 1) && !shape_valid(12, 1, 1) && !shape_valid(136, 1, 1) && !shape_valid(72, 0, 1) && !shape_valid(72, 1, 0) &&
+         !shape_valid(72, 1, 513), "shape_valid takes an invalid shape");
+}
+
 int main() {
   // every total 0, P = 1, totals that are and are not multiples of 64 (a region of 64 values is exactly 256 bytes)
   const size_t sizes[][3] = { { 0, 0, 0 }, { 1, 0, 0 }, { 1, 1, 0 }, { 1, 0, 1 }, { 1, 1, 1 }, { 1, 64, 64 }, { 1, 63, 65 }, { 3, 128, 1 },
@@ -188,6 +257,9 @@ int main() {
                               { 7, 1000, 100, 64, 3 }, { 16, 16 * 65, 65, 257, 0 } };
   for (const auto& c : calls) check_call_layout(c[0], c[1], c[2], c[3], c[4]);
   check_scatter();
+  check_pack_rows();
+  check_fill_side();
+  check_shape_valid();
   if (failures) {
     std::printf("%d checks failed\n", failures);
     return 1;

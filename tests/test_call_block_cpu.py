@@ -1,6 +1,6 @@
 """The scaffold the matchers and the place database share, no GPU: the host half (csrc/call_layout.h, place_layout.h) under the
 sanitizers as a stand-alone program, the shape of the sources that use the shared headers, and the binding's one helper behind the
-matchers' buffers."""
+matchers' buffers and one timed handle behind the image front end."""
 import ctypes as C
 import glob
 import os
@@ -8,6 +8,7 @@ import re
 import subprocess
 
 import numpy as np
+import pytest
 
 from slslam_amd import capi
 
@@ -52,6 +53,55 @@ def test_the_matchers_share_one_core_and_one_scaffold():
         assert "match_scatter(" in sources[name] and "std::memcpy(r." not in sources[name], name
     for name in ("match_api.hip", "descriptor_api.hip", "place_api.hip", "place_layout.h", "voctree_train_api.hip"):
         assert not re.search(r"=\s*y\.\w+\s*\+\s*align256\(", sources[name]), name
+
+
+def test_the_front_end_shares_one_pair_kernel_and_one_timed_handle():
+    """One gated pair kernel and one set of its constants (gated_pairs.h, call_layout.h); one pair of events, one grid limit
+    (call_block.h)."""
+    sources = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip"))}
+    assert [name for name, text in sources.items() if re.search(r"\bkQueryStride\s*=", text)] == ["gated_pairs.h"]
+    for name, text in sources.items():
+        assert not re.search(r"__global__[^;{]*\bk_(stereo|track)_pairs\b", text), name
+    for name in ("stereo_match.h", "line_track.h"):
+        assert '#include "gated_pairs.h"' in sources[name] and "__global__ __launch_bounds__(64) void k_gated_pairs" not in sources[name], name
+        assert "__ffsll(" not in sources[name], name
+    assert sources["gated_pairs.h"].count("__global__") == 1 and "#pragma STDC FP_CONTRACT OFF" in sources["gated_pairs.h"]
+    for name in ("stereo_api.hip", "track_api.hip"):
+        assert "k_gated_pairs<Pairs>" in sources[name], name
+    for name in ("descriptor_match.h", "gated_pairs.h"):
+        assert "stage_rows(" in sources[name] and "group_chains(" in sources[name], name
+    for name in ("line_detect_api.hip", "line_descriptor_api.hip", "stereo_api.hip", "track_api.hip"):
+        assert "hipEvent" not in sources[name] and "TimedHandle" in sources[name] and "handle_timing(" in sources[name], name
+    for name in ("line_detect_api.hip", "line_descriptor_api.hip", "stereo_api.hip", "track_api.hip", "match_api.hip", "descriptor_api.hip"):
+        assert "65535" not in sources[name], name
+    assert sources["call_block.h"].count("65535") == 1
+    assert sum(text.count("inline int segment_ok(") for text in sources.values()) == 1
+    assert sum(text.count("inline bool shape_valid(") for text in sources.values()) == 1
+
+
+def test_one_timed_handle_and_one_options_helper_in_the_binding():
+    image = np.zeros((32, 32), dtype=np.uint8)
+    for make, sym in ((capi.LineDescriptor, "slslam_line_descriptor"), (capi.LineDetector, "slslam_line_detector"),
+                      (lambda: capi.StereoMatcher(8), "slslam_stereo_matcher"), (lambda: capi.LineTracker(8), "slslam_line_tracker")):
+        h = make()
+        assert isinstance(h, capi._TimedHandle), sym
+        assert (h._DESTROY, h._STATS, h._TIMING) == (sym + "_destroy", sym + "_stats", sym + "_timing")
+        assert "set_timing" not in vars(type(h)) and "kernel_ms" not in vars(type(h)), sym
+        assert h.kernel_ms() == 0.0
+        h.set_timing(True)
+        h.set_timing(False)
+        assert h.kernel_ms() == 0.0
+        h.close()
+        h.close()
+    with pytest.raises(TypeError, match=r"^unknown stereo match option 'nope'$"):
+        capi.stereo_match_options(nope=1)
+    with pytest.raises(TypeError, match=r"^unknown line track option 'nope'$"):
+        capi.line_track_options(nope=1)
+    assert capi.stereo_match_options(max_disparity=64).max_disparity == 64.0 and capi.line_track_options(max_shift=3).max_shift == 3.0
+    with pytest.raises(ValueError, match=r"^an image is uint8 \[H, W\]$"):
+        capi.describe_lines(image.astype(np.float32), np.zeros((1, 4), dtype=np.float32))
+    with pytest.raises(ValueError, match=r"^an image is uint8 \[H, W\]$"):
+        capi.detect_lines(np.zeros((4, 4, 3), dtype=np.uint8))
 
 
 def test_one_buffers_helper_behind_both_matchers():
