@@ -1575,6 +1575,118 @@ int  slslam_line_tracker_timing(slslam_line_tracker* tracker, int enable, double
 int  slslam_track_lines(int D, const slslam_line_track_options* options, int num_frames, const slslam_line_track_frame* frames,
                         slslam_line_track_result* out);
 
+/* ------------------------------------------------------------------ image rectification: from a rig's raw images to what the detector takes
+ * What turns the raw, lens-distorted, not row-aligned grey images of a stereo rig into the rectified - and optionally pre-smoothed -
+ * images that slslam_line_detector_run, slslam_line_descriptor_run and the "common rows" gate of slslam_stereo_matcher_run assume
+ * (csrc/image_rectify.h).  The reference reads a tracker's files and has no code for any of it - no camera model, no
+ * map, no remap, no smoothing, no rig rectification: there is no counterpart to restate for any entry below, so this block is the
+ * contract, and tests/image_rectify_reference.py restates it in numpy.  The device is held to it bit for bit.
+ *   camera     slslam_rectify_camera (no counterpart in the reference): raw intrinsics fx, fy, cx, cy; Brown-Conrady distortion k1, k2,
+ *              p1, p2, k3; R[9] row-major with x_rect = R x_raw; rectified intrinsics fx2, fy2, cx2, cy2; src_width, src_height (the
+ *              raw image) and dst_width, dst_height (the output), each in 1 .. SLSLAM_LSD_MAX_SIDE.  Every double finite, the four
+ *              focal lengths > 0.  Pixel centres lie at integers.
+ *   map        (no counterpart) for the output pixel (u, v), in double, every operation rounded on its own (no fused multiply-add), in
+ *              this order:  xr = (u - cx2) / fx2, yr = (v - cy2) / fy2;  (X, Y, Z) = R^T (xr, yr, 1), each component as (a xr + b yr)
+ *              + c: X = (R[0] xr + R[3] yr) + R[6], Y = (R[1] xr + R[4] yr) + R[7], Z = (R[2] xr + R[5] yr) + R[8].  Z <= 0 (or NaN), or
+ *              a non-finite sx or sy below: the pixel is invalid and has no coordinates.  Else x = X / Z, y = Y / Z, r2 = x x + y y,
+ *              rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),  xd = x rad + ((2 p1) x y + p2 (r2 + 2 (x x))),  yd = y rad + (p1 (r2 + 2 (y y)) +
+ *              (2 p2) x y), with (2 p1) x y = ((2 p1) x) y;  sx = fx xd + cx, sy = fy yd + cy.
+ *   quantise   (no counterpart) qx = floor(sx 256 + 0.5), qy likewise, as 64-bit integers; the pixel is also invalid when (sx, sy) lies
+ *              outside [-0.5, src_width - 0.5) x [-0.5, src_height - 0.5).  Stored in 32 bits as min(max(qx, -256), 256 src_width) - no
+ *              valid pixel is changed by that, and for an invalid one the remap below reads the same bytes - and as
+ *              SLSLAM_RECTIFY_NO_COORD (with sx = sy = NaN) where the pixel has no coordinates.  The map depends on the camera alone:
+ *              it is computed on the device once per camera and kept in the handle.
+ *   remap      (no counterpart) integers only: ix = qx >> 8, ax = qx & 255 (arithmetic shift, two's complement), the same for y; the
+ *              four neighbours p00 = I(ix, iy), p01 = I(ix + 1, iy), p10 = I(ix, iy + 1), p11 = I(ix + 1, iy + 1) with every index
+ *              clamped into the source; p = ((256 - ax) (256 - ay) p00 + ax (256 - ay) p01 + (256 - ax) ay p10 + ax ay p11 + 32768) >> 16
+ *              (below 2^25).  An invalid pixel gets border_value under SLSLAM_RECTIFY_BORDER_CONSTANT; under _REPLICATE it gets p of
+ *              its stored coordinates - the value at the clamped position - or border_value when it has none.
+ *   smoothing  (no counterpart) off at smooth_sigma = 0, else 0 < smooth_sigma <= 16, applied to the remapped 8-bit image, so a fused
+ *              and an unfused implementation give the same bytes: a separable Gaussian with the integer taps of
+ *              slslam_rectify_smooth_taps: radius = min(7, max(1, ceil(3 sigma))), t_i = floor(w_i / sum_w 16384 + 0.5) for i >= 1 with
+ *              w_i = exp(-i i / (2 sigma sigma)) and sum_w = 1 + 2 sum w_i, t_0 = 16384 - 2 sum t_i.  The taps are an input of the
+ *              contract.  Horizontal: h = (sum t p + 32) >> 6, at most 65280, the value x 256; vertical: (sum t h + 2^21) >> 22; both
+ *              within 31 bits, both replicate at the border of the output image.
+ *   outputs    per frame the image[dst_height][stride], stride >= dst_width; num_valid and valid[dst_height dst_width] (1 / 0), which
+ *              are the camera's (either may be NULL).
+ *   rig        slslam_stereo_rectify (no counterpart; host only, double): from both cameras' raw intrinsics and distortion and the
+ *              pose of the right camera relative to the left, x_right = R x_left + t, by the construction of Fusiello, Trucco and Verri
+ *              (MVA 12, 2000): c = -R^T t, the right centre in the left camera; baseline b = |c| > 0; e1 = c / b; e2 = (-e1.y, e1.x, 0)
+ *              / its norm, which is (0, 0, 1) x e1 - a baseline along the optical axis is SLSLAM_ERR_INVALID_ARGUMENT -; e3 = e1 x e2;
+ *              the left camera's R = rows e1, e2, e3, the right camera's = that R R^T.  Both views share fx2 = fy2 = ((fx + fy of the
+ *              left) + (fx + fy of the right)) / 4 and the left principal point unless has_principal gives (cx2, cy2).  Returns the two
+ *              cameras, b, and intrinsics[4] = fx2, fy2, cx2, cy2: the fx, fy, cx, cy of slslam_stereo_match_options.  The right view
+ *              lies at +b along the rectified x axis: x_right_pixel = x_left_pixel - fx2 b / depth.
+ * No image pyramid, no 16-bit or colour input, no fisheye model; the rectified images return to the host before the detector takes
+ * them.  Frames are independent. */
+enum { SLSLAM_RECTIFY_BORDER_CONSTANT = 0, SLSLAM_RECTIFY_BORDER_REPLICATE = 1 };
+enum { SLSLAM_RECTIFY_SUBPIXEL_BITS = 8, SLSLAM_RECTIFY_MAX_RADIUS = 7,
+       SLSLAM_RECTIFY_TILE_WIDTH = 64, SLSLAM_RECTIFY_TILE_HEIGHT = 16,         /* the smoothing kernel's tile, for tests at its borders */
+       SLSLAM_RECTIFY_NO_COORD = (-2147483647 - 1) };
+typedef struct slslam_rectify_options {
+  int border_mode;               /* SLSLAM_RECTIFY_BORDER_* */
+  int border_value;              /* 0 .. 255 */
+  double smooth_sigma;           /* 0: no smoothing */
+} slslam_rectify_options;
+typedef struct slslam_rectify_camera {
+  double fx, fy, cx, cy;
+  double k1, k2, p1, p2, k3;
+  double R[9];
+  double fx2, fy2, cx2, cy2;
+  int src_width, src_height, dst_width, dst_height;
+} slslam_rectify_camera;
+typedef struct slslam_rectify_frame {
+  int camera;                    /* which of the handle's cameras took it */
+  long long stride;              /* bytes from one row to the next, src_width <= stride < 2^31 */
+  const unsigned char* image;    /* [src_height][stride] */
+} slslam_rectify_frame;
+typedef struct slslam_rectify_result {
+  unsigned char* image;          /* caller-owned [dst_height][stride]; only the dst_width bytes of a row are written */
+  long long stride;              /* >= dst_width */
+  unsigned char* valid;          /* [dst_height dst_width] or NULL */
+  int* num_valid;                /* one int or NULL */
+} slslam_rectify_result;
+typedef struct slslam_stereo_rig {
+  double left_k[4], left_dist[5];       /* fx fy cx cy; k1 k2 p1 p2 k3 */
+  double right_k[4], right_dist[5];
+  double R[9], t[3];                    /* x_right = R x_left + t */
+  int left_width, left_height, right_width, right_height, dst_width, dst_height;
+  int has_principal, reserved;
+  double cx2, cy2;                      /* the rectified principal point when has_principal != 0 */
+} slslam_stereo_rig;
+typedef struct slslam_image_rectifier slslam_image_rectifier;
+
+/* border constant 0, no smoothing */
+void slslam_rectify_default_options(slslam_rectify_options* opt);
+/* Host only.  sigma in [0, 16]: *radius and taps[8] = t_0 .. t_7 (0 beyond the radius); sigma = 0 gives radius 0 and t_0 = 16384. */
+int  slslam_rectify_smooth_taps(double sigma, int* radius, int* taps);
+/* Host only: "rig" above.  Outputs are written only on SLSLAM_OK. */
+int  slslam_stereo_rectify(const slslam_stereo_rig* rig, slslam_rectify_camera* left, slslam_rectify_camera* right, double* baseline,
+                           double* intrinsics);
+/* device < 0 selects the current HIP device.  options and the 1 .. 64 cameras are fixed for the handle; the output pixels of all
+ * cameras together <= 2^28 (their maps take 25 bytes a pixel on the device, made with the first call that reaches it and not counted
+ * in `allocations`).  max_frames >= 1 frames of max_pixels >= 1 pixels each - the larger of source and output -: what the one device
+ * block and the one page-locked block are made for at the first run.  A larger call makes larger ones and counts one allocation; a call
+ * that fits allocates nothing.  max_pixels <= 8192^2, max_frames x max_pixels <= 2^30.  Touches no device. */
+int  slslam_image_rectifier_create(int device, const slslam_rectify_options* options, int num_cameras, const slslam_rectify_camera* cameras,
+                                   int max_frames, long long max_pixels, slslam_image_rectifier** out);
+void slslam_image_rectifier_destroy(slslam_image_rectifier* handle);
+/* frames[F], results[F].  Every argument is validated before an output is written or the device is asked - a negative count, a missing
+ * array or image, a camera index out of range, a stride below the width: SLSLAM_ERR_INVALID_ARGUMENT; more than 65535 frames or 2^32
+ * bytes in one call: SLSLAM_ERR_UNSUPPORTED.  Synchronous; host pointers; one upload, one launch and one download per call whatever F.
+ * num_frames = 0 is a counted call that does nothing. */
+int  slslam_image_rectifier_run(slslam_image_rectifier* handle, int num_frames, const slslam_rectify_frame* frames,
+                                const slslam_rectify_result* results);
+/* The map of one camera as the device computed it, any pointer may be NULL: qx, qy [dst_height dst_width] int32, valid bytes, and
+ * the doubles sx, sy (NaN where a pixel has no coordinates). */
+int  slslam_image_rectifier_get_map(slslam_image_rectifier* handle, int camera, int* qx, int* qy, unsigned char* valid, double* sx,
+                                    double* sy);
+/* Since create: runs, and how often the blocks were made or made larger.  Either pointer may be NULL. */
+int  slslam_image_rectifier_stats(const slslam_image_rectifier* handle, long long* calls, long long* allocations);
+/* Any number of frames, one call (its own handle, maps and buffers, made and freed). */
+int  slslam_rectify_images(const slslam_rectify_options* options, int num_cameras, const slslam_rectify_camera* cameras, int num_frames,
+                           const slslam_rectify_frame* frames, const slslam_rectify_result* results);
+
 /* ------------------------------------------------------------------ diagnostics (benches, timing experiments)
  * Not part of the reference's surface: the reference times its back-end with StopWatch accumulators around whole calls
  * (src/stopwatch.h:42-157, proc_2 / proc_3 at src/slam.cpp:1384-1386, :1237,1312); these give the device-side split. */
@@ -1589,6 +1701,8 @@ int slslam_po_last_timing(double* total_ms, double* factor_ms, int* factor_calls
 int slslam_line_descriptor_timing(slslam_line_descriptor* handle, int enable, double* kernel_ms);
 /* The same for the line detector (tools/line_detect_bench.py): the events bracket the eleven launches of a run. */
 int slslam_line_detector_timing(slslam_line_detector* handle, int enable, double* kernel_ms);
+/* The same for the image rectifier (tools/image_rectify_bench.py): the events bracket the one launch of a run. */
+int slslam_image_rectifier_timing(slslam_image_rectifier* handle, int enable, double* kernel_ms);
 /* Timing builds only (a variant library compiled with -DSLSLAM_K1_TIMING=1, -DSLSLAM_K1_WALL=1 or -DSLSLAM_SOLVE_TIMING=1: the elimination
  * sweeps / the reduced solve and k_big_solve): wave-clock cycles per phase summed over the batch since finalize; out[16].  The product
  * library has no stamps and no stamp buffer: SLSLAM_ERR_STATE there, from this call and the next. */

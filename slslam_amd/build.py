@@ -7,7 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "_lib")
 LIB = os.path.join(LIB_DIR, "libslslam_hip.so")
-SOURCES = ["lba_api.hip", "lba_stream.hip", "lba_host_util.hip", "lba_pack.cpp", "po_api.hip", "ransac_api.hip", "frame_api.hip", "match_api.hip", "triangulate_api.hip", "place_api.hip", "voctree_train_api.hip", "descriptor_api.hip", "line_descriptor_api.hip", "line_detect_api.hip", "stereo_api.hip", "track_api.hip",
+SOURCES = ["lba_api.hip", "lba_stream.hip", "lba_host_util.hip", "lba_pack.cpp", "po_api.hip", "ransac_api.hip", "frame_api.hip", "match_api.hip", "triangulate_api.hip", "place_api.hip", "voctree_train_api.hip", "descriptor_api.hip", "line_descriptor_api.hip", "line_detect_api.hip", "stereo_api.hip", "track_api.hip", "rectify_api.hip",
            os.path.join("..", "host", "place_filter.cpp"),      # (the place recogniser's Bayes filter: host C++, exported with the rest)
            os.path.join("..", "host", "voctree_host.cpp")]      # (the tree trainer's host half: keys, centres, partition, save)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "slslam_hip.h"), os.path.join("..", "host", "place_filter.h"), os.path.join("..", "host", "voctree_host.h")]   # every header: a new one must not leave a stale library behind

@@ -194,6 +194,54 @@ class LineTrackResult(C.Structure):
                 ("num_admissible", C.POINTER(C.c_int)), ("best_row", C.POINTER(C.c_int))]
 
 
+class RectifyOptions(C.Structure):
+    _fields_ = [("border_mode", C.c_int), ("border_value", C.c_int), ("smooth_sigma", C.c_double)]
+
+
+class RectifyCamera(C.Structure):
+    """slslam_rectify_camera.  RectifyCamera.make(...) takes keywords with an identity default for everything but the sizes."""
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")] + [("R", C.c_double * 9)] + \
+               [(k, C.c_double) for k in ("fx2", "fy2", "cx2", "cy2")] + \
+               [(k, C.c_int) for k in ("src_width", "src_height", "dst_width", "dst_height")]
+
+    @classmethod
+    def make(cls, src_width, src_height, dst_width=None, dst_height=None, fx=1.0, fy=1.0, cx=0.0, cy=0.0, k1=0.0, k2=0.0, p1=0.0, p2=0.0,
+             k3=0.0, R=None, fx2=None, fy2=None, cx2=None, cy2=None):
+        c = cls()
+        c.fx, c.fy, c.cx, c.cy = float(fx), float(fy), float(cx), float(cy)
+        c.k1, c.k2, c.p1, c.p2, c.k3 = float(k1), float(k2), float(p1), float(p2), float(k3)
+        c.R[:] = np.asarray(np.eye(3) if R is None else R, dtype=np.float64).reshape(9).tolist()
+        c.fx2, c.fy2 = float(fx if fx2 is None else fx2), float(fy if fy2 is None else fy2)
+        c.cx2, c.cy2 = float(cx if cx2 is None else cx2), float(cy if cy2 is None else cy2)
+        c.src_width, c.src_height = int(src_width), int(src_height)
+        c.dst_width, c.dst_height = int(src_width if dst_width is None else dst_width), int(src_height if dst_height is None else dst_height)
+        return c
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "R"}
+        d["R"] = np.array(list(self.R)).reshape(3, 3)
+        return d
+
+
+class RectifyFrame(C.Structure):
+    _fields_ = [("camera", C.c_int), ("stride", C.c_longlong), ("image", C.POINTER(C.c_ubyte))]
+
+
+class RectifyResult(C.Structure):
+    _fields_ = [("image", C.POINTER(C.c_ubyte)), ("stride", C.c_longlong), ("valid", C.POINTER(C.c_ubyte)), ("num_valid", C.POINTER(C.c_int))]
+
+
+class StereoRig(C.Structure):
+    _fields_ = [("left_k", C.c_double * 4), ("left_dist", C.c_double * 5), ("right_k", C.c_double * 4), ("right_dist", C.c_double * 5),
+                ("R", C.c_double * 9), ("t", C.c_double * 3)] + \
+               [(k, C.c_int) for k in ("left_width", "left_height", "right_width", "right_height", "dst_width", "dst_height",
+                                       "has_principal", "reserved")] + [("cx2", C.c_double), ("cy2", C.c_double)]
+
+
+RECTIFY_BORDER = {"constant": 0, "replicate": 1}
+RECTIFY_SUBPIXEL_BITS = 8                               # SLSLAM_RECTIFY_SUBPIXEL_BITS
+RECTIFY_NO_COORD = -2 ** 31                             # SLSLAM_RECTIFY_NO_COORD
+RECTIFY_TILE = (64, 16)                                 # SLSLAM_RECTIFY_TILE_WIDTH, _HEIGHT: the smoothing kernel's tile
 STEREO_STATUS = {0: "OK", 1: "EMPTY"}
 TRACK_STATUS = {0: "OK", 1: "EMPTY"}
 TRACK_SEGMENT_STATUS = {0: "CONTINUED", 1: "NEW", 2: "SHORT", 3: "INVALID"}
@@ -264,6 +312,9 @@ EXPORTS = [
     "slslam_line_track_default_options", "slslam_line_tracker_create", "slslam_line_tracker_destroy", "slslam_line_tracker_run",
     "slslam_line_tracker_reset", "slslam_line_tracker_state", "slslam_line_tracker_stats", "slslam_line_tracker_timing",
     "slslam_track_lines",
+    "slslam_rectify_default_options", "slslam_rectify_smooth_taps", "slslam_stereo_rectify", "slslam_image_rectifier_create",
+    "slslam_image_rectifier_destroy", "slslam_image_rectifier_run", "slslam_image_rectifier_get_map", "slslam_image_rectifier_stats",
+    "slslam_image_rectifier_timing", "slslam_rectify_images",
     "slslam_voctree_train", "slslam_voctree_save", "slslam_voctree_centres", "slslam_voctree_key", "slslam_debug_voctree_step", "slslam_device_count", "slslam_release_cached_memory", "slslam_version", "slslam_status_string",
 ]
 
@@ -487,6 +538,22 @@ def lib():
         L.slslam_line_tracker_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
         L.slslam_line_tracker_timing.argtypes = [vp, C.c_int, dp]
         L.slslam_track_lines.argtypes = [C.c_int, C.POINTER(LineTrackOptions), C.c_int, C.POINTER(LineTrackFrame), C.POINTER(LineTrackResult)]
+    if hasattr(L, "slslam_rectify_images"):     # (likewise: a library built before the image rectifier existed)
+        bp = C.POINTER(C.c_ubyte)
+        L.slslam_rectify_default_options.argtypes = [C.POINTER(RectifyOptions)]
+        L.slslam_rectify_default_options.restype = None
+        L.slslam_rectify_smooth_taps.argtypes = [C.c_double, ip, ip]
+        L.slslam_stereo_rectify.argtypes = [C.POINTER(StereoRig), C.POINTER(RectifyCamera), C.POINTER(RectifyCamera), dp, dp]
+        L.slslam_image_rectifier_create.argtypes = [C.c_int, C.POINTER(RectifyOptions), C.c_int, C.POINTER(RectifyCamera), C.c_int, C.c_longlong,
+                                                    C.POINTER(vp)]
+        L.slslam_image_rectifier_destroy.argtypes = [vp]
+        L.slslam_image_rectifier_destroy.restype = None
+        L.slslam_image_rectifier_run.argtypes = [vp, C.c_int, C.POINTER(RectifyFrame), C.POINTER(RectifyResult)]
+        L.slslam_image_rectifier_get_map.argtypes = [vp, C.c_int, ip, ip, bp, dp, dp]
+        L.slslam_image_rectifier_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
+        L.slslam_image_rectifier_timing.argtypes = [vp, C.c_int, dp]
+        L.slslam_rectify_images.argtypes = [C.POINTER(RectifyOptions), C.c_int, C.POINTER(RectifyCamera), C.c_int, C.POINTER(RectifyFrame),
+                                            C.POINTER(RectifyResult)]
     L.slslam_po_set_profiling.argtypes = [C.c_int]
     L.slslam_po_last_timing.argtypes = [dp, dp, ip, ip, ip]
     L.slslam_debug_phase_cycles.argtypes = [vp, dp]
@@ -2425,4 +2492,139 @@ def detect_describe_pair_and_track(detector, descriptor, matcher, tracker, stere
     for o, t in zip(out, tracker.run(frames)):
         o["track"] = t
         o["ids"] = t["id"][stereo_observations(o["stereo"])[1]]
+    return out
+
+
+# ----------------------------------------------------------------------------- image rectification (slslam_image_rectifier_*)
+def rectify_options(border="constant", border_value=0, smooth_sigma=0.0):
+    """slslam_rectify_options: border "constant" or "replicate" (or the SLSLAM_RECTIFY_BORDER_* number), the value an invalid pixel gets,
+    and the sigma of the pre-smoothing (0: none)."""
+    mode = RECTIFY_BORDER[border] if isinstance(border, str) else int(border)
+    return RectifyOptions(mode, int(border_value), float(smooth_sigma))
+
+
+def smooth_taps(sigma):
+    """slslam_rectify_smooth_taps: (radius, taps [8] int32: t_0 .. t_7, 0 beyond the radius)."""
+    r, t = C.c_int(-1), np.zeros(8, dtype=np.int32)
+    _check(lib().slslam_rectify_smooth_taps(float(sigma), C.byref(r), _ip(t)), "slslam_rectify_smooth_taps")
+    return r.value, t
+
+
+def stereo_rectify(left, right, R, t, dst_size=None, principal=None):
+    """slslam_stereo_rectify.  left, right: dict(fx, fy, cx, cy, width, height[, k1, k2, p1, p2, k3]) of the raw cameras; R [3, 3], t [3]:
+    x_right = R x_left + t; dst_size: (width, height) of both outputs, the left camera's size by default; principal: (cx2, cy2), the
+    left principal point by default.  Returns dict(left, right: RectifyCamera; baseline; fx, fy, cx, cy: what stereo_match_options
+    takes)."""
+    g = StereoRig()
+    for side, cam in (("left", left), ("right", right)):
+        getattr(g, side + "_k")[:] = [float(cam[k]) for k in ("fx", "fy", "cx", "cy")]
+        getattr(g, side + "_dist")[:] = [float(cam.get(k, 0.0)) for k in ("k1", "k2", "p1", "p2", "k3")]
+        setattr(g, side + "_width", int(cam["width"]))
+        setattr(g, side + "_height", int(cam["height"]))
+    g.R[:] = np.asarray(R, dtype=np.float64).reshape(9).tolist()
+    g.t[:] = np.asarray(t, dtype=np.float64).reshape(3).tolist()
+    g.dst_width, g.dst_height = (int(left["width"]), int(left["height"])) if dst_size is None else (int(dst_size[0]), int(dst_size[1]))
+    if principal is not None:
+        g.has_principal, g.cx2, g.cy2 = 1, float(principal[0]), float(principal[1])
+    a, b, base, k = RectifyCamera(), RectifyCamera(), C.c_double(0.0), np.zeros(4)
+    _check(lib().slslam_stereo_rectify(C.byref(g), C.byref(a), C.byref(b), C.byref(base), _dp(k)), "slslam_stereo_rectify")
+    return dict(left=a, right=b, baseline=base.value, fx=k[0], fy=k[1], cx=k[2], cy=k[3])
+
+
+def _camera_array(cameras):
+    arr = (RectifyCamera * max(len(cameras), 1))()
+    for i, c in enumerate(cameras):
+        arr[i] = c
+    return arr
+
+
+def _rectify_frame(cameras, camera, image, valid):
+    """(RectifyFrame, RectifyResult, the arrays both point to); a camera index out of range is left for the library to refuse."""
+    img = _image_rows(image)
+    k = int(camera)
+    c = cameras[k] if 0 <= k < len(cameras) else None
+    shape = (c.dst_height, c.dst_width) if c is not None else (1, 1)
+    b = {"image": np.zeros(shape, dtype=np.uint8), "valid": np.zeros(shape, dtype=np.uint8) if valid else None,
+         "num_valid": np.full(1, -1, dtype=np.int32)}
+    ub = C.POINTER(C.c_ubyte)
+    fr = RectifyFrame(k, img.strides[0] if img.shape[0] > 0 else 0, img.ctypes.data_as(ub))
+    res = RectifyResult(b["image"].ctypes.data_as(ub), shape[1], b["valid"].ctypes.data_as(ub) if valid else None, _ip(b["num_valid"]))
+    return fr, res, (img, b)
+
+
+def _rectify_dict(keep):
+    _, b = keep
+    out = {"image": b["image"], "num_valid": int(b["num_valid"][0])}
+    if b["valid"] is not None:
+        out["valid"] = b["valid"]
+    return out
+
+
+def _rectify_check_sizes(cameras, frames):
+    for k, image in frames:
+        if 0 <= int(k) < len(cameras) and np.asarray(image).shape != (cameras[int(k)].src_height, cameras[int(k)].src_width):
+            raise ValueError("a frame has the source size of its camera")
+
+
+def rectify_images(cameras, frames, valid=False, **options):
+    """slslam_rectify_images: cameras: a list of RectifyCamera; frames: (camera index, raw uint8 image [src_height, src_width]) each.
+    Returns per frame dict(image uint8 [dst_height, dst_width], num_valid; with valid=True also valid uint8 [dst_height, dst_width])."""
+    opt = rectify_options(**options)
+    _rectify_check_sizes(cameras, frames)
+    frs, outs, keep = _frame_arrays(RectifyFrame, RectifyResult, frames, lambda f: _rectify_frame(cameras, f[0], f[1], valid))
+    _check(lib().slslam_rectify_images(C.byref(opt), len(cameras), _camera_array(cameras), len(frames), frs, outs), "slslam_rectify_images")
+    return [_rectify_dict(k) for k in keep]
+
+
+class ImageRectifier(_TimedHandle):
+    """slslam_image_rectifier: the rectified (and, with smooth_sigma > 0, smoothed) images of many raw frames per call; the cameras'
+    maps stay on the device, buffers are kept between calls.  A frame is (camera index, raw uint8 image)."""
+    _DESTROY, _STATS, _TIMING = "slslam_image_rectifier_destroy", "slslam_image_rectifier_stats", "slslam_image_rectifier_timing"
+
+    def __init__(self, cameras, max_frames=2, max_pixels=752 * 480, device=-1, **options):
+        self.opt = rectify_options(**options)
+        self.cameras = list(cameras)
+        self._h = C.c_void_p()
+        _check(lib().slslam_image_rectifier_create(int(device), C.byref(self.opt), len(self.cameras), _camera_array(self.cameras),
+                                                   int(max_frames), int(max_pixels), C.byref(self._h)), "slslam_image_rectifier_create")
+
+    def run(self, frames, valid=False):
+        """Returns one dict per frame, as rectify_images returns it."""
+        _rectify_check_sizes(self.cameras, frames)
+        frs, outs, keep = _frame_arrays(RectifyFrame, RectifyResult, frames, lambda f: _rectify_frame(self.cameras, f[0], f[1], valid))
+        _check(lib().slslam_image_rectifier_run(self._h, len(frames), frs, outs), "slslam_image_rectifier_run")
+        return [_rectify_dict(k) for k in keep]
+
+    def get_map(self, camera, fp64=False):
+        """The device's map of one camera: dict(qx, qy int32 [dst_height, dst_width], valid uint8; with fp64=True also sx, sy)."""
+        c = self.cameras[int(camera)]
+        shape = (c.dst_height, c.dst_width)
+        out = {"qx": np.zeros(shape, dtype=np.int32), "qy": np.zeros(shape, dtype=np.int32), "valid": np.zeros(shape, dtype=np.uint8)}
+        if fp64:
+            out.update(sx=np.zeros(shape), sy=np.zeros(shape))
+        _check(lib().slslam_image_rectifier_get_map(self._h, int(camera), _ip(out["qx"]), _ip(out["qy"]),
+                                                    out["valid"].ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                    _dp(out["sx"]) if fp64 else None, _dp(out["sy"]) if fp64 else None),
+               "slslam_image_rectifier_get_map")
+        return out
+
+
+def rectify_detect_describe_pair_and_track(rectifier, detector, descriptor, matcher, tracker, raw_stereo_images, predicts=None,
+                                           cameras=(0, 1), intrinsics=None, **stereo_options):
+    """The image front end from a rig's raw images: every (left, right) raw pair through the rectifier (an ImageRectifier whose cameras
+    `cameras` = (left, right) are a rectified pair, as stereo_rectify makes them) in one call, then detect_describe_pair_and_track on
+    the rectified images - five calls whatever the number of frames.  The stereo options fx, fy, cx, cy are the left camera's rectified
+    intrinsics unless `intrinsics` (a dict of the four, e.g. what stereo_rectify returned) or stereo_options give them.  Returns
+    what detect_describe_pair_and_track returns, each frame's dict with `rectified`: the (left, right) images."""
+    flat = [(cameras[i], img) for pair in raw_stereo_images for i, img in enumerate(pair)]
+    rect = rectifier.run(flat)
+    pairs = [(rect[2 * i]["image"], rect[2 * i + 1]["image"]) for i in range(len(raw_stereo_images))]
+    c = rectifier.cameras[cameras[0]]
+    k = dict(fx=c.fx2, fy=c.fy2, cx=c.cx2, cy=c.cy2)
+    if intrinsics is not None:
+        k.update({n: float(intrinsics[n]) for n in ("fx", "fy", "cx", "cy")})
+    k.update(stereo_options)
+    out = detect_describe_pair_and_track(detector, descriptor, matcher, tracker, pairs, predicts, **k)
+    for o, p in zip(out, pairs):
+        o["rectified"] = p
     return out

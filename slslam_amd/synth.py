@@ -702,3 +702,95 @@ def make_line_sequence(seed, height, width, num_segments, num_frames, shifts, dr
             out["right_segments"].append((part["segments"][rows] + np.array([sx - d, sy, sx - d, sy])).astype(np.float32))
             out["right_labels"].append(here[rows].astype(np.int32))
     return out
+
+
+def _undistort(xd, yd, k1, k2, p1, p2, k3, iterations=30):
+    """The inverse of the Brown-Conrady model by fixed-point iteration: the undistorted normalised point of a distorted one."""
+    x, y = xd.copy(), yd.copy()
+    for _ in range(iterations):
+        r2 = x * x + y * y
+        rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+        dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+        dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+        x, y = (xd - dx) / rad, (yd - dy) / rad
+    return x, y
+
+
+def _rectifying_rotations(R, t):
+    """Fusiello's construction (include/slslam_hip.h: slslam_stereo_rectify) for x_right = R x_left + t: (the left camera's rotation
+    into the rectified frame, the right camera's, the baseline)."""
+    c = -(R.T @ t)
+    b = np.sqrt(c @ c)
+    e1 = c / b
+    e2 = np.array([-e1[1], e1[0], 0.0])
+    e2 /= np.sqrt(e2 @ e2)
+    Rl = np.stack([e1, e2, np.cross(e1, e2)])
+    return Rl, Rl @ R.T, float(b)
+
+
+def make_raw_stereo_pair(seed, height=160, width=224, num_segments=8, disparity=(4.0, 14.0), background_disparity=2.5,
+                         focal=None, distortion=((-0.28, 0.09, 0.0012, -0.0009, -0.01), (-0.24, 0.07, -0.0010, 0.0014, 0.0)),
+                         rotation=(0.012, -0.02, 0.016), baseline=(0.12, 0.004, -0.003), right_gain=1.0, right_offset=0.0,
+                         min_length=24.0, max_length=70.0, margin=30.0, texture=0.35, segments=None):
+    """The raw images of a stereo rig whose right camera is rotated (`rotation`: the angle-axis of R in x_right = R x_left + t) and
+    displaced (`baseline`: its centre in the left camera), both lenses distorted (k1, k2, p1, p2, k3 each), looking at straight 3-D
+    edges - `segments` [n, 4] in rectified left pixel coordinates, each with the profile of make_edge_image, or num_segments seeded
+    ones -: every edge lies in a plane of constant depth of the RECTIFIED frame, in front of a textured background plane.  Both raw
+    images are rendered by inverse mapping through the distortion model: a raw pixel is undistorted to its ray, the ray is rotated into
+    the rectified frame and cut with each edge's plane.  The right image's grey values are right_gain * I + right_offset; the default
+    is no photometric difference, so that the two views differ by geometry alone: an edge fades out beyond its end points, and a gain
+    moves the place along the edge where a detector's gradient threshold cuts it - with 0.8 the two detections of one edge end up to
+    0.8 px of rows apart, which says nothing about the rectification.  Returns dict(left, right: raw uint8 [height, width]; rig: dict(left, right:
+    dict(fx, fy, cx, cy, k1, k2, p1, p2, k3, width, height), R, t); Rl, Rr: the rectifying rotations; baseline, focal, cx, cy: the
+    rectified geometry (focal = the mean of the four focal lengths, the left principal point);  left_segments, right_segments
+    [n, 4] float64: the drawn edges in rectified pixel coordinates, row i of both the same edge; disparity [n])."""
+    rng = np.random.default_rng(np.random.SeedSequence([20, int(seed)]))
+    f0 = float(focal) if focal is not None else 0.9 * width
+    cams = []
+    for side in range(2):
+        k = dict(zip(("k1", "k2", "p1", "p2", "k3"), [float(v) for v in distortion[side]]))
+        k.update(fx=f0 * (1.0 + 0.01 * side) + 0.7, fy=f0 * (1.0 + 0.01 * side) - 0.4, cx=0.5 * (width - 1) + (2.3 if side == 0 else -1.7),
+                 cy=0.5 * (height - 1) + (-1.9 if side == 0 else 1.2), width=int(width), height=int(height))
+        cams.append(k)
+    R = rodrigues(np.asarray(rotation, dtype=np.float64))
+    c = np.asarray(baseline, dtype=np.float64)
+    t = -(R @ c)
+    Rl, Rr, b = _rectifying_rotations(R, t)
+    f = ((cams[0]["fx"] + cams[0]["fy"]) + (cams[1]["fx"] + cams[1]["fy"])) / 4.0
+    cx2, cy2 = cams[0]["cx"], cams[0]["cy"]
+    lo, hi = float(disparity[0]), float(disparity[1])
+    n = int(num_segments) if segments is None else len(segments)
+    scene = _line_scene(seed, height, width, n, min_length, max_length, margin + hi)
+    d = rng.uniform(lo, hi, n)
+    # edges a detector with default options takes: a peak gradient of 25 to 70 grey levels a pixel
+    scene["amplitude"] = rng.uniform(45.0, 70.0, n) * rng.choice([-1.0, 1.0], n)
+    scene["softness"] = rng.uniform(1.0, 1.8, n)
+    if segments is not None:
+        scene["segments"] = np.asarray(segments, dtype=np.float64).reshape(n, 4)
+        scene["softness"], scene["reach"] = np.full(n, 1.5), np.full(n, 6.0)
+    seg = scene["segments"]
+    images = []
+    for side, (cam, rot) in enumerate(zip(cams, (Rl, Rr))):
+        vv, uu = np.mgrid[0:height, 0:width].astype(np.float64)
+        x, y = _undistort((uu - cam["cx"]) / cam["fx"], (vv - cam["cy"]) / cam["fy"], *[cam[k] for k in ("k1", "k2", "p1", "p2", "k3")])
+        ray = np.stack([x, y, np.ones_like(x)], axis=-1) @ rot.T                       # in the rectified frame
+        # where the ray meets the plane of a disparity dd, in rectified LEFT pixel coordinates: the camera's centre is (side b, 0, 0)
+        def at(dd):
+            return f * ray[..., 0] / ray[..., 2] + cx2 + side * dd, f * ray[..., 1] / ray[..., 2] + cy2
+        val = np.full((height, width), 118.0)
+        xb, yb = at(background_disparity)
+        for kk, th, ph, a in scene["waves"]:
+            val += texture * a * np.sin(kk * (np.cos(th) * xb + np.sin(th) * yb) + ph)
+        for (x0, y0, x1, y1), amp, soft, reach, dd in zip(seg, scene["amplitude"], scene["softness"], scene["reach"], d):
+            xp, yp = at(dd)
+            length = np.hypot(x1 - x0, y1 - y0)
+            ex, ey = (x1 - x0) / length, (y1 - y0) / length
+            du, dv = xp - 0.5 * (x0 + x1), yp - 0.5 * (y0 + y1)
+            along, across = du * ex + dv * ey, dv * ex - du * ey
+            fade = 0.5 * (1.0 + np.tanh(0.5 * length - np.abs(along))) * np.exp(-0.5 * (across / reach) ** 2)
+            val += amp * np.tanh(across / soft) * fade
+        gain, off = (1.0, 0.0) if side == 0 else (right_gain, right_offset)
+        images.append(np.clip(np.rint(gain * val + off), 0, 255).astype(np.uint8))
+    right = seg - np.stack([d, np.zeros(n), d, np.zeros(n)], axis=1)
+    return {"left": images[0], "right": images[1], "rig": dict(left=cams[0], right=cams[1], R=R, t=t), "Rl": Rl, "Rr": Rr, "baseline": b,
+            "focal": f, "cx": cx2, "cy": cy2, "left_segments": seg.copy(), "right_segments": right, "disparity": d}
